@@ -25,6 +25,14 @@ Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
   cpu_baseline  the REAL reference (oracle/_ref build) -- or the oracle port -- timed on this
                 box's host cores on the same batch and setting, same graphs (N = 1 only)
   per_fraction  QPS@recall>=0.95 for all 17 window fractions 2^-16..2^0 (device time, N = 1 only)
+  configs       the other BASELINE.json configurations (N = 1 only)
+per_fraction and configs are summarised on stdout (the line stays below LINE_BUDGET characters);
+the full record goes to stderr as `[bench] full: {...}`.
+
+  --dump-outputs DIR  after the timed steps, rank 0 writes the rows the LAST timed step returned:
+                      DIR/ids.npy (float64; the uint32 ids) and DIR/dists.npy (float32), (rows, k).
+                      Above DUMP_BUDGET bytes a fixed, seeded sample of rows is written, with its
+                      row numbers in DIR/rows.npy.  Same arguments = same inputs, run after run.
 Data are synthetic (no network): seeds and laws in SURVEY.md 8(d).
 """
 import argparse
@@ -43,6 +51,8 @@ K = 10
 BEAM_SIZES = [10, 20, 40, 80, 160, 320, 640, 1280]
 FINAL_MULTIPLIES = [1, 2, 3, 4, 8, 16, 32]
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+LINE_BUDGET = 6000     # characters of the stdout JSON line (readers keep the last 8 000 characters of stdout)
+DUMP_BUDGET = 64 << 20  # bytes of --dump-outputs
 
 
 def log(*a):
@@ -140,6 +150,56 @@ def recall_of(torch, gt, gcnt, ids):
     hit = ((gt[:, :, None] == ids64[:, None, :]) & (gt[:, :, None] >= 0)).any(2).sum(1)
     valid = gcnt > 0
     return float((hit[valid].double() / gcnt[valid].double()).mean().item())
+
+
+def dump_outputs(out_dir, ids, dists, budget=DUMP_BUDGET):
+    """--dump-outputs: the (rows, k) result of one step as DIR/ids.npy (float64 of the uint32 ids: exact) and DIR/dists.npy
+    (float32); a batch above `budget` bytes is cut to a sample of rows drawn with a fixed seed, listed in DIR/rows.npy."""
+    import numpy as np
+    ids = np.ascontiguousarray(ids).view(np.uint32).astype(np.float64)
+    dists = np.ascontiguousarray(dists, dtype=np.float32)
+    nrows, k = ids.shape
+    per_row = 12 * k + 8  # ids + dists + the row number when sampled
+    files = {}
+    if nrows * 12 * k > budget:
+        rows = np.sort(np.random.default_rng(0).choice(nrows, budget // per_row, replace=False))
+        files["rows"] = rows.astype(np.float64)
+        ids, dists = ids[rows], dists[rows]
+    files["ids"], files["dists"] = ids, dists
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.shape for name, a in files.items()}
+
+
+def stdout_line(result):
+    """The JSON line for stdout: the contract's keys, `config`, `roofline` and `cpu_baseline` as they are; `per_fraction` and
+    `configs` cut to a few numbers each (the full record goes to stderr)."""
+    line = {k: v for k, v in result.items() if k not in ("per_fraction", "configs")}
+    if result.get("per_fraction") is not None:
+        keys = ("qps", "recall", "beam", "mult", "roofline_frac", "reference_qps", "rows_identical_ids")
+        line["per_fraction"] = {p: {k: r[k] for k in keys if k in r} for p, r in result["per_fraction"].items()}
+    if result.get("configs") is not None:
+        cfgs = {}
+        for name, r in result["configs"].items():
+            if "error" in r:
+                cfgs[name] = {"error": r["error"][-120:]}
+                continue
+            c = {k: r[k] for k in ("qps", "mfma_qps", "recall_at_10", "setting") if k in r}
+            if isinstance(r.get("roofline"), dict):
+                c["frac"] = r["roofline"].get("frac")
+            refs = r.get("reference") or []
+            if refs:
+                c["same_ids"] = min(x.get("same_ids", 0.0) for x in refs)
+            elif isinstance(r.get("cpu_reference"), dict):
+                c["dists_identical"] = r["cpu_reference"].get("dists_identical")
+            cfgs[name] = c
+        line["configs"] = cfgs
+    s = json.dumps(line)
+    if len(s) > LINE_BUDGET and "per_fraction" in line:  # (never expected: drop the per-fraction table before the line overflows)
+        line["per_fraction"] = {p: {k: r[k] for k in ("qps", "recall") if k in r} for p, r in line["per_fraction"].items()}
+        s = json.dumps(line)
+    return s
 
 
 def free_port():
@@ -264,8 +324,12 @@ def main():
     ap.add_argument("--configs", default=None, help="N=1: the other BASELINE.json configurations as extra legs of the line: 'all' = glove "
                     "(configs[2]), deep (configs[3] on this one GPU), adverse (configs[4]), sift_u8 / fenwick / three_split (SURVEY.md 8(f)-4 / 8(f)-2 at "
                     "configs[1] size); 'none'; or a comma list (also: deep_l2 = configs[3] under squared L2)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the rows the last timed step returned to DIR/ids.npy (float64) and DIR/dists.npy (float32)")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = WORKLOADS[args.workload]
     args.n = args.n or wl["n"]
     args.dim = args.dim or wl["d"]
@@ -494,7 +558,11 @@ def main():
 
     # the same batch every step (rounds 1-3 timed this) -- reported beside `value`; then THE timed region: rotating batches
     same_elapsed, _, same_agg = timed(False) if rot > 1 else (None, None, None)
-    elapsed, _, _ = timed(True)
+    elapsed, last_out, _ = timed(True)
+    if args.dump_outputs and rank == 0:  # (every rank holds every row of the step)
+        shapes = dump_outputs(args.dump_outputs, last_out[0].cpu().numpy(), last_out[1].cpu().numpy())
+        log(f"outputs of timed step {args.steps} (rotation {(args.steps - 1) % rot}, beam {beam} x{mult}) -> {args.dump_outputs}: {shapes}")
+    del last_out
     ms_per_step = elapsed / args.steps * 1e3
     qps = gnq * args.steps / elapsed
     timed_agg = dict(agg)
@@ -681,7 +749,8 @@ def main():
         result["configs"] = other_configs(want, args.cache, ncpu, cache if args.workload == "sift" and n == 1_000_000 and d == 128 else None)
 
     if rank == 0:
-        print(json.dumps(result), flush=True)
+        log("full:", json.dumps(result))
+        print(stdout_line(result), flush=True)
     if distributed:
         dist.destroy_process_group()
 

@@ -1,12 +1,14 @@
 """GPU: the N > 1 product path on the RCCL backend -- sharded_batch_search / level_dealt_batch_search drive the HIP kernels on
 every rank and their all-gathers run over RCCL; rows must equal the single-GPU call.  With ONE device the process group has one
 rank (the collective still runs); on a box with more GPUs the same worker runs with 2 .. 8 ranks (it SKIPS LOUDLY on one GPU).
-Also: bench.py under the driver's launch line with one rank prints a line with n_gpus = 1."""
+Also: bench.py under the driver's launch line with one rank prints a line with n_gpus = 1, and its --dump-outputs rows repeat run
+after run."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from util import REPO
@@ -57,3 +59,33 @@ def test_bench_under_the_launcher_with_one_rank(gpu, tmp_path):
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and "RCCL" in line["config"]["parallelism"]
     assert line["roofline"]["frac"] > 0 and line["scaling"] == "weak"
+
+
+def test_bench_dump_outputs_are_the_same_run_after_run(gpu, tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same rows of their last timed step (queries, windows and the
+    setting pinned by the arguments), and they are the rows the host-buffer call returns for that step's batch"""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--points", "30000", "--nq", "500",
+               "--fractions", "headline", "--configs", "none", "--no-cpu-baseline", "--pipeline", "0", "--setting", "40,1", "--cache", str(tmp_path / "cache"),
+               "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=_env())
+        assert out.returncode == 0, out.stderr[-3000:]
+        assert json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])["steps"] == 3
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert set(dumps[0]) == {"ids.npy", "dists.npy"}
+    assert dumps[0]["ids.npy"].dtype == np.float64 and dumps[0]["dists.npy"].dtype == np.float32 and dumps[0]["ids.npy"].shape == (500, 10)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    # the third timed step searched rotation 2 of the four: the same queries and windows through the host-buffer call, on the graphs
+    # the runs left in their cache
+    sys.path.insert(0, REPO)
+    import bench
+    import window_ann as wa
+    X, Qall, labels = bench.make_data(30000, 128, 500, 4)
+    idx = wa.VamanaRangeFilterTreeIndexFloatEuclidian(X, labels, cutoff=1000, split_factor=2, build_params=wa.BuildParams(64, 500, 1.0, str(tmp_path / "cache" / "siftlike_n30000_d128_R64_L500_c1000_s2") + "/"))
+    W = bench.make_windows(np.sort(labels), 500, -3, 1000 + 7919 * 2)
+    ids, dists = idx.batch_search(Qall[1000:1500], W, 500, "optimized_postfilter", wa.QueryParams(10, 40, 1.35, 10_000_000, 10_000, 1, 10000, None, False))
+    assert np.array_equal(dumps[0]["ids.npy"], np.asarray(ids).view(np.uint32).astype(np.float64))
+    assert np.array_equal(dumps[0]["dists.npy"], np.asarray(dists))

@@ -1,29 +1,55 @@
-"""CPU, authoring container only: the oracle against the REAL reference built from /root/reference
-(oracle/_ref, `make -C oracle ref`).  Skipped where no reference build is present (the committed
-golden vectors in tests/golden/ carry the same pin everywhere else)."""
+"""CPU: the oracle against the REAL reference.  Where a reference build is present (oracle/_ref, `make -C oracle ref`) the two
+run side by side on the same graph files.  Everywhere else the oracle builds the graphs itself and its graph files and rows are
+checked against the SHA-256 digests of what the reference wrote and returned for the same inputs
+(tests/golden/oracle_vs_reference.json, written by tests/golden/make_oracle_vs_reference_golden.py)."""
+import hashlib
+import json
 import os
 
 import numpy as np
 import pytest
 
-from util import distinct_labels, quiet_stdout, sift_like, unit_mixture, windows
+from util import REPO, distinct_labels, quiet_stdout, sift_like, unit_mixture, windows
+
+GOLDEN = os.path.join(REPO, "tests", "golden", "oracle_vs_reference.json")
+
+
+def digest(a, dtype):
+    return hashlib.sha256(np.ascontiguousarray(np.asarray(a).astype(dtype)).tobytes()).hexdigest()
+
+
+def row_digests(ids, dists):
+    return {"ids": digest(ids, np.int64), "dists": digest(dists, np.float32)}
+
+
+def file_digests(path):
+    return {f: hashlib.sha256(open(os.path.join(path, f), "rb").read()).hexdigest() for f in sorted(os.listdir(path))}
 
 
 @pytest.fixture(scope="module")
 def ref(oracle):
+    """the reference's module, or None: replay the stored digests"""
     os.environ.setdefault("PARLAY_NUM_THREADS", "4")
-    mod = oracle.load_reference()
-    if mod is None:
-        pytest.skip("no reference build under oracle/_ref")
-    return mod
+    return oracle.load_reference()
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return json.load(open(GOLDEN))
 
 
 KINDS = ["VamanaRangeFilterTreeIndex", "SuperOptimizedPostfilterTreeIndex", "PostfilterVamanaIndex", "RangeFilterTreeIndex", "PrefilterIndex"]
+EQUALS_CASES = [("Euclidian", sift_like, 128), ("mips", unit_mixture, 100), ("Euclidian", unit_mixture, 104)]
+RATIO_CASES = [("Euclidian", sift_like, 64), ("mips", unit_mixture, 100)]
+BUILDER_CASES = [("Euclidian", 1500, 16, 16, 40), ("mips", 3000, 24, 12, 32), ("Euclidian", 9000, 16, 8, 20)]
 
 
-@pytest.mark.parametrize("metric,gen,d", [("Euclidian", sift_like, 128), ("mips", unit_mixture, 100), ("Euclidian", unit_mixture, 104)])
-@pytest.mark.parametrize("kind", KINDS)
-def test_oracle_equals_reference(oracle, ref, tmp_path, metric, gen, d, kind):
+def equals_key(kind, metric, gen, d):
+    return f"equals|{kind}|{metric}|{gen.__name__}|{d}"
+
+
+def equals_rows(mod, cache, kind, metric, gen, d):
+    """`mod`'s index of the case on the graph files under `cache` (built there when absent) and its rows: {case: (ids, dists)}"""
     n, nq = 2500, 60
     g = gen(n, d, 31)
     X, Q = g(n), g(nq)
@@ -33,78 +59,122 @@ def test_oracle_equals_reference(oracle, ref, tmp_path, metric, gen, d, kind):
     if kind.startswith("Super"):
         kw["shift_factor"] = 0.5
     labkw = "filters" if kind == "PostfilterVamanaIndex" else "filter_values"
-    cache = str(tmp_path) + "/"
-    with quiet_stdout():  # the reference builds and writes the graph cache; the oracle loads it
-        ridx = getattr(ref, kind + sfx)(X, **{labkw: labels}, build_params=ref.BuildParams(24, 48, 1.0, cache), **kw)
-    oidx = getattr(oracle, kind + sfx)(X, **{labkw: labels}, build_params=oracle.BuildParams(24, 48, 1.0, cache), **kw)
-    integer_data = gen is sift_like
+    with quiet_stdout():
+        idx = getattr(mod, kind + sfx)(X, **{labkw: labels}, build_params=mod.BuildParams(24, 48, 1.0, cache), **kw)
     methods = ["optimized_postfilter", "fenwick", "three_split"] if kind.endswith("RangeFilterTreeIndex") else [None]
+    rows = {}
     for p in (-5, -3, -1, 0):
         W = windows(labels, nq, p, 40 + p)
         for method in methods:
             for beam, mult in [(10, 1), (40, 2)]:
                 a = (Q, W, nq) + ((method,) if method else ())
                 with quiet_stdout():
-                    ri, rd = ridx.batch_search(*a, ref.QueryParams(10, beam, 1.35, 10**7, 10**4, mult, 10000, None, False))
-                oi, od = oidx.batch_search(*a, oracle.QueryParams(10, beam, 1.35, 10**7, 10**4, mult, 10000, None, False))
-                assert np.array_equal(rd, od), (kind, p, method, beam, mult)
-                if not integer_data or (kind == "VamanaRangeFilterTreeIndex" and method == "optimized_postfilter") \
-                        or kind in ("SuperOptimizedPostfilterTreeIndex", "PostfilterVamanaIndex"):
-                    assert np.array_equal(ri, oi), (kind, p, method, beam, mult)
+                    rows[f"{p}|{method}|{beam}|{mult}"] = idx.batch_search(*a, mod.QueryParams(10, beam, 1.35, 10**7, 10**4, mult, 10000, None, False))
+    return rows
 
 
-@pytest.mark.parametrize("metric,gen,d", [("Euclidian", sift_like, 64), ("mips", unit_mixture, 100)])
-def test_oracle_ratio_fallback_equals_reference(oracle, ref, tmp_path, metric, gen, d):
-    """min_query_to_bucket_ratio (src/range_filter_tree.h:460-466): windows that are a small share of their smallest containing
-    bucket take fenwick_tree_search -- distances identical for every ratio, ids wherever no merged list is involved"""
+@pytest.mark.parametrize("metric,gen,d", EQUALS_CASES)
+@pytest.mark.parametrize("kind", KINDS)
+def test_oracle_equals_reference(oracle, ref, golden, tmp_path, metric, gen, d, kind):
+    cache = str(tmp_path) + "/"
+    want = None
+    if ref is not None:  # the reference builds and writes the graph cache; the oracle loads it
+        want = equals_rows(ref, cache, kind, metric, gen, d)
+    got = equals_rows(oracle, cache, kind, metric, gen, d)
+    g = golden[equals_key(kind, metric, gen, d)]
+    if ref is None:  # the oracle built the graphs: the reference's files, byte for byte
+        assert file_digests(cache) == g["graphs"]
+    integer_data = gen is sift_like
+    check_ids = not integer_data or kind in ("SuperOptimizedPostfilterTreeIndex", "PostfilterVamanaIndex")
+    for case, (oi, od) in got.items():
+        ids_too = check_ids or (kind == "VamanaRangeFilterTreeIndex" and case.split("|")[1] == "optimized_postfilter")
+        if want is not None:
+            ri, rd = want[case]
+            assert np.array_equal(rd, od), (kind, case)
+            if ids_too:
+                assert np.array_equal(ri, oi), (kind, case)
+        else:
+            assert row_digests(oi, od)["dists"] == g["rows"][case]["dists"], (kind, case)
+            if ids_too:
+                assert row_digests(oi, od)["ids"] == g["rows"][case]["ids"], (kind, case)
+
+
+def ratio_key(metric, gen, d):
+    return f"ratio|{metric}|{gen.__name__}|{d}"
+
+
+def ratio_rows(mod, cache, metric, gen, d):
     n, nq = 2500, 60
     g = gen(n, d, 77)
     X, Q = g(n), g(nq)
     labels = distinct_labels(n, 13)
     sfx = "FloatMips" if metric == "mips" else "FloatEuclidian"
-    cache = str(tmp_path) + "/"
     with quiet_stdout():
-        ridx = getattr(ref, "VamanaRangeFilterTreeIndex" + sfx)(X, labels, 250, 2, ref.BuildParams(24, 48, 1.0, cache))
-    oidx = getattr(oracle, "VamanaRangeFilterTreeIndex" + sfx)(X, filter_values=labels, cutoff=250, split_factor=2,
-                                                               build_params=oracle.BuildParams(24, 48, 1.0, cache))
-    changed = 0
+        idx = getattr(mod, "VamanaRangeFilterTreeIndex" + sfx)(X, filter_values=labels, cutoff=250, split_factor=2,
+                                                                   build_params=mod.BuildParams(24, 48, 1.0, cache))
+    rows = {}
     for p in (-5, -3, -1):
         W = windows(labels, nq, p, 90 + p)
-        base = None
         for ratio in (None, 1.0, 1.5, 3.0, 8.0):
             for beam, mult in [(10, 1), (40, 2)]:
                 with quiet_stdout():
-                    ri, rd = ridx.batch_search(Q, W, nq, "optimized_postfilter", ref.QueryParams(10, beam, 1.35, 10**7, 10**4, mult, 10000, ratio, False))
-                oi, od = oidx.batch_search(Q, W, nq, "optimized_postfilter", oracle.QueryParams(10, beam, 1.35, 10**7, 10**4, mult, 10000, ratio, False))
-                assert np.array_equal(rd, od), (p, ratio, beam, mult)
-                if gen is not sift_like:  # (integer data: merged lists hold distance ties the reference orders arbitrarily)
-                    assert np.array_equal(ri, oi), (p, ratio, beam, mult)
-                if ratio is None and (beam, mult) == (40, 2):
-                    base = rd
-                elif (beam, mult) == (40, 2) and not np.array_equal(base, rd):
-                    changed += 1
+                    rows[f"{p}|{ratio}|{beam}|{mult}"] = idx.batch_search(Q, W, nq, "optimized_postfilter",
+                                                                          mod.QueryParams(10, beam, 1.35, 10**7, 10**4, mult, 10000, ratio, False))
+    return rows
+
+
+@pytest.mark.parametrize("metric,gen,d", RATIO_CASES)
+def test_oracle_ratio_fallback_equals_reference(oracle, ref, golden, tmp_path, metric, gen, d):
+    """min_query_to_bucket_ratio (src/range_filter_tree.h:460-466): windows that are a small share of their smallest containing
+    bucket take fenwick_tree_search -- distances identical for every ratio, ids wherever no merged list is involved"""
+    cache = str(tmp_path) + "/"
+    want = ratio_rows(ref, cache, metric, gen, d) if ref is not None else None
+    got = ratio_rows(oracle, cache, metric, gen, d)
+    g = golden[ratio_key(metric, gen, d)]
+    if ref is None:
+        assert file_digests(cache) == g["graphs"]
+    changed = 0
+    for case, (oi, od) in got.items():
+        if want is not None:
+            ri, rd = want[case]
+            assert np.array_equal(rd, od), case
+            if gen is not sift_like:  # (integer data: merged lists hold distance ties the reference orders arbitrarily)
+                assert np.array_equal(ri, oi), case
+        else:
+            assert row_digests(oi, od)["dists"] == g["rows"][case]["dists"], case
+            if gen is not sift_like:
+                assert row_digests(oi, od)["ids"] == g["rows"][case]["ids"], case
+        p, ratio, beam, mult = case.split("|")
+        if ratio != "None" and (beam, mult) == ("40", "2") and not np.array_equal(got[f"{p}|None|40|2"][1], od):
+            changed += 1
     assert changed > 0  # some ratio did send queries down the other branch
 
 
-@pytest.mark.parametrize("metric,n,d,R,L", [("Euclidian", 1500, 16, 16, 40), ("mips", 3000, 24, 12, 32), ("Euclidian", 9000, 16, 8, 20)])  # L2: d % 8 == 0 (the reference reads past d otherwise, SURVEY 8 a11)
-def test_oracle_builder_equals_reference_builder(oracle, ref, tmp_path, metric, n, d, R, L):
-    """Whole tree of graphs (every partition size down to the leaves) on continuous coordinates: every cache
-    file the oracle's builder writes equals the reference builder's.  (With exactly equidistant candidates
-    the reference's result depends on libstdc++'s std::sort tie order -- vamana/index.h:77-78, graph.h:106 --
-    and the restatement breaks such ties by id instead; see DESIGN.md 3.6.)"""
+def builder_key(metric, n, d, R, L):
+    return f"builder|{metric}|{n}|{d}|{R}|{L}"
+
+
+def builder_files(mod, cache, metric, n, d, R, L):
     rng = np.random.default_rng(n + d)
     X = rng.standard_normal((n, d)).astype(np.float32)
     if metric == "mips":
         X /= np.linalg.norm(X, axis=1, keepdims=True)
     labels = distinct_labels(n, 3)
     sfx = "FloatMips" if metric == "mips" else "FloatEuclidian"
-    rdir, odir = str(tmp_path / "ref") + "/", str(tmp_path / "orc") + "/"
-    os.makedirs(rdir), os.makedirs(odir)
+    os.makedirs(cache)
     with quiet_stdout():
-        getattr(ref, "VamanaRangeFilterTreeIndex" + sfx)(X, labels, 400, 2, ref.BuildParams(R, L, 1.0, rdir))
-    getattr(oracle, "VamanaRangeFilterTreeIndex" + sfx)(X, filter_values=labels, cutoff=400, split_factor=2,
-                                                        build_params=oracle.BuildParams(R, L, 1.0, odir))
-    rf, of = sorted(os.listdir(rdir)), sorted(os.listdir(odir))
-    assert rf == of and len(rf) > 3
-    differing = [f for f in rf if open(rdir + f, "rb").read() != open(odir + f, "rb").read()]
+        getattr(mod, "VamanaRangeFilterTreeIndex" + sfx)(X, filter_values=labels, cutoff=400, split_factor=2, build_params=mod.BuildParams(R, L, 1.0, cache))
+    return file_digests(cache)
+
+
+@pytest.mark.parametrize("metric,n,d,R,L", BUILDER_CASES)  # L2: d % 8 == 0 (the reference reads past d otherwise, SURVEY 8 a11)
+def test_oracle_builder_equals_reference_builder(oracle, ref, golden, tmp_path, metric, n, d, R, L):
+    """Whole tree of graphs (every partition size down to the leaves) on continuous coordinates: every cache
+    file the oracle's builder writes equals the reference builder's.  (With exactly equidistant candidates
+    the reference's result depends on libstdc++'s std::sort tie order -- vamana/index.h:77-78, graph.h:106 --
+    and the restatement breaks such ties by id instead; see DESIGN.md 3.6.)"""
+    want = builder_files(ref, str(tmp_path / "ref") + "/", metric, n, d, R, L) if ref is not None else golden[builder_key(metric, n, d, R, L)]
+    got = builder_files(oracle, str(tmp_path / "orc") + "/", metric, n, d, R, L)
+    assert sorted(got) == sorted(want) and len(got) > 3
+    differing = [f for f in want if got[f] != want[f]]
     assert not differing, differing
