@@ -45,8 +45,18 @@ enum { WANN_OK = 0, WANN_ERR_INVALID = 1, WANN_ERR_NO_DEVICE = 2, WANN_ERR_HIP =
 /* distance: Euclidian_Point (squared L2, euclidian_point.h:62-75) / Mips_Point (-<q,p>, mips_point.h:60-76) */
 enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
 /* element type of points/queries (python_bindings.cpp:232-237): float32 rows, or uint8 / int8 BYTE rows scored with
- * v_dot4 into exact int32 sums (euclidian_point.h:44-60, mips_point.h:44-58), any dimension */
-enum { WANN_DTYPE_F32 = 0, WANN_DTYPE_U8 = 1, WANN_DTYPE_I8 = 2 };
+ * v_dot4 into exact int32 sums (euclidian_point.h:44-60, mips_point.h:44-58), any dimension.
+ * WANN_DTYPE_F16 (not a type of the reference): IEEE binary16 points, stored on the device as half rows (half the vector bytes
+ * of float32).  Every binary16 value converts to float32 exactly, and the kernels score each row in the float32 path's own
+ * arithmetic and order, so a float16 index returns -- ids, distance bits and the reference's operation counters -- what the
+ * float32 index of the same kind / metric / parameters returns for the points and queries upcast to float32 (ids of
+ * equidistant points in an exact scan may permute, as between the GPU and the reference).  Its graphs are the float32 index's
+ * graphs on the upcast points, byte for byte, under the same cache file names: the two share a graph cache.  (A float32 index
+ * on the UNROUNDED points gets the same file names but other graphs: keep such caches apart.)  Host-buffer calls take
+ * float16 queries; device-buffer calls take fp32 queries (not rounded).  Labels stay float32.  The MFMA prefilter path is
+ * float32-only: a float16 PrefilterIndex batch takes the exact scan (gemm_queries == 0), as uint8 / int8 batches do.  The
+ * unfiltered wann_vamana_* API refuses float16. */
+enum { WANN_DTYPE_F32 = 0, WANN_DTYPE_U8 = 1, WANN_DTYPE_I8 = 2, WANN_DTYPE_F16 = 3 };
 /* index classes */
 enum {
   WANN_KIND_PREFILTER = 0,      /* PrefilterIndex                                   */
@@ -229,6 +239,14 @@ int wann_raw_beam_search(int metric, const float *points, int64_t n, int64_t d,
                          int64_t degree_limit, int32_t *out_ids /* nq x beam */,
                          float *out_dists /* nq x beam */, int32_t *out_sizes /* nq */,
                          int64_t *out_hops /* nq */, int64_t *out_dist_cmps /* nq */, int device);
+/* the same over points of any element type (`dtype`: WANN_DTYPE_*, rows as wann_index_create takes them); queries stay fp32 */
+int wann_raw_beam_search_typed(int metric, int dtype, const void *points, int64_t n, int64_t d,
+                               const int32_t *graph_rows /* n x (maxdeg+1) */, int64_t maxdeg,
+                               int64_t subset_start, int64_t subset_n, const float *queries, int64_t nq,
+                               const int64_t *query_ids, int64_t beam, int64_t limit,
+                               int64_t degree_limit, int32_t *out_ids /* nq x beam */,
+                               float *out_dists /* nq x beam */, int32_t *out_sizes /* nq */,
+                               int64_t *out_hops /* nq */, int64_t *out_dist_cmps /* nq */, int device);
 
 /* Unfiltered VamanaIndex<T,Point> (ParlayANN/python/vamana_index.cpp:42-76, bound at python_bindings.cpp:92-109): a graph
  * index opened from a point file (uint32 n, uint32 d, n*d elements of dtype: point_range.h:63-93) and a graph file

@@ -132,7 +132,7 @@ int wann_device_count(void) { return usable_devices(); }
 wann_index *wann_index_create(int kind, int metric, int dtype, const void *points, int64_t n, int64_t d,
                               const float *labels, int32_t cutoff, double split_factor, double shift_factor,
                               const wann_build_params *bp, int device, int build_threads) {
-  if (dtype != WANN_DTYPE_F32 && dtype != WANN_DTYPE_U8 && dtype != WANN_DTYPE_I8) {
+  if (dtype != WANN_DTYPE_F32 && dtype != WANN_DTYPE_U8 && dtype != WANN_DTYPE_I8 && dtype != WANN_DTYPE_F16) {
     fail(WANN_ERR_INVALID, "unknown dtype");
     return nullptr;
   }
@@ -360,7 +360,7 @@ int wann_batch_search_allgather(wann_index *I, const void *queries, const float 
       r->open(devs);
       I->rccl = std::move(r);
     }
-    const int64_t k = qp->k, d = I->H.spec.d, esz = I->dtype == WANN_DTYPE_F32 ? 4 : 1;
+    const int64_t k = qp->k, d = I->H.spec.d, esz = element_bytes(I->dtype);
     int64_t cap = 0;
     wann_gather_layout(nq, G, 0, nullptr, nullptr, &cap);
     if (cap == 0) cap = 1;
@@ -577,7 +577,7 @@ int wann_batch_search(wann_index *I, const void *queries, const float *ranges, i
   // In-process multi-device mode (WANN_DEVICES): contiguous shards that keep their global query numbers (the reference uses
   // a query's row number as its own id, range_filter_tree.h:62-96 + beamSearch.h:128), one host thread and one stream per
   // replica, rows land in the caller's arrays.
-  const int64_t d = I->H.spec.d, esz = I->dtype == WANN_DTYPE_F32 ? 4 : 1;
+  const int64_t d = I->H.spec.d, esz = element_bytes(I->dtype);
   std::vector<std::thread> threads;
   std::vector<int> codes((size_t)G, WANN_OK);
   std::vector<std::string> errs((size_t)G);
@@ -673,7 +673,8 @@ int wann_num_replicas(const wann_index *I) { return I ? 1 + (int)I->replicas.siz
 int wann_build_cache_shard(int kind, int metric, int dtype, const void *points, int64_t n, int64_t d,
                            const float *labels, int32_t cutoff, double split_factor, double shift_factor,
                            const wann_build_params *bp, int shard, int nshards, int build_threads) {
-  if (dtype != WANN_DTYPE_F32 && dtype != WANN_DTYPE_U8 && dtype != WANN_DTYPE_I8) return fail(WANN_ERR_INVALID, "unknown dtype");
+  if (dtype != WANN_DTYPE_F32 && dtype != WANN_DTYPE_U8 && dtype != WANN_DTYPE_I8 && dtype != WANN_DTYPE_F16)
+    return fail(WANN_ERR_INVALID, "unknown dtype");
   if (!bp || !bp->cache_path || !*bp->cache_path) return fail(WANN_ERR_INVALID, "cache_path required");
   if (nshards <= 0 || shard < 0 || shard >= nshards) return fail(WANN_ERR_INVALID, "bad shard");
   try {

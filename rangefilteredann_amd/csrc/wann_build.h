@@ -30,8 +30,8 @@ struct HostPart {
 
 struct BuildSpec {
   int kind = 0, metric = 0;
-  int dtype = 0;  // element type of the rows (wann.h WANN_DTYPE_*): float32, or uint8 / int8 bytes
-  int64_t n = 0, d = 0, stride = 0;
+  int dtype = 0;  // element type of the caller's rows (wann.h WANN_DTYPE_*): float32, uint8 / int8 bytes, or float16
+  int64_t n = 0, d = 0, stride = 0;  // stride: 32-bit words per row of HostIndex::pts
   int32_t cutoff = 1000;
   double split_factor = 2, shift_factor = 0.5;
   int64_t R = 64, L = 500;
@@ -44,7 +44,8 @@ struct HostIndex {
   BuildSpec spec;
   bool vamana_leaves = false, sorted = false;
   std::vector<float> pts;          // n x stride 32-bit words: zero padded rows (label-sorted for tree kinds); float32 values, or the
-                                   // d bytes of a uint8 / int8 row
+                                   // d bytes of a uint8 / int8 row (float16 points: their exact float32 upcast -- the host builder
+                                   // and the GPU builder score float32 rows; upload_index stores the device rows as halves)
   std::vector<float> labels;       // same order as pts
   std::vector<uint32_t> decoding;  // row -> original id
   std::vector<std::vector<int64_t>> offsets;  // WST bucket offsets per level
@@ -58,7 +59,8 @@ struct HostIndex {
 void parallel_for(int64_t n, int threads, const std::function<void(int64_t)> &f);
 int default_threads();
 
-// metric: bit 0 = inner product, bits 4-5 = element type of the rows behind p / q (0 float32, 1 uint8, 2 int8)
+// metric: bit 0 = inner product, bits 4-5 = element type of the rows behind p / q (0 float32, 1 uint8, 2 int8; float16 point
+// sets are built from their float32 upcast and pass 0)
 float host_distance(int metric, const float *p, const float *q, int d);
 
 bool graph_file_load(const std::string &path, HostGraph &g);

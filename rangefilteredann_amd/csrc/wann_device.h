@@ -42,9 +42,14 @@ struct IndexView {
   const int64_t *sup_shift;
   int64_t n;
   int32_t d, stride, rs, maxdeg, metric, kind, nlevels, cutoff, split, vamana_leaves;
-  int32_t dtype;  // element type of `points` (wann.h WANN_DTYPE_*): float32 rows, or uint8 / int8 rows of d bytes padded to a
-                  // multiple of 64 -- `stride` counts 32-bit words in every case and `points` is addressed in words
+  int32_t dtype;  // element type of `points` (wann.h WANN_DTYPE_*): float32 rows, uint8 / int8 rows of d bytes padded to a
+                  // multiple of 64, or float16 rows of d halves padded to a multiple of 32 -- `stride` counts 32-bit words in every
+                  // case and `points` is addressed in words
 };
+
+// 32-bit words of a staged query (fp32, zero padded; the LDS the kernels reserve for it): `stride` for float32 / byte rows, the
+// float32 row length (d rounded up to 16) for float16 rows -- the same LDS layout as the float32 index (host side of qv_words)
+inline int query_words(const IndexView &v) { return v.dtype == 3 ? ((v.d + 15) & ~15) : v.stride; }
 
 enum { T_EMPTY = 0, T_GRAPH = 1, T_BRUTE = 2, T_BRUTE_GATHER = 3, T_PARENT = 4 };
 // Task::flags: 1 = heavy (schedule first), 2 = final_beam_multiply forced to 1, 4 = speculative sub-task, 8 = mid priority
@@ -294,7 +299,7 @@ int launch_brute(const BruteArgs &a, int blocks, void *stream);
 int launch_finalize(const FinalizeArgs &a, void *stream);
 int launch_task_cost(const CostArgs &a, void *stream);
 // bytes of LDS one wave of k_search needs: common scratch + the beam / seen-filter pool
-int search_lds_bytes_per_wave(int stride, int pool_bytes);
+int search_lds_bytes_per_wave(int qwords, int pool_bytes);  // qwords: query_words(view)
 const char *launch_last_error();
 
 constexpr int kWavesPerBlock = 4;

@@ -6,6 +6,7 @@
 // There is no CPU search path in this library: every compute entry point needs a gfx950 device
 // and fails loudly otherwise.
 #include "wann_host_internal.h"
+#include "wann_half.h"
 
 namespace wann_host {
 
@@ -69,7 +70,8 @@ void upload_index(wann_index &I) {
   IndexView &v = I.view;
   v.n = s.n;
   v.d = (int32_t)s.d;
-  v.stride = (int32_t)s.stride;
+  // float16 points: the host rows are their float32 upcast; the device rows are halves again (exact), 64-byte padded
+  v.stride = (int32_t)(s.dtype == WANN_DTYPE_F16 ? ((s.d * 2 + 63) / 64) * 16 : s.stride);
   v.metric = s.metric;
   v.dtype = s.dtype;
   v.kind = s.kind;
@@ -80,7 +82,17 @@ void upload_index(wann_index &I) {
   v.rs = (int32_t)(((s.R + 15) / 16) * 16);
   v.nlevels = (int32_t)H.levels.size();
 
-  I.d_points.upload(H.pts);
+  if (s.dtype == WANN_DTYPE_F16) {
+    std::vector<float> rows((size_t)s.n * v.stride, 0.f);
+    parallel_for(s.n, s.threads > 0 ? s.threads : default_threads(), [&](int64_t r) {
+      const float *src = H.pts.data() + r * s.stride;
+      uint16_t *dst = reinterpret_cast<uint16_t *>(rows.data() + r * v.stride);
+      for (int64_t j = 0; j < s.d; j++) dst[j] = float_to_half(src[j]);
+    });
+    I.d_points.upload(rows);
+  } else {
+    I.d_points.upload(H.pts);
+  }
   I.d_labels.upload(H.labels);
   I.d_decoding.upload(H.decoding);
   v.points = I.d_points.p;
@@ -216,7 +228,7 @@ RoundCfg config_for(const wann_index &I, const Tuning &T, int64_t first_beam, in
   // search of such an index runs in the one-wave kernel that holds it (k_search<., 2>), eight workgroups per CU.
   if (I.view.rs > 64) big_lds = legacy = true;
   const int wpb = big_lds ? 1 : kWavesPerBlock;
-  const int common = search_lds_bytes_per_wave(I.view.stride, 0);
+  const int common = search_lds_bytes_per_wave(query_words(I.view), 0);
   if (big_lds && !legacy && cap_bytes + 4096 + kScoreBoxBytes > 150 * 1024 - common) legacy = true;
   const int box_bytes = (big_lds && !legacy) ? kScoreBoxBytes : 0;
   if (big_lds && !legacy) force_table = true;
@@ -232,7 +244,7 @@ RoundCfg config_for(const wann_index &I, const Tuning &T, int64_t first_beam, in
   // register budget: the L2 kernel holds two whole 512-B rows per lane pair in flight (2 waves/SIMD)
   // (four-wave kernel: the squared-L2 float kernel needs 232 registers: two waves per SIMD; the inner-product and byte-row
   // kernels are built for three)
-  const int waves_per_cu = (I.view.metric == 1 || I.view.dtype != WANN_DTYPE_F32) ? 12 : 8;
+  const int waves_per_cu = (I.view.metric == 1 || byte_rows(I.view)) ? 12 : 8;
   int blocks_per_cu = std::min((big_lds ? 8 : waves_per_cu) / wpb, lds_blocks_per_cu(per_block));
   blocks_per_cu = std::max(1, blocks_per_cu);
   int64_t blocks = (int64_t)I.num_cus * blocks_per_cu;
@@ -258,8 +270,8 @@ RoundCfg config_for(const wann_index &I, const Tuning &T, int64_t first_beam, in
 // fit three waves per SIMD): the in-kernel cap's beam (10 KiB) still fits, the seen-filter of beams up to 90 too.  0: this
 // index can not use it (rows too long).
 int lean_pool_bytes(const wann_index &I, const Tuning &T) {
-  if (!(I.view.metric == 1 || I.view.dtype != WANN_DTYPE_F32)) return 0;
-  const int common = search_lds_bytes_per_wave(I.view.stride, 0);
+  if (!(I.view.metric == 1 || byte_rows(I.view))) return 0;
+  const int common = search_lds_bytes_per_wave(query_words(I.view), 0);
   // 52 KiB per workgroup.  Three workgroups of 53 KiB (159 of the CU's 160 KiB) are NOT co-resident on gfx950, whatever
   // hipOccupancyMaxActiveBlocksPerMultiprocessor says (3): a launch of 768 such workgroups ran at the speed of 512 until round 4
   // measured it (stand-alone inner-product graph, 30 000 searches at beam 80: 6.65 ms at 53 KiB, 5.22 ms at 52.5 KiB and below).
@@ -435,7 +447,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   // at 32 MiB per workgroup)
   int32_t big_cap = 0;
   if (spec && T.big) {
-    const int common = search_lds_bytes_per_wave(I.view.stride, 0);
+    const int common = search_lds_bytes_per_wave(query_words(I.view), 0);
     const int64_t big_pool = (int64_t)(common + kSearchPoolBytes) * kWavesPerBlock - common;
     big_cap = (int32_t)std::min<int64_t>(big_pool / 8, 5792);
     if (big_cap <= ra.cap_inkernel || (common + kSearchPoolBytes) * kWavesPerBlock > 160 * 1024) big_cap = 0;
@@ -517,7 +529,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
     }
     // (as many waves as the chip holds at once -- by the registers: two per SIMD for squared-L2 float rows (two 512-byte rows
     // per lane pair in flight), three for inner-product float rows, five for byte rows -- deal the tickets among themselves)
-    const int brute_per_cu = I.view.dtype != WANN_DTYPE_F32 ? 5 : (I.view.metric == 1 ? 3 : 2);
+    const int brute_per_cu = byte_rows(I.view) ? 5 : (I.view.metric == 1 ? 3 : 2);
     int blocks = (int)std::min<int64_t>((int64_t)I.num_cus * brute_per_cu, (nq * std::min(maxt, 2) + kWavesPerBlock - 1) / kWavesPerBlock);
     if (launch_brute(ba, blocks, scan_st)) throw HipError(std::string("k_brute: ") + launch_last_error());
     if (scans_aside) HIP_CHECK(hipEventRecord(W.ev_scan, scan_st));
@@ -604,7 +616,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
         // companion launch for the speculative levels beyond `cap`: one wave per workgroup, one workgroup per
         // CU, the beam (up to with_big_cap entries) in the LDS, the seen-filter in g_table_big
         with_big = true;
-        const int common = search_lds_bytes_per_wave(I.view.stride, 0);
+        const int common = search_lds_bytes_per_wave(query_words(I.view), 0);
         big = a;
         big_lc.big = a.old_general ? 2 : 1;  // (WANN_OLD_GENERAL: the first-generation core also for the companion's searches)
         big.helper = (big_lc.big == 2 || !T.helper) ? 0 : kHelpers;
@@ -1071,9 +1083,19 @@ void build_pending(wann_index &I, std::vector<HostPart *> &pending) {
     build_pending_on_host(H, pending);
     for (auto &t : targets) upload_part_rows(I, *t.part, I.parts[t.part_index]);
   } else {
+    // float16 points are built from their float32 upcast (the host rows) by the float32 build kernels: the graphs are those of
+    // the float32 index on the upcast points, byte for byte.  The float32 rows live on the device for the build only.
+    IndexView bv = I.view;
+    DevBuf<float> rows32;
+    if (s.dtype == WANN_DTYPE_F16) {
+      rows32.upload(H.pts);
+      bv.points = rows32.p;
+      bv.stride = (int32_t)s.stride;
+      bv.dtype = WANN_DTYPE_F32;
+    }
     for (int vis_scale = 1;; vis_scale *= 2) {
       try {
-        gpu_build_graphs(I.view, I.d_graph.p, I.parts, targets, s.R, s.L, s.alpha, I.num_cus, s.threads, I.own_stream, vis_scale);
+        gpu_build_graphs(bv, I.d_graph.p, I.parts, targets, s.R, s.L, s.alpha, I.num_cus, s.threads, I.own_stream, vis_scale);
         break;
       } catch (std::runtime_error &e) {
         if (std::string(e.what()).find("gpu build overflow: a visited list") == std::string::npos || vis_scale >= 8) throw;
@@ -1086,7 +1108,10 @@ void build_pending(wann_index &I, std::vector<HostPart *> &pending) {
 
 std::vector<float> bytes_to_float(int dtype, const void *src, int64_t count) {
   std::vector<float> out((size_t)count);
-  if (dtype == WANN_DTYPE_U8) {
+  if (dtype == WANN_DTYPE_F16) {
+    const uint16_t *p = (const uint16_t *)src;
+    for (int64_t i = 0; i < count; i++) out[(size_t)i] = half_to_float(p[i]);
+  } else if (dtype == WANN_DTYPE_U8) {
     const uint8_t *p = (const uint8_t *)src;
     for (int64_t i = 0; i < count; i++) out[(size_t)i] = (float)p[i];
   } else {

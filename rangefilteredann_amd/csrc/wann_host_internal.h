@@ -129,7 +129,7 @@ struct wann_index {
   const HostIndex &host() const { return Hp ? *Hp : H; }
   std::vector<std::unique_ptr<wann_index>> replicas;
   int device = 0;
-  int dtype = WANN_DTYPE_F32;  // element type of the caller's points / host queries (device rows are fp32)
+  int dtype = WANN_DTYPE_F32;  // element type of the caller's points / host queries (device queries are fp32)
   int num_cus = 256;
   DevBuf<float> d_points, d_labels, d_fv;
   DevBuf<uint32_t> d_decoding;
@@ -200,7 +200,12 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
                const int64_t *d_qids = nullptr);
 void build_pending(wann_index &I, std::vector<HostPart *> &pending);
+// host queries of the index's element type (uint8 / int8 / float16) -> the fp32 rows every kernel stages (exact)
 std::vector<float> bytes_to_float(int dtype, const void *src, int64_t count);
+// bytes per element of the caller's points / host queries
+inline int64_t element_bytes(int dtype) { return dtype == WANN_DTYPE_F32 ? 4 : dtype == WANN_DTYPE_F16 ? 2 : 1; }
+// uint8 / int8 rows: scored with v_dot4 by kernels built for more waves per SIMD (float16 rows keep float32's launch shapes)
+inline bool byte_rows(const IndexView &v) { return v.dtype == WANN_DTYPE_U8 || v.dtype == WANN_DTYPE_I8; }
 BuildSpec make_spec(int kind, int metric, int dtype, int64_t n, int64_t d, int32_t cutoff, double split_factor, double shift_factor,
                     const wann_build_params *bp, int threads);
 

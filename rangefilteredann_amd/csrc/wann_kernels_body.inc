@@ -24,15 +24,26 @@
 
 namespace wann {
 
-// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip before this body is
+// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip before this body is
 // included): the search and scan kernels and their launchers live in a per-type namespace; the type-independent
 // kernels (routing, finalisation) and the dispatchers are compiled with the float32 unit only.
 #if WANN_DT == 0
 #define WANN_DT_NS dt_f32
 #elif WANN_DT == 1
 #define WANN_DT_NS dt_u8
-#else
+#elif WANN_DT == 2
 #define WANN_DT_NS dt_i8
+#else
+#define WANN_DT_NS dt_f16
+#endif
+// The float16 unit's search kernels carry the element type as a third template argument (k_search<METRIC, KIND, 3>): their
+// symbols differ from the float32 / byte-row kernels' in more than the namespace, and per-type tools and tests that select
+// the reference's three types by the kernel name's template arguments keep selecting exactly those (tests/test_float16.py
+// checks the float16 kernels' own register budget).
+#if WANN_DT == 3
+#define WANN_DT_TPARAM , int ROWS_DT = 3
+#else
+#define WANN_DT_TPARAM
 #endif
 #ifndef WANN_MIPS_WAVES
 #define WANN_MIPS_WAVES 3  // waves per SIMD the four-wave kernel of inner-product / byte rows is built for (dev: 4 = 128 registers)
@@ -120,9 +131,9 @@ __device__ __forceinline__ uint32_t next_filter_epoch(const SearchArgs &A, int s
   return tag;
 }
 
-template <int METRIC, int KIND>
+template <int METRIC, int KIND WANN_DT_TPARAM>
 __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 : 64 * kWavesPerBlock),
-                             KIND == 1 ? 2 : (KIND == 0 ? ((METRIC == 1 || WANN_DT != 0) ? WANN_MIPS_WAVES : 2) : 1)) void k_search(SearchArgs A) {
+                             KIND == 1 ? 2 : (KIND == 0 ? ((METRIC == 1 || WANN_BYTE_ROWS) ? WANN_MIPS_WAVES : 2) : 1)) void k_search(SearchArgs A) {
   // (four-wave kernel, inner product / byte rows: three waves per SIMD -- these searches wait for memory two thirds of their
   // time, and a third workgroup per CU is 50 % more loads in flight; the squared-L2 float kernel keeps two 512-B rows per
   // lane pair in flight and stays at two)  // (KIND 0 must stay within 256 VGPRs: two waves per SIMD; an explicit occupancy hint made the schedule 5 % slower)
@@ -133,7 +144,7 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
   const int wib = threadIdx.x >> 6;
   // four searching waves per workgroup; the one-wave kernel has ONE searching wave (plus, with A.helper, its prefetch helper)
   const int slot = BIG ? (int)blockIdx.x : (int)(blockIdx.x * (blockDim.x >> 6) + wib);
-  const int per_wave = wave_lds_common_bytes(ix.stride) + A.pool_bytes;
+  const int per_wave = wave_lds_common_bytes(qv_words(ix)) + A.pool_bytes;
   unsigned char *base = smem + (BIG ? 0 : (size_t)wib * per_wave);
   // the helper waves' mailbox takes the last bytes of the pool
   ScoreBox *const box = (KIND == 1 && A.helper) ? reinterpret_cast<ScoreBox *>(base + per_wave - kScoreBoxBytes) : nullptr;
@@ -409,9 +420,9 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
       const int beam_bytes = ((B + 1) & ~1) * 8;
       const bool beam_lds = beam_bytes <= pool_bytes;
       const bool table_lds = beam_lds && (beam_bytes + (4 << bits) <= pool_bytes);
-      WaveLds L = carve_wave_lds(base, ix.stride, B, beam_lds);
+      WaveLds L = carve_wave_lds(base, qv_words(ix), B, beam_lds);
       // stage the query (zero padded); every search restarts from scratch
-      for (int i = lane; i < ix.stride; i += 64) L.qv[i] = stage_query_word(A.queries, qrow, i, ix.d);
+      for (int i = lane; i < qv_words(ix); i += 64) L.qv[i] = stage_query_word(A.queries, qrow, i, ix.d);
       WAVE_SYNC();
       int m;
       long long nvis, ncmp;
@@ -467,8 +478,8 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
         }
         // (rows of 128 floats under squared L2 -- the SIFT shape -- get the core with its block count compiled in: no branch per
         // 16-byte block of a row, twice per hop)
-        if (METRIC == 0 && WANN_DT == 0 && RowRegsFor<METRIC>::NR >= 16 && uni(row_regs_blocks<METRIC>(ix)) == 16)
-          wave_beam_search_mid<METRIC, (METRIC == 0 && WANN_DT == 0) ? 16 : 0>(ix, part, L, gtable, tag, B, bits, qid, A.limit, A.degree_limit, mini, mini_mask, m, nvis, ncmp, A.prof, wbits, wwords, wshift);
+        if (METRIC == 0 && !WANN_BYTE_ROWS && RowRegsFor<METRIC>::NR >= 16 && uni(row_regs_blocks<METRIC>(ix)) == 16)
+          wave_beam_search_mid<METRIC, (METRIC == 0 && !WANN_BYTE_ROWS) ? 16 : 0>(ix, part, L, gtable, tag, B, bits, qid, A.limit, A.degree_limit, mini, mini_mask, m, nvis, ncmp, A.prof, wbits, wwords, wshift);
         else
           wave_beam_search_mid<METRIC>(ix, part, L, gtable, tag, B, bits, qid, A.limit, A.degree_limit, mini, mini_mask, m, nvis, ncmp, A.prof, wbits, wwords, wshift);
       } else if (KIND == 1 && beam_lds && A.g_seen && gtable) {
@@ -740,11 +751,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_brute(BruteArgs A) {
   const int lane = lane_id();
   const int wib = threadIdx.x >> 6;
   const int K = A.k;
-  int per_wave = ((ix.stride * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((K + 1) & ~1) * 8;
+  int per_wave = ((qv_words(ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((K + 1) & ~1) * 8;
   per_wave = (per_wave + 15) & ~15;
   unsigned char *base = smem + (size_t)wib * per_wave;
   float *qv = reinterpret_cast<float *>(base);
-  int off = (ix.stride * 4 + 15) & ~15;
+  int off = (qv_words(ix) * 4 + 15) & ~15;
   u64 *cand_key = reinterpret_cast<u64 *>(base + off);
   off += 64 * 8;
   int32_t *cand_id = reinterpret_cast<int32_t *>(base + off);
@@ -781,7 +792,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_brute(BruteArgs A) {
     const int ti = A.list[li];
     const Task task = A.tasks[ti];
     const int64_t qrow = task.query;
-    for (int i = lane; i < ix.stride; i += 64) qv[i] = stage_query_word(A.queries, qrow, i, ix.d);
+    for (int i = lane; i < qv_words(ix); i += 64) qv[i] = stage_query_word(A.queries, qrow, i, ix.d);
     WAVE_SYNC();
     int64_t ra = task.a, rb = task.b;
     if (S > 1) {
@@ -1442,8 +1453,8 @@ static int check(hipError_t e) {
 
 #if WANN_DT == 0
 
-int search_lds_bytes_per_wave(int stride, int pool_bytes) {
-  return ((stride * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + pool_bytes;
+int search_lds_bytes_per_wave(int qwords, int pool_bytes) {
+  return ((qwords * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + pool_bytes;
 }
 
 int launch_route(const RouteArgs &a, void *stream) {
@@ -1541,7 +1552,7 @@ static int search_occupancy_t(int threads, size_t lds) {
 
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
   const int wpb = cfg.waves_per_block > 0 ? cfg.waves_per_block : kWavesPerBlock;
-  const size_t lds = (size_t)search_lds_bytes_per_wave(a.ix.stride, a.pool_bytes) * wpb;
+  const size_t lds = (size_t)search_lds_bytes_per_wave(query_words(a.ix), a.pool_bytes) * wpb;
   const int threads = 64 * wpb + ((cfg.big == 1 && a.helper) ? 64 * a.helper : 0);
   if (cfg.big == 1) return a.ix.metric == 1 ? search_occupancy_t<1, 1>(threads, lds) : search_occupancy_t<0, 1>(threads, lds);
   if (cfg.big == 2) return a.ix.metric == 1 ? search_occupancy_t<1, 2>(threads, lds) : search_occupancy_t<0, 2>(threads, lds);
@@ -1551,7 +1562,7 @@ int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
 int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
   if (cfg.blocks <= 0) return 0;
   const int wpb = cfg.waves_per_block > 0 ? cfg.waves_per_block : kWavesPerBlock;
-  size_t lds = (size_t)search_lds_bytes_per_wave(a.ix.stride, a.pool_bytes) * wpb;
+  size_t lds = (size_t)search_lds_bytes_per_wave(query_words(a.ix), a.pool_bytes) * wpb;
   dim3 grid(cfg.blocks), block(64 * wpb + ((cfg.big == 1 && a.helper) ? 64 * a.helper : 0));  // (+ the scoring helper waves)
   hipStream_t s = (hipStream_t)stream;
   if (cfg.big == 1) return a.ix.metric == 1 ? launch_search_t<1, 1>(a, grid, block, lds, s) : launch_search_t<0, 1>(a, grid, block, lds, s);
@@ -1561,7 +1572,7 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
 
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   if (blocks <= 0) return 0;
-  int per_wave = ((a.ix.stride * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((a.k + 1) & ~1) * 8;
+  int per_wave = ((query_words(a.ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((a.k + 1) & ~1) * 8;
   per_wave = (per_wave + 15) & ~15;
   size_t lds = (size_t)per_wave * kWavesPerBlock;
   dim3 grid(blocks), block(64 * kWavesPerBlock);
@@ -1584,14 +1595,22 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
 int launch_brute(const BruteArgs &a, int blocks, void *stream);
 }
+namespace dt_f16 {
+int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
+int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
+int launch_brute(const BruteArgs &a, int blocks, void *stream);
+}
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
-  return a.ix.dtype == 1 ? dt_u8::search_occupancy(a, cfg) : a.ix.dtype == 2 ? dt_i8::search_occupancy(a, cfg) : dt_f32::search_occupancy(a, cfg);
+  return a.ix.dtype == 1 ? dt_u8::search_occupancy(a, cfg) : a.ix.dtype == 2 ? dt_i8::search_occupancy(a, cfg)
+       : a.ix.dtype == 3 ? dt_f16::search_occupancy(a, cfg) : dt_f32::search_occupancy(a, cfg);
 }
 int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
-  return a.ix.dtype == 1 ? dt_u8::launch_search(a, cfg, stream) : a.ix.dtype == 2 ? dt_i8::launch_search(a, cfg, stream) : dt_f32::launch_search(a, cfg, stream);
+  return a.ix.dtype == 1 ? dt_u8::launch_search(a, cfg, stream) : a.ix.dtype == 2 ? dt_i8::launch_search(a, cfg, stream)
+       : a.ix.dtype == 3 ? dt_f16::launch_search(a, cfg, stream) : dt_f32::launch_search(a, cfg, stream);
 }
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
-  return a.ix.dtype == 1 ? dt_u8::launch_brute(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_brute(a, blocks, stream) : dt_f32::launch_brute(a, blocks, stream);
+  return a.ix.dtype == 1 ? dt_u8::launch_brute(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_brute(a, blocks, stream)
+       : a.ix.dtype == 3 ? dt_f16::launch_brute(a, blocks, stream) : dt_f32::launch_brute(a, blocks, stream);
 }
 
 int launch_finalize(const FinalizeArgs &a, void *stream) {

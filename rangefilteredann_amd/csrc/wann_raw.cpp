@@ -22,7 +22,7 @@ struct RawGraph {
   DevBuf<unsigned long long> g_beam, d_prof;
   DevBuf<uint32_t> g_seen;
   int64_t layout = -1;
-  // points: (n, d) rows of `dtype` elements (float32, or uint8 / int8 bytes: stored as byte rows)
+  // points: (n, d) rows of `dtype` elements (float32, uint8 / int8 bytes: stored as byte rows, or float16: stored as halves)
   void load(int device, int metric, const void *points, int64_t n_, int64_t d_, const int32_t *graph_rows, int64_t maxdeg_,
             int64_t subset_start, int64_t subset_n_, int dtype = WANN_DTYPE_F32) {
     HIP_CHECK(hipSetDevice(device));
@@ -35,7 +35,7 @@ struct RawGraph {
     d = d_;
     subset_n = subset_n_;
     maxdeg = (int32_t)maxdeg_;
-    const int64_t esz = dtype == WANN_DTYPE_F32 ? 4 : 1;
+    const int64_t esz = element_bytes(dtype);
     const int64_t stride = ((d * esz + 63) / 64) * 16;  // 32-bit words per row
     std::vector<float> pts((size_t)n * stride, 0.f);
     for (int64_t i = 0; i < n; i++) memcpy(pts.data() + i * stride, (const char *)points + i * d * esz, (size_t)(d * esz));
@@ -188,12 +188,22 @@ int wann_raw_beam_search(int metric, const float *points, int64_t n, int64_t d, 
                          const int64_t *query_ids, int64_t beam, int64_t limit, int64_t degree_limit,
                          int32_t *out_ids, float *out_dists, int32_t *out_sizes, int64_t *out_hops,
                          int64_t *out_dist_cmps, int device) {
+  return wann_raw_beam_search_typed(metric, WANN_DTYPE_F32, points, n, d, graph_rows, maxdeg, subset_start, subset_n, queries, nq,
+                                    query_ids, beam, limit, degree_limit, out_ids, out_dists, out_sizes, out_hops, out_dist_cmps, device);
+}
+
+int wann_raw_beam_search_typed(int metric, int dtype, const void *points, int64_t n, int64_t d, const int32_t *graph_rows,
+                               int64_t maxdeg, int64_t subset_start, int64_t subset_n, const float *queries, int64_t nq,
+                               const int64_t *query_ids, int64_t beam, int64_t limit, int64_t degree_limit,
+                               int32_t *out_ids, float *out_dists, int32_t *out_sizes, int64_t *out_hops,
+                               int64_t *out_dist_cmps, int device) {
+  if (dtype < WANN_DTYPE_F32 || dtype > WANN_DTYPE_F16) return fail(WANN_ERR_INVALID, "unknown dtype");
   if (usable_devices() <= device || device < 0)
     return fail(WANN_ERR_NO_DEVICE, "no usable gfx950 device (this library has no CPU search path)");
   if (maxdeg > WANN_MAX_DEGREE) return fail(WANN_ERR_UNSUPPORTED, "max_degree > 128 is not supported");
   try {
     RawGraph G;
-    G.load(device, metric, points, n, d, graph_rows, maxdeg, subset_start, subset_n);
+    G.load(device, metric, points, n, d, graph_rows, maxdeg, subset_start, subset_n, dtype);
     G.search(queries, nq, query_ids, beam, limit, degree_limit, 0, 0.0, out_ids, out_dists, out_sizes, out_hops, out_dist_cmps);
   } catch (HipError &e) {
     return fail(WANN_ERR_HIP, e.what());

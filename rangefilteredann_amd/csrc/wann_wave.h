@@ -81,6 +81,41 @@ __device__ __forceinline__ u64 hash64_2(u64 x) {
 }
 
 // --------------------------------------------------------------------------------------------
+// element type of the point rows: one translation unit per type (wann_kernels.hip, _u8, _i8, _f16)
+// --------------------------------------------------------------------------------------------
+#ifndef WANN_DT
+#define WANN_DT 0  // 0 = float32 rows, 1 = uint8, 2 = int8, 3 = float16
+#endif
+#define WANN_BYTE_ROWS (WANN_DT == 1 || WANN_DT == 2)
+
+// A row BLOCK is four consecutive elements e..e+3 of a row (e a multiple of 4): a float4 of a float32 row, 8 bytes of a
+// float16 row.  Float16 rows (WANN_DT = 3) keep the natural element order, padded with zeros to a multiple of 32 halves
+// (64 B); `stride` still counts 32-bit words, so element e of a row sits at half e of its first word.  ld_blk issues the load,
+// cvt_blk turns a block into the float32 values the float32 routines work on: every half is converted EXACTLY (v_cvt_f32_f16;
+// f16 denormals are preserved by the kernels' default FP mode), and the arithmetic that follows is the float32 path's own,
+// in its own order -- a float16 row scores to the bits of its float32 upcast.  Blocks held across a memory round trip stay
+// halves (half the registers of a float32 block); the conversion happens where the block is consumed.
+// (macros: the float32 and byte-row units compile exactly the expressions they compiled before the float16 unit existed)
+#if WANN_DT == 3
+typedef uint2 rowblk_t;
+__device__ __forceinline__ float h2f(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
+__device__ __forceinline__ float4 h4_to_f4(uint2 w) {
+  return make_float4(h2f(w.x & 0xffffu), h2f(w.x >> 16), h2f(w.y & 0xffffu), h2f(w.y >> 16));
+}
+#define ld_blk(prow, e) (*reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(prow) + (e)))
+#define cvt_blk(w) h4_to_f4(w)
+#else
+typedef float4 rowblk_t;
+// (no parentheses round `e`: `prow + 8 * b + 4 * h` is the address arithmetic the float32 unit has always compiled)
+#define ld_blk(prow, e) (*reinterpret_cast<const float4 *>(prow + e))
+#define cvt_blk(w) (w)
+#endif
+// 32-bit words of the staged (fp32, zero padded) query and of the LDS reserved for it: `stride` for float32 / byte rows; for
+// float16 rows the float32 row length, d rounded up to 16 -- every routine reads the query up to d rounded up to 8, and the
+// LDS layout of a float16 index equals the float32 index's (query_words in wann_device.h is the host side)
+__device__ __forceinline__ int qv_words(const IndexView &ix) { return WANN_DT == 3 ? ((ix.d + 15) & ~15) : ix.stride; }
+
+// --------------------------------------------------------------------------------------------
 // distances in the reference's evaluation order
 // --------------------------------------------------------------------------------------------
 // Squared L2 (NSGDist.h:33-69): 8 accumulators (the AVX lanes); a lane PAIR owns one candidate:
@@ -93,13 +128,13 @@ __device__ __forceinline__ float l2_pair(const float *__restrict__ prow, const f
   if (active) {
     const bool odd = D8 & 1;
     for (int i0 = 0; i0 < D8; i0 += NB) {
-      float4 buf[NB];
+      rowblk_t buf[NB];
 #pragma unroll
       for (int j = 0; j < NB; j++) {
         int i = i0 + j;
         if (i < D8) {
           int b = odd ? (i == 0 ? D8 - 1 : i - 1) : i;
-          buf[j] = *reinterpret_cast<const float4 *>(prow + 8 * b + 4 * h);
+          buf[j] = ld_blk(prow, 8 * b + 4 * h);
         }
       }
 #pragma unroll
@@ -109,10 +144,10 @@ __device__ __forceinline__ float l2_pair(const float *__restrict__ prow, const f
           int b = odd ? (i == 0 ? D8 - 1 : i - 1) : i;
           float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
           float t;
-          t = buf[j].x - q.x; a0 = fmaf(t, t, a0);
-          t = buf[j].y - q.y; a1 = fmaf(t, t, a1);
-          t = buf[j].z - q.z; a2 = fmaf(t, t, a2);
-          t = buf[j].w - q.w; a3 = fmaf(t, t, a3);
+          t = cvt_blk(buf[j]).x - q.x; a0 = fmaf(t, t, a0);
+          t = cvt_blk(buf[j]).y - q.y; a1 = fmaf(t, t, a1);
+          t = cvt_blk(buf[j]).z - q.z; a2 = fmaf(t, t, a2);
+          t = cvt_blk(buf[j]).w - q.w; a3 = fmaf(t, t, a3);
         }
       }
     }
@@ -142,17 +177,17 @@ __device__ __forceinline__ float l2_pair_ct(const float *__restrict__ prow, cons
   (void)active;
   constexpr bool odd = D8C & 1;
   f32x2 alo = {0.f, 0.f}, ahi = {0.f, 0.f};
-  float4 buf[D8C];
+  rowblk_t buf[D8C];
 #pragma unroll
   for (int i = 0; i < D8C; i++) {
     const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    buf[i] = *reinterpret_cast<const float4 *>(prow + 8 * b + 4 * h);
+    buf[i] = ld_blk(prow, 8 * b + 4 * h);
   }
 #pragma unroll
   for (int i = 0; i < D8C; i++) {
     const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
     const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
-    sq_acc(alo, ahi, buf[i], q);
+    sq_acc(alo, ahi, cvt_blk(buf[i]), q);
   }
   float s = ((alo.x + alo.y) + ahi.x) + ahi.y;
   float other = __shfl_xor(s, 1);
@@ -165,24 +200,24 @@ template <int D8C>
 __device__ __forceinline__ void l2_pair2_ct(const float *__restrict__ prow0, const float *__restrict__ prow1,
                                             const float *qv, int h, float &d0, float &d1) {
   constexpr bool odd = D8C & 1;
-  float4 b0[D8C], b1[D8C];
+  rowblk_t b0[D8C], b1[D8C];
 #pragma unroll
   for (int i = 0; i < D8C; i++) {
     const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    b0[i] = *reinterpret_cast<const float4 *>(prow0 + 8 * b + 4 * h);
+    b0[i] = ld_blk(prow0, 8 * b + 4 * h);
   }
 #pragma unroll
   for (int i = 0; i < D8C; i++) {
     const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    b1[i] = *reinterpret_cast<const float4 *>(prow1 + 8 * b + 4 * h);
+    b1[i] = ld_blk(prow1, 8 * b + 4 * h);
   }
   f32x2 alo = {0.f, 0.f}, ahi = {0.f, 0.f}, clo = {0.f, 0.f}, chi = {0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < D8C; i++) {
     const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
     const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
-    sq_acc(alo, ahi, b0[i], q);
-    sq_acc(clo, chi, b1[i], q);
+    sq_acc(alo, ahi, cvt_blk(b0[i]), q);
+    sq_acc(clo, chi, cvt_blk(b1[i]), q);
   }
   float s = ((alo.x + alo.y) + ahi.x) + ahi.y;
   float other = __shfl_xor(s, 1);
@@ -234,14 +269,14 @@ __device__ __forceinline__ float mips_step(float r, const float4 &p, const float
 template <int NP>
 __device__ __forceinline__ float mips_pair_ct(const float *__restrict__ prow, const float *qv, int d, int h) {
   const int tail_from = (d & ~7) >> 3;  // first fused step
-  float4 buf[NP];
+  rowblk_t buf[NP];
 #pragma unroll
-  for (int t = 0; t < NP; t++) buf[t] = *reinterpret_cast<const float4 *>(prow + 8 * t + 4 * h);
+  for (int t = 0; t < NP; t++) buf[t] = ld_blk(prow, 8 * t + 4 * h);
   float r = 0.f;
 #pragma unroll
   for (int t = 0; t < NP; t++) {
     const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
-    r = mips_step(r, buf[t], q, t >= tail_from);
+    r = mips_step(r, cvt_blk(buf[t]), q, t >= tail_from);
   }
   return -r;
 }
@@ -251,18 +286,18 @@ template <int NP>
 __device__ __forceinline__ void mips_pair2_ct(const float *__restrict__ prow0, const float *__restrict__ prow1,
                                               const float *qv, int d, int h, float &d0, float &d1) {
   const int tail_from = (d & ~7) >> 3;
-  float4 b0[NP], b1[NP];
+  rowblk_t b0[NP], b1[NP];
 #pragma unroll
-  for (int t = 0; t < NP; t++) b0[t] = *reinterpret_cast<const float4 *>(prow0 + 8 * t + 4 * h);
+  for (int t = 0; t < NP; t++) b0[t] = ld_blk(prow0, 8 * t + 4 * h);
 #pragma unroll
-  for (int t = 0; t < NP; t++) b1[t] = *reinterpret_cast<const float4 *>(prow1 + 8 * t + 4 * h);
+  for (int t = 0; t < NP; t++) b1[t] = ld_blk(prow1, 8 * t + 4 * h);
   float r0 = 0.f, r1 = 0.f;
 #pragma unroll
   for (int t = 0; t < NP; t++) {
     const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
     const bool tail = t >= tail_from;
-    r0 = mips_step(r0, b0[t], q, tail);
-    r1 = mips_step(r1, b1[t], q, tail);
+    r0 = mips_step(r0, cvt_blk(b0[t]), q, tail);
+    r1 = mips_step(r1, cvt_blk(b1[t]), q, tail);
   }
   d0 = -r0;
   d1 = -r1;
@@ -273,15 +308,15 @@ __device__ __forceinline__ float mips_pair(const float *__restrict__ prow, const
   const int np = (((d + 3) >> 2) + 1) >> 1, tail_from = (d & ~7) >> 3;
   float r = 0.f;
   for (int t0 = 0; t0 < np; t0 += 8) {
-    float4 buf[8];
+    rowblk_t buf[8];
 #pragma unroll
     for (int j = 0; j < 8; j++)
-      if (t0 + j < np) buf[j] = *reinterpret_cast<const float4 *>(prow + 8 * (t0 + j) + 4 * h);
+      if (t0 + j < np) buf[j] = ld_blk(prow, 8 * (t0 + j) + 4 * h);
 #pragma unroll
     for (int j = 0; j < 8; j++)
       if (t0 + j < np) {
         const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * (t0 + j) + 4 * h);
-        r = mips_step(r, buf[j], q, t0 + j >= tail_from);
+        r = mips_step(r, cvt_blk(buf[j]), q, t0 + j >= tail_from);
       }
   }
   return -r;
@@ -295,10 +330,7 @@ __device__ __forceinline__ float mips_pair(const float *__restrict__ prow, const
 // multiply-adds per instruction; squared L2 = sum a^2 + sum q^2 - 2 sum a q (each sum an exact integer).
 // Both lanes of the pair return the distance.
 // --------------------------------------------------------------------------------------------
-#ifndef WANN_DT
-#define WANN_DT 0  // 0 = float32 rows, 1 = uint8, 2 = int8
-#endif
-#if WANN_DT != 0
+#if WANN_BYTE_ROWS
 __device__ __forceinline__ int dot4_acc(uint32_t a, uint32_t b, int c) {
 #if WANN_DT == 1
   return (int)__builtin_amdgcn_udot4(a, b, (uint32_t)c, false);
@@ -354,9 +386,9 @@ __device__ __forceinline__ float pack_query_word(const float *q, int64_t base, i
 }
 #endif
 
-// staged query word i of `stride` (zero padded): a float for float32 rows, four packed elements for byte rows
+// staged query word i of qv_words(stride) (zero padded): a float for float32 / float16 rows, four packed elements for byte rows
 __device__ __forceinline__ float stage_query_word(const float *queries, int64_t qrow, int i, int d) {
-#if WANN_DT == 0
+#if !WANN_BYTE_ROWS
   return (i < d) ? queries[qrow * d + i] : 0.f;
 #else
   return pack_query_word(queries, qrow * d, i, d);
@@ -386,7 +418,7 @@ __device__ __forceinline__ float wave_distances(const IndexView &ix, const int32
                                                 float *scratch_lds, const float *qv, int cnt,
                                                 int64_t row_off) {
   const int lane = lane_id();
-#if WANN_DT != 0
+#if WANN_BYTE_ROWS
   {
     const int h = lane & 1;
     for (int base = 0; base < cnt; base += 32) {
@@ -709,7 +741,7 @@ struct WaveLds {
   int32_t *ltable;
 };
 
-__device__ __forceinline__ int wave_lds_common_bytes(int stride) {
+__device__ __forceinline__ int wave_lds_common_bytes(int stride) {  // stride: qv_words(ix)
   return ((stride * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4;
 }
 
@@ -1122,7 +1154,7 @@ __device__ __forceinline__ float wave_distances_own(const IndexView &ix, int a, 
     const int id = (base + s < nt) ? ev : 0;  // idle pairs score node 0: no branches
     const float *prow = ix.points + (row_off + id) * (int64_t)ix.stride;
     float dd;
-#if WANN_DT != 0
+#if WANN_BYTE_ROWS
     dd = byte_pair<METRIC>(prow, qv, ix.stride, h);
 #else
     if (LEAN) {
@@ -1790,18 +1822,18 @@ __device__ __forceinline__ void wave_beam_search_big(const IndexView &ix, const 
 // --------------------------------------------------------------------------------------------
 // (NR = the most blocks a lane holds: what the kernel's register budget affords -- 16 in the squared-L2 float kernel (two waves
 // per SIMD), fewer or none in the kernels built for three)
-#if WANN_DT != 0
+#if WANN_BYTE_ROWS
 constexpr int kRowRegs = 4;  // byte rows of up to 128 elements (8 cost the byte kernels, built for three waves per SIMD, a scratch segment)
 #else
 constexpr int kRowRegsL2 = 16, kRowRegsMips = 0;
 #endif
 template <int NR>
 struct RowRegs {
-  float4 v[NR > 0 ? NR : 1];
+  rowblk_t v[NR > 0 ? NR : 1];  // (float16 rows: the blocks stay halves until they are scored)
 };
 template <int METRIC>
 struct RowRegsFor {
-#if WANN_DT != 0
+#if WANN_BYTE_ROWS
   static constexpr int NR = kRowRegs;
 #else
   static constexpr int NR = METRIC == 1 ? kRowRegsMips : kRowRegsL2;
@@ -1814,7 +1846,7 @@ struct RowRegsFor {
 // hipcc merge the cases' loads into one block with an address register pair per load -- 270 registers.)
 template <int METRIC>
 __device__ __forceinline__ int row_regs_blocks(const IndexView &ix) {
-#if WANN_DT != 0
+#if WANN_BYTE_ROWS
   const int chunks = ix.stride >> 3;  // 16-byte chunks per lane
   return chunks <= RowRegsFor<METRIC>::NR ? chunks : 0;
 #else
@@ -1835,14 +1867,14 @@ template <int NR, int NBC = 0>
 __device__ __forceinline__ void row_regs_load(RowRegs<NR> &rr, const float *__restrict__ prow, int h, int nblk) {
 #pragma unroll
   for (int j = 0; j < NR; j++)
-    if (NBC > 0 ? j < NBC : j < nblk) rr.v[j] = *reinterpret_cast<const float4 *>(prow + 8 * j + 4 * h);
+    if (NBC > 0 ? j < NBC : j < nblk) rr.v[j] = ld_blk(prow, 8 * j + 4 * h);
 }
 
 template <int METRIC, int NR, int NBC = 0>
 __device__ __forceinline__ float row_regs_score(const RowRegs<NR> &rr, const float *qv, const IndexView &ix, int h, int nblk) {
   if (NR == 0) return 0.f;
   if (NBC > 0) nblk = NBC;
-#if WANN_DT != 0
+#if WANN_BYTE_ROWS
   int ab = 0, aa = 0, qq = 0;  // byte_pair's arithmetic (exact integer sums: any order)
 #pragma unroll
   for (int j = 0; j < NR; j++)
@@ -1875,7 +1907,7 @@ __device__ __forceinline__ float row_regs_score(const RowRegs<NR> &rr, const flo
     for (int t = 0; t < NR; t++)
       if (t < nblk) {
         const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
-        r = mips_step(r, rr.v[t], q, t >= tail_from);
+        r = mips_step(r, cvt_blk(rr.v[t]), q, t >= tail_from);
       }
     return -r;
   }
@@ -1884,14 +1916,14 @@ __device__ __forceinline__ float row_regs_score(const RowRegs<NR> &rr, const flo
   int nfull = nblk;
   if (NR > 12 && nblk == 13) {
     const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * 12 + 4 * h);
-    sq_acc(alo, ahi, rr.v[NR > 12 ? 12 : 0], q);
+    sq_acc(alo, ahi, cvt_blk(rr.v[NR > 12 ? 12 : 0]), q);
     nfull = 12;
   }
 #pragma unroll
   for (int i = 0; i < NR; i++)
     if (i < nfull) {
       const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * i + 4 * h);
-      sq_acc(alo, ahi, rr.v[i], q);
+      sq_acc(alo, ahi, cvt_blk(rr.v[i]), q);
     }
   const float s = ((alo.x + alo.y) + ahi.x) + ahi.y;
   const float other = __shfl_xor(s, 1);

@@ -56,6 +56,15 @@ static const BuildParams &default_build_params() {  // python_bindings.cpp:88
 }
 
 using FArray = py::array_t<float, py::array::c_style | py::array::forcecast>;
+
+// any array -> a C-contiguous array of the element type `dtype` (py::array_t<T>::ensure semantics; float16, which pybind11 has no
+// C++ type for, through numpy: astype rounds to nearest, ties to even)
+static py::array as_elem(int dtype, const py::handle &a) {
+  if (dtype == WANN_DTYPE_F16) return py::module_::import("numpy").attr("ascontiguousarray")(a, "dtype"_a = "float16");
+  if (dtype == WANN_DTYPE_F32) return FArray::ensure(a);
+  if (dtype == WANN_DTYPE_U8) return py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(a);
+  return py::array_t<int8_t, py::array::c_style | py::array::forcecast>::ensure(a);
+}
 using NeighborsAndDistances = std::pair<py::array_t<unsigned int>, py::array_t<float>>;
 
 class Index {
@@ -64,9 +73,7 @@ class Index {
         double shift, const BuildParams &bp)
       : kind_(kind), dtype_(dtype) {
     // py::array_t<T> semantics of the reference (python_bindings.cpp:113,121,...): any array is cast to T
-    py::array pts = dtype == WANN_DTYPE_F32 ? py::array(FArray::ensure(points))
-                  : dtype == WANN_DTYPE_U8 ? py::array(py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(points))
-                                           : py::array(py::array_t<int8_t, py::array::c_style | py::array::forcecast>::ensure(points));
+    py::array pts = as_elem(dtype, points);
     if (!pts) throw std::runtime_error("points must be convertible to an array of the index's element type");
     if (pts.ndim() != 2) throw std::runtime_error("points numpy array must be 2-dimensional");           // tree_utils.h:46
     if (labels.ndim() != 1) throw std::runtime_error("filter data numpy array must be 1-dimensional");    // tree_utils.h:53
@@ -100,9 +107,7 @@ class Index {
     if (!fr) throw std::runtime_error("filters must be a sequence of (lo, hi) pairs");
     if (fr.ndim() != 2 || fr.shape(1) != 2 || (uint64_t)fr.shape(0) < nq)
       throw std::runtime_error("filters must have shape (num_queries, 2)");
-    py::array queries = dtype_ == WANN_DTYPE_F32 ? py::array(FArray::ensure(queries_in))
-                      : dtype_ == WANN_DTYPE_U8 ? py::array(py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(queries_in))
-                                                : py::array(py::array_t<int8_t, py::array::c_style | py::array::forcecast>::ensure(queries_in));
+    py::array queries = as_elem(dtype_, queries_in);
     if (!queries) throw std::runtime_error("queries must be convertible to an array of the index's element type");
     if (queries.ndim() != 2 || (uint64_t)queries.shape(0) < nq || queries.shape(1) != wann_dim(h_))
       throw std::runtime_error("queries must have shape (num_queries, dimension)");
@@ -474,6 +479,9 @@ PYBIND11_MODULE(_window_ann, m) {
   add_variant<WANN_METRIC_MIPS, WANN_DTYPE_U8>(m, "UInt8Mips");
   add_variant<WANN_METRIC_L2, WANN_DTYPE_I8>(m, "Int8Euclidian");
   add_variant<WANN_METRIC_MIPS, WANN_DTYPE_I8>(m, "Int8Mips");
+  // not a type of the reference: float16 points (wann.h WANN_DTYPE_F16), rows of the float32 index on the upcast points
+  add_variant<WANN_METRIC_L2, WANN_DTYPE_F16>(m, "Float16Euclidian");
+  add_variant<WANN_METRIC_MIPS, WANN_DTYPE_F16>(m, "Float16Mips");
 
   // python_bindings.cpp:67-86: builder and index names of the unfiltered Vamana variants
   add_vamana<WANN_METRIC_L2, WANN_DTYPE_F32>(m, "float_euclidian", "VamanaFloatEuclidianIndex");
@@ -531,5 +539,30 @@ PYBIND11_MODULE(_window_ann, m) {
         return py::make_tuple(ids, dists, sizes, hops, cmps);
       },
       "metric"_a, "points"_a, "graph_rows"_a, "subset_start"_a, "queries"_a, "query_ids"_a, "beam"_a,
+      "limit"_a = 10000000, "degree_limit"_a = 10000, "device"_a = 0);
+  // raw_beam_search over points of any element type (dtype: 0 float32, 1 uint8, 2 int8, 3 float16); queries stay float32
+  m.def(
+      "raw_beam_search_typed",
+      [](int metric, int dtype, py::array points_in, py::array_t<int32_t, py::array::c_style | py::array::forcecast> graph_rows,
+         int64_t subset_start, FArray queries, py::array_t<int64_t, py::array::c_style | py::array::forcecast> query_ids,
+         int64_t beam, int64_t limit, int64_t degree_limit, int device) {
+        if (dtype < WANN_DTYPE_F32 || dtype > WANN_DTYPE_F16) throw std::runtime_error("unknown dtype");
+        py::array points = as_elem(dtype, points_in);
+        if (points.ndim() != 2 || graph_rows.ndim() != 2 || queries.ndim() != 2) throw std::runtime_error("bad shapes");
+        int64_t n = points.shape(0), d = points.shape(1), sn = graph_rows.shape(0), md = graph_rows.shape(1) - 1;
+        int64_t nq = queries.shape(0);
+        if (queries.shape(1) != d) throw std::runtime_error("queries must have the points' dimension");
+        py::array_t<int32_t> ids({(size_t)nq, (size_t)beam});
+        py::array_t<float> dists({(size_t)nq, (size_t)beam});
+        py::array_t<int32_t> sizes((size_t)nq);
+        py::array_t<int64_t> hops((size_t)nq), cmps((size_t)nq);
+        int rc = wann_raw_beam_search_typed(metric, dtype, points.data(), n, d, graph_rows.data(), md, subset_start, sn,
+                                            queries.data(), nq, query_ids.data(), beam, limit, degree_limit,
+                                            ids.mutable_data(), dists.mutable_data(), sizes.mutable_data(),
+                                            hops.mutable_data(), cmps.mutable_data(), device);
+        if (rc) raise_last("raw_beam_search_typed failed");
+        return py::make_tuple(ids, dists, sizes, hops, cmps);
+      },
+      "metric"_a, "dtype"_a, "points"_a, "graph_rows"_a, "subset_start"_a, "queries"_a, "query_ids"_a, "beam"_a,
       "limit"_a = 10000000, "degree_limit"_a = 10000, "device"_a = 0);
 }

@@ -59,31 +59,36 @@ def _module():
 # wrapper.py counterparts
 # ----------------------------------------------------------------------------------------------------------
 _DTYPES = {"float": "Float", "uint8": "Uint8", "int8": "Int8"}
+# "float16" is not a type of the reference (wrapper.py raises "Invalid data type" for it, and so do these constructors by
+# default): float16 points, rows of the float32 index on the upcast points (include/wann.h WANN_DTYPE_F16).  The --dtype float16
+# experiments ask for it with float16=True.
+_FLOAT16 = {"float16": "Float16"}
 _METRICS = {"Euclidian": "Euclidian", "mips": "Mips"}
 
 
-def _constructor(prefix: str, metric: str, dtype: str):
+def _constructor(prefix: str, metric: str, dtype: str, float16: bool = False):
     if metric not in _METRICS:
         raise Exception("Invalid metric " + metric)
-    if dtype not in _DTYPES:
+    types = {**_DTYPES, **_FLOAT16} if float16 else _DTYPES
+    if dtype not in types:
         raise Exception("Invalid data type " + dtype)
-    return getattr(_module(), prefix + _DTYPES[dtype] + _METRICS[metric])
+    return getattr(_module(), prefix + types[dtype] + _METRICS[metric])
 
 
-def prefilter_index_constructor(metric, dtype):
-    return _constructor("PrefilterIndex", metric, dtype)
+def prefilter_index_constructor(metric, dtype, float16=False):
+    return _constructor("PrefilterIndex", metric, dtype, float16)
 
 
-def postfilter_vamana_constructor(metric, dtype):
-    return _constructor("PostfilterVamanaIndex", metric, dtype)
+def postfilter_vamana_constructor(metric, dtype, float16=False):
+    return _constructor("PostfilterVamanaIndex", metric, dtype, float16)
 
 
-def vamana_range_filter_tree_constructor(metric, dtype):
-    return _constructor("VamanaRangeFilterTreeIndex", metric, dtype)
+def vamana_range_filter_tree_constructor(metric, dtype, float16=False):
+    return _constructor("VamanaRangeFilterTreeIndex", metric, dtype, float16)
 
 
-def super_optimized_postfilter_tree_constructor(metric, dtype):
-    return _constructor("SuperOptimizedPostfilterTreeIndex", metric, dtype)
+def super_optimized_postfilter_tree_constructor(metric, dtype, float16=False):
+    return _constructor("SuperOptimizedPostfilterTreeIndex", metric, dtype, float16)
 
 
 def build_query_params(k, beam_size, cut=1.35, limit=10_000_000, degree_limit=10_000, final_beam_multiply=1,
@@ -214,6 +219,10 @@ class Settings:
     write_results: bool = True
     threads: int = os.cpu_count() or 1
     methods: Tuple[str, ...] = ()  # subset of: prefiltering postfiltering vamana_tree optimized_postfiltering smart_combined three_split super_opt_postfiltering
+    # "float16": points and queries rounded to float16 (numpy astype: nearest, ties to even) and searched by the Float16 classes;
+    # recall is still taken against the dataset's stored ground truth of the original data.  Graph caches go to a subdirectory
+    # of their own: a float16 index's graphs are those of the ROUNDED points, under the same file names as the float32 graphs.
+    dtype: str = "float"
 
 
 class Experiments:
@@ -226,11 +235,14 @@ class Experiments:
     # -- helpers
     def _dataset(self, name):
         if name not in self._dataset_cache:
-            self._dataset_cache = {name: initialize_dataset(self.s.dataset_folder, name)}
+            data, queries, filter_values, metric = initialize_dataset(self.s.dataset_folder, name)
+            if self.s.dtype == "float16":
+                data, queries = data.astype(np.float16), queries.astype(np.float16)
+            self._dataset_cache = {name: (data, queries, filter_values, metric)}
         return self._dataset_cache[name]
 
     def _cache(self, sub):
-        path = os.path.join(self.s.cache_root, sub)
+        path = os.path.join(self.s.cache_root, *(["float16"] if self.s.dtype == "float16" else []), sub)
         os.makedirs(path if path.endswith("/") else os.path.dirname(path), exist_ok=True)
         return path
 
@@ -254,7 +266,7 @@ class Experiments:
     def run_prefiltering_experiment(self, all_results, dataset_name, filter_width):
         data, queries, filter_values, metric = self._dataset(dataset_name)
         t0 = time.time()
-        index = prefilter_index_constructor(metric, "float")(data, filter_values)
+        index = prefilter_index_constructor(metric, self.s.dtype, float16=True)(data, filter_values)
         print(f"Prefiltering index build time: {time.time() - t0:.3f}s", flush=True)
         ranges, gt = get_queries_and_gt(self.s.dataset_folder, dataset_name, filter_width)
         qp = build_query_params(k=TOP_K, beam_size=0, verbose=self.s.verbose)
@@ -264,7 +276,7 @@ class Experiments:
         data, queries, filter_values, metric = self._dataset(dataset_name)
         bp = BuildParams(64, 500, alpha, self._cache(f"{dataset_name}/unsorted-"))
         t0 = time.time()
-        index = postfilter_vamana_constructor(metric, "float")(data, filter_values, build_params=bp)
+        index = postfilter_vamana_constructor(metric, self.s.dtype, float16=True)(data, filter_values, build_params=bp)
         print(f"Naive postfilter build time: {time.time() - t0:.3f}s", flush=True)
         ranges, gt = get_queries_and_gt(self.s.dataset_folder, dataset_name, filter_width)
         self._sweep(all_results, filter_width, lambda b, m: f"postfiltering_{alpha}_{b}_{m}",
@@ -278,7 +290,7 @@ class Experiments:
         gc.disable()
         rss0 = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss
         t0 = time.time()
-        tree = vamana_range_filter_tree_constructor(metric, "float")(
+        tree = vamana_range_filter_tree_constructor(metric, self.s.dtype, float16=True)(
             data, filter_values, cutoff=1_000, split_factor=split_factor,
             build_params=BuildParams(64, 500, alpha, self._cache(f"{dataset_name}/")))
         build_time = time.time() - t0
@@ -310,7 +322,7 @@ class Experiments:
         t0 = time.time()
         gc.disable()
         rss0 = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss
-        tree = super_optimized_postfilter_tree_constructor(metric, "float")(
+        tree = super_optimized_postfilter_tree_constructor(metric, self.s.dtype, float16=True)(
             data, filter_values, cutoff=1_000, split_factor=split_factor, shift_factor=shift_factor,
             build_params=BuildParams(64, 500, alpha, self._cache(f"{dataset_name}-super_opt_postfiltering/")))
         memory = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss - rss0
@@ -326,7 +338,8 @@ class Experiments:
         if not self.s.write_results:
             return None
         os.makedirs(self.s.results_dir, exist_ok=True)
-        path = os.path.join(self.s.results_dir, f"{self.s.results_file_prefix}{dataset_name}_results.csv")
+        half = "float16_" if self.s.dtype == "float16" else ""
+        path = os.path.join(self.s.results_dir, f"{self.s.results_file_prefix}{half}{dataset_name}_results.csv")
         if not os.path.exists(path):
             with open(path, "a") as f:
                 f.write(RESULTS_HEADER)
@@ -382,16 +395,21 @@ def natural_size(nbytes: int) -> str:
     return "%.1f PB" % v
 
 
-def build_for_memory(index_type, data, filter_values, metric, dataset_name, alpha=1.0, split_factor=2, cache_root="index_cache"):
+def build_for_memory(index_type, data, filter_values, metric, dataset_name, alpha=1.0, split_factor=2, cache_root="index_cache",
+                     dtype="float"):
     """Construct the index exactly as all_memories.py:25-83 does and return (index, bytes).  The reference reports the
     growth of the process RSS (its index lives in host memory); this engine's index lives in HBM, so the figure is the
-    device footprint (`index.device_bytes()`: vectors + labels + decoding + adjacency pool + partition tables)."""
+    device footprint (`index.device_bytes()`: vectors + labels + decoding + adjacency pool + partition tables).
+    dtype "float16": the points are rounded to float16 and the Float16 class is built, its graphs in <cache_root>/float16/."""
+    half = dtype == "float16"
+    if half:
+        data, cache_root = np.asarray(data).astype(np.float16), os.path.join(cache_root, "float16")
     if index_type == "postfiltering":
-        cons, kw, sub = postfilter_vamana_constructor(metric, "float"), {}, f"{dataset_name}/unsorted-"
+        cons, kw, sub = (postfilter_vamana_constructor(metric, dtype, float16=True) if half else postfilter_vamana_constructor(metric, "float")), {}, f"{dataset_name}/unsorted-"
     elif index_type == "vamana-tree":
-        cons, kw, sub = vamana_range_filter_tree_constructor(metric, "float"), dict(cutoff=1_000, split_factor=split_factor), f"{dataset_name}/"
+        cons, kw, sub = (vamana_range_filter_tree_constructor(metric, dtype, float16=True) if half else vamana_range_filter_tree_constructor(metric, "float")), dict(cutoff=1_000, split_factor=split_factor), f"{dataset_name}/"
     elif index_type == "super-postfiltering":
-        cons, kw, sub = super_optimized_postfilter_tree_constructor(metric, "float"), dict(cutoff=1_000, split_factor=split_factor, shift_factor=0.5), f"{dataset_name}-super_opt_postfiltering/"
+        cons, kw, sub = (super_optimized_postfilter_tree_constructor(metric, dtype, float16=True) if half else super_optimized_postfilter_tree_constructor(metric, "float")), dict(cutoff=1_000, split_factor=split_factor, shift_factor=0.5), f"{dataset_name}-super_opt_postfiltering/"
     else:
         raise ValueError("Invalid index type")  # all_memories.py:119-120
     path = os.path.join(cache_root, sub)
@@ -418,11 +436,12 @@ def memory_main(args):
     data, _, filter_values, metric = initialize_dataset(args.dataset_folder, args.dataset)
     if args.index_type:  # all_memories.py: method, dataset, humanised size
         label = {"postfiltering": "postfiltering", "vamana-tree": "vamana-tree", "super-postfiltering": "super postfiltering"}
-        _, nbytes = build_for_memory(args.index_type, data, filter_values, metric, args.dataset, 1.0, 2)
+        _, nbytes = build_for_memory(args.index_type, data, filter_values, metric, args.dataset, 1.0, 2, dtype=args.dtype)
         print(write_memory_csv("results", "memory_usage.csv", ["method", "dataset", "memory"], [label[args.index_type], args.dataset, natural_size(nbytes)]))
     else:  # memory_footprint.py: method, branching factor, KiB (ru_maxrss units)
         b = args.vamana_tree_split_factor
-        _, nbytes = build_for_memory("vamana-tree", data, filter_values, metric, args.dataset, args.alpha if args.alpha is not None else 1.0, b)
+        _, nbytes = build_for_memory("vamana-tree", data, filter_values, metric, args.dataset, args.alpha if args.alpha is not None else 1.0, b,
+                                     dtype=args.dtype)
         print(write_memory_csv("results", "vamana_tree_memory_usage.csv", ["method", "branching_factor", "memory"], ["vamana-tree", b, nbytes // 1024]))
     return 0
 
@@ -456,6 +475,9 @@ def main(argv=None):
                          "super-postfiltering} as experiments/all_memories.py, else with --vamana_tree_split_factor as "
                          "experiments/memory_footprint.py")
     ap.add_argument("--index_type", type=str, default=None)
+    ap.add_argument("--dtype", choices=("float", "float16"), default="float",
+                    help="float16: round points and queries to float16 and search the Float16 index classes (own graph cache "
+                         "subdirectory and results prefix; recall against the original data's ground truth)")
     args = ap.parse_args(argv)
     threads = args.threads or (os.cpu_count() or 1)
     os.environ["PARLAY_NUM_THREADS"] = str(threads)
@@ -480,7 +502,8 @@ def main(argv=None):
     settings = Settings(dataset_folder=args.dataset_folder, results_file_prefix=args.results_file_prefix,
                         beam_sizes=[args.beam_search_size] if args.beam_search_size else list(BEAM_SIZES),
                         final_multiplies=[args.num_final_multiplies] if args.num_final_multiplies else list(FINAL_MULTIPLIES),
-                        verbose=args.verbose, write_results=not args.dont_write_to_results_file, threads=threads, methods=methods)
+                        verbose=args.verbose, write_results=not args.dont_write_to_results_file, threads=threads, methods=methods,
+                        dtype=args.dtype)
     Experiments(settings).run(
         datasets, widths,
         alphas=[args.alpha] if args.alpha is not None else ALPHAS,
