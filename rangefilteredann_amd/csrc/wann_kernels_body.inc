@@ -1312,6 +1312,9 @@ __global__ void k_route(RouteArgs A) {
     t.hi = hi;
     prefilter_bounds(ix.fv_sorted, ix.n, lo, hi, t.a, t.b);
     t.mode = (t.b > t.a) ? T_BRUTE_GATHER : T_EMPTY;
+    // (an empty window emits no task, but the dense path's k_group_insert reads EVERY query's task slot: it must say T_EMPTY,
+    // not hold an earlier batch's window -- that one would be scanned again, or even join a group)
+    if (t.mode == T_EMPTY) A.tasks[q * A.maxt] = t;
     E.push(t);
   } else if (KIND == 1) {  // stand-alone PostfilterVamanaIndex: always the one graph, no window lookup
     Task t;

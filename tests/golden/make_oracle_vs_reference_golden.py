@@ -38,6 +38,13 @@ for metric, gen, d in tv.RATIO_CASES:
     cache = tempfile.mkdtemp() + "/"
     rows = tv.ratio_rows(ref, cache, metric, gen, d)
     out[tv.ratio_key(metric, gen, d)] = {"graphs": tv.file_digests(cache), "rows": rows_digests(rows)}
+for kind, sfx, labs in tv.TIE_CASES:
+    cache = tempfile.mkdtemp() + "/"
+    X, labels, Q, rows = tv.ties_rows(ref, cache, kind, sfx, labs)
+    out[tv.ties_key(kind, sfx, labs)] = {
+        "graphs": tv.file_digests(cache),
+        "rows": {case: tv.row_digests(*tv.canonical_rows(kind, ids, dists, labels, W, method))
+                 for case, (ids, dists, W, method) in rows.items()}}
 for case in tv.BUILDER_CASES:
     out[tv.builder_key(*case)] = tv.builder_files(ref, os.path.join(tempfile.mkdtemp(), "g") + "/", *case)
 # the reference-legs test: the oracle writes the graphs (standing in for the GPU build), the reference answers on them

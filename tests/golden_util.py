@@ -72,17 +72,42 @@ def cases(data, kind):
 
 class RowContext:
     """What a tie-aware comparison needs to VERIFY an id that the expectation does not list: the inputs of the batch.
-    metric: "l2" or "mips"; ids are original point numbers (rows of X)."""
+    metric: "l2" or "mips"; ids are original point numbers (rows of X).
+    window: which points the reference's exact scan can return for a window [lo, hi] (window_rule()):
+      "inclusive"  lo <= label <= hi;
+      "half_open"  sorted positions [lower_bound(lo), lower_bound(hi)): lo <= label < hi (fenwick_tree_search's brute ranges and
+                   leaves, src/range_filter_tree.h:297-401: exclusive_end = first_greater_than_or_equal_to(hi));
+      "prefilter"  PrefilterIndex (prefiltering.h:159-184): half_open with both ends clipped to n - 1, so the last point of the
+                   stable (label, id) order is never returned either;
+      "candidates" what candidates(row) returns: the ids the oracle's scan considers for that row (RangeFilterTreeIndex, whose
+                   leaves are PrefilterIndex slices that each drop their own last point -- which leaves a query uses follows
+                   from its cover, so the oracle itself, asked for every candidate, is the exact rule)."""
 
-    def __init__(self, X, labels, Q, W, metric):
+    def __init__(self, X, labels, Q, W, metric, window="inclusive", candidates=None):
         self.X, self.labels, self.Q, self.W, self.metric = X, np.asarray(labels, dtype=np.float32), Q, np.asarray(W), metric
+        if window not in ("inclusive", "half_open", "prefilter", "candidates"):
+            raise ValueError(window)
+        if (window == "candidates") != (candidates is not None):
+            raise ValueError("the 'candidates' window rule needs (only) a candidates(row) callable")
+        self.window, self.candidates, self._cand = window, candidates, {}
+        self.last = int(np.argsort(self.labels, kind="stable")[-1]) if window == "prefilter" else -1
+
+    def in_window(self, row, pid):
+        lo, hi = np.float32(self.W[row][0]), np.float32(self.W[row][1])
+        lab = self.labels[pid]
+        if self.window == "inclusive":
+            return bool(lo <= lab <= hi)
+        if self.window == "candidates":
+            if row not in self._cand:
+                self._cand[row] = set(int(x) for x in self.candidates(row))
+            return pid in self._cand[row]
+        return bool(lo <= lab < hi) and pid != self.last
 
     def plausible(self, row, pid, dist):
-        """pid lies in the row's label window and its (float64) distance to the query is `dist` up to fp32 rounding"""
+        """pid lies in the row's window and its (float64) distance to the query is `dist` up to fp32 rounding"""
         if pid < 0 or pid >= len(self.labels):
             return False
-        lo, hi = np.float32(self.W[row][0]), np.float32(self.W[row][1])
-        if not (lo <= self.labels[pid] <= hi):
+        if not self.in_window(row, pid):
             return False
         x, q = self.X[pid].astype(np.float64), self.Q[row].astype(np.float64)
         d64 = -float(x @ q) if self.metric == "mips" else float(((x - q) ** 2).sum())
@@ -93,9 +118,50 @@ def metric_of(class_suffix):
     return "mips" if class_suffix.endswith("Mips") else "l2"
 
 
+def window_rule(kind, method=None):
+    """RowContext.window for the rows of `kind` / `method` that the reference answers with an exact scan (see exact_rows);
+    "candidates" needs a callable that lists them (oracle_candidates)"""
+    if kind == "PrefilterIndex":
+        return "prefilter"
+    if kind == "RangeFilterTreeIndex":
+        return "candidates"
+    if kind == "VamanaRangeFilterTreeIndex" and method == "three_split":
+        # (the side searches are optimized_postfiltering_search calls on [lo, label of the cover's start] and [label of the cover's
+        # end, hi]: their graph leaves post-filter inclusively, src/postfilter_vamana.h:234-251)
+        return "inclusive"
+    return "half_open"
+
+
+def exact_rows(kind, method, labels, W, cutoff=None):
+    """Per query: True where the reference answers with an exact scan or a merged list, whose unstable sort-by-distance may order
+    equal distances either way (tie-aware comparison); False where it returns one beam search's rows (bit-exact).  From the
+    routing rules: PrefilterIndex and RangeFilterTreeIndex scan; fenwick and three_split merge; optimized_postfiltering_search
+    takes fenwick_tree_search when 4 * (lower_bound(hi) - lower_bound(lo)) < cutoff (src/range_filter_tree.h:403-416); empty
+    windows are padding either way."""
+    nq = len(W)
+    if kind in TIE_AWARE_KINDS or method in ("fenwick", "three_split"):
+        return np.ones(nq, dtype=bool)
+    if kind != "VamanaRangeFilterTreeIndex":
+        return np.zeros(nq, dtype=bool)
+    s = np.sort(np.asarray(labels, dtype=np.float32))
+    lo, hi = np.asarray(W, dtype=np.float64).astype(np.float32).T
+    w = np.searchsorted(s, hi, "left").astype(np.int64) - np.searchsorted(s, lo, "left")
+    return (w >= 0) & (4 * w < int(cutoff))
+
+
+def oracle_candidates(oracle_index, Q, W, method, qp_of_k):
+    """candidates(row) for RowContext: every id the oracle index returns for that one query when asked for all n of them
+    (qp_of_k(k) -> the batch's QueryParams with k replaced); the padding of shorter lists is left out"""
+    def cands(row):
+        a = (Q[row:row + 1], np.asarray(W)[row:row + 1], 1) + ((method,) if method else ())
+        ids, dists = oracle_index.batch_search(*a, qp_of_k(oracle_index.n))
+        return ids[0][dists[0] != np.finfo(np.float32).max]
+    return cands
+
+
 def same_rows(exp_ids, exp_d, got_ids, got_d, tie_aware, ctx=None):
-    """Row-wise equality; tie_aware: distances equal exactly and ids equal as multisets inside each run of equal
-    distances.  A run cut by the k boundary may be the prefix of a larger tie group of which the expectation shows
+    """Row-wise equality; tie_aware (one flag for the batch or one per row): distances equal exactly and ids equal as multisets
+    inside each run of equal distances.  A run cut by the k boundary may be the prefix of a larger tie group of which the expectation shows
     only a part: there every returned id must be one the expectation lists or -- checked from the batch's inputs
     (ctx, required) -- a point inside the query's window at exactly that distance, and no id may repeat more often
     than the expectation repeats ids in that run."""
@@ -106,8 +172,10 @@ def same_rows(exp_ids, exp_d, got_ids, got_d, tie_aware, ctx=None):
         return False, f"dist mismatch at {tuple(bad)}: {exp_d[tuple(bad)]!r} vs {got_d[tuple(bad)]!r}"
     if np.array_equal(exp_ids, got_ids):
         return True, ""
-    if not tie_aware:
-        bad = np.argwhere(exp_ids != got_ids)[0]
+    tie_rows = np.broadcast_to(np.asarray(tie_aware, dtype=bool), (exp_ids.shape[0],))
+    strict = np.argwhere((exp_ids != got_ids) & ~tie_rows[:, None])
+    if len(strict):
+        bad = strict[0]
         return False, f"id mismatch at {tuple(bad)}: {exp_ids[bad[0]]} vs {got_ids[bad[0]]}"
     if ctx is None:
         raise ValueError("tie-aware comparison needs the batch inputs (RowContext) to verify ids at the k boundary")

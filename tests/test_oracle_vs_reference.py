@@ -9,7 +9,8 @@ import os
 import numpy as np
 import pytest
 
-from util import REPO, distinct_labels, quiet_stdout, sift_like, unit_mixture, windows
+import golden_util as gu
+from util import REPO, distinct_labels, quiet_stdout, repeated_labels, sift_like, tie_heavy, tie_queries, tie_windows, unit_mixture, windows
 
 GOLDEN = os.path.join(REPO, "tests", "golden", "oracle_vs_reference.json")
 
@@ -178,3 +179,117 @@ def test_oracle_builder_equals_reference_builder(oracle, ref, golden, tmp_path, 
     assert sorted(got) == sorted(want) and len(got) > 3
     differing = [f for f in want if got[f] != want[f]]
     assert not differing, differing
+
+
+# ------------------------------------------------------------------------------------------
+# tie-heavy rows: d = 6 small integers, 15 % duplicated rows -- most distances are shared by many points
+# ------------------------------------------------------------------------------------------
+FLT_MAX = np.finfo(np.float32).max
+TIE_CASES = [(kind, sfx, "distinct") for sfx in ("FloatEuclidian", "UInt8Euclidian") for kind in KINDS] + \
+            [("PrefilterIndex", sfx, "repeated") for sfx in ("FloatEuclidian", "UInt8Euclidian")]
+
+
+def ties_key(kind, sfx, labs):
+    return f"ties|{kind}|{sfx}|{labs}"
+
+
+def ties_rows(mod, cache, kind, sfx, labs):
+    """`mod`'s index of the case, built on the graph files under `cache` (written there when absent), and its rows with the
+    inputs they came from: {case: (ids, dists, W, method)}"""
+    n, nq = 2500, 60
+    d = 8 if sfx.startswith("Float") else 6  # (float32 L2: d % 8 == 0, the reference reads past d otherwise, SURVEY 8 a11)
+    X = tie_heavy(n, d, 17)
+    Q = tie_queries(X, nq, 18)
+    labels = distinct_labels(n, 12) if labs == "distinct" else repeated_labels(n, 12, 40)
+    kw = dict(cutoff=250, split_factor=2) if "Tree" in kind else {}
+    if kind.startswith("Super"):
+        kw["shift_factor"] = 0.5
+    labkw = "filters" if kind == "PostfilterVamanaIndex" else "filter_values"
+    with quiet_stdout():
+        idx = getattr(mod, kind + sfx)(X, **{labkw: labels}, build_params=mod.BuildParams(24, 48, 1.0, cache), **kw)
+    methods = ["optimized_postfilter", "fenwick", "three_split"] if kind.endswith("RangeFilterTreeIndex") else [None]
+    rows = {}
+    for p in (-7, -5, -3, -1):
+        W = tie_windows(labels, nq, p, 20 + p)
+        for method in methods:
+            for beam, mult in [(10, 1), (40, 2)]:
+                a = (Q, W, nq) + ((method,) if method else ())
+                with quiet_stdout():
+                    ids, dists = idx.batch_search(*a, mod.QueryParams(10, beam, 1.35, 10**7, 10**4, mult, 10000, None, False))
+                rows[f"{p}|{method}|{beam}|{mult}"] = (ids, dists, W, method)
+    return X, labels, Q, rows
+
+
+def prefilter_counts(labels, W, k):
+    """rows a PrefilterIndex returns per window: positions [lower_bound(lo), lower_bound(hi)), both clipped to n - 1
+    (prefiltering.h:159-184); the reference reads past the end of shorter lists, so only these entries are defined"""
+    s = np.sort(np.asarray(labels, dtype=np.float32))
+    lo, hi = np.asarray(W, dtype=np.float64).astype(np.float32).T
+    a = np.minimum(np.searchsorted(s, lo, "left"), len(s) - 1)
+    b = np.minimum(np.searchsorted(s, hi, "left"), len(s) - 1)
+    return np.clip(b.astype(np.int64) - a, 0, k)
+
+
+def canonical_rows(kind, ids, dists, labels, W, method):
+    """The rows with what the reference leaves open replaced by what it does not: undefined padding -> (-1, FLT_MAX); in rows
+    answered by an exact scan or a merged list (gu.exact_rows: an unstable sort-by-distance) the ids of each run of equal
+    distances sorted, and those of a run that reaches the k boundary -- part of a larger tie group -- replaced by -2."""
+    ids, dists = np.asarray(ids).astype(np.int64), np.array(dists, dtype=np.float32)
+    k = ids.shape[1]
+    if kind == "PrefilterIndex":
+        cnt = prefilter_counts(labels, W, k)
+        pad = np.arange(k)[None, :] >= cnt[:, None]
+        ids[pad], dists[pad] = -1, FLT_MAX
+    for r in np.flatnonzero(gu.exact_rows(kind, method, labels, W, 250)):
+        j = 0
+        while j < k:
+            e = j
+            while e + 1 < k and dists[r, e + 1] == dists[r, j]:
+                e += 1
+            ids[r, j:e + 1] = -2 if (e == k - 1 and dists[r, j] != FLT_MAX) else np.sort(ids[r, j:e + 1])
+            j = e + 1
+    return ids, dists
+
+
+@pytest.mark.parametrize("kind,sfx,labs", TIE_CASES)
+def test_oracle_equals_reference_on_tie_heavy_rows(oracle, ref, golden, tmp_path, kind, sfx, labs):
+    """Small integer rows (d = 8 float32, d = 6 uint8, values 0..11), with distinct labels for every kind: both builders break distance ties the same
+    way, so the graph files are byte-equal and the rows of a single beam search exact; rows that the reference answers with an
+    exact scan or a merged list are equal up to the order of equal distances.  Repeated labels (40 values, runs of about 60
+    points) for PrefilterIndex only: which points a window selects does not depend on how the reference's unstable
+    parlay::sort_inplace orders equal labels, its rows up to ties do not either.  The tree kinds cannot be held to the reference
+    on repeated labels -- its unstable label sort (tree_utils.h:68-73) changes which points each partition holds -- the GPU
+    tests (tests/test_gpu_ties.py) check them against the oracle, which sorts stably by (label, id) as the product does."""
+    co = str(tmp_path / "orc") + "/"
+    os.makedirs(co)
+    X, labels, Q, got = ties_rows(oracle, co, kind, sfx, labs)
+    g = golden.get(ties_key(kind, sfx, labs)) if ref is not None else golden[ties_key(kind, sfx, labs)]
+    if ref is not None:  # both build their own graphs: byte for byte the same files
+        cr = str(tmp_path / "ref") + "/"
+        os.makedirs(cr)
+        want = ties_rows(ref, cr, kind, sfx, labs)[3]
+        assert file_digests(co) == file_digests(cr)
+    else:
+        assert file_digests(co) == g["graphs"]
+    metric = gu.metric_of(sfx)
+    if kind == "RangeFilterTreeIndex":  # (the exact window rule of this kind: the oracle's own candidates, gu.window_rule)
+        with quiet_stdout():
+            cand_index = getattr(oracle, kind + sfx)(X, filter_values=labels, cutoff=250, split_factor=2,
+                                                     build_params=oracle.BuildParams(24, 48, 1.0, co))
+    for case, (oi, od, W, method) in got.items():
+        ci, cd = canonical_rows(kind, oi, od, labels, W, method)
+        if ref is not None:
+            ri, rd, _, _ = want[case]
+            cri, crd = canonical_rows(kind, ri, rd, labels, W, method)
+            assert np.array_equal(crd, cd) and np.array_equal(cri, ci), (kind, case)
+            rule = gu.window_rule(kind, method)
+            beam, mult = (int(x) for x in case.split("|")[2:])
+            cands = None
+            if rule == "candidates":
+                cands = gu.oracle_candidates(cand_index, Q, W, method,
+                                             lambda k: oracle.QueryParams(k, beam, 1.35, 10**7, 10**4, mult, 10000, None, False))
+            ctx = gu.RowContext(X, labels, Q, W, metric, rule, cands)
+            ok, why = gu.same_rows(np.where(cri == -1, oi, ri), crd, oi, cd, gu.exact_rows(kind, method, labels, W, 250), ctx)
+            assert ok, (kind, case, why)
+        else:
+            assert row_digests(ci, cd) == g["rows"][case], (kind, case)

@@ -2,8 +2,9 @@
 flip the engine's development switches between batches on one index, wann_tuning.h), so every other GPU test runs an engine that
 re-reads its switches before each call.  The shipped configuration -- no hooks, the switches fixed at index creation, development
 switches ignored -- is what a user of the reference runs: a child pytest process with WANN_TEST_HOOKS=0 replays the golden vectors
-of the real reference, the index-level oracle comparisons and the C-ABI end-to-end test, and one full-size configuration
-(configs[1], SIFT-1M-like, rows against the real reference, mid-fraction legs repeated five times)."""
+of the real reference, the index-level oracle comparisons (tie-heavy rows and repeated labels included) and the C-ABI end-to-end
+test, and one full-size configuration (configs[1], SIFT-1M-like, rows against the real reference, mid-fraction legs repeated five
+times)."""
 import os
 import subprocess
 import sys
@@ -30,10 +31,10 @@ def _child(args, timeout):
 
 
 def test_golden_and_oracle_parity_without_test_hooks(gpu):
-    out = _child(["tests/test_gpu_parity.py", "-k",
+    out = _child(["tests/test_gpu_parity.py", "tests/test_gpu_ties.py", "-k",
                   "golden_reference_outputs or golden_ratio_fallback or golden_quirks or index_matches_oracle or edge_cases or tiny_shapes "
                   "or c_abi_end_to_end or fenwick_and_three_split or device_resident_call or asynchronous_calls or raw_beam_search_matches_oracle "
-                  "or (tie_heavy_data and default)"], 1500)
+                  "or (tie_heavy_data and default) or index_ties_and_repeated_labels"], 1500)
     assert "skipped" not in out.splitlines()[-1], out[-400:]
 
 

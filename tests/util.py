@@ -104,3 +104,56 @@ def recall(gt, ids, k=10):
         tot += len(set(g.tolist()) & set(r[:k].tolist())) / len(g)
         cnt += 1
     return tot / max(cnt, 1)
+
+
+def tie_heavy(n, d, seed, lo=0, hi=12, dup_frac=0.15, zero_rows=0):
+    """Rows of small integers in [lo, hi) as float32 (exact in fp32, bf16, uint8 / int8): nearly every distance is shared by many
+    points.  A dup_frac share of the rows copies other rows, and a block of zero_rows rows in the middle is all zero."""
+    rng = np.random.default_rng(seed)
+    X = rng.integers(lo, hi, size=(n, d)).astype(np.float32)
+    ndup = int(n * dup_frac)
+    X[rng.choice(n, ndup, replace=False)] = X[rng.choice(n, ndup)]
+    if zero_rows:
+        at = (n - zero_rows) // 2
+        X[at:at + zero_rows] = 0
+    return X
+
+
+def tie_queries(X, nq, seed, lo=0, hi=12):
+    """Queries over the same small integers: a quarter of them are points of X, and the last one is all zero."""
+    rng = np.random.default_rng(seed)
+    Q = rng.integers(lo, hi, size=(nq, X.shape[1])).astype(np.float32)
+    Q[::4] = X[rng.choice(len(X), len(Q[::4]))]
+    Q[-1] = 0
+    return Q
+
+
+def repeated_labels(n, seed, n_values):
+    """Labels drawn from n_values distinct float32 values: runs of about n / n_values points share a label."""
+    rng = np.random.default_rng(seed)
+    return ((rng.integers(0, n_values, n) + 1.0) / n_values).astype(np.float32)
+
+
+def tie_windows(labels, nq, p, seed):
+    """windows() of a 2^p fraction, and where labels repeat, every fifth row of each of the windows that end inside runs:
+    [v, v] (zero width, a whole run carries v), [v1, v2] with both ends existing labels, hi equal to the largest label,
+    lo below the smallest label."""
+    out = windows(labels, nq, p, seed)
+    s = np.sort(labels)
+    if len(np.unique(s)) == len(s):
+        return out
+    rng = np.random.default_rng(seed + 1)
+    n = len(s)
+    w = max(1, int(n * 2.0 ** p))
+    for i in range(nq):
+        st = int(rng.integers(0, n - w))
+        kind = i % 5
+        if kind == 1:
+            out[i] = (s[st], s[st])
+        elif kind == 2:
+            out[i] = (s[st], s[st + w])
+        elif kind == 3:
+            out[i] = (s[n - 1 - w], s[-1])
+        elif kind == 4:
+            out[i] = (s[0] - 1, s[w])
+    return out
