@@ -4,7 +4,7 @@ recall@10 >= 0.95 (BASELINE.json metric), on BASELINE.json configs[1]: SIFT-1M-l
 d = 128, squared L2), 2-ary window search tree (cutoff 1000, R = 64, L = 500, alpha = 1),
 query method "optimized_postfilter", 10 000 queries per GPU, k = 10.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full]
 
 N > 1: one process per GPU.  Either the caller starts the ranks (python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N: RANK / LOCAL_RANK / WORLD_SIZE in the environment), or --
@@ -20,12 +20,21 @@ top-k are exchanged with ONE RCCL all-gather inside the timed region (SURVEY.md 
   --scaling weak   (default) 10 000 queries PER GPU: the job's batch is N x 10 000 queries
   --scaling strong ONE 10 000-query batch cut N ways (1 250 queries per GPU at N = 8)
 
-Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
+Rank 0 prints ONE JSON line.  Besides the contract's keys it carries `config` (the setting, recall@10 of
+the timed setting, index size) and
   roofline      algorithmic bytes of the beam-search kernel / its HIP-event time vs 8 TB/s HBM
+A plain run does only what that line needs: data, index, the headline sweep, the warm-up and timed steps,
+--dump-outputs and the line.  Its index is built in memory, without graph files (N > 1 --workload deep
+excepted: rank 0 builds into --cache, the other ranks load its files).  Everything else runs with --full
+(N = 1 only):
   cpu_baseline  the REAL reference (oracle/_ref build) -- or the oracle port -- timed on this
-                box's host cores on the same batch and setting, same graphs (N = 1 only)
-  per_fraction  QPS@recall>=0.95 for all 17 window fractions 2^-16..2^0 (device time, N = 1 only)
-  configs       the other BASELINE.json configurations (N = 1 only)
+                box's host cores on the same batch and setting, same graphs (--no-cpu-baseline: skip)
+  per_fraction  QPS@recall>=0.95 for all 17 window fractions 2^-16..2^0 (device time; --fractions)
+  configs       the other BASELINE.json configurations (--configs)
+  config.same_batch_*, config.pipelined (--pipeline), config.host_buffer_*: the same-batch replay, the
+                asynchronous call with batches in flight, the reference's numpy-in / numpy-out boundary
+With --full the index's graph files go to --cache, where the reference legs load them.  --fractions,
+--configs and --pipeline choose among these legs; asking for one without --full is an error.
 per_fraction and configs are summarised on stdout (the line stays below LINE_BUDGET characters);
 the full record goes to stderr as `[bench] full: {...}`.
 
@@ -310,18 +319,22 @@ def main():
     ap.add_argument("--nq", type=int, default=10_000)
     ap.add_argument("--dim", type=int, default=0)
     ap.add_argument("--fraction", type=int, default=-3, help="headline window fraction exponent")
-    ap.add_argument("--fractions", default=None, help="'all' = also sweep 2^-16..2^0 (N=1; default for sift), 'headline' = skip, or a list of exponents '-9,-6'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also the CPU baseline, the other window fractions and configurations, the same-batch replay, batches in flight "
+                         "and the host-buffer call (a plain run does only what the headline needs)")
+    ap.add_argument("--fractions", default=None, help="with --full: 'all' = also sweep 2^-16..2^0 (N=1; default for sift), 'headline' = skip, "
+                    "or a list of exponents '-9,-6'")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--setting", default="", help="'beam,mult': skip the sweep and time this setting (profiling runs)")
     ap.add_argument("--balance", choices=("count", "cost", "levels"), default="count",
                     help="shard cut of a step's batch: equal query counts; equal predicted work (wann_predict_costs + weighted_bounds; what "
                          "--scaling strong wants: the step takes as long as its slowest shard); or `levels`: no query shards at all -- the "
                          "single doubling levels of every chain are dealt to the ranks (level_dealt_batch_search, wann_batch_search_device_ids)")
-    ap.add_argument("--pipeline", type=int, default=2, help="N = 1: also time the rotating batches through the ASYNCHRONOUS call, this many in flight "
-                    "(wann_batch_search_device_async; reported as config.pipelined_*, never as `value`); 0 / 1 = skip")
+    ap.add_argument("--pipeline", type=int, default=None, help="with --full, N = 1: also time the rotating batches through the ASYNCHRONOUS call, this "
+                    "many in flight (wann_batch_search_device_async; reported as config.pipelined, never as `value`); default 2; 0 / 1 = skip")
     ap.add_argument("--rotate", type=int, default=4, help="distinct query / window draws the timed steps rotate through (1 = the same batch every step)")
     ap.add_argument("--cache", default=os.environ.get("WANN_BENCH_CACHE", "/tmp/wann_bench_cache"))
-    ap.add_argument("--configs", default=None, help="N=1: the other BASELINE.json configurations as extra legs of the line: 'all' = glove "
+    ap.add_argument("--configs", default=None, help="with --full, N=1: the other BASELINE.json configurations as extra legs of the line: 'all' = glove "
                     "(configs[2]), deep (configs[3] on this one GPU), adverse (configs[4]), sift_u8 / fenwick / three_split (SURVEY.md 8(f)-4 / 8(f)-2 at "
                     "configs[1] size); 'none'; or a comma list (also: deep_l2 = configs[3] under squared L2)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -333,10 +346,23 @@ def main():
     wl = WORKLOADS[args.workload]
     args.n = args.n or wl["n"]
     args.dim = args.dim or wl["d"]
+    if not args.full:  # a plain run: the headline alone; the legs beyond it need --full
+        extra = []
+        if args.fractions not in (None, "headline"):
+            extra.append("--fractions " + args.fractions)
+        if args.configs not in (None, "none"):
+            extra.append("--configs " + args.configs)
+        if args.pipeline is not None and args.pipeline >= 2:
+            extra.append(f"--pipeline {args.pipeline}")
+        if extra:
+            ap.error(f"{', '.join(extra)}: legs beyond the headline run with --full only")
+        args.fractions, args.configs, args.pipeline = "headline", "none", 0
     if args.fractions is None:
         args.fractions = "all" if args.workload == "sift" else "headline"
     if args.configs is None:
         args.configs = "all" if args.workload == "sift" else "none"
+    if args.pipeline is None:
+        args.pipeline = 2
 
     # ---- N > 1 without a launcher: start the ranks ourselves, BEFORE torch / HIP are touched in this process
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -382,9 +408,12 @@ def main():
     Qg = Qall[:gnq]
     log(f"data n={n} d={d} batch={gnq} ({args.scaling} scaling, {world} rank(s)) in {time.time() - t0:.1f}s; host cpus={ncpu}")
 
+    # graph files only where something reads them: the reference legs of --full, the other ranks of a shared build.  A plain
+    # single-GPU run builds its graphs in memory -- the same graphs, byte for byte -- and reads nothing an earlier run wrote.
     cache = os.path.join(args.cache, f"{wl['cache']}_n{n}_d{d}_R{R}_L{L}_c{cutoff}_s{split}") + "/"
-    os.makedirs(cache, exist_ok=True)
-    bp = wa.BuildParams(R, L, alpha, cache)
+    if args.full or (world > 1 and wl["shared_cache"]):
+        os.makedirs(cache, exist_ok=True)
+    bp = wa.BuildParams(R, L, alpha, cache if args.full or world > 1 else "")
     t0 = time.time()
     make_index = lambda params: getattr(wa, wl["cls"])(X, labels, cutoff=cutoff, split_factor=split, build_params=params)  # noqa: E731
     if world > 1 and wl["shared_cache"]:
@@ -468,6 +497,7 @@ def main():
         return Wg, Wgt, rows, best
 
     # ---- headline fraction: pick the setting, then time K steps
+    t0 = time.time()
     if args.setting:
         sb, sm = (int(x) for x in args.setting.split(","))
         Wg = global_windows(args.fraction, 1000)
@@ -482,6 +512,7 @@ def main():
         best = max(rows, key=lambda r: r["recall"])
         log("WARNING: no sweep setting reached recall 0.95; timing the most accurate one")
     beam, mult = best["beam"], best["mult"]
+    log(f"setting ({beam}, x{mult}) picked in {time.time() - t0:.1f}s")
     if distributed:  # every rank must time the same setting: take rank 0's choice
         bm = torch.tensor([beam, mult], device=dev)
         dist.broadcast(bm, 0)
@@ -556,8 +587,8 @@ def main():
             el = float(te.item())
         return el, out, dict(agg)
 
-    # the same batch every step (rounds 1-3 timed this) -- reported beside `value`; then THE timed region: rotating batches
-    same_elapsed, _, same_agg = timed(False) if rot > 1 else (None, None, None)
+    # --full: the same batch every step (rounds 1-3 timed this) -- reported beside `value`; then THE timed region: rotating batches
+    same_elapsed, _, same_agg = timed(False) if args.full and rot > 1 else (None, None, None)
     elapsed, last_out, _ = timed(True)
     if args.dump_outputs and rank == 0:  # (every rank holds every row of the step)
         shapes = dump_outputs(args.dump_outputs, last_out[0].cpu().numpy(), last_out[1].cpu().numpy())
@@ -623,9 +654,9 @@ def main():
         log(f"pipelined: {pipe}")
 
     # the reference's own boundary (numpy in, numpy out): the same batch through the host-buffer entry point,
-    # PCIe copies included -- reported beside `value`, never as `value`
+    # PCIe copies included -- reported beside `value`, never as `value` (--full)
     host_ms = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         Wn = W.astype(np.float32)
         index.batch_search(Q, Wn, nq, method, qparams(wa, beam, mult))
         t1 = time.perf_counter()
@@ -686,7 +717,7 @@ def main():
         legs["ids|" + name] = ids_np
         legs["dists|" + name] = d_np
 
-    want_ref = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_ref = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     head_names = []
     if want_ref:
         add_leg(f"h:{beam},{mult}", W, beam, mult, all_ids.cpu().numpy().view(np.uint32), all_d.cpu().numpy())

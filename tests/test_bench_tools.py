@@ -118,3 +118,10 @@ def test_dump_outputs(tmp_path):
 def test_steps_must_be_positive():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_plain_run_refuses_legs_of_full():
+    """the legs beyond the headline run with --full only: asking a plain run for one is an error, not a silent no-op"""
+    for extra in (["--fractions", "all"], ["--configs", "glove"], ["--pipeline", "2"]):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1"] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and "--full" in r.stderr and extra[0] in r.stderr, (extra, r.stderr[-500:])

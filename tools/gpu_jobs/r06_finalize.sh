@@ -5,7 +5,7 @@ O=gpurun_out/r06g
 mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1
 tail -3 $O/gpu_tests.log | cut -c1-200
-python bench.py --fractions headline --configs glove --no-cpu-baseline --setting 80,1 --steps 30 --warmup 5 > $O/bench.json 2> $O/bench.log
+python bench.py --full --fractions headline --configs glove --no-cpu-baseline --setting 80,1 --steps 30 --warmup 5 > $O/bench.json 2> $O/bench.log
 python3 - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r06g/bench.json") if l.startswith("{")][-1])

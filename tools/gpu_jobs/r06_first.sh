@@ -15,7 +15,7 @@ for v in tree head tree head; do
 done
 export LD_LIBRARY_PATH=$BASE_LD
 cat $O/ab.log
-B="python3 bench.py --fraction -3 --configs none --no-cpu-baseline --setting 80,1 --steps 10 --warmup 2"
+B="python3 bench.py --full --fraction -3 --configs none --no-cpu-baseline --setting 80,1 --steps 10 --warmup 2"
 for n in 2 3 4; do
   timeout 900 $B --fractions=-9,-6 --pipeline $n > $O/inflight_$n.json 2> $O/inflight_$n.log
 done

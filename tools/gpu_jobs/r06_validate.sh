@@ -6,7 +6,7 @@ mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -x -q --durations=12 -rs ${PYTEST_SELECT:-} > $O/gpu_tests.log 2>&1
 tail -22 $O/gpu_tests.log | cut -c1-200
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-SECONDS=0; python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.log; echo "bench.py wall: $SECONDS s"
+SECONDS=0; python bench.py --full --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.log; echo "bench.py wall: $SECONDS s"
 
 python3 - <<'PY'
 import json

@@ -1,6 +1,6 @@
 """CPU baseline worker for bench.py: times the REAL reference (oracle/_ref build; falls back to the oracle
 port) on the bench's batch with a given PARLAY_NUM_THREADS, in its own process (the reference reads the
-thread count once).  Loads the graphs bench.py left in the cache; prints one JSON line."""
+thread count once).  Loads the graphs bench.py --full left in the cache; prints one JSON line."""
 import argparse, json, os, sys, time
 
 ap = argparse.ArgumentParser()

@@ -1,5 +1,5 @@
 """CPU-baseline worker of bench.py: the REAL reference (oracle/_ref build; falls back to the oracle port) on the bench's index --
-loaded ONCE from the graph files bench.py left in the cache -- answering any number of "legs" (a window set + a (beam, mult)
+loaded ONCE from the graph files bench.py --full left in the cache -- answering any number of "legs" (a window set + a (beam, mult)
 setting + the GPU's rows for them) with one PARLAY_NUM_THREADS (the reference fixes its thread count at first use, so every
 thread count is its own process).  Prints one JSON object: {leg name: {qps, reps, same_dists, same_ids, same_id_sets}}.
 
