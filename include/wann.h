@@ -53,9 +53,13 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * equidistant points in an exact scan may permute, as between the GPU and the reference).  Its graphs are the float32 index's
  * graphs on the upcast points, byte for byte, under the same cache file names: the two share a graph cache.  (A float32 index
  * on the UNROUNDED points gets the same file names but other graphs: keep such caches apart.)  Host-buffer calls take
- * float16 queries; device-buffer calls take fp32 queries (not rounded).  Labels stay float32.  The MFMA prefilter path is
- * float32-only: a float16 PrefilterIndex batch takes the exact scan (gemm_queries == 0), as uint8 / int8 batches do.  The
- * unfiltered wann_vamana_* API refuses float16. */
+ * float16 queries; device-buffer calls take fp32 queries (not rounded).  Labels stay float32.  The unfiltered wann_vamana_*
+ * API refuses float16.
+ * The MFMA prefilter path (PrefilterIndex batches in which queries share windows, counted in gemm_queries) serves every
+ * element type and returns the exact scan's rows: float32 rows of up to 512 elements; float16 rows of up to 128 elements (the
+ * float32 kernels on the exact upcast, half loads; longer float16 rows take the exact scan); uint8 / int8 rows of up to 512
+ * bytes on the int8 MFMA with exact int32 scores (longer byte rows take the exact scan).  Queries of a byte index become bytes
+ * by the exact scan's rule, (int)q & 0xff, on both paths. */
 enum { WANN_DTYPE_F32 = 0, WANN_DTYPE_U8 = 1, WANN_DTYPE_I8 = 2, WANN_DTYPE_F16 = 3 };
 /* index classes */
 enum {

@@ -1,4 +1,4 @@
-// wann_gemm_device.h -- argument block of the dense prefilter path (wann_gemm_kernels.hip).
+// wann_gemm_device.h -- argument block of the dense prefilter path (wann_gemm_kernels_body.inc).
 #pragma once
 #include <stdint.h>
 
@@ -42,8 +42,9 @@ struct GemmArgs {
   int32_t *gq;        // grouped query rows
   int32_t *tq_group;  // per grouped query: its group and its row inside the group
   int32_t *tq_local;
-  const float *pnorm2;
+  const float *pnorm2;   // float32 / float16 rows: |p|^2 per point and the bits of its maximum
   const unsigned int *pnorm2_max_bits;
+  const int32_t *pterm;  // uint8 / int8 rows: the per-point integer term of the score (wann_gemm_kernels_bytes.inc)
   float *scores;      // what k_gemm_scores hands to k_rerank's selection: per query, step and half wave the four smallest scores
   int64_t score_cap;  // floats; groups that do not fit any more are left to the exact scan
   int32_t k;
@@ -54,7 +55,9 @@ struct GemmArgs {
   unsigned long long *prof;           // dev tool (make PROFILE=1): phase-cycle sums of k_gemm_scores
 };
 
-int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);
+// (the launchers dispatch on ix.dtype: one set of kernels per element type)
+int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);  // float32 / float16 rows
+int launch_point_terms(const IndexView &ix, int32_t *term, void *stream);                         // uint8 / int8 rows
 int launch_group_windows(const GemmArgs &a, Counters *ctr, void *stream);
 int launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 int launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);

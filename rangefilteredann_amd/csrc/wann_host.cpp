@@ -286,17 +286,28 @@ int method_code(const char *m) {
 }
 
 // PrefilterIndex batches in which many queries share a window: those windows are scored as Q x P^T GEMMs on the
-// matrix cores (wann_gemm_kernels.hip), ~32 candidates per query are kept and re-ranked exactly; everything else (and
+// matrix cores (wann_gemm_kernels_body.inc), ~32 candidates per query are kept and re-ranked exactly; everything else (and
 // every query whose top-k cannot be proven from the MFMA scores) goes through the exact scan kernel.  Grouping,
 // tile planning and the hand-over to the exact scan all happen on the device: the host enqueues six launches and
 // never waits.
 void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *d_queries, int64_t nq, int k, hipStream_t st) {
-  if (k > kSelect / 2 || I.view.stride > 512 || (I.view.stride & 15)) return;  // (rows of up to 512 floats: RedCaps)
+  // rows the score kernels take, per element type: float32 up to 512 floats (RedCaps), float16 up to 128 elements (the narrow
+  // kernel only), uint8 / int8 up to 512 bytes; everything longer stays on the exact scan
+  const int dtype = I.view.dtype;
+  const bool bytes = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8;
+  if (k > kSelect / 2 || (I.view.stride & 15)) return;
+  if (dtype == WANN_DTYPE_F16 ? query_words(I.view) > 128 : I.view.stride > (bytes ? 128 : 512)) return;
   if (!I.have_norms) {
-    I.d_pnorm2.ensure((size_t)I.view.n);
-    I.d_pnorm2_max.ensure(1);
-    HIP_CHECK(hipMemsetAsync(I.d_pnorm2_max.p, 0, sizeof(unsigned int), st));
-    if (launch_point_norms(I.view, I.d_pnorm2.p, I.d_pnorm2_max.p, st)) throw HipError(std::string("k_point_norms: ") + gemm_launch_last_error());
+    if (bytes) {  // exact integer sums of the rows (wann_gemm_kernels_bytes.inc)
+      I.d_pterm.ensure((size_t)I.view.n);
+      if (launch_point_terms(I.view, I.d_pterm.p, st)) throw HipError(std::string("k_point_terms_b: ") + gemm_launch_last_error());
+      I.device_bytes += (int64_t)I.d_pterm.bytes();
+    } else {
+      I.d_pnorm2.ensure((size_t)I.view.n);
+      I.d_pnorm2_max.ensure(1);
+      HIP_CHECK(hipMemsetAsync(I.d_pnorm2_max.p, 0, sizeof(unsigned int), st));
+      if (launch_point_norms(I.view, I.d_pnorm2.p, I.d_pnorm2_max.p, st)) throw HipError(std::string("k_point_norms: ") + gemm_launch_last_error());
+    }
     I.have_norms = true;
   }
   size_t cap = 64;
@@ -340,6 +351,7 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   ga.tq_local = I.g_tq_local.p;
   ga.pnorm2 = I.d_pnorm2.p;
   ga.pnorm2_max_bits = I.d_pnorm2_max.p;
+  ga.pterm = I.d_pterm.p;
   ga.scores = I.g_scores.p;
   ga.score_cap = (int64_t)score_cap;
   ga.k = k;
@@ -347,6 +359,7 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   // additions, u = 2^-24 with a rounding adder, 2^-23 with a truncating one; 3 = the truncating bound and half as much again.
   // (Round 2 used 8: at d = 512 that one term was 7.4e-4 |q||p|, 46 % of the adversarial queries could not be proven.)
   // The knob can only widen the margin (Tuning clamps it to >= 3): a smaller factor would certify unproven results.
+  // (float types only: byte scores are exact integers and need no bound)
   ga.acc_factor = T.proof_factor;
   ga.out_key = W.out_key.p;
   ga.out_cnt = W.out_cnt.p;
@@ -480,7 +493,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   // row it is only tried every eighth batch until one forms a group again (WANN_DENSE_ALWAYS: every batch).  Results do not
   // depend on it: what the dense path does not take goes through the exact scan.
   bool tried_dense = false;
-  if (I.host().spec.kind == WANN_KIND_PREFILTER && nq >= 32 && I.host().spec.dtype == WANN_DTYPE_F32 && T.gemm &&
+  if (I.host().spec.kind == WANN_KIND_PREFILTER && nq >= 32 && T.gemm &&
       (I.dense_idle < 2 || (I.dense_batches & 7) == 0 || T.dense_always)) {
     dense_prefilter(I, T, W, d_queries, nq, k, st);
     tried_dense = true;

@@ -141,9 +141,11 @@ struct wann_index {
   IndexView view{};
   int64_t device_bytes = 0;
   wann_host::Workspace ws;
-  // dense prefilter path (wann_gemm_kernels.hip): |p|^2 per point, computed at first use
+  // dense prefilter path (wann_gemm_kernels_body.inc): |p|^2 per point, computed at first use
+  // (float32 / float16 rows; uint8 / int8 rows keep one exact integer term per point instead, counted in device_bytes)
   DevBuf<float> d_pnorm2;
   DevBuf<unsigned int> d_pnorm2_max;
+  DevBuf<int32_t> d_pterm;
   bool have_norms = false;
   // (touched by the blocking calls and by both asynchronous lanes, outside dense_mu for every class but PrefilterIndex)
   std::atomic<int> dense_idle{0};  // batches in a row on which the dense path found no window group (run_batch)

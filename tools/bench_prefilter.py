@@ -3,11 +3,34 @@ queries; experiments/generate_advserial_dataset.py:8-69), PrefilterIndex brute f
   (i)  native windows [c - 0.5, c + 0.5] = one cluster = 1 % of the points: dense MFMA path vs the exact per-query scan
   (ii) synthetic 2^-12 windows (244 points): the exact scan kernel k_brute against its HBM roofline
 each against the REAL reference at its best thread count (child processes: the reference fixes its thread count at first use).
+--dtype float32 | float16 | uint8 | int8 (default float32) selects the element type of the point set: float16 rounds the same
+set (MIPS), the byte types quantise it -- round(127 x) for int8 (MIPS), + 128 for uint8 (Euclidian), queries likewise -- and run
+on the int8 MFMA with exact scores.  Every leg is timed as the median of repeated calls (min / max beside it: the spread).
 Run from the repo root.  Prints one JSON object."""
 import json, os, subprocess, sys, time
 os.environ.setdefault("WANN_TEST_HOOKS", "1")  # this tool flips WANN_* switches between calls on one index
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
+
+
+DTYPE = sys.argv[sys.argv.index("--dtype") + 1] if "--dtype" in sys.argv else "float32"
+CLASS = {"float32": "FloatMips", "float16": "Float16Mips", "int8": "Int8Mips", "uint8": "UInt8Euclidian"}[DTYPE]
+ELEM_BYTES = {"float32": 4, "float16": 2, "int8": 1, "uint8": 1}[DTYPE]
+
+
+def as_elem(a):
+    """a (unit-norm float32 rows) as the index of --dtype holds it"""
+    if DTYPE == "float32":
+        return a
+    if DTYPE == "float16":
+        return a.astype(np.float16)
+    q = np.rint(127.0 * a)
+    return q.astype(np.int8) if DTYPE == "int8" else (q + 128).astype(np.uint8)
+
+
+def padded_row_bytes(d):
+    """bytes of a stored row: float32 rows are padded to 16 floats, float16 rows to 32 halves, byte rows to 64 bytes"""
+    return 64 * ((d * ELEM_BYTES + 63) // 64)
 
 
 def make():
@@ -28,7 +51,7 @@ def make():
     w = int(n * 2.0 ** -12)
     st = np.random.default_rng(5).integers(1, n - w - 1, size=Q.shape[0])
     W2 = np.stack([ls[st], ls[st + w]], 1).astype(np.float32)
-    return X, Q, labels, W1, W2, per, w
+    return as_elem(X), as_elem(Q), labels, W1, W2, per, w
 
 
 if len(sys.argv) > 2 and sys.argv[1] == "--ref-worker":  # child: the real reference with PARLAY_NUM_THREADS from the environment
@@ -40,7 +63,9 @@ if len(sys.argv) > 2 and sys.argv[1] == "--ref-worker":  # child: the real refer
     ref = orc.load_reference(prefer=("x86-64-v4", "native"))
     assert ref is not None
     with quiet_stdout():
-        ridx = ref.PrefilterIndexFloatMips(X, labels)
+        ridx = getattr(ref, "PrefilterIndex" + CLASS.replace("Float16", "Float"))(X.astype(np.float32) if DTYPE == "float16" else X, labels)
+    if DTYPE == "float16":
+        Q = Q.astype(np.float32)  # (the reference has no float16 classes: a float16 index answers like the float32 one on the upcast)
     out = {}
     for name, W in (("native", W1), ("p12", W2)):
         best = 1e9
@@ -60,24 +85,31 @@ import window_ann as wa
 X, Q, labels, W1, W2, per, w = make()
 d = X.shape[1]
 nq = Q.shape[0]
-idx = wa.PrefilterIndexFloatMips(X, labels)
+idx = getattr(wa, "PrefilterIndex" + CLASS)(X, labels)
 qp = wa.QueryParams(10, 10, 1.35, 10**7, 10**4, 1, 10000, None, False)
 dev = torch.device("cuda:0")
-Qt = torch.from_numpy(Q).to(dev)
+Qt = torch.from_numpy(Q.astype(np.float32)).to(dev)  # (device-buffer calls take fp32 queries; every element type converts exactly)
 it, dt = torch.empty((nq, 10), dtype=torch.int32, device=dev), torch.empty((nq, 10), dtype=torch.float32, device=dev)
+
+
+REPS = int(os.environ.get("WANN_PF_REPS", "21"))
 
 
 def timed(Wt, env):
     if env: os.environ["WANN_NO_GEMM"] = env
     else: os.environ.pop("WANN_NO_GEMM", None)
-    for _ in range(2):
+    for _ in range(3):
         idx.batch_search_device(Qt.data_ptr(), Wt.data_ptr(), nq, 0, "", qp, it.data_ptr(), dt.data_ptr(), 0)
-    t = time.perf_counter()
-    reps = 5
-    for _ in range(reps):
+    wall, devms = [], []
+    for _ in range(REPS):  # (the call returns after the batch's last kernel: it synchronises)
+        t = time.perf_counter()
         idx.batch_search_device(Qt.data_ptr(), Wt.data_ptr(), nq, 0, "", qp, it.data_ptr(), dt.data_ptr(), 0)
-    ms = (time.perf_counter() - t) / reps * 1e3
-    return dict(ms=round(ms, 3), qps=round(nq / ms * 1e3), counters=idx.counters(), ids=it.cpu().numpy().view(np.uint32).copy(), d=dt.cpu().numpy().copy())
+        wall.append((time.perf_counter() - t) * 1e3)
+        devms.append(idx.counters()["device_ms"])
+    ms = float(np.median(wall))
+    c = dict(idx.counters(), device_ms=float(np.median(devms)))
+    return dict(ms=round(ms, 3), ms_min=round(min(wall), 3), ms_max=round(max(wall), 3), device_ms_min=round(min(devms), 3), device_ms_max=round(max(devms), 3),
+                qps=round(nq / ms * 1e3), counters=c, ids=it.cpu().numpy().view(np.uint32).copy(), d=dt.cpu().numpy().copy())
 
 
 W1t, W2t = torch.from_numpy(W1).to(dev), torch.from_numpy(W2).to(dev)
@@ -86,6 +118,8 @@ if os.environ.get("WANN_PF_ONLY") == "p12":  # dev runs under a profiler: the sy
     print(json.dumps(dict(ms=r["ms"], device_ms=r["counters"]["device_ms"], brute_rows=int(r["counters"]["brute_rows"]))))
     sys.exit(0)
 out = {"mfma": timed(W1t, None), "scan": timed(W1t, "1"), "p12": timed(W2t, None)}
+# (the two legs of the comparison once more, alternating: what one leg moves between its two runs is the spread to beat)
+again = {"mfma": timed(W1t, None), "scan": timed(W1t, "1")}
 os.environ.pop("WANN_NO_GEMM", None)
 same = np.array_equal(out["mfma"]["d"], out["scan"]["d"])
 # the reference at several thread counts (its best is what is reported)
@@ -93,9 +127,12 @@ res_path = "/tmp/wann_prefilter_gpu_rows.npz"
 np.savez(res_path, d_native=out["mfma"]["d"], d_p12=out["p12"]["d"])
 cpu = {}
 ncpu = os.cpu_count() or 1
-for th in ([] if os.environ.get("WANN_PF_NO_REF") else sorted({ncpu, max(1, ncpu // 2), max(1, ncpu // 4), max(1, ncpu // 8)}, reverse=True)):  # (WANN_PF_NO_REF=1: dev runs)
+ref_threads = sorted({ncpu, max(1, ncpu // 2), max(1, ncpu // 4), max(1, ncpu // 8)}, reverse=True)
+if os.environ.get("WANN_PF_REF_THREADS"):  # (a box that grants fewer CPUs than it shows: the thread counts to try, e.g. 16,8)
+    ref_threads = [int(x) for x in os.environ["WANN_PF_REF_THREADS"].split(",")]
+for th in ([] if os.environ.get("WANN_PF_NO_REF") else ref_threads):  # (WANN_PF_NO_REF=1: dev runs)
     try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--ref-worker", res_path], env=dict(os.environ, PARLAY_NUM_THREADS=str(th)),
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--ref-worker", res_path, "--dtype", DTYPE], env=dict(os.environ, PARLAY_NUM_THREADS=str(th)),
                            capture_output=True, text=True, timeout=900)
         r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
         for name, v in r.items():
@@ -104,10 +141,15 @@ for th in ([] if os.environ.get("WANN_PF_NO_REF") else sorted({ncpu, max(1, ncpu
     except Exception as e:  # noqa: BLE001
         print(f"[prefilter] reference with {th} threads failed: {e!r}", file=sys.stderr)
 flops = 2.0 * nq * per * d
-scan_bytes = float(out["p12"]["counters"]["brute_rows"]) * d * 4  # w * d * sizeof(T) per brute-force query
+scan_bytes = float(out["p12"]["counters"]["brute_rows"]) * d * ELEM_BYTES  # w * d * sizeof(T) per brute-force query
+win_bytes = 100 * per * padded_row_bytes(d)  # a window group reads each of its (padded) point rows once
 p12_dev_ms = out["p12"]["counters"]["device_ms"]
-print(json.dumps(dict(workload=f"adversarial 100x10000 d={d} MIPS, 9900 queries, window = 1 cluster", mfma_ms=out["mfma"]["ms"], mfma_qps=out["mfma"]["qps"],
+spread = lambda leg: dict(ms=[out[leg]["ms"], again[leg]["ms"]], ms_min=[out[leg]["ms_min"], again[leg]["ms_min"]], ms_max=[out[leg]["ms_max"], again[leg]["ms_max"]],
+                          device_ms=[round(out[leg]["counters"]["device_ms"], 3), round(again[leg]["counters"]["device_ms"], 3)])
+print(json.dumps(dict(workload=f"adversarial 100x10000 d={d} {DTYPE} {'Euclidian' if CLASS.endswith('Euclidian') else 'MIPS'}, 9900 queries, window = 1 cluster", mfma_ms=out["mfma"]["ms"], mfma_qps=out["mfma"]["qps"],
                       scan_ms=out["scan"]["ms"], scan_qps=out["scan"]["qps"], mfma_equals_scan=bool(same),
+                      scan_device_ms=round(out["scan"]["counters"]["device_ms"], 3), timed_calls_per_leg=REPS,
+                      repeated_legs=dict(mfma=spread("mfma"), scan=spread("scan")),
                       gemm_queries=out["mfma"]["counters"]["gemm_queries"], gemm_unproven=out["mfma"]["counters"]["gemm_unproven"], gemm_rescued=out["mfma"]["counters"]["gemm_rescued"], device_ms=round(out["mfma"]["counters"]["device_ms"], 3), gemm_tflops_incl_select=round(flops / out["mfma"]["ms"] / 1e9, 2),
                       cpu_reference=cpu.get("native"),
                       # the MFMA leg against its roofline: a window group reads each of its point rows ONCE (padded row of
@@ -115,10 +157,10 @@ print(json.dumps(dict(workload=f"adversarial 100x10000 d={d} MIPS, 9900 queries,
                       # pipes' (DESIGN.md 3.3b "Round 3"); `achieved` is over the WHOLE call's device time (ten small launches) --
                       # k_gemm_scores alone: profiles/*_prefilter_rocprofv3_kernel_stats.csv
                       roofline=dict(bound="hbm", kernel="k_gemm_scores (whole call: route + grouping + GEMM + select / re-rank + finalize)",
-                                    achieved=round(100 * per * (16 * ((d + 15) // 16)) * 4 / (out["mfma"]["counters"]["device_ms"] * 1e-3) / 1e9, 1),
+                                    achieved=round(win_bytes / (out["mfma"]["counters"]["device_ms"] * 1e-3) / 1e9, 1),
                                     peak=8000.0, unit="GB/s",
-                                    frac=round(100 * per * (16 * ((d + 15) // 16)) * 4 / (out["mfma"]["counters"]["device_ms"] * 1e-3) / 1e9 / 8000.0, 4),
-                                    algorithmic_gb=round(100 * per * (16 * ((d + 15) // 16)) * 4 / 1e9, 4), traffic=None),
+                                    frac=round(win_bytes / (out["mfma"]["counters"]["device_ms"] * 1e-3) / 1e9 / 8000.0, 4),
+                                    algorithmic_gb=round(win_bytes / 1e9, 4), traffic=None),
                       synthetic_2pow_minus12=dict(workload=f"same points, synthetic windows of {w} points (2^-12), exact scan (k_brute)", ms=out["p12"]["ms"], qps=out["p12"]["qps"],
                                                   device_ms=round(p12_dev_ms, 4), brute_rows=int(out["p12"]["counters"]["brute_rows"]),
                                                   algorithmic_gb=round(scan_bytes / 1e9, 4),
