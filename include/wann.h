@@ -195,6 +195,31 @@ int wann_predict_costs(wann_index *index, const float *ranges, int64_t nq, const
 
 int wann_get_counters(const wann_index *index, wann_counters *out);
 
+/* Distinct wide windows of a PrefilterIndex batch on the matrix cores (opt-in; off when an index is created).  The dense
+ * prefilter path takes a batch's queries that SHARE a window (gemm_queries).  With this option on, the queries it left over whose
+ * window holds at least 1 024 points are grouped by 2 048-position block of the label order instead -- a COVER GROUP is one block
+ * and the queries whose window touches it, provided at least 32 such queries touch every block of a query's window and the batch's
+ * eligible windows hold at least 2 GiB of rows in all (smaller batches are faster on the scan) -- and scored
+ * by the same kernels; candidates outside a query's own window are dropped before the exact re-rank.  Rows are those of the
+ * exact scan (same ids, same distance bits: both order by (distance, id)); only the work counters differ: brute_rows no longer
+ * counts the rows of the queries taken.  Row lengths the dense path does not take (float16 above 128 elements, bytes above 512)
+ * and k > 16 stay on the exact scan.  Applies to every replica of WANN_DEVICES and to every call form.
+ * Returns the previous setting (0 / 1) or a NEGATIVE error: -WANN_ERR_UNSUPPORTED for on = 1 on any kind but
+ * WANN_KIND_PREFILTER, -WANN_ERR_INVALID for a null index. */
+int wann_set_dense_windows(wann_index *index, int on);
+/* Cover-path counters of the last batch (all zero with the option off; gemm_queries / gemm_unproven / gemm_rescued of
+ * wann_counters keep counting shared-window groups only). */
+typedef struct {
+  int64_t queries;        /* queries taken by the cover path                                                     */
+  int64_t unproven;       /* of those: sent on to the exact scan because the scores could not prove the top k    */
+  int64_t rescued;        /* of those: proven after an exact scan of a few 64-position blocks                    */
+  int64_t groups;         /* cover groups (position block x its query list), summed over the passes              */
+  int64_t tiles;          /* tiles (cover group x 128 queries)                                                   */
+  int64_t passes;         /* passes over query ranges (the hand-over of one pass fits the 256-MiB score buffer)  */
+  int64_t handover_bytes; /* bytes reserved for the score kernels' hand-over to the selection, summed over the passes */
+} wann_dense_window_counters;
+int wann_get_dense_window_counters(const wann_index *index, wann_dense_window_counters *out);
+
 /* Introspection (tests, tools). */
 int64_t wann_num_points(const wann_index *index);
 int64_t wann_dim(const wann_index *index);

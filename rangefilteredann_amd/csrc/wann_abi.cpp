@@ -631,12 +631,43 @@ int wann_batch_search(wann_index *I, const void *queries, const float *ranges, i
     sum.search_kernel_ms = std::max(sum.search_kernel_ms, c.search_kernel_ms);
   }
   I->last = sum;
+  {  // (the cover path's counters likewise)
+    std::lock_guard<std::mutex> lk(I->dense_mu);
+    for (auto &R : I->replicas) {
+      std::lock_guard<std::mutex> lr(R->dense_mu);
+      const wann_dense_window_counters &c = R->last_cover;
+      I->last_cover.queries += c.queries;
+      I->last_cover.unproven += c.unproven;
+      I->last_cover.rescued += c.rescued;
+      I->last_cover.groups += c.groups;
+      I->last_cover.tiles += c.tiles;
+      I->last_cover.passes = std::max(I->last_cover.passes, c.passes);
+      I->last_cover.handover_bytes += c.handover_bytes;
+    }
+  }
   return WANN_OK;
 }
 
 int wann_get_counters(const wann_index *I, wann_counters *out) {
   if (!I || !out) return fail(WANN_ERR_INVALID, "null argument");
   *out = I->last;
+  return WANN_OK;
+}
+
+int wann_set_dense_windows(wann_index *I, int on) {
+  // (the previous setting is 0 / 1, so errors are the NEGATIVE codes here)
+  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
+  if (on && I->host().spec.kind != WANN_KIND_PREFILTER) return -fail(WANN_ERR_UNSUPPORTED, "dense windows: PrefilterIndex only");
+  const int prev = I->dense_windows.exchange(on ? 1 : 0);
+  for (auto &R : I->replicas) R->dense_windows = on ? 1 : 0;
+  return prev;
+}
+
+int wann_get_dense_window_counters(const wann_index *I, wann_dense_window_counters *out) {
+  if (!I || !out) return fail(WANN_ERR_INVALID, "null argument");
+  wann_index *M = const_cast<wann_index *>(I);
+  std::lock_guard<std::mutex> lk(M->dense_mu);
+  *out = I->last_cover;
   return WANN_OK;
 }
 

@@ -67,6 +67,12 @@ struct Task {
   float lo, hi;
 };
 
+// cover groups of the dense prefilter path (wann_set_dense_windows; wann_gemm_device.h): queries taken / of those, sent on to the
+// exact scan / settled by an exact scan of a few blocks; cover groups, tiles and passes planned; bytes handed to the selection
+struct CoverCounters {
+  unsigned long long queries, unproven, rescued, groups, tiles, passes, handover_bytes;
+};
+
 struct Counters {
   unsigned long long beam_searches, hops, dist_cmps, brute_rows, label_reads, unsupported;
   // searches run speculatively at beams beyond the one the sequential loop stops at (extra work,
@@ -82,6 +88,7 @@ struct Counters {
   unsigned long long big_searches, big_hops, packet_hops, own_scorings, prefetched_hops;
   unsigned long long lookaheads_issued;  // look-ahead searches handed to pollers (used or not)
   unsigned long long empty_windows;      // tree classes: queries whose window lies outside the index's label range (the reference prints a line for each)
+  CoverCounters cover;
 };
 
 struct RouteArgs {

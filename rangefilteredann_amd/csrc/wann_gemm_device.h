@@ -10,6 +10,14 @@ constexpr int kSelect = 32;      // candidates kept per query by MFMA score befo
 constexpr int kGemmPointChunk = 2048;  // window positions per tile (multiple of 128)
 // (a window hands over three candidates per 64 positions: too short a window could never prove a top 10)
 constexpr int kGroupMinQueries = 16, kGroupMinWindow = 1024;
+// cover groups (distinct windows, wann_set_dense_windows): a query is eligible if its window has at least kCoverMinWindow
+// positions and every kGemmPointChunk-position block it touches is touched by at least kCoverMinQueries such queries
+// (measured crossover, tools/bench_windows.py --sweep, DESIGN.md 3.5: at 16 queries per block the eighth-filled tiles and the
+// queries left ineligible lose against the scan at every batch size below 10 000; the window width itself does not decide --
+// the batch's total scan work does, CoverArgs::min_rows)
+constexpr int kCoverMinQueries = 32, kCoverMinWindow = 1024;
+constexpr long long kCoverMinScanBytes = 1ll << 31;  // eligible windows' rows x bytes per row below which the scan is faster than the cover path's ~0.2 ms of launches
+constexpr int kCoverPairFloats = (kGemmPointChunk / 128) * 8;  // hand-over of one (query, block) pair: 16 steps x 2 half waves x 4 floats
 
 struct GemmGroup {   // queries sharing the window [a, b) of the label argsort
   int64_t a, b;
@@ -55,12 +63,43 @@ struct GemmArgs {
   unsigned long long *prof;           // dev tool (make PROFILE=1): phase-cycle sums of k_gemm_scores
 };
 
+// Cover groups: the queries the window grouping left over, grouped by position block of the label argsort instead of by window.
+// A cover group is a GemmGroup (a, b = the block's bounds clipped to n, nch = 1), so the score kernels run on it as they are; a
+// batch whose hand-over outgrows the score buffer runs in PASSES over query ranges, all planned at once (k_cover_*).
+enum { CP_NPASS = 0, CP_QUERIES = 1, CP_INTS = 4 };
+struct CoverArgs {
+  GemmArgs g;           // the shared-window path's arguments (tasks, queries, q_slot / slot_group, scores, out_*, brute_*)
+  int32_t nblocks;      // position blocks of the index: ceil(n / kGemmPointChunk)
+  int32_t max_passes;   // passes the host enqueues (the device uses cplan[CP_NPASS] <= max_passes of them)
+  int32_t pass;         // k_rerank_cover: the pass this launch serves
+  int32_t pass_pairs;   // (query, block) pairs a pass starts queries for; a pass holds < pass_pairs + nblocks pairs
+  int32_t pair_stride;  // pairs of gq reserved per pass (>= pass_pairs + nblocks)
+  int32_t tile_stride;  // tile_group entries reserved per pass
+  int64_t min_rows;     // the batch takes the cover path only if its eligible windows hold at least this many rows in all (0: always)
+  int32_t *cplan;       // CP_*
+  int32_t *diff;        // [nblocks + 1] difference array -> wide queries per block
+  int32_t *badp;        // [nblocks + 1] exclusive prefix of 'block has too few wide queries'
+  int32_t *pdiff;       // [max_passes][nblocks + 1] difference arrays of the passes' queries
+  int32_t *pfill;       // [max_passes][nblocks] rows of a block's query list handed out so far
+  int32_t *blk_group;   // [max_passes][nblocks] the block's cover group in its pass (-1: none)
+  int32_t *pplan;       // [max_passes][P_INTS] what GemmArgs::plan is to a pass's score kernel
+  GemmGroup *groups;    // [max_passes][nblocks]
+  int32_t *tile_group;  // [max_passes][tile_stride]
+  int32_t *gq;          // [max_passes][pair_stride] the blocks' query lists
+  int32_t *q_pass;      // [nq] the query's pass, -1 = not on the cover path
+  int32_t *q_off;       // [nq] first of the query's pairs inside its pass
+  int32_t *qb_base;     // [max_passes][pair_stride] per pair: index (in 16-byte entries) of the query's row in the block's hand-over
+  CoverCounters *cctr;  // of the batch
+};
+
 // (the launchers dispatch on ix.dtype: one set of kernels per element type)
 int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);  // float32 / float16 rows
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream);                         // uint8 / int8 rows
 int launch_group_windows(const GemmArgs &a, Counters *ctr, void *stream);
 int launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 int launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
+int launch_cover_plan(const CoverArgs &c, void *stream);     // after launch_group_windows, before launch_select_rerank
+int launch_cover_pass(const CoverArgs &c, int pass, int num_cus, void *stream);  // score kernel + selection / re-rank of one pass
 const char *gemm_launch_last_error();
 
 }  // namespace wann

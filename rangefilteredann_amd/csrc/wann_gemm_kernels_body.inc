@@ -260,6 +260,193 @@ __global__ void k_group_scatter(GemmArgs A) {
   A.tq_local[tq] = A.q_rank[q];
 }
 
+// ------------------------------------------------------------------------------------------------
+// cover groups: the queries the window grouping left to the exact scan, grouped by position block (opt-in: wann_set_dense_windows)
+//
+//   k_cover_count    ungrouped queries with a window of >= kCoverMinWindow positions ("wide") add themselves to a difference array
+//                    over the position blocks they touch; narrower ones go to the exact scan's list
+//   k_cover_blocks   one workgroup: wide queries per block, and the prefix count of blocks with fewer than kCoverMinQueries
+//   k_cover_assign   one workgroup: a wide query none of whose blocks is such a block takes the cover path (the others: exact
+//                    scan); prefix sum of the (query, block) pairs in query order -> the query's pass and its place in the pass
+//   k_cover_plan     one workgroup per pass: queries per block -> cover groups (GemmGroup: a, b = the block clipped to n, one
+//                    slice), their query lists, hand-over rows and tiles
+//   k_cover_scatter  one wave per query: the query takes a row in every block it touches
+// A (query, block) pair owns kCoverPairFloats floats of the score buffer; a pass starts queries until pass_pairs pairs are
+// reached, so it holds fewer than pass_pairs + nblocks pairs = the buffer.  All passes are planned at once; the score buffer is
+// theirs one after the other (stream order).
+// ------------------------------------------------------------------------------------------------
+// 0 = not ours (no scan task, or in a window group), 1 = narrow, 2 = wide
+__device__ __forceinline__ int cover_state(const CoverArgs &C, int64_t q, int64_t &a, int64_t &b) {
+  const int pos = C.g.q_slot[q];
+  if (pos < 0 || C.g.slot_group[pos] >= 0) return 0;
+  const Task t = C.g.tasks[q];
+  a = t.a;
+  b = t.b;
+  return b - a >= kCoverMinWindow ? 2 : 1;
+}
+
+__global__ void k_cover_count(CoverArgs C) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= C.g.nq) return;
+  C.q_pass[q] = -1;
+  int64_t a = 0, b = 0;
+  const int st = cover_state(C, q, a, b);
+  if (st == 1) C.g.brute_list[atomicAdd(C.g.brute_count, 1)] = (int32_t)q;
+  if (st == 2) {
+    atomicAdd(&C.diff[a / kGemmPointChunk], 1);
+    atomicAdd(&C.diff[(b - 1) / kGemmPointChunk + 1], -1);
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_cover_blocks(CoverArgs C) {
+  __shared__ int wsum32[16];
+  const int tid = threadIdx.x;
+  int run = 0, bad_run = 0;
+  for (int i0 = 0; i0 < C.nblocks; i0 += blockDim.x) {
+    const int i = i0 + tid;
+    const int v = i < C.nblocks ? C.diff[i] : 0;
+    int tot, bad_tot;
+    const int cnt = run + block_excl_scan(v, wsum32, tot) + v;
+    const int bad = (i < C.nblocks && cnt < kCoverMinQueries) ? 1 : 0;
+    const int bp = bad_run + block_excl_scan(bad, wsum32, bad_tot);
+    if (i < C.nblocks) C.badp[i] = bp;
+    run += tot;
+    bad_run += bad_tot;
+  }
+  if (tid == 0) C.badp[C.nblocks] = bad_run;
+}
+
+__global__ __launch_bounds__(1024) void k_cover_assign(CoverArgs C) {
+  __shared__ unsigned long long wsum64[16];
+  __shared__ int wsum32[16];
+  const int tid = threadIdx.x;
+  unsigned long long run = 0;
+  int taken = 0;
+  // the batch's gate: the rows the scan would read for the eligible queries -- below C.min_rows the scan is the faster path
+  bool open = true;
+  if (C.min_rows > 0) {
+    unsigned long long rows = 0;
+    for (int64_t q0 = 0; q0 < C.g.nq; q0 += blockDim.x) {
+      const int64_t q = q0 + tid;
+      int64_t a = 0, b = 0;
+      unsigned long long w = 0;
+      if (q < C.g.nq && cover_state(C, q, a, b) == 2 && C.badp[(b - 1) / kGemmPointChunk + 1] == C.badp[a / kGemmPointChunk]) w = (unsigned long long)(b - a);
+      unsigned long long tot;
+      (void)block_excl_scan(w, wsum64, tot);
+      rows += tot;
+    }
+    open = rows >= (unsigned long long)C.min_rows;  // (workgroup-uniform)
+  }
+  for (int64_t q0 = 0; q0 < C.g.nq; q0 += blockDim.x) {
+    const int64_t q = q0 + tid;
+    int64_t a = 0, b = 0;
+    int B0 = 0, B1 = 0;
+    bool wide = false, ok = false;
+    if (q < C.g.nq && cover_state(C, q, a, b) == 2) {
+      wide = true;
+      B0 = (int)(a / kGemmPointChunk);
+      B1 = (int)((b - 1) / kGemmPointChunk);
+      ok = open && C.badp[B1 + 1] == C.badp[B0];
+    }
+    unsigned long long tot;
+    const unsigned long long off = run + block_excl_scan(ok ? (unsigned long long)(B1 - B0 + 1) : 0ull, wsum64, tot);
+    const unsigned long long pass = off / (unsigned long long)C.pass_pairs;
+    ok = ok && pass < (unsigned long long)C.max_passes;  // (beyond the passes the host enqueued: exact scan)
+    if (ok) {
+      C.q_pass[q] = (int32_t)pass;
+      C.q_off[q] = (int32_t)(off - pass * (unsigned long long)C.pass_pairs);
+      int32_t *pd = C.pdiff + (int64_t)pass * (C.nblocks + 1);
+      atomicAdd(&pd[B0], 1);
+      atomicAdd(&pd[B1 + 1], -1);
+    } else if (wide) {
+      C.g.brute_list[atomicAdd(C.g.brute_count, 1)] = (int32_t)q;
+    }
+    int ntaken;
+    (void)block_excl_scan(ok ? 1 : 0, wsum32, ntaken);
+    taken += ntaken;
+    run += tot;
+  }
+  if (tid == 0) {
+    const unsigned long long np = (run + (unsigned long long)C.pass_pairs - 1ull) / (unsigned long long)C.pass_pairs;
+    const int npass = (int)(np < (unsigned long long)C.max_passes ? np : (unsigned long long)C.max_passes);
+    C.cplan[CP_NPASS] = taken ? npass : 0;
+    C.cplan[CP_QUERIES] = taken;
+    C.cctr->queries = (unsigned long long)taken;
+    C.cctr->passes = (unsigned long long)(taken ? npass : 0);
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_cover_plan(CoverArgs C) {
+  __shared__ int wsum32[16];
+  const int tid = threadIdx.x, p = blockIdx.x;
+  if (p >= C.cplan[CP_NPASS]) return;  // (its plan stays zero: the pass's launches find nothing to do)
+  const int32_t *pd = C.pdiff + (int64_t)p * (C.nblocks + 1);
+  GemmGroup *groups = C.groups + (int64_t)p * C.nblocks;
+  int32_t *tile_group = C.tile_group + (int64_t)p * C.tile_stride;
+  int32_t *blk_group = C.blk_group + (int64_t)p * C.nblocks;
+  int run = 0, ng = 0, nq = 0, nt = 0;
+  for (int i0 = 0; i0 < C.nblocks; i0 += blockDim.x) {
+    const int i = i0 + tid;
+    const int v = i < C.nblocks ? pd[i] : 0;
+    int tot, g_tot, q_tot, t_tot;
+    const int cnt = run + block_excl_scan(v, wsum32, tot) + v;
+    const bool has = i < C.nblocks && cnt > 0;
+    const int nqt = (cnt + 127) >> 7;
+    const int g = ng + block_excl_scan(has ? 1 : 0, wsum32, g_tot);
+    const int qoff = nq + block_excl_scan(has ? cnt : 0, wsum32, q_tot);
+    const int tile0 = nt + block_excl_scan(has ? nqt : 0, wsum32, t_tot);
+    if (has) {
+      GemmGroup G;
+      G.a = (int64_t)i * kGemmPointChunk;
+      G.b = G.a + kGemmPointChunk < C.g.ix.n ? G.a + kGemmPointChunk : C.g.ix.n;
+      G.soff = (int64_t)qoff * kCoverPairFloats;
+      G.qoff = qoff;
+      G.qcount = cnt;
+      G.nqt = nqt;
+      G.nch = 1;
+      G.tile0 = tile0;
+      G.pad = 0;
+      groups[g] = G;
+      for (int t = 0; t < nqt; t++) tile_group[tile0 + t] = g;
+    }
+    if (i < C.nblocks) blk_group[i] = has ? g : -1;
+    run += tot;
+    ng += g_tot;
+    nq += q_tot;
+    nt += t_tot;
+  }
+  if (tid == 0) {
+    int32_t *pp = C.pplan + p * P_INTS;
+    pp[P_NGROUPS] = ng;
+    pp[P_NTQ] = nq;
+    pp[P_NTILES] = nt;
+    atomicAdd(&C.cctr->groups, (unsigned long long)ng);
+    atomicAdd(&C.cctr->tiles, (unsigned long long)nt);
+    atomicAdd(&C.cctr->handover_bytes, (unsigned long long)nq * (kCoverPairFloats * 4ull));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_cover_scatter(CoverArgs C) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); q < C.g.nq; q += (int64_t)gridDim.x * 4) {
+    const int p = C.q_pass[q];
+    if (p < 0) continue;
+    const Task t = C.g.tasks[q];
+    const int B0 = (int)(t.a / kGemmPointChunk), B1 = (int)((t.b - 1) / kGemmPointChunk);
+    const GemmGroup *groups = C.groups + (int64_t)p * C.nblocks;
+    const int64_t pbase = (int64_t)p * C.pair_stride;
+    for (int B = B0 + lane; B <= B1; B += 64) {
+      const GemmGroup *G = groups + C.blk_group[(int64_t)p * C.nblocks + B];
+      const int qoff = G->qoff;
+      const int nsteps = (int)((G->b - G->a + 127) >> 7);
+      const int row = atomicAdd(&C.pfill[(int64_t)p * C.nblocks + B], 1);
+      C.gq[pbase + qoff + row] = (int32_t)q;
+      // (16-byte entries: the group's matrix starts at soff / 4 = 32 qoff, a row is 2 nsteps entries)
+      C.qb_base[pbase + C.q_off[q] + (B - B0)] = qoff * (kCoverPairFloats / 4) + row * nsteps * 2;
+    }
+  }
+}
+
 #endif  // WANN_DT == 0 (grouping)
 
 // ------------------------------------------------------------------------------------------------
@@ -880,7 +1067,11 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_wide4(GemmArgs A) {
 // positions in another); candidates below the current cut are inserted one by one with a ballot + one-lane shift.
 // (one wave, one query; result in registers: lane l < filled holds the window-relative position of a selected candidate,
 // `cut` / `blk_bound` are the two bounds on everything that was not selected, FLT_MAX = nothing was left out that way)
-__device__ __forceinline__ void select_scores(const f32x4 *erow, int64_t nblk, int &sel_pos, int &sel_cnt, float &cut, float &blk_bound) {
+// `load(blk)` returns block blk's entry: EntryRow for a shared-window group, CoverRow for a query of the cover path (there a
+// candidate outside the query's own window comes back as 'no score'; entries need not be sorted any more, nothing below
+// relies on it).
+template <class LOAD>
+__device__ __forceinline__ void select_scores(const LOAD &load, int64_t nblk, int &sel_pos, int &sel_cnt, float &cut, float &blk_bound) {
   const int lane = lane_id();
   {
     uint32_t top_s = 0xffffffffu, thr = 0xffffffffu;  // 0xffffffff (no float maps to it) = empty slot; thr = lane kSelect-1
@@ -888,7 +1079,7 @@ __device__ __forceinline__ void select_scores(const f32x4 *erow, int64_t nblk, i
     float bound = kHuge;
     for (int64_t b0 = 0; b0 < nblk; b0 += 64) {
       const int64_t blk = b0 + lane;
-      const f32x4 e = (blk < nblk) ? erow[blk] : f32x4{kHuge, kHuge, kHuge, kHuge};
+      const f32x4 e = (blk < nblk) ? load(blk) : f32x4{kHuge, kHuge, kHuge, kHuge};
       bound = fminf(bound, e[3]);
       if (b0 == 0) {
         // The list starts as the kSelect smallest of the first 64 blocks' MINIMA, by one bitonic sort across the wave (21
@@ -953,26 +1144,56 @@ __device__ __forceinline__ void select_scores(const f32x4 *erow, int64_t nblk, i
 // (what a hand-over entry says about its position's score: the entry itself)
 template <int METRIC>
 __device__ __forceinline__ float entry_score(float e) { return e; }
+__device__ __forceinline__ float no_entry() { return kHuge; }
 #else  // byte rows
 #include "wann_gemm_kernels_bytes.inc"
+__device__ __forceinline__ float no_entry() { return __uint_as_float(kNoKey); }
 #endif
 
+// a query's hand-over entries, block by block (two blocks per 128-position step: one per half wave)
+struct EntryRow {  // shared-window group: the query's row of the group's matrix
+  const f32x4 *erow;
+  __device__ __forceinline__ f32x4 operator()(int64_t blk) const { return erow[blk]; }
+};
+// Cover path: block 0 is the first half of the 128-position step that holds the window's first position a; step s of the label
+// argsort lies in position block s >> 4, whose cover group keeps this query's row at entry qb[(s >> 4) - B0].  The WINDOW MASK:
+// a cover group scores the whole block for every query on its list, so a candidate at a position outside [a, b) is dropped here
+// (only the window's first and last step can hold one).  A block's fourth entry stays as it is: it bounds every position the
+// block kept to itself, inside the window or not.
+struct CoverRow {
+  const f32x4 *sc;
+  const int32_t *qb;
+  int64_t s0, a, b;
+  int32_t B0;
+  __device__ __forceinline__ f32x4 operator()(int64_t blk) const {
+    const int64_t s = s0 + (blk >> 1), p0 = s << 7;
+    f32x4 e = sc[(int64_t)qb[(int32_t)(s >> 4) - B0] + (int64_t)(((int)s & 15) * 2 + (int)(blk & 1))];
+    if (p0 < a || p0 + 128 > b) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const uint32_t ix6 = __float_as_uint(e[c]) & 63u;
+        const int64_t pos = p0 + 32 * (ix6 >> 4) + 8 * ((ix6 >> 2) & 3) + 4 * (blk & 1) + (ix6 & 3);
+        if (pos < a || pos >= b) e[c] = no_entry();
+      }
+    }
+    return e;
+  }
+};
 
-// one wave per grouped query: exact distances of the selected candidates, (dist, id) order, proof
+
+// one wave, one query: exact distances of the selected candidates, (dist, id) order, proof.  The query's entries are
+// load(0 .. nblk - 1); block 0 starts at position `abase` of the label argsort; [wa, wb) is the query's own window (what
+// the rescue scan may touch); n_rescued / n_unproven: the counters of the path that calls.
 WANN_GNS_BEGIN
-template <int METRIC>
-__global__ __launch_bounds__(256) void k_rerank(GemmArgs A, Counters *ctr) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+template <int METRIC, class LOAD>
+__device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L, const int qrow, const LOAD &load, const int64_t nblk_sel,
+                                             const int64_t abase, const int64_t wa, const int64_t wb, unsigned long long *n_rescued,
+                                             unsigned long long *n_unproven) {
   const IndexView &ix = A.ix;
-  const int lane = lane_id(), wv = threadIdx.x >> 6;
+  const int lane = lane_id();
   const int K = A.k;
   const int qw = qv_words(ix);
-  const int per_wave = wave_lds_common_bytes(qw) + ((K + 1) & ~1) * 8;
-  const WaveLds L = carve_wave_lds(smem + (size_t)wv * per_wave, qw, K, true);
-  const int64_t ntq = A.plan[P_NTQ];
-  for (int64_t tq = (int64_t)blockIdx.x * 4 + wv; tq < ntq; tq += (int64_t)gridDim.x * 4) {
-    const GemmGroup grp = A.groups[A.tq_group[tq]];
-    const int qrow = A.gq[tq];
+  {
     float q2 = 0.f;  // (the query row is on its way while the selection runs)
 #if WANN_BYTE_ROWS
     for (int i = lane; i < qw; i += 64) L.qv[i] = stage_query_word(A.queries, qrow, i, ix.d);  // packed bytes, k_brute's rule
@@ -983,17 +1204,16 @@ __global__ __launch_bounds__(256) void k_rerank(GemmArgs A, Counters *ctr) {
       q2 = fmaf(v, v, q2);
     }
 #endif
-    const int64_t nblk_sel = ((grp.b - grp.a + 127) >> 7) * 2;
     int sel_pos, cnt;
     float cut_sel, cut_blk;
 #if WANN_BYTE_ROWS
-    select_keys<METRIC>(reinterpret_cast<const f32x4 *>(A.scores + grp.soff) + (int64_t)A.tq_local[tq] * nblk_sel, nblk_sel, sel_pos, cnt, cut_sel, cut_blk);
+    select_keys<METRIC>(load, nblk_sel, sel_pos, cnt, cut_sel, cut_blk);
 #else
-    select_scores(reinterpret_cast<const f32x4 *>(A.scores + grp.soff) + (int64_t)A.tq_local[tq] * nblk_sel, nblk_sel, sel_pos, cnt, cut_sel, cut_blk);
+    select_scores(load, nblk_sel, sel_pos, cnt, cut_sel, cut_blk);
 #endif
     for (int o = 32; o > 0; o >>= 1) q2 += __shfl_xor(q2, o);
     int rid = 0;
-    if (lane < cnt) rid = ix.fi_sorted[grp.a + sel_pos];
+    if (lane < cnt) rid = ix.fi_sorted[abase + sel_pos];
     L.cand_id[lane] = rid;
     WAVE_SYNC();
     const float dist = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, cnt, 0);
@@ -1021,7 +1241,10 @@ __global__ __launch_bounds__(256) void k_rerank(GemmArgs A, Counters *ctr) {
     const float cerr = 3.02f * 1.52587890625e-5f + A.acc_factor * (float)(3 * ix.d + 8) * 5.9604645e-8f;
     // + 2^-17 relative for the six mantissa bits that carry the position (|score| <= |q||p| resp. 2 (|q|^2 + |p|^2))
     const float cerr2 = cerr + 7.62939453125e-6f;
-    const float E = (METRIC == 1) ? cerr2 * sqrtf(q2 * pmax) : 2.f * cerr2 * (q2 + pmax);
+    // (never zero: an all-zero query under the inner product scores 0 everywhere, the position bits make every entry a
+    // different denormal, and d_k = -0 < cut would "prove" a top k among points that all tie -- only the scan's id order
+    // settles those)
+    const float E = fmaxf((METRIC == 1) ? cerr2 * sqrtf(q2 * pmax) : 2.f * cerr2 * (q2 + pmax), 1.17549435e-38f);
 #endif
     const int kk = cnt < K ? cnt : K;
     float dk = -3.402823466e+38f;  // k-th exact distance (the worst one that is returned)
@@ -1042,12 +1265,11 @@ __global__ __launch_bounds__(256) void k_rerank(GemmArgs A, Counters *ctr) {
       // (Labels that correlate with the geometry put a query's best points next to each other: the same block.)
       int m = 0, p0;
       m = wave_merge(L.lbeam, m, K, lane < cnt, ((u64)fkey(dist) << 32) | ((u64)(uint32_t)rid << 1), L.cand_key, &p0);
-      const int64_t w = grp.b - grp.a, nblk = ((w + 127) >> 7) * 2;
-      const f32x4 *erow = reinterpret_cast<const f32x4 *>(A.scores + grp.soff) + (int64_t)A.tq_local[tq] * nblk;
+      const int64_t nblk = nblk_sel;
       int scanned = 0;
       bool gave_up = false;
       for (int64_t b0 = 0; b0 < nblk && !gave_up; b0 += 64) {
-        const float m4 = (b0 + lane < nblk) ? entry_score<METRIC>(erow[b0 + lane][3]) : kHuge;
+        const float m4 = (b0 + lane < nblk) ? entry_score<METRIC>(load(b0 + lane)[3]) : kHuge;
         u64 hide = ballot64(m4 < kHugeTest && m4 + qoff - E <= dk + E);
         while (hide) {
           const int64_t b = b0 + ctz64(hide);
@@ -1056,9 +1278,9 @@ __global__ __launch_bounds__(256) void k_rerank(GemmArgs A, Counters *ctr) {
             gave_up = true;
             break;
           }
-          const int64_t pos = (b >> 1) * 128 + 32 * (lane >> 4) + 8 * ((lane >> 2) & 3) + 4 * (b & 1) + (lane & 3);
-          const bool valid = pos < w;
-          const int r2 = valid ? ix.fi_sorted[grp.a + pos] : 0;
+          const int64_t pos = abase + (b >> 1) * 128 + 32 * (lane >> 4) + 8 * ((lane >> 2) & 3) + 4 * (b & 1) + (lane & 3);
+          const bool valid = pos >= wa && pos < wb;  // (the query's own window: a cover group's block reaches beyond it)
+          const int r2 = valid ? ix.fi_sorted[pos] : 0;
           L.cand_id[lane] = r2;
           WAVE_SYNC();
           const float d2 = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, 64, 0);
@@ -1075,17 +1297,55 @@ __global__ __launch_bounds__(256) void k_rerank(GemmArgs A, Counters *ctr) {
         }
         outn = m;
         proven = true;
-        if (lane == 0) atomicAdd(&ctr->gemm_rescued, 1ull);
+        if (lane == 0) atomicAdd(n_rescued, 1ull);
       }
     }
     if (lane == 0) {
       A.out_cnt[ti] = outn;
       if (!proven) {
         A.brute_list[atomicAdd(A.brute_count, 1)] = ti;
-        atomicAdd(&ctr->gemm_unproven, 1ull);
+        atomicAdd(n_unproven, 1ull);
       }
     }
     WAVE_SYNC();
+  }
+}
+
+// one wave per grouped query of the shared-window path
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_rerank(GemmArgs A, Counters *ctr) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int wv = threadIdx.x >> 6;
+  const int qw = qv_words(A.ix);
+  const int per_wave = wave_lds_common_bytes(qw) + ((A.k + 1) & ~1) * 8;
+  const WaveLds L = carve_wave_lds(smem + (size_t)wv * per_wave, qw, A.k, true);
+  const int64_t ntq = A.plan[P_NTQ];
+  for (int64_t tq = (int64_t)blockIdx.x * 4 + wv; tq < ntq; tq += (int64_t)gridDim.x * 4) {
+    const GemmGroup grp = A.groups[A.tq_group[tq]];
+    const int64_t nblk = ((grp.b - grp.a + 127) >> 7) * 2;
+    const EntryRow load{reinterpret_cast<const f32x4 *>(A.scores + grp.soff) + (int64_t)A.tq_local[tq] * nblk};
+    rerank_query<METRIC>(A, L, A.gq[tq], load, nblk, grp.a, grp.a, grp.b, &ctr->gemm_rescued, &ctr->gemm_unproven);
+  }
+}
+
+// one wave per query of the cover path that belongs to pass C.pass: its entries lie in the cover groups of the position blocks
+// its window touches (contiguous block numbers; k_cover_scatter left the place of its row in each)
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_rerank_cover(CoverArgs C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const GemmArgs &A = C.g;
+  const int wv = threadIdx.x >> 6;
+  const int qw = qv_words(A.ix);
+  const int per_wave = wave_lds_common_bytes(qw) + ((A.k + 1) & ~1) * 8;
+  const WaveLds L = carve_wave_lds(smem + (size_t)wv * per_wave, qw, A.k, true);
+  if (C.pass >= C.cplan[CP_NPASS]) return;
+  for (int64_t q = (int64_t)blockIdx.x * 4 + wv; q < A.nq; q += (int64_t)gridDim.x * 4) {
+    if (C.q_pass[q] != C.pass) continue;  // (wave-uniform)
+    const Task t = A.tasks[q];
+    const int64_t s0 = t.a >> 7, nblk = (((t.b - 1) >> 7) - s0 + 1) * 2;
+    const CoverRow load{reinterpret_cast<const f32x4 *>(A.scores), C.qb_base + (int64_t)C.pass * C.pair_stride + C.q_off[q], s0, t.a, t.b,
+                        (int32_t)(t.a / kGemmPointChunk)};
+    rerank_query<METRIC>(A, L, (int)q, load, nblk, s0 << 7, t.a, t.b, &C.cctr->rescued, &C.cctr->unproven);
   }
 }
 WANN_GNS_END
@@ -1093,6 +1353,21 @@ WANN_GNS_END
 // ------------------------------------------------------------------------------------------------
 // launchers: the float32 unit holds the entry points (wann_gemm_device.h) and hands float16 / byte indexes to their units'
 // (a null return = launched; otherwise the error text)
+// LDS of the selection / re-rank kernels: four waves x (staged query row, candidate arrays, the k-entry merge list)
+static inline size_t rerank_lds_bytes(const IndexView &ix, int k) {
+  return (size_t)4 * (((query_words(ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((k + 1) & ~1) * 8);
+}
+WANN_GNS_BEGIN
+static hipError_t launch_rerank_cover_unit(const CoverArgs &c, void *stream) {  // this unit's k_rerank_cover
+  const GemmArgs &a = c.g;
+  const int blocks = (int)std::min<int64_t>(4096, (a.nq + 3) / 4);
+  const size_t lds = rerank_lds_bytes(a.ix, a.k);
+  if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank_cover<1>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
+  else hipLaunchKernelGGL(k_rerank_cover<0>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
+  return hipGetLastError();
+}
+WANN_GNS_END
+
 #if WANN_DT != 0
 namespace WANN_DT_NS_G {
 static const char *gerr_of(hipError_t e) { return e == hipSuccess ? nullptr : hipGetErrorString(e); }
@@ -1159,24 +1434,29 @@ const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream) {
 const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const int blocks = (int)std::min<int64_t>(4096, (a.nq + 3) / 4);
-  const size_t lds = (size_t)4 * (((query_words(a.ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((a.k + 1) & ~1) * 8);
+  const size_t lds = rerank_lds_bytes(a.ix, a.k);
   if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank<1>, dim3(blocks), dim3(256), lds, s, a, ctr);
   else hipLaunchKernelGGL(k_rerank<0>, dim3(blocks), dim3(256), lds, s, a, ctr);
   return gerr_of(hipGetLastError());
 }
+
+const char *launch_rerank_cover(const CoverArgs &c, void *stream) { return gerr_of(launch_rerank_cover_unit(c, stream)); }
 }  // namespace WANN_DT_NS_G
 #else  // WANN_DT == 0
 namespace dt_u8 {
+const char *launch_rerank_cover(const CoverArgs &c, void *stream);
 const char *launch_point_terms(const IndexView &ix, int32_t *term, void *stream);
 const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
 }
 namespace dt_i8 {
+const char *launch_rerank_cover(const CoverArgs &c, void *stream);
 const char *launch_point_terms(const IndexView &ix, int32_t *term, void *stream);
 const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
 }
 namespace dt_f16 {
+const char *launch_rerank_cover(const CoverArgs &c, void *stream);
 const char *launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);
 const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
@@ -1263,10 +1543,37 @@ int launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream) {
   if (a.ix.dtype == 3) return gtyped(dt_f16::launch_select_rerank(a, ctr, stream));
   hipStream_t s = (hipStream_t)stream;
   const int blocks = (int)std::min<int64_t>(4096, (a.nq + 3) / 4);
-  const size_t lds = (size_t)4 * (((a.ix.stride * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((a.k + 1) & ~1) * 8);
+  const size_t lds = rerank_lds_bytes(a.ix, a.k);
   if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank<1>, dim3(blocks), dim3(256), lds, s, a, ctr);
   else hipLaunchKernelGGL(k_rerank<0>, dim3(blocks), dim3(256), lds, s, a, ctr);
   return gcheck(hipGetLastError());
+}
+
+int launch_cover_plan(const CoverArgs &c, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned qb = (unsigned)((c.g.nq + 255) / 256);
+  hipLaunchKernelGGL(k_cover_count, dim3(qb), dim3(256), 0, s, c);
+  hipLaunchKernelGGL(k_cover_blocks, dim3(1), dim3(1024), 0, s, c);
+  hipLaunchKernelGGL(k_cover_assign, dim3(1), dim3(1024), 0, s, c);
+  hipLaunchKernelGGL(k_cover_plan, dim3((unsigned)c.max_passes), dim3(1024), 0, s, c);
+  hipLaunchKernelGGL(k_cover_scatter, dim3((unsigned)std::min<int64_t>(2048, (c.g.nq + 3) / 4)), dim3(256), 0, s, c);
+  return gcheck(hipGetLastError());
+}
+
+int launch_cover_pass(const CoverArgs &c, int pass, int num_cus, void *stream) {
+  // the pass's plan, groups, tiles and query lists stand where the score kernels look for a batch's
+  GemmArgs a = c.g;
+  a.plan = c.pplan + pass * P_INTS;
+  a.groups = c.groups + (int64_t)pass * c.nblocks;
+  a.tile_group = c.tile_group + (int64_t)pass * c.tile_stride;
+  a.gq = c.gq + (int64_t)pass * c.pair_stride;
+  if (launch_gemm_scores(a, num_cus, stream)) return 1;
+  CoverArgs cp = c;
+  cp.pass = pass;
+  if (c.g.ix.dtype == 1) return gtyped(dt_u8::launch_rerank_cover(cp, stream));
+  if (c.g.ix.dtype == 2) return gtyped(dt_i8::launch_rerank_cover(cp, stream));
+  if (c.g.ix.dtype == 3) return gtyped(dt_f16::launch_rerank_cover(cp, stream));
+  return gcheck(launch_rerank_cover_unit(cp, stream));
 }
 
 #endif  // WANN_DT == 0

@@ -208,15 +208,15 @@ WANN_GNS_END
 // select_scores on keys: the kSelect smallest keys of the blocks' (three smallest) entries, sorted in lanes 0 .. kSelect-1;
 // `cut` / `blk_bound` are the DISTANCES of the two bounds on everything that was not selected (FLT_MAX = nothing was left out
 // that way): an unselected position's distance is >= the bound, possibly equal to it.
-template <int METRIC>
-__device__ __forceinline__ void select_keys(const f32x4 *erow, int64_t nblk, int &sel_pos, int &sel_cnt, float &cut, float &blk_bound) {
+template <int METRIC, class LOAD>
+__device__ __forceinline__ void select_keys(const LOAD &load, int64_t nblk, int &sel_pos, int &sel_cnt, float &cut, float &blk_bound) {
   const int lane = lane_id();
   uint32_t top_s = kNoKey, thr = kNoKey;  // kNoKey = empty slot; thr = lane kSelect-1
   int top_p = 0, filled = 0;
   uint32_t bound = kNoKey;
   for (int64_t b0 = 0; b0 < nblk; b0 += 64) {
     const int64_t blk = b0 + lane;
-    const u32x4 e = (blk < nblk) ? __builtin_bit_cast(u32x4, erow[blk]) : u32x4{kNoKey, kNoKey, kNoKey, kNoKey};
+    const u32x4 e = (blk < nblk) ? __builtin_bit_cast(u32x4, load(blk)) : u32x4{kNoKey, kNoKey, kNoKey, kNoKey};
     bound = min(bound, e[3]);
     if (b0 == 0) {  // the list starts as the kSelect smallest of the first 64 blocks' minima: one bitonic sort across the wave
       uint32_t key = e[0];

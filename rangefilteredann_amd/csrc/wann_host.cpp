@@ -371,8 +371,67 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   ga.prof = I.g_prof.p;
 #endif
   if (launch_group_windows(ga, W.ctr.p, st)) throw HipError(std::string("k_group_*: ") + gemm_launch_last_error());
+  // Cover groups (opt-in): what the window grouping left over is grouped by position block of the label argsort.  A (query,
+  // block) pair hands over kCoverPairFloats floats; a batch that needs more than the score buffer holds runs in passes over
+  // query ranges, planned on the device all at once.  The host cannot know how many passes the windows need without waiting,
+  // so it enqueues the most that nq queries of full width could need (at most kCoverMaxPasses; the device leaves what lies
+  // beyond to the exact scan); the launches of an unused pass find an empty plan.
+  CoverArgs ca{};
+  bool cover = I.dense_windows.load() != 0;
+  if (cover) {
+    constexpr int64_t kCoverMaxPasses = 64;
+    const int64_t nblocks = (I.view.n + kGemmPointChunk - 1) / kGemmPointChunk;
+    const int64_t cap_pairs = std::min<int64_t>(nq * nblocks, (int64_t)(64ll << 20) / kCoverPairFloats);
+    I.g_scores.ensure((size_t)cap_pairs * kCoverPairFloats);
+    ga.scores = I.g_scores.p;  // (the window groups' limit stays score_cap)
+    // a pass starts queries until pass_pairs pairs are reached: it ends below pass_pairs + nblocks = cap_pairs
+    const int64_t pass_pairs = cap_pairs == nq * nblocks ? cap_pairs : cap_pairs - nblocks;
+    if (pass_pairs < nblocks || pass_pairs < 1) cover = false;  // (an index of billions of points: a query's blocks alone would fill the buffer)
+    if (cover) {
+      const int64_t max_passes = std::min<int64_t>(kCoverMaxPasses, (nq * nblocks + pass_pairs - 1) / pass_pairs);
+      const int64_t pair_stride = std::min<int64_t>(cap_pairs, nq * nblocks), tile_stride = pair_stride / 128 + nblocks + 1;
+      const size_t n_ints = (size_t)(CP_INTS + (nblocks + 1) + max_passes * (nblocks + 1) + max_passes * nblocks + max_passes * P_INTS);
+      I.c_ints.ensure(n_ints);
+      I.c_badp.ensure((size_t)nblocks + 1);
+      I.c_blk_group.ensure((size_t)(max_passes * nblocks));
+      I.c_groups.ensure((size_t)(max_passes * nblocks));
+      I.c_tile_group.ensure((size_t)(max_passes * tile_stride));
+      I.c_gq.ensure((size_t)(max_passes * pair_stride));
+      I.c_qb_base.ensure((size_t)(max_passes * pair_stride));
+      I.c_q_pass.ensure((size_t)nq);
+      I.c_q_off.ensure((size_t)nq);
+      HIP_CHECK(hipMemsetAsync(I.c_ints.p, 0, n_ints * sizeof(int32_t), st));
+      HIP_CHECK(hipMemsetAsync(W.ints.p + I_BRUTE_COUNT, 0, sizeof(int32_t), st));  // k_cover_count / _assign rebuild the exact scan's list
+      ca.g = ga;
+      ca.nblocks = (int32_t)nblocks;
+      ca.max_passes = (int32_t)max_passes;
+      ca.pass_pairs = (int32_t)pass_pairs;
+      ca.pair_stride = (int32_t)pair_stride;
+      ca.tile_stride = (int32_t)tile_stride;
+      // (WANN_DENSE_ALWAYS under test hooks: no gate, so that small test batches reach the path)
+      ca.min_rows = T.dense_always ? 0 : kCoverMinScanBytes / std::max<int64_t>(1, (int64_t)I.view.d * element_bytes(I.dtype));
+      ca.cplan = I.c_ints.p;
+      ca.diff = ca.cplan + CP_INTS;
+      ca.pdiff = ca.diff + (nblocks + 1);
+      ca.pfill = ca.pdiff + max_passes * (nblocks + 1);
+      ca.pplan = ca.pfill + max_passes * nblocks;
+      ca.badp = I.c_badp.p;
+      ca.blk_group = I.c_blk_group.p;
+      ca.groups = I.c_groups.p;
+      ca.tile_group = I.c_tile_group.p;
+      ca.gq = I.c_gq.p;
+      ca.q_pass = I.c_q_pass.p;
+      ca.q_off = I.c_q_off.p;
+      ca.qb_base = I.c_qb_base.p;
+      ca.cctr = &W.ctr.p->cover;
+      if (launch_cover_plan(ca, st)) throw HipError(std::string("k_cover_*: ") + gemm_launch_last_error());
+    }
+  }
   if (launch_gemm_scores(ga, I.num_cus, st)) throw HipError(std::string("k_gemm_scores: ") + gemm_launch_last_error());
   if (launch_select_rerank(ga, W.ctr.p, st)) throw HipError(std::string("k_rerank: ") + gemm_launch_last_error());
+  if (cover)
+    for (int p = 0; p < ca.max_passes; p++)
+      if (launch_cover_pass(ca, p, I.num_cus, st)) throw HipError(std::string("cover pass: ") + gemm_launch_last_error());
 #ifdef WANN_GEMM_PROF
   unsigned long long h[8];
   HIP_CHECK(hipMemcpyAsync(h, I.g_prof.p, 64, hipMemcpyDeviceToHost, st));
@@ -494,7 +553,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   // depend on it: what the dense path does not take goes through the exact scan.
   bool tried_dense = false;
   if (I.host().spec.kind == WANN_KIND_PREFILTER && nq >= 32 && T.gemm &&
-      (I.dense_idle < 2 || (I.dense_batches & 7) == 0 || T.dense_always)) {
+      (I.dense_idle < 2 || (I.dense_batches & 7) == 0 || T.dense_always || I.dense_windows.load())) {
     dense_prefilter(I, T, W, d_queries, nq, k, st);
     tried_dense = true;
   }
@@ -1055,6 +1114,11 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   if (tried_dense) I.dense_idle = W.h_ctr->gemm_queries ? 0 : I.dense_idle.load() + 1;
   last.gemm_unproven = (int64_t)W.h_ctr->gemm_unproven;
   last.gemm_rescued = (int64_t)W.h_ctr->gemm_rescued;
+  if (I.host().spec.kind == WANN_KIND_PREFILTER) {  // (dense_mu is held)
+    const CoverCounters &cc = W.h_ctr->cover;
+    I.last_cover = wann_dense_window_counters{(int64_t)cc.queries, (int64_t)cc.unproven, (int64_t)cc.rescued, (int64_t)cc.groups,
+                                              (int64_t)cc.tiles,   (int64_t)cc.passes,   (int64_t)cc.handover_bytes};
+  }
   last.deep_handoffs = (int64_t)W.h_ctr->deep_handoffs;
   last.lookaheads_used = (int64_t)W.h_ctr->lookaheads_used;
   last.big_searches = (int64_t)W.h_ctr->big_searches;

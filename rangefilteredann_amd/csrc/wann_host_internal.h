@@ -155,6 +155,12 @@ struct wann_index {
   DevBuf<unsigned long long> g_slot_key, g_score_used;
   DevBuf<float> g_scores;
   DevBuf<unsigned long long> g_prof;
+  // cover groups (wann_set_dense_windows): distinct wide windows of a PrefilterIndex batch on the matrix cores, grouped by
+  // position block.  c_ints is what a batch clears: cplan | diff | pdiff | pfill | pplan
+  std::atomic<int> dense_windows{0};
+  DevBuf<int32_t> c_ints, c_badp, c_blk_group, c_tile_group, c_gq, c_q_pass, c_q_off, c_qb_base;
+  DevBuf<GemmGroup> c_groups;
+  wann_dense_window_counters last_cover{};  // of the last batch (under dense_mu)
   hipStream_t own_stream = nullptr;
   hipStream_t side_stream = nullptr;  // companion (big) k_search launches, concurrent with the caller's stream
   wann_counters last{};

@@ -189,6 +189,25 @@ class Index {
     return counters_dict(c);
   }
 
+  // PrefilterIndex only: distinct wide windows on the matrix cores (wann_set_dense_windows); returns the previous setting
+  bool set_dense_windows(bool on) {
+    const int rc = wann_set_dense_windows(h_, on ? 1 : 0);
+    if (rc < 0) raise_last("set_dense_windows failed");
+    return rc != 0;
+  }
+  py::dict dense_window_counters() const {
+    wann_dense_window_counters c;
+    if (wann_get_dense_window_counters(h_, &c)) raise_last("dense_window_counters failed");
+    py::dict d;
+    d["queries"] = c.queries;
+    d["unproven"] = c.unproven;
+    d["rescued"] = c.rescued;
+    d["groups"] = c.groups;
+    d["tiles"] = c.tiles;
+    d["passes"] = c.passes;
+    d["handover_bytes"] = c.handover_bytes;
+    return d;
+  }
   py::dict counters() const {
     wann_counters c;
     wann_get_counters(h_, &c);
@@ -286,7 +305,9 @@ static void add_variant(py::module_ &m, const std::string &agnostic) {
           "points"_a, "filter_values"_a, "build_params"_a = default_build_params())
         .def("batch_search",
              [](C &self, py::array q, py::object f, uint64_t nq, const QueryParams &qp) { return self.search(q, f, nq, "", qp); },
-             "queries"_a, "filters"_a, "num_queries"_a, "query_params"_a);
+             "queries"_a, "filters"_a, "num_queries"_a, "query_params"_a)
+        .def("set_dense_windows", &C::set_dense_windows, "on"_a)
+        .def("dense_window_counters", &C::dense_window_counters);
     common_defs(c);
   }
   {

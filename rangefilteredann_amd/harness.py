@@ -79,6 +79,16 @@ def prefilter_index_constructor(metric, dtype, float16=False):
     return _constructor("PrefilterIndex", metric, dtype, float16)
 
 
+def use_dense_windows(index, on=True):
+    """Distinct wide windows of a PrefilterIndex batch on the matrix cores (`set_dense_windows`: same rows as the exact scan, a
+    fraction of its time on wide windows).  Only an index object that has the option is touched: the same driver runs over other
+    implementations of the reference's classes."""
+    setter = getattr(index, "set_dense_windows", None)
+    if on and setter is not None:
+        setter(True)
+    return index
+
+
 def postfilter_vamana_constructor(metric, dtype, float16=False):
     return _constructor("PostfilterVamanaIndex", metric, dtype, float16)
 
@@ -151,7 +161,7 @@ def get_queries_and_gt(folder, dataset_name, filter_width):
 
 
 def write_synthetic_dataset(folder, dataset_name, n, d, num_queries, widths: Sequence[str] = ("2pow-3",), seed=1234,
-                            top_k=TOP_K):
+                            top_k=TOP_K, dense_windows=True):
     """A dataset folder in the reference's layout from the SURVEY.md 8(d) recipes: 'SIFT-like' integer-valued vectors for
     Euclidean names, unit-norm mixture vectors for '*angular*' names; distinct labels ((perm + 0.5) / n); windows as the
     reference generates them (`generate_datasets/filter_generation_utils.py:11-52`, data-distribution branch): w = int(n * 2^p)
@@ -180,7 +190,7 @@ def write_synthetic_dataset(folder, dataset_name, n, d, num_queries, widths: Seq
     np.save(os.path.join(folder, f"{dataset_name}_queries.npy"), queries)
     np.save(os.path.join(folder, f"{dataset_name}_filter-values.npy"), labels)
     metric = "mips" if angular else "Euclidian"
-    exact = prefilter_index_constructor(metric, "float")(data, labels)
+    exact = use_dense_windows(prefilter_index_constructor(metric, "float")(data, labels), dense_windows)
     sorted_labels = np.sort(labels)
     for width in widths:
         p = int(width.replace("2pow", ""))
@@ -223,6 +233,7 @@ class Settings:
     # recall is still taken against the dataset's stored ground truth of the original data.  Graph caches go to a subdirectory
     # of their own: a float16 index's graphs are those of the ROUNDED points, under the same file names as the float32 graphs.
     dtype: str = "float"
+    dense_windows: bool = True  # the prefiltering experiment scores distinct wide windows on the matrix cores (--no-dense-windows: exact scan)
 
 
 class Experiments:
@@ -266,7 +277,7 @@ class Experiments:
     def run_prefiltering_experiment(self, all_results, dataset_name, filter_width):
         data, queries, filter_values, metric = self._dataset(dataset_name)
         t0 = time.time()
-        index = prefilter_index_constructor(metric, self.s.dtype, float16=True)(data, filter_values)
+        index = use_dense_windows(prefilter_index_constructor(metric, self.s.dtype, float16=True)(data, filter_values), self.s.dense_windows)
         print(f"Prefiltering index build time: {time.time() - t0:.3f}s", flush=True)
         ranges, gt = get_queries_and_gt(self.s.dataset_folder, dataset_name, filter_width)
         qp = build_query_params(k=TOP_K, beam_size=0, verbose=self.s.verbose)
@@ -463,6 +474,8 @@ def main(argv=None):
     ap.add_argument("--num_final_multiplies", type=int, default=None)
     ap.add_argument("--dataset", type=str, default=None)
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--no-dense-windows", action="store_true",
+                    help="ground truth and the prefiltering experiment keep the exact scan for distinct wide windows")
     ap.add_argument("--dont_write_to_results_file", action="store_true")
     ap.add_argument("--vamana_tree_split_factor", type=int)
     ap.add_argument("--alpha", type=float)
@@ -486,7 +499,7 @@ def main(argv=None):
             ap.error("--memory needs --dataset and --index_type or --vamana_tree_split_factor")
         if args.synthetic:
             n, d, nq = (int(x) for x in args.synthetic.split(","))
-            write_synthetic_dataset(args.dataset_folder, args.dataset, n, d, nq, ["2pow-3"])
+            write_synthetic_dataset(args.dataset_folder, args.dataset, n, d, nq, ["2pow-3"], dense_windows=not args.no_dense_windows)
         return memory_main(args)
     methods = ALL_METHODS if args.all_methods else tuple(m for m in ALL_METHODS if getattr(args, m))
     if not methods:
@@ -498,12 +511,13 @@ def main(argv=None):
     if args.synthetic:
         n, d, nq = (int(x) for x in args.synthetic.split(","))
         for name in datasets:
-            write_synthetic_dataset(args.dataset_folder, name, n, d, nq, [""] if name == "adversarial-100-angular" else widths)
+            write_synthetic_dataset(args.dataset_folder, name, n, d, nq, [""] if name == "adversarial-100-angular" else widths,
+                                    dense_windows=not args.no_dense_windows)
     settings = Settings(dataset_folder=args.dataset_folder, results_file_prefix=args.results_file_prefix,
                         beam_sizes=[args.beam_search_size] if args.beam_search_size else list(BEAM_SIZES),
                         final_multiplies=[args.num_final_multiplies] if args.num_final_multiplies else list(FINAL_MULTIPLIES),
                         verbose=args.verbose, write_results=not args.dont_write_to_results_file, threads=threads, methods=methods,
-                        dtype=args.dtype)
+                        dtype=args.dtype, dense_windows=not args.no_dense_windows)
     Experiments(settings).run(
         datasets, widths,
         alphas=[args.alpha] if args.alpha is not None else ALPHAS,
