@@ -1243,8 +1243,10 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
     const float cerr2 = cerr + 7.62939453125e-6f;
     // (never zero: an all-zero query under the inner product scores 0 everywhere, the position bits make every entry a
     // different denormal, and d_k = -0 < cut would "prove" a top k among points that all tie -- only the scan's id order
-    // settles those)
-    const float E = fmaxf((METRIC == 1) ? cerr2 * sqrtf(q2 * pmax) : 2.f * cerr2 * (q2 + pmax), 1.17549435e-38f);
+    // settles those).  The inner product's |q||p| is formed from the two roots: q2 * pmax underflows to 0 in fp32 once |q||p| is
+    // below about 2^-75 (rows and queries both scaled by 2^-40: E fell to FLT_MIN under scores of 2^-80 and wrong rows were
+    // certified) and overflows above 2^64.
+    const float E = fmaxf((METRIC == 1) ? cerr2 * (sqrtf(q2) * sqrtf(pmax)) : 2.f * cerr2 * (q2 + pmax), 1.17549435e-38f);
 #endif
     const int kk = cnt < K ? cnt : K;
     float dk = -3.402823466e+38f;  // k-th exact distance (the worst one that is returned)
