@@ -220,6 +220,35 @@ typedef struct {
 } wann_dense_window_counters;
 int wann_get_dense_window_counters(const wann_index *index, wann_dense_window_counters *out);
 
+/* Exact answers for small windows of the graph-backed tree indexes (opt-in; 0 = off, the state of a new index).  With a limit
+ * L > 0 a query whose window [istart, eend) of the label order holds 0 < w <= L points is ONE exact task over those positions,
+ * whatever the query method: its row is what the reference's brute-force branch returns for that window -- the k nearest
+ * in-window points, distances in the exact scan's fp32 order, ordered by (distance, sorted position), ids through `decoding`,
+ * the class's own padding when w < k -- instead of the rows of the doubling graph search (so the reference's rows are no longer
+ * what such a query returns).  The rule is tested once, on the query's whole window, before three_split / fenwick decompose it
+ * and before the super tree scans its levels.  Queries with w > L, empty windows and windows outside the label span take the
+ * ordinary path and return the ordinary rows bit for bit.  In a batch of at least 32 queries the flagged queries take the dense
+ * prefilter path (shared-window groups and cover groups on the matrix cores, under its usual gates: windows of >= 1 024
+ * points, >= 32 queries per block, 2 GiB of eligible rows per batch, k <= 16, the row-length limits per element type); what it
+ * does not take or cannot prove goes to the exact scan, and both return the same rows bit for bit.  The scans and the dense
+ * launches run beside the graph searches of the same batch.  While the limit is non-zero a batch holds the index's dense
+ * buffers: the asynchronous lanes then run one batch at a time.  A call with wann_query_params::verbose set ignores the option
+ * (its purpose is the reference's trace), and so does wann_predict_costs.  Applies to every replica of WANN_DEVICES and to every
+ * call form.  Returns the previous limit or a NEGATIVE error: -WANN_ERR_INVALID for a null index or a negative limit,
+ * -WANN_ERR_UNSUPPORTED for any kind but WANN_KIND_TREE_VAMANA and WANN_KIND_SUPER (the stand-alone post filter has no sorted
+ * labels; PrefilterIndex and the prefilter-leaf tree are exact already). */
+int64_t wann_set_exact_windows(wann_index *index, int64_t max_points);
+/* Exact-window counters of the last batch (all zero with the option off). */
+typedef struct {
+  int64_t queries;       /* queries answered exactly because of the option                                   */
+  int64_t dense_queries; /* of those: taken by the matrix-core path (shared-window groups + cover groups)    */
+  int64_t unproven;      /* of dense_queries: sent on to the exact scan because the scores could not prove the top k */
+  int64_t rescued;       /* of dense_queries: proven after an exact scan of a few 64-position blocks         */
+  int64_t passes;        /* cover passes over query ranges                                                   */
+  int64_t rows_scanned;  /* rows the exact scan scored for `queries`                                         */
+} wann_exact_window_counters;
+int wann_get_exact_window_counters(const wann_index *index, wann_exact_window_counters *out);
+
 /* Introspection (tests, tools). */
 int64_t wann_num_points(const wann_index *index);
 int64_t wann_dim(const wann_index *index);

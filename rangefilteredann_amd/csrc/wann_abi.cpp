@@ -643,6 +643,13 @@ int wann_batch_search(wann_index *I, const void *queries, const float *ranges, i
       I->last_cover.tiles += c.tiles;
       I->last_cover.passes = std::max(I->last_cover.passes, c.passes);
       I->last_cover.handover_bytes += c.handover_bytes;
+      const wann_exact_window_counters &e = R->last_exact;
+      I->last_exact.queries += e.queries;
+      I->last_exact.dense_queries += e.dense_queries;
+      I->last_exact.unproven += e.unproven;
+      I->last_exact.rescued += e.rescued;
+      I->last_exact.passes = std::max(I->last_exact.passes, e.passes);
+      I->last_exact.rows_scanned += e.rows_scanned;
     }
   }
   return WANN_OK;
@@ -668,6 +675,36 @@ int wann_get_dense_window_counters(const wann_index *I, wann_dense_window_counte
   wann_index *M = const_cast<wann_index *>(I);
   std::lock_guard<std::mutex> lk(M->dense_mu);
   *out = I->last_cover;
+  return WANN_OK;
+}
+
+int64_t wann_set_exact_windows(wann_index *I, int64_t max_points) {
+  // (the previous limit is >= 0, so errors are the NEGATIVE codes here)
+  if (!I) return -(int64_t)fail(WANN_ERR_INVALID, "null argument");
+  if (max_points < 0) return -(int64_t)fail(WANN_ERR_INVALID, "exact windows: the limit must be >= 0");
+  const int kind = I->host().spec.kind;
+  if (kind != WANN_KIND_TREE_VAMANA && kind != WANN_KIND_SUPER)
+    return -(int64_t)fail(WANN_ERR_UNSUPPORTED, "exact windows: VamanaRangeFilterTreeIndex and SuperOptimizedPostfilterTreeIndex only");
+  // (under dense_mu: a batch that runs with the old limit has finished and left its counters)
+  int64_t prev;
+  {
+    std::lock_guard<std::mutex> lk(I->dense_mu);
+    prev = I->exact_windows.exchange(max_points);
+    if (max_points == 0) I->last_exact = wann_exact_window_counters{};
+  }
+  for (auto &R : I->replicas) {
+    std::lock_guard<std::mutex> lr(R->dense_mu);
+    R->exact_windows = max_points;
+    if (max_points == 0) R->last_exact = wann_exact_window_counters{};
+  }
+  return prev;
+}
+
+int wann_get_exact_window_counters(const wann_index *I, wann_exact_window_counters *out) {
+  if (!I || !out) return fail(WANN_ERR_INVALID, "null argument");
+  wann_index *M = const_cast<wann_index *>(I);
+  std::lock_guard<std::mutex> lk(M->dense_mu);
+  *out = I->last_exact;
   return WANN_OK;
 }
 

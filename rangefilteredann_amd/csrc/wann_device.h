@@ -53,7 +53,10 @@ inline int query_words(const IndexView &v) { return v.dtype == 3 ? ((v.d + 15) &
 
 enum { T_EMPTY = 0, T_GRAPH = 1, T_BRUTE = 2, T_BRUTE_GATHER = 3, T_PARENT = 4 };
 // Task::flags: 1 = heavy (schedule first), 2 = final_beam_multiply forced to 1, 4 = speculative sub-task, 8 = mid priority
-// (a = beam level, b = parent task index); a T_PARENT task has a = number of sub-tasks, b = first sub-task slot
+// (a = beam level, b = parent task index); a T_PARENT task has a = number of sub-tasks, b = first sub-task slot;
+// 32 = exact window (wann_set_exact_windows): the T_BRUTE task in a query's slot 0 is the query's WHOLE window and its only task --
+// unlike the end scans of fenwick / three_split, which are T_BRUTE tasks of multi-task queries.  The dense path takes these.
+constexpr int kTaskExactWindow = 32;
 enum { M_OPTIMIZED = 0, M_THREE_SPLIT = 1, M_FENWICK = 2 };
 
 // One unit of device work: search partition `part` (T_GRAPH) or scan sorted rows [a,b) (T_BRUTE)
@@ -89,6 +92,8 @@ struct Counters {
   unsigned long long lookaheads_issued;  // look-ahead searches handed to pollers (used or not)
   unsigned long long empty_windows;      // tree classes: queries whose window lies outside the index's label range (the reference prints a line for each)
   CoverCounters cover;
+  // wann_set_exact_windows: queries answered exactly because of the option, and the rows k_brute scored for them
+  unsigned long long exact_queries, exact_rows;
 };
 
 struct RouteArgs {
@@ -115,6 +120,10 @@ struct RouteArgs {
   int32_t *risk_count;                // graph tasks whose predicted beam (k * partition / window) reaches half of cap_inkernel:
                                       // they may have to double beyond it (the host then starts the continuation pollers)
   int32_t *brute_list, *brute_count;
+  // wann_set_exact_windows: a query whose whole window holds at most exact_limit points is ONE flagged T_BRUTE task in its
+  // slot 0 (0 = off).  exact_unlisted: such tasks stay off brute_list -- the dense path lists what it does not take itself.
+  int64_t exact_limit;
+  int32_t exact_unlisted;
   // speculative doubling: a heavy task spawns one sub-task per beam level b0 << r, r = 0 .. nsub-1,
   // in the slots [sub_base0, sub_cap); the parent is resolved by whichever sub-task finishes last
   int32_t spec;         // 0 = off
@@ -303,6 +312,8 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
 // workgroups of that launch the runtime expects to be resident per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor); -1 on error
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
 int launch_brute(const BruteArgs &a, int blocks, void *stream);
+// wann_set_exact_windows: adds the widths of the flagged tasks on k_brute's list to Counters::exact_rows (nq sizes the launch)
+int launch_exact_rows(const BruteArgs &a, int64_t nq, void *stream);
 int launch_finalize(const FinalizeArgs &a, void *stream);
 int launch_task_cost(const CostArgs &a, void *stream);
 // bytes of LDS one wave of k_search needs: common scratch + the beam / seen-filter pool

@@ -37,6 +37,13 @@ struct GemmArgs {
   const float *queries;
   const Task *tasks;
   int64_t nq;
+  // Query q's task is tasks[q * tstride] (its slot 0): 1 for a PrefilterIndex.  The sorted kinds (wann_set_exact_windows) run
+  // with the index's task stride; only slots that hold an exact-window task are taken (dense_task).
+  int32_t tstride;
+  // Sorted kinds: the exact scan's list also holds tasks that are none of the dense path's business (end scans of fenwick /
+  // three_split, the reference's tiny windows), so the list is APPENDED to, never rebuilt (list_keep), and the queries the
+  // window grouping leaves over are listed by exactly one stage: k_group_scatter (scatter_lists) or the cover stage.
+  int32_t list_keep, scatter_lists;
   // grouping (open-addressing table over (a, b), `cap` slots, cleared per batch)
   unsigned long long *slot_key;
   int32_t *slot_count, *slot_group;

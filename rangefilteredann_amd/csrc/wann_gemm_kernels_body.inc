@@ -76,6 +76,13 @@ constexpr unsigned long long kEmptySlot = ~0ull;
 
 constexpr float kHuge = 3.0e38f, kHugeTest = 1.0e38f;  // stands for 'no score' where the bits must stay finite
 
+// Row of window position `pos`: a PrefilterIndex keeps its rows in the caller's order and reaches them through the label
+// argsort; the sorted kinds (tree / super indexes, wann_set_exact_windows) have no table -- their rows ARE in label order, the
+// position is the row.  The pointer is a kernel argument: the test is wave-uniform, one scalar compare.
+__device__ __forceinline__ int window_row(const IndexView &ix, int64_t pos) { return ix.fi_sorted ? ix.fi_sorted[pos] : (int)pos; }
+// a task the dense path may take: a PrefilterIndex window, or the exact window of a query of a sorted kind
+__device__ __forceinline__ bool dense_task(const Task &t) { return t.mode == T_BRUTE_GATHER || (t.mode == T_BRUTE && (t.flags & kTaskExactWindow)); }
+
 #if !WANN_BYTE_ROWS
 WANN_GNS_BEGIN
 __global__ void k_point_norms(IndexView ix, float *norm2, unsigned int *max_bits) {
@@ -119,8 +126,8 @@ __global__ void k_group_clear(GemmArgs A) {
 __global__ void k_group_insert(GemmArgs A) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= A.nq) return;
-  const Task t = A.tasks[q];
-  if (t.mode != T_BRUTE_GATHER) {
+  const Task t = A.tasks[q * A.tstride];
+  if (!dense_task(t)) {
     A.q_slot[q] = -1;
     return;
   }
@@ -182,7 +189,7 @@ __global__ __launch_bounds__(1024) void k_group_plan(GemmArgs A, Counters *ctr) 
   __shared__ unsigned long long wsum64[16];
   __shared__ int wsum32[16];
   const int tid = threadIdx.x;
-  if (tid == 0) *A.brute_count = 0;  // k_group_scatter rebuilds the exact-scan list
+  if (tid == 0 && !A.list_keep) *A.brute_count = 0;  // k_group_scatter rebuilds the exact-scan list
   const int nslots = A.plan[P_NSLOTS];
   unsigned long long used = 0;
   int ngroups = 0, ntq = 0, ntiles = 0;
@@ -251,7 +258,7 @@ __global__ void k_group_scatter(GemmArgs A) {
   if (pos < 0) return;
   const int g = A.slot_group[pos];
   if (g < 0) {
-    A.brute_list[atomicAdd(A.brute_count, 1)] = (int32_t)q;  // stand-alone PrefilterIndex: one task slot per query
+    if (A.scatter_lists) A.brute_list[atomicAdd(A.brute_count, 1)] = (int32_t)q * A.tstride;  // the query's slot 0
     return;
   }
   const int tq = A.groups[g].qoff + A.q_rank[q];
@@ -279,7 +286,7 @@ __global__ void k_group_scatter(GemmArgs A) {
 __device__ __forceinline__ int cover_state(const CoverArgs &C, int64_t q, int64_t &a, int64_t &b) {
   const int pos = C.g.q_slot[q];
   if (pos < 0 || C.g.slot_group[pos] >= 0) return 0;
-  const Task t = C.g.tasks[q];
+  const Task t = C.g.tasks[q * C.g.tstride];
   a = t.a;
   b = t.b;
   return b - a >= kCoverMinWindow ? 2 : 1;
@@ -291,7 +298,7 @@ __global__ void k_cover_count(CoverArgs C) {
   C.q_pass[q] = -1;
   int64_t a = 0, b = 0;
   const int st = cover_state(C, q, a, b);
-  if (st == 1) C.g.brute_list[atomicAdd(C.g.brute_count, 1)] = (int32_t)q;
+  if (st == 1) C.g.brute_list[atomicAdd(C.g.brute_count, 1)] = (int32_t)q * C.g.tstride;
   if (st == 2) {
     atomicAdd(&C.diff[a / kGemmPointChunk], 1);
     atomicAdd(&C.diff[(b - 1) / kGemmPointChunk + 1], -1);
@@ -359,7 +366,7 @@ __global__ __launch_bounds__(1024) void k_cover_assign(CoverArgs C) {
       atomicAdd(&pd[B0], 1);
       atomicAdd(&pd[B1 + 1], -1);
     } else if (wide) {
-      C.g.brute_list[atomicAdd(C.g.brute_count, 1)] = (int32_t)q;
+      C.g.brute_list[atomicAdd(C.g.brute_count, 1)] = (int32_t)q * C.g.tstride;
     }
     int ntaken;
     (void)block_excl_scan(ok ? 1 : 0, wsum32, ntaken);
@@ -431,7 +438,7 @@ __global__ __launch_bounds__(256) void k_cover_scatter(CoverArgs C) {
   for (int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); q < C.g.nq; q += (int64_t)gridDim.x * 4) {
     const int p = C.q_pass[q];
     if (p < 0) continue;
-    const Task t = C.g.tasks[q];
+    const Task t = C.g.tasks[q * C.g.tstride];
     const int B0 = (int)(t.a / kGemmPointChunk), B1 = (int)((t.b - 1) / kGemmPointChunk);
     const GemmGroup *groups = C.groups + (int64_t)p * C.nblocks;
     const int64_t pbase = (int64_t)p * C.pair_stride;
@@ -526,7 +533,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
     // (row numbers fetched ahead are clamped to THIS tile's last position: the block behind a tile's end belongs to another
     // workgroup -- fetching it, rows and all, was 6 % of the kernel's traffic)
     const int64_t tlast = p_end - 1;
-    if (tid < 128) rid[tid] = ix.fi_sorted[grp.a + min(p_begin + tid, wlast)];
+    if (tid < 128) rid[tid] = window_row(ix, grp.a + min(p_begin + tid, wlast));
     // A operand: row 32 wv + col, columns 16 s + 8 half + (0..7).  The query tile passes through the LDS (where
     // the points will be staged) so that the global loads are coalesced; loads are unconditional (clamped indices,
     // select afterwards).
@@ -588,7 +595,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
     WANN_FETCH_ROWS                                                                                        \
     if (tid < 128) {                                                                                       \
       if (!mips) pre_n = A.pnorm2[rid[tid]];                                                               \
-      pre_rid = ix.fi_sorted[grp.a + min((C0) + 128 + tid, tlast)];                                        \
+      pre_rid = window_row(ix, grp.a + min((C0) + 128 + tid, tlast));                                        \
     }                                                                                                      \
   }
 #else
@@ -600,7 +607,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
     }                                                                                                      \
     if (tid < 128) {                                                                                       \
       if (!mips) pre_n = A.pnorm2[rid[tid]];  /* (inner product: no |p|^2 -- a 4-byte gather costs a 128-byte line per point) */ \
-      pre_rid = ix.fi_sorted[grp.a + min((C0) + 128 + tid, tlast)];                                        \
+      pre_rid = window_row(ix, grp.a + min((C0) + 128 + tid, tlast));                                        \
     }                                                                                                      \
   }
 #endif
@@ -730,7 +737,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_wide(GemmArgs A) {
     const int64_t p_begin = (int64_t)ch * kGemmPointChunk;
     const int64_t p_end = (p_begin + kGemmPointChunk < w) ? (p_begin + kGemmPointChunk) : w;
     __syncthreads();  // the previous tile is done with the staging area
-    if (tid < 128) rid[tid] = ix.fi_sorted[grp.a + min(p_begin + tid, wlast)];
+    if (tid < 128) rid[tid] = window_row(ix, grp.a + min(p_begin + tid, wlast));
     // A operand, slab by slab through the LDS (coalesced global loads): row 32 wv + col, columns 128 sl + 16 s + 8 half + (0..7)
     u32x4 ah[S * SLABS], al[S * SR];
     {
@@ -789,7 +796,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_wide(GemmArgs A) {
     }                                                                                                      \
     if ((NEWSTEP) && tid < 128) {                                                                          \
       if (!mips) pre_n = A.pnorm2[rid[tid]];                                                               \
-      pre_rid = ix.fi_sorted[grp.a + min((C0) + 128 + tid, wlast)];                                        \
+      pre_rid = window_row(ix, grp.a + min((C0) + 128 + tid, wlast));                                        \
     }                                                                                                      \
   }
     // (four slabs: the A operand alone is 256 registers -- the fetch is then NOT overlapped with the MFMAs: the 64 registers
@@ -808,7 +815,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_wide(GemmArgs A) {
         // (the barrier that ended the previous slab: nobody reads Ps / base any more)
         if (!PIPE && sl == 0 && tid < 128) {  // (rid_cur = this step's rows; pre_rid = the next step's, published at the last slab)
           if (!mips) pre_n = A.pnorm2[rid_cur[tid]];
-          pre_rid = ix.fi_sorted[grp.a + min(c0 + 128 + tid, wlast)];
+          pre_rid = window_row(ix, grp.a + min(c0 + 128 + tid, wlast));
         }
 #pragma unroll
         for (int p = 0; p < 2; p++) {
@@ -931,7 +938,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_wide4(GemmArgs A) {
     const int64_t p_end = (p_begin + kGemmPointChunk < w) ? (p_begin + kGemmPointChunk) : w;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (nothing of the previous tile is on its way into R any more)
     __syncthreads();  // the previous tile is done with the staging area
-    if (tid < 128) rid[tid] = ix.fi_sorted[grp.a + min(p_begin + tid, wlast)];
+    if (tid < 128) rid[tid] = window_row(ix, grp.a + min(p_begin + tid, wlast));
     u32x4 ah[S * SLABS], al[S * SR];
     {
       constexpr int DP = W + 4;
@@ -1011,7 +1018,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_wide4(GemmArgs A) {
           }
           if (tid < 128) {
             if (sl == 0 && hf == 0) base_cur[tid] = (c0 + tid < p_end) ? (mips ? 0.f : pre_n) : kHuge;  // positions beyond the window never win
-            if (sl == 2 && hf == 0) pre_rid = ix.fi_sorted[grp.a + min(c0 + 128 + tid, wlast)];
+            if (sl == 2 && hf == 0) pre_rid = window_row(ix, grp.a + min(c0 + 128 + tid, wlast));
             if (sl == 2 && hf == 1) rid_nxt[tid] = pre_rid;
             if (sl == 3 && hf == 0 && !mips) pre_n = A.pnorm2[rid_nxt[tid]];
           }
@@ -1213,7 +1220,7 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
 #endif
     for (int o = 32; o > 0; o >>= 1) q2 += __shfl_xor(q2, o);
     int rid = 0;
-    if (lane < cnt) rid = ix.fi_sorted[abase + sel_pos];
+    if (lane < cnt) rid = window_row(ix, abase + sel_pos);
     L.cand_id[lane] = rid;
     WAVE_SYNC();
     const float dist = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, cnt, 0);
@@ -1223,7 +1230,7 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
       const u64 kl = rdlane64(key, l);
       rank += (kl < key || (kl == key && l < lane)) ? 1 : 0;
     }
-    const int ti = qrow;  // stand-alone PrefilterIndex: one task slot per query
+    const int ti = qrow * A.tstride;  // the query's slot 0 (stand-alone PrefilterIndex: one task slot per query)
     if (lane < cnt && rank < K) A.out_key[(size_t)ti * K + rank] = key;
     // proof: every unselected point has score >= cut, and |score - exact distance| <= E.
     // E: the products the bf16 split drops (q1 p3 + q3 p1 + q2 p2 + ...) <= 3.02 * 2^-16 |q||p| (Cauchy-Schwarz over
@@ -1282,7 +1289,7 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
           }
           const int64_t pos = abase + (b >> 1) * 128 + 32 * (lane >> 4) + 8 * ((lane >> 2) & 3) + 4 * (b & 1) + (lane & 3);
           const bool valid = pos >= wa && pos < wb;  // (the query's own window: a cover group's block reaches beyond it)
-          const int r2 = valid ? ix.fi_sorted[pos] : 0;
+          const int r2 = valid ? window_row(ix, pos) : 0;
           L.cand_id[lane] = r2;
           WAVE_SYNC();
           const float d2 = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, 64, 0);
@@ -1343,7 +1350,7 @@ __global__ __launch_bounds__(256) void k_rerank_cover(CoverArgs C) {
   if (C.pass >= C.cplan[CP_NPASS]) return;
   for (int64_t q = (int64_t)blockIdx.x * 4 + wv; q < A.nq; q += (int64_t)gridDim.x * 4) {
     if (C.q_pass[q] != C.pass) continue;  // (wave-uniform)
-    const Task t = A.tasks[q];
+    const Task t = A.tasks[q * A.tstride];
     const int64_t s0 = t.a >> 7, nblk = (((t.b - 1) >> 7) - s0 + 1) * 2;
     const CoverRow load{reinterpret_cast<const f32x4 *>(A.scores), C.qb_base + (int64_t)C.pass * C.pair_stride + C.q_off[q], s0, t.a, t.b,
                         (int32_t)(t.a / kGemmPointChunk)};

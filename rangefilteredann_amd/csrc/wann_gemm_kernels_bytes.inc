@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256, NCH > 4 ? 1 : 2) void k_gemm_scores_b(GemmArgs
     const int64_t p_end = (p_begin + kGemmPointChunk < w) ? (p_begin + kGemmPointChunk) : w;
     __syncthreads();  // the previous tile is done with the staging area
     const int64_t tlast = p_end - 1;
-    if (tid < 128) rid[tid] = ix.fi_sorted[grp.a + min(p_begin + tid, wlast)];
+    if (tid < 128) rid[tid] = window_row(ix, grp.a + min(p_begin + tid, wlast));
     // B operand: query 32 wv + col, bytes 32 s + 16 half + (0..15).  The tile's queries are packed into the staging area
     // (coalesced loads, clamped query rows, dead rows zero), each lane then takes its share and the query's sums.
     for (int idx = tid; idx < 128 * SW; idx += 256) {
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256, NCH > 4 ? 1 : 2) void k_gemm_scores_b(GemmArgs
     }                                                                                                                          \
     if (tid < 128) {                                                                                                           \
       if (need_term) pre_t = A.pterm[rid[tid]];                                                                                \
-      pre_rid = ix.fi_sorted[grp.a + min((C0) + 128 + tid, tlast)];                                                            \
+      pre_rid = window_row(ix, grp.a + min((C0) + 128 + tid, tlast));                                                            \
     }                                                                                                                          \
   }
     WANN_FETCHB(p_begin)

@@ -290,13 +290,24 @@ int method_code(const char *m) {
 // every query whose top-k cannot be proven from the MFMA scores) goes through the exact scan kernel.  Grouping,
 // tile planning and the hand-over to the exact scan all happen on the device: the host enqueues six launches and
 // never waits.
-void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *d_queries, int64_t nq, int k, hipStream_t st) {
-  // rows the score kernels take, per element type: float32 up to 512 floats (RedCaps), float16 up to 128 elements (the narrow
-  // kernel only), uint8 / int8 up to 512 bytes; everything longer stays on the exact scan
+// rows the score kernels take, per element type: float32 up to 512 floats (RedCaps), float16 up to 128 elements (the narrow
+// kernel only), uint8 / int8 up to 512 bytes; everything longer (and k > 16) stays on the exact scan
+static bool dense_rows_ok(const wann_index &I, int k) {
   const int dtype = I.view.dtype;
   const bool bytes = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8;
-  if (k > kSelect / 2 || (I.view.stride & 15)) return;
-  if (dtype == WANN_DTYPE_F16 ? query_words(I.view) > 128 : I.view.stride > (bytes ? 128 : 512)) return;
+  if (k > kSelect / 2 || (I.view.stride & 15)) return false;
+  if (dtype == WANN_DTYPE_F16 ? query_words(I.view) > 128 : I.view.stride > (bytes ? 128 : 512)) return false;
+  return true;
+}
+
+// tstride: task slots per query (the dense kernels read a query's slot 0).  sorted_exact: the exact windows of a tree / super
+// index (wann_set_exact_windows) -- rows in label order (no argsort table), cover groups always on, and an exact-scan list that
+// also holds other tasks: it is appended to, never rebuilt.
+void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *d_queries, int64_t nq, int k, hipStream_t st, int tstride = 1,
+                     bool sorted_exact = false) {
+  const int dtype = I.view.dtype;
+  const bool bytes = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8;
+  if (!dense_rows_ok(I, k)) return;
   if (!I.have_norms) {
     if (bytes) {  // exact integer sums of the rows (wann_gemm_kernels_bytes.inc)
       I.d_pterm.ensure((size_t)I.view.n);
@@ -307,6 +318,9 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
       I.d_pnorm2_max.ensure(1);
       HIP_CHECK(hipMemsetAsync(I.d_pnorm2_max.p, 0, sizeof(unsigned int), st));
       if (launch_point_norms(I.view, I.d_pnorm2.p, I.d_pnorm2_max.p, st)) throw HipError(std::string("k_point_norms: ") + gemm_launch_last_error());
+      // (not a double count: nothing else adds the float norms.  A PrefilterIndex has never reported them -- wann_device_bytes
+      // of existing indexes stays what it was -- while the byte terms above have been counted at first use from the start)
+      if (sorted_exact) I.device_bytes += (int64_t)(I.d_pnorm2.bytes() + I.d_pnorm2_max.bytes());
     }
     I.have_norms = true;
   }
@@ -335,6 +349,8 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   ga.queries = d_queries;
   ga.tasks = W.tasks.p;
   ga.nq = nq;
+  ga.tstride = tstride;
+  ga.list_keep = sorted_exact ? 1 : 0;
   ga.slot_key = I.g_slot_key.p;
   ga.slot_count = I.g_slot_count.p;
   ga.slot_group = I.g_slot_group.p;
@@ -370,24 +386,28 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   HIP_CHECK(hipMemsetAsync(I.g_prof.p, 0, 64, st));
   ga.prof = I.g_prof.p;
 #endif
-  if (launch_group_windows(ga, W.ctr.p, st)) throw HipError(std::string("k_group_*: ") + gemm_launch_last_error());
   // Cover groups (opt-in): what the window grouping left over is grouped by position block of the label argsort.  A (query,
   // block) pair hands over kCoverPairFloats floats; a batch that needs more than the score buffer holds runs in passes over
   // query ranges, planned on the device all at once.  The host cannot know how many passes the windows need without waiting,
   // so it enqueues the most that nq queries of full width could need (at most kCoverMaxPasses; the device leaves what lies
   // beyond to the exact scan); the launches of an unused pass find an empty plan.
   CoverArgs ca{};
-  bool cover = I.dense_windows.load() != 0;
+  bool cover = I.dense_windows.load() != 0 || sorted_exact;
+  constexpr int64_t kCoverMaxPasses = 64;
+  const int64_t nblocks = (I.view.n + kGemmPointChunk - 1) / kGemmPointChunk;
+  const int64_t cap_pairs = std::min<int64_t>(nq * nblocks, (int64_t)(64ll << 20) / kCoverPairFloats);
+  // a pass starts queries until pass_pairs pairs are reached: it ends below pass_pairs + nblocks = cap_pairs
+  const int64_t pass_pairs = cap_pairs == nq * nblocks ? cap_pairs : cap_pairs - nblocks;
+  if (pass_pairs < nblocks || pass_pairs < 1) cover = false;  // (an index of billions of points: a query's blocks alone would fill the buffer)
   if (cover) {
-    constexpr int64_t kCoverMaxPasses = 64;
-    const int64_t nblocks = (I.view.n + kGemmPointChunk - 1) / kGemmPointChunk;
-    const int64_t cap_pairs = std::min<int64_t>(nq * nblocks, (int64_t)(64ll << 20) / kCoverPairFloats);
     I.g_scores.ensure((size_t)cap_pairs * kCoverPairFloats);
     ga.scores = I.g_scores.p;  // (the window groups' limit stays score_cap)
-    // a pass starts queries until pass_pairs pairs are reached: it ends below pass_pairs + nblocks = cap_pairs
-    const int64_t pass_pairs = cap_pairs == nq * nblocks ? cap_pairs : cap_pairs - nblocks;
-    if (pass_pairs < nblocks || pass_pairs < 1) cover = false;  // (an index of billions of points: a query's blocks alone would fill the buffer)
-    if (cover) {
+  }
+  // (an appended list: the queries the window grouping leaves over are listed once -- by the cover stage where it runs)
+  ga.scatter_lists = (sorted_exact && cover) ? 0 : 1;
+  if (launch_group_windows(ga, W.ctr.p, st)) throw HipError(std::string("k_group_*: ") + gemm_launch_last_error());
+  if (cover) {
+    {
       const int64_t max_passes = std::min<int64_t>(kCoverMaxPasses, (nq * nblocks + pass_pairs - 1) / pass_pairs);
       const int64_t pair_stride = std::min<int64_t>(cap_pairs, nq * nblocks), tile_stride = pair_stride / 128 + nblocks + 1;
       const size_t n_ints = (size_t)(CP_INTS + (nblocks + 1) + max_passes * (nblocks + 1) + max_passes * nblocks + max_passes * P_INTS);
@@ -401,7 +421,7 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
       I.c_q_pass.ensure((size_t)nq);
       I.c_q_off.ensure((size_t)nq);
       HIP_CHECK(hipMemsetAsync(I.c_ints.p, 0, n_ints * sizeof(int32_t), st));
-      HIP_CHECK(hipMemsetAsync(W.ints.p + I_BRUTE_COUNT, 0, sizeof(int32_t), st));  // k_cover_count / _assign rebuild the exact scan's list
+      if (!sorted_exact) HIP_CHECK(hipMemsetAsync(W.ints.p + I_BRUTE_COUNT, 0, sizeof(int32_t), st));  // k_cover_count / _assign rebuild the exact scan's list
       ca.g = ga;
       ca.nblocks = (int32_t)nblocks;
       ca.max_passes = (int32_t)max_passes;
@@ -450,7 +470,15 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   if (qp.postfiltering_max_beam > (1 << 20)) throw std::runtime_error("postfiltering_max_beam too large");
   HIP_CHECK(hipSetDevice(I.device));
   std::unique_lock<std::mutex> dense_lock(I.dense_mu, std::defer_lock);
-  if (I.host().spec.kind == WANN_KIND_PREFILTER) dense_lock.lock();
+  const int kind = I.host().spec.kind;
+  // wann_set_exact_windows (graph-backed tree kinds): the dense buffers belong to the index, so a batch that runs with a
+  // non-zero limit holds dense_mu -- two asynchronous lanes then serialise (with the option off they never take the lock)
+  const bool exact_kind = kind == WANN_KIND_TREE_VAMANA || kind == WANN_KIND_SUPER;
+  const int64_t exact_set = exact_kind ? I.exact_windows.load() : 0;
+  if (kind == WANN_KIND_PREFILTER || exact_set > 0) dense_lock.lock();
+  if (exact_set > 0) I.last_exact = wann_exact_window_counters{};
+  // (a verbose call is the reference's trace: it ignores the option)
+  const int64_t exact_limit = qp.verbose ? 0 : exact_set;
   const int k = (int)qp.k;
   const int mcode = method_code(method);
   const bool tree = I.host().spec.kind == WANN_KIND_TREE_PREFILTER || I.host().spec.kind == WANN_KIND_TREE_VAMANA;
@@ -506,6 +534,12 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   ra.risk_count = W.ints.p + I_RISK;
   ra.brute_list = W.list_brute.p;
   ra.brute_count = W.ints.p + I_BRUTE_COUNT;
+  // exact windows: the dense path takes the flagged queries of a batch of >= 32 (and lists what it leaves to the scan).  Neither
+  // dense stage takes a window narrower than kGroupMinWindow / kCoverMinWindow: a limit below both flags no such window, and the
+  // dense launches -- all of them empty -- are left out.
+  const bool exact_dense = exact_limit >= std::min(kGroupMinWindow, kCoverMinWindow) && nq >= 32 && T.gemm && dense_rows_ok(I, k);
+  ra.exact_limit = exact_limit;
+  ra.exact_unlisted = exact_dense ? 1 : 0;
   ra.spec = spec ? 1 : 0;
   ra.spec_num = 8;
   ra.spec_extra = kSpecExtraLevels;
@@ -559,8 +593,21 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   }
   I.dense_batches++;
 
-  const bool may_brute = I.host().spec.kind != WANN_KIND_POSTFILTER && I.host().spec.kind != WANN_KIND_SUPER;
-  bool scans_aside = false;
+  const bool may_brute = I.host().spec.kind != WANN_KIND_POSTFILTER && (I.host().spec.kind != WANN_KIND_SUPER || exact_limit > 0);
+  // fenwick / three_split (range_filter_tree.h:297-401,473-540): every query has end scans AND graph searches -- up to two leaf-sized
+  // scans per query, a streaming read of ~8 GB per 10 000 queries at n = 10^6 -- and the two touch different task slots.  The scans
+  // run beside the searches on a stream of their own (they were 0.7 ms of a 3 ms batch in front of k_search); k_finalize_multi waits
+  // for both.  Batches of the one-task methods keep the single stream (their scans are the tiny windows' and mostly absent) --
+  // unless exact windows are on: those scans and the dense launches in front of them run beside the searches too.
+  const bool scans_aside = may_brute && (maxt > 1 || exact_limit > 0) && sized;
+  hipStream_t scan_st = st;
+  if (scans_aside) {
+    if (!W.scan_stream) HIP_CHECK(hipStreamCreateWithFlags(&W.scan_stream, hipStreamNonBlocking));
+    if (!W.ev_scan) HIP_CHECK(hipEventCreateWithFlags(&W.ev_scan, hipEventDisableTiming));
+    scan_st = W.scan_stream;
+    HIP_CHECK(hipStreamWaitEvent(scan_st, W.ev_route, 0));  // (recorded behind k_route and this batch's clears)
+  }
+  if (exact_dense) dense_prefilter(I, T, W, d_queries, nq, k, scan_st, maxt, true);
   if (may_brute) {
     BruteArgs ba{};
     ba.ix = I.view;
@@ -573,18 +620,6 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
     ba.out_key = W.out_key.p;
     ba.out_cnt = W.out_cnt.p;
     ba.ctr = W.ctr.p;
-    // fenwick / three_split (range_filter_tree.h:297-401,473-540): every query has end scans AND graph searches -- up to two leaf-sized
-    // scans per query, a streaming read of ~8 GB per 10 000 queries at n = 10^6 -- and the two touch different task slots.  The scans
-    // run beside the searches on a stream of their own (they were 0.7 ms of a 3 ms batch in front of k_search); k_finalize_multi waits
-    // for both.  Batches of the one-task methods keep the single stream (their scans are the tiny windows' and mostly absent).
-    scans_aside = maxt > 1 && sized;
-    hipStream_t scan_st = st;
-    if (scans_aside) {
-      if (!W.scan_stream) HIP_CHECK(hipStreamCreateWithFlags(&W.scan_stream, hipStreamNonBlocking));
-      if (!W.ev_scan) HIP_CHECK(hipEventCreateWithFlags(&W.ev_scan, hipEventDisableTiming));
-      scan_st = W.scan_stream;
-      HIP_CHECK(hipStreamWaitEvent(scan_st, W.ev_route, 0));  // (recorded behind k_route and this batch's clears)
-    }
     if (T.split_scan) {
       const size_t part_cap = (size_t)4 << 20, part_slots = 8192;  // 32 MiB of partial lists
       // (a list is only split while it has far fewer entries than there are waves)
@@ -604,6 +639,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
     const int brute_per_cu = byte_rows(I.view) ? 5 : (I.view.metric == 1 ? 3 : 2);
     int blocks = (int)std::min<int64_t>((int64_t)I.num_cus * brute_per_cu, (nq * std::min(maxt, 2) + kWavesPerBlock - 1) / kWavesPerBlock);
     if (launch_brute(ba, blocks, scan_st)) throw HipError(std::string("k_brute: ") + launch_last_error());
+    if (exact_limit > 0 && launch_exact_rows(ba, nq * std::min(maxt, 2), scan_st)) throw HipError(std::string("k_exact_rows: ") + launch_last_error());
     if (scans_aside) HIP_CHECK(hipEventRecord(W.ev_scan, scan_st));
   }
 
@@ -1114,6 +1150,15 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   if (tried_dense) I.dense_idle = W.h_ctr->gemm_queries ? 0 : I.dense_idle.load() + 1;
   last.gemm_unproven = (int64_t)W.h_ctr->gemm_unproven;
   last.gemm_rescued = (int64_t)W.h_ctr->gemm_rescued;
+  if (exact_limit > 0) {  // (dense_mu is held; the dense path of a sorted kind takes flagged queries only)
+    const CoverCounters &cc = W.h_ctr->cover;
+    I.last_exact.queries = (int64_t)W.h_ctr->exact_queries;
+    I.last_exact.dense_queries = (int64_t)(W.h_ctr->gemm_queries + cc.queries);
+    I.last_exact.unproven = (int64_t)(W.h_ctr->gemm_unproven + cc.unproven);
+    I.last_exact.rescued = (int64_t)(W.h_ctr->gemm_rescued + cc.rescued);
+    I.last_exact.passes = (int64_t)cc.passes;
+    I.last_exact.rows_scanned = (int64_t)W.h_ctr->exact_rows;
+  }
   if (I.host().spec.kind == WANN_KIND_PREFILTER) {  // (dense_mu is held)
     const CoverCounters &cc = W.h_ctr->cover;
     I.last_cover = wann_dense_window_counters{(int64_t)cc.queries, (int64_t)cc.unproven, (int64_t)cc.rescued, (int64_t)cc.groups,

@@ -161,6 +161,10 @@ struct wann_index {
   DevBuf<int32_t> c_ints, c_badp, c_blk_group, c_tile_group, c_gq, c_q_pass, c_q_off, c_qb_base;
   DevBuf<GemmGroup> c_groups;
   wann_dense_window_counters last_cover{};  // of the last batch (under dense_mu)
+  // wann_set_exact_windows (tree / super indexes): a query whose window holds at most this many points is answered exactly
+  // (0 = off).  A batch that runs with a non-zero limit holds dense_mu: the dense buffers above belong to the index.
+  std::atomic<int64_t> exact_windows{0};
+  wann_exact_window_counters last_exact{};  // of the last batch (under dense_mu)
   hipStream_t own_stream = nullptr;
   hipStream_t side_stream = nullptr;  // companion (big) k_search launches, concurrent with the caller's stream
   wann_counters last{};

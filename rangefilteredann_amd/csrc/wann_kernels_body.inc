@@ -926,7 +926,8 @@ struct Emitter {
   const RouteArgs &A;
   int64_t q;
   int n;
-  __device__ Emitter(const RouteArgs &a, int64_t qq) : A(a), q(qq), n(0) {}
+  bool exact;  // the query is one exact-window task (wann_set_exact_windows)
+  __device__ Emitter(const RouteArgs &a, int64_t qq) : A(a), q(qq), n(0), exact(false) {}
   // QueryParams::verbose: one entry of the descent's dump (RouteArgs::vroute)
   __device__ __forceinline__ void note(int64_t kind, int64_t a = 0, int64_t b = 0, int64_t c = 0, int64_t d = 0, int64_t size = 0) {
     if (!A.vroute) return;
@@ -956,7 +957,7 @@ struct Emitter {
       if (t.flags & 1) A.heavy_list[atomicAdd(A.heavy_count, 1)] = ti;
       else if (t.flags & 8) A.mid_list[atomicAdd(A.mid_count, 1)] = ti;
       else A.graph_list[atomicAdd(A.graph_count, 1)] = ti;
-    } else {
+    } else if (!((t.flags & kTaskExactWindow) && A.exact_unlisted)) {  // (the dense path lists the exact windows it leaves to the scan)
       A.brute_list[atomicAdd(A.brute_count, 1)] = ti;
     }
   }
@@ -1056,13 +1057,13 @@ struct Emitter {
     }
     push(t);
   }
-  __device__ __forceinline__ void brute(uint64_t a, uint64_t b) {  // rows [a,b) of the sorted order, no label test
+  __device__ __forceinline__ void brute(uint64_t a, uint64_t b, int32_t flags = 0) {  // rows [a,b) of the sorted order, no label test
     if (b <= a) return;
     Task t;
     t.query = (int32_t)q;
     t.mode = T_BRUTE;
     t.part = 0;
-    t.flags = 0;
+    t.flags = flags;
     t.a = (int64_t)a;
     t.b = (int64_t)b;
     t.lo = t.hi = 0.f;
@@ -1150,6 +1151,12 @@ __device__ __forceinline__ void emit_tree(Emitter &E, float lo0, float hi0, int 
     uint64_t istart, eend;
     first_ge2(ix.labels, ix.n, lo, hi, istart, eend);
     const uint64_t w = eend - istart;
+    // wann_set_exact_windows: tested once, on the query's whole window, before three_split decomposes it and before find_centre
+    if (it == 0 && w > 0 && w <= (uint64_t)E.A.exact_limit) {
+      E.exact = true;
+      E.brute(istart, eend, kTaskExactWindow);
+      return;
+    }
     Centre c;
     bool have_centre = false;
     if (mode != W_OPTIMIZED) have_centre = find_centre(ix, istart, eend, c);
@@ -1263,6 +1270,11 @@ __device__ __forceinline__ void emit_super(Emitter &E, float lo, float hi) {
   uint64_t istart, eend;
   first_ge2(ix.labels, ix.n, lo, hi, istart, eend);
   const uint64_t w = eend - istart;
+  if (w > 0 && w <= (uint64_t)E.A.exact_limit) {  // wann_set_exact_windows: before the level scan
+    E.exact = true;
+    E.brute(istart, eend, kTaskExactWindow);
+    return;
+  }
   int level;
   int64_t idx = 0;
   for (level = ix.nlevels - 1; level >= 0; level--) {
@@ -1332,6 +1344,37 @@ __global__ void k_route(RouteArgs A) {
     emit_tree(E, lo, hi, A.method == M_OPTIMIZED ? W_OPTIMIZED : (A.method == M_THREE_SPLIT ? W_THREE_SPLIT : W_FENWICK));
   }
   A.qtask_cnt[q] = E.n;
+  if ((KIND == 4 || KIND == 2) && A.exact_limit > 0) {
+    // (a query without a task: the dense grouping reads EVERY query's slot 0 -- it must not hold an earlier batch's window)
+    if (E.n == 0) {
+      Task t;
+      t.query = (int32_t)q;
+      t.mode = T_EMPTY;
+      t.part = 0;
+      t.flags = 0;
+      t.a = t.b = 0;
+      t.lo = lo;
+      t.hi = hi;
+      A.tasks[q * A.maxt] = t;
+    }
+    const unsigned long long em = __ballot(E.exact);  // one counter update per wave
+    if (em && (threadIdx.x & 63) == __builtin_ctzll(em)) atomicAdd(&A.ctr->exact_queries, (unsigned long long)__builtin_popcountll(em));
+  }
+}
+
+// wann_set_exact_windows: the rows k_brute scores for exact-window tasks = the widths of the flagged tasks on its list (the
+// slices of a split scan add up to the task).  A kernel of its own, launched with the option on only, keeps the count out of
+// k_brute's loop: a second running sum there cost the float32 instance 29 registers.  One counter update per wave.
+__global__ void k_exact_rows(const Task *tasks, const int32_t *list, const int32_t *list_count, Counters *ctr) {
+  const int total = *list_count;
+  unsigned long long rows = 0;
+  for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < total; i += (int)(gridDim.x * blockDim.x)) {
+    const Task t = tasks[list[i]];
+    if (t.mode == T_BRUTE && (t.flags & kTaskExactWindow) && t.b > t.a) rows += (unsigned long long)(t.b - t.a);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rows += __shfl_down(rows, o);
+  if ((threadIdx.x & 63) == 0 && rows) atomicAdd(&ctr->exact_rows, rows);
 }
 
 // Longest first: the heavy list comes out of k_route in query order; one workgroup reorders it by speculated level,
@@ -1471,6 +1514,13 @@ int launch_route(const RouteArgs &a, void *stream) {
     case 4: hipLaunchKernelGGL(k_route<4>, dim3(blocks), dim3(threads), 0, s, a); break;
     default: hipLaunchKernelGGL(k_route<2>, dim3(blocks), dim3(threads), 0, s, a); break;
   }
+  return check(hipGetLastError());
+}
+
+int launch_exact_rows(const BruteArgs &a, int64_t nq, void *stream) {
+  const int threads = 256, blocks = (int)std::min<int64_t>(64, (nq + threads - 1) / threads);
+  if (blocks <= 0) return 0;
+  hipLaunchKernelGGL(k_exact_rows, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, a.tasks, a.list, a.list_count, a.ctr);
   return check(hipGetLastError());
 }
 

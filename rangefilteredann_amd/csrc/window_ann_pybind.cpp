@@ -208,6 +208,25 @@ class Index {
     d["handover_bytes"] = c.handover_bytes;
     return d;
   }
+  // graph-backed tree indexes only: exact answers for windows of at most max_points points (wann_set_exact_windows; 0 = off);
+  // returns the previous limit
+  int64_t set_exact_windows(int64_t max_points) {
+    const int64_t rc = wann_set_exact_windows(h_, max_points);
+    if (rc < 0) raise_last("set_exact_windows failed");
+    return rc;
+  }
+  py::dict exact_window_counters() const {
+    wann_exact_window_counters c;
+    if (wann_get_exact_window_counters(h_, &c)) raise_last("exact_window_counters failed");
+    py::dict d;
+    d["queries"] = c.queries;
+    d["dense_queries"] = c.dense_queries;
+    d["unproven"] = c.unproven;
+    d["rescued"] = c.rescued;
+    d["passes"] = c.passes;
+    d["rows_scanned"] = c.rows_scanned;
+    return d;
+  }
   py::dict counters() const {
     wann_counters c;
     wann_get_counters(h_, &c);
@@ -349,7 +368,9 @@ static void add_variant(py::module_ &m, const std::string &agnostic) {
              [](C &self, py::array q, py::object f, uint64_t nq, const std::string &method, const QueryParams &qp) {
                return self.search(q, f, nq, method, qp);
              },
-             "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a);
+             "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a)
+        .def("set_exact_windows", &C::set_exact_windows, "max_points"_a)
+        .def("exact_window_counters", &C::exact_window_counters);
     common_defs(c);
   }
   {
@@ -362,7 +383,9 @@ static void add_variant(py::module_ &m, const std::string &agnostic) {
           "build_params"_a = default_build_params())
         .def("batch_search",
              [](C &self, py::array q, py::object f, uint64_t nq, const QueryParams &qp) { return self.search(q, f, nq, "", qp); },
-             "queries"_a, "filters"_a, "num_queries"_a, "query_params"_a);
+             "queries"_a, "filters"_a, "num_queries"_a, "query_params"_a)
+        .def("set_exact_windows", &C::set_exact_windows, "max_points"_a)
+        .def("exact_window_counters", &C::exact_window_counters);
     common_defs(c);
   }
 }

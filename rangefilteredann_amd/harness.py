@@ -89,6 +89,16 @@ def use_dense_windows(index, on=True):
     return index
 
 
+def use_exact_windows(index, max_points=0):
+    """Exact answers for windows of at most `max_points` points on the graph-backed tree indexes (`set_exact_windows`: such a
+    query returns the exact scan's rows, not the reference's graph-search rows).  Only a non-zero limit is applied, and only to
+    an index object that has the option: the same driver runs over other implementations of the reference's classes."""
+    setter = getattr(index, "set_exact_windows", None)
+    if max_points and setter is not None:
+        setter(int(max_points))
+    return index
+
+
 def postfilter_vamana_constructor(metric, dtype, float16=False):
     return _constructor("PostfilterVamanaIndex", metric, dtype, float16)
 
@@ -234,6 +244,9 @@ class Settings:
     # of their own: a float16 index's graphs are those of the ROUNDED points, under the same file names as the float32 graphs.
     dtype: str = "float"
     dense_windows: bool = True  # the prefiltering experiment scores distinct wide windows on the matrix cores (--no-dense-windows: exact scan)
+    # --exact-windows N: the tree experiments answer windows of at most N points exactly (0 = off: the reference's rows).  The
+    # limit is part of the results file's name, so runs with and without it do not overwrite each other.
+    exact_windows: int = 0
 
 
 class Experiments:
@@ -304,6 +317,7 @@ class Experiments:
         tree = vamana_range_filter_tree_constructor(metric, self.s.dtype, float16=True)(
             data, filter_values, cutoff=1_000, split_factor=split_factor,
             build_params=BuildParams(64, 500, alpha, self._cache(f"{dataset_name}/")))
+        use_exact_windows(tree, self.s.exact_windows)
         build_time = time.time() - t0
         print(f"Vamana tree build time: {build_time:.3f}s", flush=True)
         memory = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss - rss0
@@ -336,6 +350,7 @@ class Experiments:
         tree = super_optimized_postfilter_tree_constructor(metric, self.s.dtype, float16=True)(
             data, filter_values, cutoff=1_000, split_factor=split_factor, shift_factor=shift_factor,
             build_params=BuildParams(64, 500, alpha, self._cache(f"{dataset_name}-super_opt_postfiltering/")))
+        use_exact_windows(tree, self.s.exact_windows)
         memory = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss - rss0
         gc.enable()
         build_time = time.time() - t0
@@ -350,7 +365,8 @@ class Experiments:
             return None
         os.makedirs(self.s.results_dir, exist_ok=True)
         half = "float16_" if self.s.dtype == "float16" else ""
-        path = os.path.join(self.s.results_dir, f"{self.s.results_file_prefix}{half}{dataset_name}_results.csv")
+        exact = f"exact{int(self.s.exact_windows)}_" if self.s.exact_windows else ""
+        path = os.path.join(self.s.results_dir, f"{self.s.results_file_prefix}{half}{exact}{dataset_name}_results.csv")
         if not os.path.exists(path):
             with open(path, "a") as f:
                 f.write(RESULTS_HEADER)
@@ -476,6 +492,9 @@ def main(argv=None):
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--no-dense-windows", action="store_true",
                     help="ground truth and the prefiltering experiment keep the exact scan for distinct wide windows")
+    ap.add_argument("--exact-windows", type=int, default=0, metavar="N",
+                    help="tree experiments: windows of at most N points are answered exactly (set_exact_windows; 0 = off); "
+                         "the limit becomes part of the results file's name")
     ap.add_argument("--dont_write_to_results_file", action="store_true")
     ap.add_argument("--vamana_tree_split_factor", type=int)
     ap.add_argument("--alpha", type=float)
@@ -517,7 +536,7 @@ def main(argv=None):
                         beam_sizes=[args.beam_search_size] if args.beam_search_size else list(BEAM_SIZES),
                         final_multiplies=[args.num_final_multiplies] if args.num_final_multiplies else list(FINAL_MULTIPLIES),
                         verbose=args.verbose, write_results=not args.dont_write_to_results_file, threads=threads, methods=methods,
-                        dtype=args.dtype, dense_windows=not args.no_dense_windows)
+                        dtype=args.dtype, dense_windows=not args.no_dense_windows, exact_windows=args.exact_windows)
     Experiments(settings).run(
         datasets, widths,
         alphas=[args.alpha] if args.alpha is not None else ALPHAS,
