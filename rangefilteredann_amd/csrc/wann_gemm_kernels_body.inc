@@ -1066,6 +1066,170 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_wide4(GemmArgs A) {
   }
 }
 
+// Rows of 513 .. 2048 floats (five to sixteen slabs; today's embedding models, GIST): a true K-loop with a run-time slab
+// count.  Only the fp32 accumulators of the wave's four 32 x 32 tiles live across the slabs of a step; BOTH operands move slab
+// by slab through the LDS -- at sixteen slabs the query operand alone would be 1024 registers.  The queries arrive already
+// split (k_split_queries, once per batch: GemmArgs::qsplit), so staging them is a copy; the points are split where they are
+// staged, as in the kernels above.  The unit of work is a (step, slab): stage both operands from the registers they were
+// fetched into | barrier | fetch the NEXT unit into registers | the slab's MFMAs | barrier.  The last slab runs only the
+// k-steps the row has (stride is a multiple of 16): what the staging areas hold beyond them is never read.  Arithmetic, tile
+// shape, selection network and hand-over format are k_gemm_scores_wide's.
+__global__ void k_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out) {
+  const int hw = stride >> 1;  // bf16 pairs per term
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq * hw) return;
+  const int64_t q = i / hw;
+  const int c = (int)(i - q * hw) * 2;
+  const float a = c < d ? queries[q * d + c] : 0.f, b = c + 1 < d ? queries[q * d + c + 1] : 0.f;
+  uint32_t hi, lo;
+  split2(a, b, hi, lo);
+  out[q * stride + (c >> 1)] = hi;
+  out[q * stride + hw + (c >> 1)] = lo;
+}
+
+__global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const IndexView &ix = A.ix;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  constexpr int W = 128, S = W / 16, RB = 4 * W + 16;
+  unsigned char *Ps = smem;                                      // [128][RB] points of the slab: hi | lo bf16
+  unsigned char *Qs = smem + 128 * RB;                           // [128][RB] queries of the slab, the same layout
+  float *base = reinterpret_cast<float *>(smem + 2 * 128 * RB);  // [128] per staged point: |p|^2 / 0
+  int *rid = reinterpret_cast<int *>(base + 128);                // [128] point rows of the step being fetched
+  constexpr int nx = W >> 4;  // 16-byte pieces per thread and half slab
+  const int half = lane >> 5, col = lane & 31;
+  const bool mips = ix.metric == 1;
+  const float scale = mips ? -1.f : -2.f;
+  const int ntiles = A.plan[P_NTILES];
+  const int stride = ix.stride, nslab = (stride + W - 1) / W;
+
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const GemmGroup grp = A.groups[A.tile_group[t]];
+    const int tl = t - grp.tile0, ch = tl / grp.nqt, q0 = (tl - ch * grp.nqt) << 7;
+    const int64_t w = grp.b - grp.a, wlast = w - 1;
+    const int64_t p_begin = (int64_t)ch * kGemmPointChunk;
+    const int64_t p_end = (p_begin + kGemmPointChunk < w) ? (p_begin + kGemmPointChunk) : w;
+    __syncthreads();  // the previous tile is done with the staging areas and the rows
+    if (tid < 128) rid[tid] = window_row(ix, grp.a + min(p_begin + tid, wlast));
+    // this thread's two query rows (64 p + tid / 4), split: stride words, hi pairs then lo pairs (rows beyond the group's last
+    // query repeat it; their lanes store nothing)
+    const unsigned char *qsrc[2];
+#pragma unroll
+    for (int p = 0; p < 2; p++)
+      qsrc[p] = reinterpret_cast<const unsigned char *>(A.qsplit + (int64_t)A.gq[grp.qoff + min(q0 + 64 * p + (tid >> 2), grp.qcount - 1)] * stride);
+    __syncthreads();  // the step's rows are in `rid`
+    const int myrow = q0 + 32 * wv + col;
+    const bool live = myrow < grp.qcount;
+    const int64_t nsteps = (w + 127) >> 7;
+    f32x4 *erow = reinterpret_cast<f32x4 *>(A.scores + grp.soff) + ((int64_t)(live ? myrow : q0) * nsteps + (p_begin >> 7)) * 2 + half;
+    // fetch pipeline: the next (step, slab) travels to registers during the MFMAs of the current one.  `rid` holds the rows of
+    // the step being fetched; it moves on to the next step when a step's LAST slab is staged (k_gemm_scores_wide's scheme).
+    // Offsets are clamped into the row: a last, partial slab fetches bytes it never multiplies.
+    f32x4 pre[2 * nx];
+    u32x4 qre[2 * nx];  // pieces 0 .. nx/2-1 of a half: hi pairs, the others: lo pairs
+    float pre_n = 0.f;
+    int pre_rid = 0;
+#define WANN_FETCHL(C0, SL, NEWSTEP)                                                                       \
+  {                                                                                                        \
+    _Pragma("unroll") for (int p = 0; p < 2; p++) {                                                        \
+      const float *src = ix.points + (int64_t)rid[64 * p + (tid >> 2)] * stride;                           \
+      _Pragma("unroll") for (int x = 0; x < nx; x++)                                                       \
+        pre[p * nx + x] = *reinterpret_cast<const f32x4 *>(src + min(W * (SL) + 4 * (tid & 3) + 16 * x, stride - 4)); \
+      _Pragma("unroll") for (int x = 0; x < nx; x++) {                                                     \
+        const int term = x / (nx / 2), cb = 2 * W * (SL) + 16 * (tid & 3) + 64 * (x % (nx / 2));           \
+        qre[p * nx + x] = *reinterpret_cast<const u32x4 *>(qsrc[p] + term * 2 * stride + min(cb, 2 * stride - 16)); \
+      }                                                                                                    \
+    }                                                                                                      \
+    if ((NEWSTEP) && tid < 128) {                                                                          \
+      if (!mips) pre_n = A.pnorm2[rid[tid]];                                                               \
+      pre_rid = window_row(ix, grp.a + min((C0) + 128 + tid, wlast));                                        \
+    }                                                                                                      \
+  }
+    WANN_FETCHL(p_begin, 0, true)
+    f32x16 acc[4];
+    for (int64_t c0 = p_begin; c0 < p_end; c0 += 128) {
+      for (int sl = 0; sl < nslab; sl++) {
+        // (the barrier that ended the previous unit: nobody reads Ps / Qs / base any more)
+#pragma unroll
+        for (int p = 0; p < 2; p++) {
+          unsigned char *dst = Ps + (64 * p + (tid >> 2)) * RB + 8 * (tid & 3);
+#pragma unroll
+          for (int x = 0; x < nx; x++) {
+            const f32x4 v = pre[p * nx + x];
+            uint32_t h0, l0, h1, l1;
+            split2(v[0], v[1], h0, l0);
+            split2(v[2], v[3], h1, l1);
+            *reinterpret_cast<uint2 *>(dst + 32 * x) = make_uint2(h0, h1);
+            *reinterpret_cast<uint2 *>(dst + 2 * W + 32 * x) = make_uint2(l0, l1);
+          }
+          unsigned char *qdst = Qs + (64 * p + (tid >> 2)) * RB + 16 * (tid & 3);
+#pragma unroll
+          for (int x = 0; x < nx; x++) *reinterpret_cast<u32x4 *>(qdst + (x / (nx / 2)) * 2 * W + 64 * (x % (nx / 2))) = qre[p * nx + x];
+        }
+        if (tid < 128) {
+          if (sl == 0) base[tid] = (c0 + tid < p_end) ? (mips ? 0.f : pre_n) : kHuge;  // positions beyond the window never win
+          if (sl == nslab - 1) rid[tid] = pre_rid;
+        }
+        __syncthreads();
+        {  // the next unit: the next slab of this step, or slab 0 of the next step (none after the tile's last unit)
+          const bool newstep = sl + 1 == nslab;
+          const int nsl = newstep ? 0 : sl + 1;
+          if (!newstep || c0 + 128 < p_end) WANN_FETCHL(c0 + 128, nsl, newstep)
+        }
+        if (sl == 0) {
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[j][r] = 0.f;
+        }
+        const unsigned char *pb = Ps + col * RB + 16 * half;
+        const unsigned char *qa = Qs + (32 * wv + col) * RB + 16 * half;
+        // A operand: two ds_read_b128 per k-step beside the eight of the B operand, for twelve MFMAs
+#define WANN_KSTEP(s)                                                                                      \
+  {                                                                                                        \
+    const bf16x8 a_hi = *reinterpret_cast<const bf16x8 *>(qa + 32 * (s));                                  \
+    const bf16x8 a_lo = *reinterpret_cast<const bf16x8 *>(qa + 2 * W + 32 * (s));                          \
+    bf16x8 bh[4], bl[4];                                                                                   \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                        \
+      bh[j] = *reinterpret_cast<const bf16x8 *>(pb + j * 32 * RB + 32 * (s));                              \
+      bl[j] = *reinterpret_cast<const bf16x8 *>(pb + j * 32 * RB + 2 * W + 32 * (s));                      \
+    }                                                                                                      \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[j], a_hi, acc[j], 0, 0, 0); \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[j], a_lo, acc[j], 0, 0, 0); \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[j], a_hi, acc[j], 0, 0, 0); \
+  }
+        const int ks = min(S, (stride - W * sl) >> 4);  // k-steps of this slab (workgroup-uniform)
+        if (ks == S) {
+#pragma unroll
+          for (int s = 0; s < S; s++) WANN_KSTEP(s)
+        } else {
+#pragma unroll 1
+          for (int s = 0; s < ks; s++) WANN_KSTEP(s)
+        }
+#undef WANN_KSTEP
+        if (sl + 1 < nslab) __syncthreads();  // every wave is done with this slab's operands
+      }
+      // the four smallest of this lane's 64 scores, sorted; low six mantissa bits = 16 j + reg (which position)
+      float m1 = kHuge, m2 = kHuge, m3 = kHuge, m4 = kHuge;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+          const f32x4 b4 = *reinterpret_cast<const f32x4 *>(base + 32 * j + 8 * g + 4 * half);
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const float sc = fmaf(scale, acc[j][4 * g + r], b4[r]);
+            const float x = __uint_as_float((__float_as_uint(sc) & ~63u) | (uint32_t)(16 * j + 4 * g + r));
+            insert4(m1, m2, m3, m4, x);
+          }
+        }
+      if (live) erow[(c0 - p_begin) >> 6] = f32x4{m1, m2, m3, m4};
+      __syncthreads();  // every wave is done with Ps / Qs / base
+    }
+#undef WANN_FETCHL
+  }
+}
+
 #endif  // WANN_DT == 0 (wide rows)
 
 // One wave per grouped query.  Its window's blocks each handed over their four smallest scores (sorted, position in
@@ -1494,6 +1658,13 @@ int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits
   return gcheck(hipGetLastError());
 }
 
+int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream) {
+  const int64_t pairs = nq * (stride >> 1);
+  if (pairs <= 0) return 0;
+  hipLaunchKernelGGL(k_split_queries, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, queries, nq, d, stride, out);
+  return gcheck(hipGetLastError());
+}
+
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream) {
   return gtyped(ix.dtype == 1 ? dt_u8::launch_point_terms(ix, term, stream) : dt_i8::launch_point_terms(ix, term, stream));
 }
@@ -1513,9 +1684,19 @@ int launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream) {
   if (a.ix.dtype == 2) return gtyped(dt_i8::launch_gemm_scores(a, num_cus, stream));
   if (a.ix.dtype == 3) return gtyped(dt_f16::launch_gemm_scores(a, num_cus, stream));
   if (a.ix.stride > 128) {  // 129 .. 512 floats: slabs of 128, A operand in registers, one workgroup per CU
-    if (a.ix.stride > 512 || (a.ix.stride & 15)) {
+    if (a.ix.stride > kGemmMaxFloats || (a.ix.stride & 15)) {
       g_gerr = "dimension too large for the dense prefilter tile";
       return 1;
+    }
+    if (a.ix.stride > 512) {  // 513 .. 2048 floats: run-time slab count, both operands staged per slab (queries pre-split)
+      if (!a.qsplit) {
+        g_gerr = "k_gemm_scores_long needs the split queries";
+        return 1;
+      }
+      const size_t ldsl = (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4;
+      if (gcheck(hipFuncSetAttribute((const void *)k_gemm_scores_long, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsl))) return 1;
+      hipLaunchKernelGGL(k_gemm_scores_long, dim3(num_cus > 0 ? num_cus : 256), dim3(256), ldsl, (hipStream_t)stream, a);
+      return gcheck(hipGetLastError());
     }
     const int slabs = (a.ix.stride + 127) / 128;
     // (four slabs: + the low halves of the last slab's A operand; the overlapped kernel: + its parity arrays and the raw half slab)

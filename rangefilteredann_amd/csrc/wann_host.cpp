@@ -290,13 +290,15 @@ int method_code(const char *m) {
 // every query whose top-k cannot be proven from the MFMA scores) goes through the exact scan kernel.  Grouping,
 // tile planning and the hand-over to the exact scan all happen on the device: the host enqueues six launches and
 // never waits.
-// rows the score kernels take, per element type: float32 up to 512 floats (RedCaps), float16 up to 128 elements (the narrow
-// kernel only), uint8 / int8 up to 512 bytes; everything longer (and k > 16) stays on the exact scan
-static bool dense_rows_ok(const wann_index &I, int k) {
+// rows the score kernels take, per element type: float32 up to 512 floats (the query operand in registers, RedCaps) -- up to
+// 2048 (kGemmMaxFloats) where WANN_DENSE_LONG_ROWS=1 opts in: k_gemm_scores_long stages both operands slab by slab, and until it
+// is timed against the scan no batch moves to it by default --, float16 up to 128 elements (the narrow kernel only), uint8 / int8
+// up to 512 bytes; everything longer (and k > 16) stays on the exact scan
+static bool dense_rows_ok(const wann_index &I, const Tuning &T, int k) {
   const int dtype = I.view.dtype;
   const bool bytes = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8;
   if (k > kSelect / 2 || (I.view.stride & 15)) return false;
-  if (dtype == WANN_DTYPE_F16 ? query_words(I.view) > 128 : I.view.stride > (bytes ? 128 : 512)) return false;
+  if (dtype == WANN_DTYPE_F16 ? query_words(I.view) > 128 : I.view.stride > (bytes ? 128 : T.dense_long ? kGemmMaxFloats : 512)) return false;
   return true;
 }
 
@@ -307,7 +309,10 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
                      bool sorted_exact = false) {
   const int dtype = I.view.dtype;
   const bool bytes = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8;
-  if (!dense_rows_ok(I, k)) return;
+  if (!dense_rows_ok(I, T, k)) return;
+  // rows of more than 512 floats need the batch's queries split into their bf16 terms (nq x stride x 4 bytes, below) before the
+  // device has grouped anything: a batch whose split would exceed 256 MiB (the score buffer's cap) stays on the exact scan
+  if (dtype == WANN_DTYPE_F32 && I.view.stride > 512 && (unsigned long long)nq * (unsigned long long)I.view.stride > (64ull << 20)) return;
   if (!I.have_norms) {
     if (bytes) {  // exact integer sums of the rows (wann_gemm_kernels_bytes.inc)
       I.d_pterm.ensure((size_t)I.view.n);
@@ -368,6 +373,17 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   ga.pnorm2 = I.d_pnorm2.p;
   ga.pnorm2_max_bits = I.d_pnorm2_max.p;
   ga.pterm = I.d_pterm.p;
+  if (dtype == WANN_DTYPE_F32 && I.view.stride > 512) {
+    // k_gemm_scores_long takes the queries already split into their bf16 terms: once per batch instead of once per (tile,
+    // step), nq x stride x 4 bytes.  Counted like the norms: a PrefilterIndex has never reported its dense buffers.
+    I.g_qsplit.ensure((size_t)nq * (size_t)I.view.stride);
+    if (sorted_exact && (int64_t)I.g_qsplit.bytes() > I.qsplit_counted) {
+      I.device_bytes += (int64_t)I.g_qsplit.bytes() - I.qsplit_counted;
+      I.qsplit_counted = (int64_t)I.g_qsplit.bytes();
+    }
+    if (launch_split_queries(d_queries, nq, I.view.d, I.view.stride, I.g_qsplit.p, st)) throw HipError(std::string("k_split_queries: ") + gemm_launch_last_error());
+    ga.qsplit = I.g_qsplit.p;
+  }
   ga.scores = I.g_scores.p;
   ga.score_cap = (int64_t)score_cap;
   ga.k = k;
@@ -537,7 +553,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   // exact windows: the dense path takes the flagged queries of a batch of >= 32 (and lists what it leaves to the scan).  Neither
   // dense stage takes a window narrower than kGroupMinWindow / kCoverMinWindow: a limit below both flags no such window, and the
   // dense launches -- all of them empty -- are left out.
-  const bool exact_dense = exact_limit >= std::min(kGroupMinWindow, kCoverMinWindow) && nq >= 32 && T.gemm && dense_rows_ok(I, k);
+  const bool exact_dense = exact_limit >= std::min(kGroupMinWindow, kCoverMinWindow) && nq >= 32 && T.gemm && dense_rows_ok(I, T, k);
   ra.exact_limit = exact_limit;
   ra.exact_unlisted = exact_dense ? 1 : 0;
   ra.spec = spec ? 1 : 0;

@@ -40,6 +40,7 @@ struct Tuning {
   long long deep_min_tasks = 4096;  // WANN_DEEP_MIN_TASKS: graph tasks from which a launch counts as saturated (deep-chain pollers)
   bool serialized = false;     // HIP_LAUNCH_BLOCKING / AMD_SERIALIZE_KERNEL / CUDA_LAUNCH_BLOCKING: launches never overlap
   float proof_factor = 3.f;    // WANN_PROOF_FACTOR, clamped to >= 3 (see dense_prefilter)
+  bool dense_long = false;     // WANN_DENSE_LONG_ROWS=1: float32 rows of 513 .. 2048 floats take the dense path too (opt-in: not yet timed against the scan)
   // hooks that force rare paths
   bool force_pollers = false, force_poll_timeout = false, la_eager = false, force_general = false, old_general = false,
        raw_big_lds = false;
@@ -64,7 +65,7 @@ struct Tuning {
   // every WANN_* name this library or its Python package reads (beside the laboratory): anything else in the environment is a
   // typo or a switch of another version -- named once on stderr (a sweep over a variable nothing reads ran silently)
   static bool known_name(const char *name, size_t len) {
-    static const char *const names[] = {"WANN_TEST_HOOKS", "WANN_VERBOSE", "WANN_PROOF_FACTOR", "WANN_DEVICES", "WANN_DEVICE", "WANN_ASYNC_LANES",
+    static const char *const names[] = {"WANN_TEST_HOOKS", "WANN_VERBOSE", "WANN_PROOF_FACTOR", "WANN_DENSE_LONG_ROWS", "WANN_DEVICES", "WANN_DEVICE", "WANN_ASYNC_LANES",
                                         "WANN_HOST_BUILD", "WANN_REF_TIES", "WANN_BUILD_VIS_CAP", "WANN_NO_TORCH", "WANN_DATASET_FOLDER", "WANN_LIB", nullptr};
     static const char *const prefixes[] = {"WANN_BENCH_", "WANN_PF_", "WANN_FULLSIZE_", nullptr};  // (bench.py / tools / tests)
     for (const char *const *n = names; *n; n++)
@@ -99,6 +100,7 @@ struct Tuning {
       const float f = (float)atof(v);
       t.proof_factor = (f == f && f > 3.f) ? f : 3.f;
     }
+    t.dense_long = on("WANN_DENSE_LONG_ROWS");
     if (!t.hooks_live) {
       static std::atomic<bool> told{false};
       if (!told.load(std::memory_order_relaxed)) {

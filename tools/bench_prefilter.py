@@ -6,15 +6,30 @@ each against the REAL reference at its best thread count (child processes: the r
 --dtype float32 | float16 | uint8 | int8 (default float32) selects the element type of the point set: float16 rounds the same
 set (MIPS), the byte types quantise it -- round(127 x) for int8 (MIPS), + 128 for uint8 (Euclidian), queries likewise -- and run
 on the int8 MFMA with exact scores.  Every leg is timed as the median of repeated calls (min / max beside it: the spread).
+--dim D sets the row length (default 100; 512 = RedCaps, 768 / 1536 = the long float32 rows of k_gemm_scores_long), --clusters C
+the number of clusters (default 100), --metric l2 | mips the metric of the float types (default mips).  WANN_PF_CACHE=<dir> keeps
+the generated set there for the next run of the same shape; WANN_PF_ONLY=mfma times the dense leg alone (runs under a profiler),
+WANN_PF_ONLY=scan the exact-scan leg alone, twice (the baseline run of a parent build); WANN_PF_NO_REF=1 leaves the CPU reference out.
 Run from the repo root.  Prints one JSON object."""
 import json, os, subprocess, sys, time
 os.environ.setdefault("WANN_TEST_HOOKS", "1")  # this tool flips WANN_* switches between calls on one index
+os.environ.setdefault("WANN_DENSE_LONG_ROWS", "1")  # (float32 rows of 513 .. 2048 floats: the dense leg is the opt-in kernel)
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
 
 
-DTYPE = sys.argv[sys.argv.index("--dtype") + 1] if "--dtype" in sys.argv else "float32"
+def _opt(name, default):
+    return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+
+
+DTYPE = _opt("--dtype", "float32")
+DIM = int(_opt("--dim", os.environ.get("WANN_PF_DIM", "100")))  # (WANN_PF_DIM: the option's older spelling)
+NCLU = int(_opt("--clusters", "100"))
+METRIC = _opt("--metric", "mips")
 CLASS = {"float32": "FloatMips", "float16": "Float16Mips", "int8": "Int8Mips", "uint8": "UInt8Euclidian"}[DTYPE]
+if METRIC == "l2" and DTYPE in ("float32", "float16"):
+    CLASS = CLASS.replace("Mips", "Euclidian")
+SHAPE_ARGS = ["--dtype", DTYPE, "--dim", str(DIM), "--clusters", str(NCLU), "--metric", METRIC]
 ELEM_BYTES = {"float32": 4, "float16": 2, "int8": 1, "uint8": 1}[DTYPE]
 
 
@@ -34,8 +49,20 @@ def padded_row_bytes(d):
 
 
 def make():
+    cache = os.environ.get("WANN_PF_CACHE")
+    path = os.path.join(cache, f"pf_{DTYPE}_{DIM}_{NCLU}.npz") if cache else None
+    if path and os.path.exists(path):
+        z = np.load(path)
+        return z["X"], z["Q"], z["labels"], z["W1"], z["W2"], int(z["per"]), int(z["w"])
+    out = _make()
+    if path:
+        np.savez(path, X=out[0], Q=out[1], labels=out[2], W1=out[3], W2=out[4], per=out[5], w=out[6])
+    return out
+
+
+def _make():
     rng = np.random.default_rng(0)
-    nclu, per, d = 100, 10000, int(os.environ.get("WANN_PF_DIM", "100"))  # (WANN_PF_DIM=512: the RedCaps row length)
+    nclu, per, d = NCLU, 10000, DIM
     n = nclu * per
     cent = rng.standard_normal((nclu, d)).astype(np.float32)
     X = cent[np.repeat(np.arange(nclu), per)] + 0.1 * rng.standard_normal((n, d)).astype(np.float32)
@@ -117,6 +144,14 @@ if os.environ.get("WANN_PF_ONLY") == "p12":  # dev runs under a profiler: the sy
     r = timed(W2t, None)
     print(json.dumps(dict(ms=r["ms"], device_ms=r["counters"]["device_ms"], brute_rows=int(r["counters"]["brute_rows"]))))
     sys.exit(0)
+if os.environ.get("WANN_PF_ONLY") == "mfma":  # under a kernel trace: the dense leg alone
+    r = timed(W1t, None)
+    print(json.dumps(dict(ms=r["ms"], device_ms=r["counters"]["device_ms"], gemm_queries=int(r["counters"]["gemm_queries"]), calls=REPS + 3)))
+    sys.exit(0)
+if os.environ.get("WANN_PF_ONLY") == "scan":  # the exact-scan leg alone, twice: all that a build without the dense kernel of this row length can run
+    r = [timed(W1t, "1"), timed(W1t, "1")]
+    print(json.dumps(dict(scan_ms=[x["ms"] for x in r], scan_device_ms=[round(x["counters"]["device_ms"], 3) for x in r], gemm_queries=int(r[1]["counters"]["gemm_queries"]))))
+    sys.exit(0)
 out = {"mfma": timed(W1t, None), "scan": timed(W1t, "1"), "p12": timed(W2t, None)}
 # (the two legs of the comparison once more, alternating: what one leg moves between its two runs is the spread to beat)
 again = {"mfma": timed(W1t, None), "scan": timed(W1t, "1")}
@@ -132,7 +167,7 @@ if os.environ.get("WANN_PF_REF_THREADS"):  # (a box that grants fewer CPUs than 
     ref_threads = [int(x) for x in os.environ["WANN_PF_REF_THREADS"].split(",")]
 for th in ([] if os.environ.get("WANN_PF_NO_REF") else ref_threads):  # (WANN_PF_NO_REF=1: dev runs)
     try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--ref-worker", res_path, "--dtype", DTYPE], env=dict(os.environ, PARLAY_NUM_THREADS=str(th)),
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--ref-worker", res_path] + SHAPE_ARGS, env=dict(os.environ, PARLAY_NUM_THREADS=str(th)),
                            capture_output=True, text=True, timeout=900)
         r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
         for name, v in r.items():
@@ -142,11 +177,11 @@ for th in ([] if os.environ.get("WANN_PF_NO_REF") else ref_threads):  # (WANN_PF
         print(f"[prefilter] reference with {th} threads failed: {e!r}", file=sys.stderr)
 flops = 2.0 * nq * per * d
 scan_bytes = float(out["p12"]["counters"]["brute_rows"]) * d * ELEM_BYTES  # w * d * sizeof(T) per brute-force query
-win_bytes = 100 * per * padded_row_bytes(d)  # a window group reads each of its (padded) point rows once
+win_bytes = NCLU * per * padded_row_bytes(d)  # a window group reads each of its (padded) point rows once
 p12_dev_ms = out["p12"]["counters"]["device_ms"]
 spread = lambda leg: dict(ms=[out[leg]["ms"], again[leg]["ms"]], ms_min=[out[leg]["ms_min"], again[leg]["ms_min"]], ms_max=[out[leg]["ms_max"], again[leg]["ms_max"]],
                           device_ms=[round(out[leg]["counters"]["device_ms"], 3), round(again[leg]["counters"]["device_ms"], 3)])
-print(json.dumps(dict(workload=f"adversarial 100x10000 d={d} {DTYPE} {'Euclidian' if CLASS.endswith('Euclidian') else 'MIPS'}, 9900 queries, window = 1 cluster", mfma_ms=out["mfma"]["ms"], mfma_qps=out["mfma"]["qps"],
+print(json.dumps(dict(workload=f"adversarial {NCLU}x10000 d={d} {DTYPE} {'Euclidian' if CLASS.endswith('Euclidian') else 'MIPS'}, {nq} queries, window = 1 cluster", mfma_ms=out["mfma"]["ms"], mfma_qps=out["mfma"]["qps"],
                       scan_ms=out["scan"]["ms"], scan_qps=out["scan"]["qps"], mfma_equals_scan=bool(same),
                       scan_device_ms=round(out["scan"]["counters"]["device_ms"], 3), timed_calls_per_leg=REPS,
                       repeated_legs=dict(mfma=spread("mfma"), scan=spread("scan")),
