@@ -9,6 +9,7 @@ namespace wann {
 constexpr int kSelect = 32;      // candidates kept per query by MFMA score before the exact re-rank
 constexpr int kGemmPointChunk = 2048;  // window positions per tile (multiple of 128)
 constexpr int kGemmMaxFloats = 2048;   // longest padded float32 row the score kernels take (k_gemm_scores_long; 512 without it)
+constexpr int kGemmMaxBytes = 2048;    // longest padded uint8 / int8 row they take (k_gemm_scores_bslab; 512 without it)
 // (a window hands over three candidates per 64 positions: too short a window could never prove a top 10)
 constexpr int kGroupMinQueries = 16, kGroupMinWindow = 1024;
 // cover groups (distinct windows, wann_set_dense_windows): a query is eligible if its window has at least kCoverMinWindow
@@ -62,7 +63,9 @@ struct GemmArgs {
   const unsigned int *pnorm2_max_bits;
   const int32_t *pterm;  // uint8 / int8 rows: the per-point integer term of the score (wann_gemm_kernels_bytes.inc)
   // float32 rows of more than 512 floats (k_gemm_scores_long): the batch's queries split into their two bf16 terms, per query
-  // `stride` words -- stride / 2 pairs of high terms, then the pairs of low terms; columns d .. stride are zero.  Null otherwise.
+  // `stride` words -- stride / 2 pairs of high terms, then the pairs of low terms; columns d .. stride are zero.
+  // uint8 / int8 rows of more than 512 bytes (k_gemm_scores_bslab): the batch's queries packed to bytes by pack_query_word's
+  // rule and biased like the rows, per query `stride` words = the padded row.  Null otherwise.
   const uint32_t *qsplit;
   float *scores;      // what k_gemm_scores hands to k_rerank's selection: per query, step and half wave the four smallest scores
   int64_t score_cap;  // floats; groups that do not fit any more are left to the exact scan
@@ -107,6 +110,7 @@ struct CoverArgs {
 int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);  // float32 / float16 rows
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream);                         // uint8 / int8 rows
 int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream);  // float32 rows > 512 floats
+int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);  // uint8 / int8 rows > 512 bytes
 int launch_group_windows(const GemmArgs &a, Counters *ctr, void *stream);
 int launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 int launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);

@@ -30,7 +30,8 @@
 //                    bf16's smallest normal number), so scores, selection, proof bound and re-rank are the float32 path's on the
 //                    exact upcast.  Rows of more than 128 elements take the exact scan.
 //   byte rows (WANN_DT = 1 / 2) k_gemm_scores_b on v_mfma_i32_32x32x32_i8: exact int32 sums, one product, no error bound --
-//                    see wann_gemm_kernels_bytes.inc.  Rows of more than 512 bytes take the exact scan.
+//                    see wann_gemm_kernels_bytes.inc.  Rows of 513 .. 2048 bytes: k_gemm_scores_bslab (both operands staged per
+//                    256-byte slab, quantised keys; opt-in), longer ones take the exact scan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -1313,7 +1314,7 @@ __device__ __forceinline__ void select_scores(const LOAD &load, int64_t nblk, in
   }
 }
 // (what a hand-over entry says about its position's score: the entry itself)
-template <int METRIC>
+template <int METRIC, int KSH>
 __device__ __forceinline__ float entry_score(float e) { return e; }
 __device__ __forceinline__ float no_entry() { return kHuge; }
 #else  // byte rows
@@ -1356,7 +1357,8 @@ struct CoverRow {
 // load(0 .. nblk - 1); block 0 starts at position `abase` of the label argsort; [wa, wb) is the query's own window (what
 // the rescue scan may touch); n_rescued / n_unproven: the counters of the path that calls.
 WANN_GNS_BEGIN
-template <int METRIC, class LOAD>
+// KSH: byte rows of more than 512 bytes hand over quantised keys (S of wann_gemm_kernels_bytes.inc); 0 everywhere else.
+template <int METRIC, int KSH, class LOAD>
 __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L, const int qrow, const LOAD &load, const int64_t nblk_sel,
                                              const int64_t abase, const int64_t wa, const int64_t wb, unsigned long long *n_rescued,
                                              unsigned long long *n_unproven) {
@@ -1378,7 +1380,7 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
     int sel_pos, cnt;
     float cut_sel, cut_blk;
 #if WANN_BYTE_ROWS
-    select_keys<METRIC>(load, nblk_sel, sel_pos, cnt, cut_sel, cut_blk);
+    select_keys<METRIC, KSH>(load, nblk_sel, sel_pos, cnt, cut_sel, cut_blk);
 #else
     select_scores(load, nblk_sel, sel_pos, cnt, cut_sel, cut_blk);
 #endif
@@ -1401,7 +1403,8 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
     // the columns), fp32 accumulation of 3 d products (A.acc_factor x the rounding adder's worst case), fp32 norms and the
     // reference's own rounding.
 #if WANN_BYTE_ROWS
-    // Byte rows: the scores ARE the distances k_brute returns (exact int32 sums cast to float), so E = 0 and |q|^2 is part of
+    // Byte rows: the scores ARE the distances k_brute returns (exact int32 sums cast to float; rows of more than 512 bytes:
+    // lower bounds of them, at most 3 below -- the bounds below then only err towards the scan), so E = 0 and |q|^2 is part of
     // the score.  What was not selected is only known to be NO BETTER than the cut in distance; at an equal distance a smaller
     // id would win under k_brute's (dist, id) order, so the top k is certain only when d_k is STRICTLY below the cut, and a
     // block is re-scanned when its fourth entry is <= d_k.
@@ -1442,7 +1445,7 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
       int scanned = 0;
       bool gave_up = false;
       for (int64_t b0 = 0; b0 < nblk && !gave_up; b0 += 64) {
-        const float m4 = (b0 + lane < nblk) ? entry_score<METRIC>(load(b0 + lane)[3]) : kHuge;
+        const float m4 = (b0 + lane < nblk) ? entry_score<METRIC, KSH>(load(b0 + lane)[3]) : kHuge;
         u64 hide = ballot64(m4 < kHugeTest && m4 + qoff - E <= dk + E);
         while (hide) {
           const int64_t b = b0 + ctz64(hide);
@@ -1497,7 +1500,7 @@ __global__ __launch_bounds__(256) void k_rerank(GemmArgs A, Counters *ctr) {
     const GemmGroup grp = A.groups[A.tq_group[tq]];
     const int64_t nblk = ((grp.b - grp.a + 127) >> 7) * 2;
     const EntryRow load{reinterpret_cast<const f32x4 *>(A.scores + grp.soff) + (int64_t)A.tq_local[tq] * nblk};
-    rerank_query<METRIC>(A, L, A.gq[tq], load, nblk, grp.a, grp.a, grp.b, &ctr->gemm_rescued, &ctr->gemm_unproven);
+    rerank_query<METRIC, 0>(A, L, A.gq[tq], load, nblk, grp.a, grp.a, grp.b, &ctr->gemm_rescued, &ctr->gemm_unproven);
   }
 }
 
@@ -1518,9 +1521,48 @@ __global__ __launch_bounds__(256) void k_rerank_cover(CoverArgs C) {
     const int64_t s0 = t.a >> 7, nblk = (((t.b - 1) >> 7) - s0 + 1) * 2;
     const CoverRow load{reinterpret_cast<const f32x4 *>(A.scores), C.qb_base + (int64_t)C.pass * C.pair_stride + C.q_off[q], s0, t.a, t.b,
                         (int32_t)(t.a / kGemmPointChunk)};
-    rerank_query<METRIC>(A, L, (int)q, load, nblk, s0 << 7, t.a, t.b, &C.cctr->rescued, &C.cctr->unproven);
+    rerank_query<METRIC, 0>(A, L, (int)q, load, nblk, s0 << 7, t.a, t.b, &C.cctr->rescued, &C.cctr->unproven);
   }
 }
+
+#if WANN_BYTE_ROWS
+// The same two kernels on the quantised keys of rows of more than 512 bytes (k_gemm_scores_bslab; KSH = kLongKeyShift).  Kernels
+// of their own, so that the shift is a constant and k_rerank / k_rerank_cover stay the code they were.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_rerank_bslab(GemmArgs A, Counters *ctr) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int wv = threadIdx.x >> 6;
+  const int qw = qv_words(A.ix);
+  const int per_wave = wave_lds_common_bytes(qw) + ((A.k + 1) & ~1) * 8;
+  const WaveLds L = carve_wave_lds(smem + (size_t)wv * per_wave, qw, A.k, true);
+  const int64_t ntq = A.plan[P_NTQ];
+  for (int64_t tq = (int64_t)blockIdx.x * 4 + wv; tq < ntq; tq += (int64_t)gridDim.x * 4) {
+    const GemmGroup grp = A.groups[A.tq_group[tq]];
+    const int64_t nblk = ((grp.b - grp.a + 127) >> 7) * 2;
+    const EntryRow load{reinterpret_cast<const f32x4 *>(A.scores + grp.soff) + (int64_t)A.tq_local[tq] * nblk};
+    rerank_query<METRIC, kLongKeyShift>(A, L, A.gq[tq], load, nblk, grp.a, grp.a, grp.b, &ctr->gemm_rescued, &ctr->gemm_unproven);
+  }
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_rerank_cover_bslab(CoverArgs C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const GemmArgs &A = C.g;
+  const int wv = threadIdx.x >> 6;
+  const int qw = qv_words(A.ix);
+  const int per_wave = wave_lds_common_bytes(qw) + ((A.k + 1) & ~1) * 8;
+  const WaveLds L = carve_wave_lds(smem + (size_t)wv * per_wave, qw, A.k, true);
+  if (C.pass >= C.cplan[CP_NPASS]) return;
+  for (int64_t q = (int64_t)blockIdx.x * 4 + wv; q < A.nq; q += (int64_t)gridDim.x * 4) {
+    if (C.q_pass[q] != C.pass) continue;  // (wave-uniform)
+    const Task t = A.tasks[q * A.tstride];
+    const int64_t s0 = t.a >> 7, nblk = (((t.b - 1) >> 7) - s0 + 1) * 2;
+    const CoverRow load{reinterpret_cast<const f32x4 *>(A.scores), C.qb_base + (int64_t)C.pass * C.pair_stride + C.q_off[q], s0, t.a, t.b,
+                        (int32_t)(t.a / kGemmPointChunk)};
+    rerank_query<METRIC, kLongKeyShift>(A, L, (int)q, load, nblk, s0 << 7, t.a, t.b, &C.cctr->rescued, &C.cctr->unproven);
+  }
+}
+#endif
 WANN_GNS_END
 
 // ------------------------------------------------------------------------------------------------
@@ -1535,6 +1577,13 @@ static hipError_t launch_rerank_cover_unit(const CoverArgs &c, void *stream) {  
   const GemmArgs &a = c.g;
   const int blocks = (int)std::min<int64_t>(4096, (a.nq + 3) / 4);
   const size_t lds = rerank_lds_bytes(a.ix, a.k);
+#if WANN_BYTE_ROWS
+  if (a.ix.stride > 128) {  // (rows of more than 512 bytes: quantised keys)
+    if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank_cover_bslab<1>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
+    else hipLaunchKernelGGL(k_rerank_cover_bslab<0>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
+    return hipGetLastError();
+  }
+#endif
   if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank_cover<1>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
   else hipLaunchKernelGGL(k_rerank_cover<0>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
   return hipGetLastError();
@@ -1553,8 +1602,22 @@ const char *launch_point_terms(const IndexView &ix, int32_t *term, void *stream)
   return gerr_of(hipGetLastError());
 }
 
+const char *launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream) {
+  const int64_t words = nq * ix.stride;
+  if (words <= 0) return nullptr;
+  hipLaunchKernelGGL(k_pack_queries_b, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, queries, nq, ix.d, ix.stride, out);
+  return gerr_of(hipGetLastError());
+}
+
 const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream) {
-  if (a.ix.stride > 128 || (a.ix.stride & 15)) return "row too long for the dense prefilter tile";
+  if (a.ix.stride * 4 > kGemmMaxBytes || (a.ix.stride & 15)) return "row too long for the dense prefilter tile";
+  if (a.ix.stride > 128) {  // 513 .. 2048 bytes: run-time slab count, both operands staged per slab (queries pre-packed)
+    if (!a.qsplit) return "k_gemm_scores_bslab needs the packed queries";
+    const size_t ldss = (size_t)2 * 128 * (256 + 16) + 3 * 128 * 4;
+    if (const char *e = gerr_of(hipFuncSetAttribute((const void *)k_gemm_scores_bslab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldss))) return e;
+    hipLaunchKernelGGL(k_gemm_scores_bslab, dim3(2 * (num_cus > 0 ? num_cus : 256)), dim3(256), ldss, (hipStream_t)stream, a);
+    return gerr_of(hipGetLastError());
+  }
   const int nch = a.ix.stride / 16;
   const size_t lds = (size_t)128 * (64 * nch + 16) + 3 * 128 * 4;
   void (*kern)(GemmArgs) = nullptr;
@@ -1608,6 +1671,13 @@ const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream)
   hipStream_t s = (hipStream_t)stream;
   const int blocks = (int)std::min<int64_t>(4096, (a.nq + 3) / 4);
   const size_t lds = rerank_lds_bytes(a.ix, a.k);
+#if WANN_BYTE_ROWS
+  if (a.ix.stride > 128) {  // (rows of more than 512 bytes: quantised keys)
+    if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank_bslab<1>, dim3(blocks), dim3(256), lds, s, a, ctr);
+    else hipLaunchKernelGGL(k_rerank_bslab<0>, dim3(blocks), dim3(256), lds, s, a, ctr);
+    return gerr_of(hipGetLastError());
+  }
+#endif
   if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank<1>, dim3(blocks), dim3(256), lds, s, a, ctr);
   else hipLaunchKernelGGL(k_rerank<0>, dim3(blocks), dim3(256), lds, s, a, ctr);
   return gerr_of(hipGetLastError());
@@ -1619,12 +1689,14 @@ const char *launch_rerank_cover(const CoverArgs &c, void *stream) { return gerr_
 namespace dt_u8 {
 const char *launch_rerank_cover(const CoverArgs &c, void *stream);
 const char *launch_point_terms(const IndexView &ix, int32_t *term, void *stream);
+const char *launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);
 const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
 }
 namespace dt_i8 {
 const char *launch_rerank_cover(const CoverArgs &c, void *stream);
 const char *launch_point_terms(const IndexView &ix, int32_t *term, void *stream);
+const char *launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);
 const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
 }
@@ -1667,6 +1739,10 @@ int launch_split_queries(const float *queries, int64_t nq, int d, int stride, ui
 
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream) {
   return gtyped(ix.dtype == 1 ? dt_u8::launch_point_terms(ix, term, stream) : dt_i8::launch_point_terms(ix, term, stream));
+}
+
+int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream) {
+  return gtyped(ix.dtype == 1 ? dt_u8::launch_pack_queries(ix, queries, nq, out, stream) : dt_i8::launch_pack_queries(ix, queries, nq, out, stream));
 }
 
 int launch_group_windows(const GemmArgs &a, Counters *ctr, void *stream) {
