@@ -60,7 +60,18 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * float32 kernels on the exact upcast, half loads; longer float16 rows take the exact scan); uint8 / int8 rows of up to 512
  * bytes on the int8 MFMA with exact int32 scores -- up to 2048 bytes in a process started with WANN_DENSE_LONG_ROWS=1 (a kernel
  * that walks the row in slabs; opt-in until it is timed against the scan) -- longer byte rows take the exact scan.  Queries of
- * a byte index become bytes by the exact scan's rule, (int)q & 0xff, on both paths. */
+ * a byte index become bytes by the exact scan's rule, (int)q & 0xff, on both paths.
+ * HALF-PRECISION SHADOW ROWS of a float32 index.  A WANN_DTYPE_F32 index that has graphs (the post filter, the graph-backed tree,
+ * the super tree) and whose n x d values are ALL finite binary16 values -- wann_rows_fp16_exact: half(x) converts back to the bits
+ * of x, which keeps -0.0 and the binary16 subnormals and drops NaN, the infinities and |x| > 65504; SIFT / BIGANN vectors, integers
+ * in [0, 255], qualify -- keeps a second copy of its points as half rows (64-byte padded, wann_half_rows_bytes) and its BEAM
+ * SEARCHES read that copy through the float16 kernels: the same rows, distance bits and operation counters (see above), half the
+ * vector bytes per scored row.  Everything else -- routing, the exact scans, the dense path, the GPU builder, the raw-search
+ * hooks, the unfiltered wann_vamana_* API -- reads the float32 rows, which stay where they were.  The property is tested once,
+ * when the index is created; an index that is not eligible (or found no memory for the copy) has no shadow and behaves as before.
+ * wann_set_half_rows switches the use of the copy off and on between batches (on by default where the copy exists).
+ * wann_device_bytes does NOT count the copy (it reports what it always has: a float32 index and the float16 index of the same
+ * points differ there by the bytes of their rows); wann_half_rows_bytes does. */
 enum { WANN_DTYPE_F32 = 0, WANN_DTYPE_U8 = 1, WANN_DTYPE_I8 = 2, WANN_DTYPE_F16 = 3 };
 /* index classes */
 enum {
@@ -261,7 +272,22 @@ int wann_partition_range(const wann_index *index, int64_t level, int64_t idx, in
 int wann_partition_graph(const wann_index *index, int64_t level, int64_t idx, int32_t *rows, int64_t cap_rows,
                          int64_t max_degree);
 int64_t wann_max_degree(const wann_index *index);
-int64_t wann_device_bytes(const wann_index *index);
+int64_t wann_device_bytes(const wann_index *index);  /* (without the half-precision shadow rows: wann_half_rows_bytes) */
+
+/* Half-precision shadow rows (see WANN_DTYPE_*).
+ * wann_rows_fp16_exact: 1 if every one of the n x d float32 values (row-major, contiguous) is a finite IEEE binary16 value, else 0;
+ * 1 for an empty set.  Pure host code: needs no device.
+ * wann_set_half_rows: whether the beam searches of the NEXT batches read the shadow rows (a batch submitted earlier keeps what it
+ * was submitted with).  Returns the setting now in force, 0 / 1: asking for 1 on an index without a shadow leaves it at 0 and
+ * returns 0.  Allocates and frees nothing; applies to every replica of WANN_DEVICES; a NEGATIVE error for a null index.
+ * wann_half_rows: that setting.  wann_half_rows_bytes: device bytes of the shadow rows, n * 64 * ceil(2 d / 64), or 0 without one.
+ * wann_last_half_rows: 1 if the beam searches of the last finished batch -- the last blocking call, or the ticket last waited
+ * for -- read the shadow rows (wann_counters keeps its ABI 5 layout, so this is a call of its own). */
+int wann_rows_fp16_exact(const float *rows, int64_t n, int64_t d);
+int wann_set_half_rows(wann_index *index, int on);
+int wann_half_rows(const wann_index *index);
+int64_t wann_half_rows_bytes(const wann_index *index);
+int wann_last_half_rows(const wann_index *index);
 /* In-process multi-device mode: with WANN_DEVICES=a,b,... in the environment wann_index_create makes the index resident on
  * every listed device (a device may be listed twice) and wann_batch_search -- the host-buffer call, the reference's boundary
  * (src/range_filter_tree.h:62-96: one call parallelises over all queries) -- cuts its batch into contiguous shards, one host

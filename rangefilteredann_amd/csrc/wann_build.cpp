@@ -141,6 +141,28 @@ int default_threads() {
   return hc > 0 ? hc : 1;
 }
 
+// Every value is a finite binary16 value: half_to_float(float_to_half(x)) has the bits of x (keeps -0.0 and the binary16
+// subnormals, drops everything above 65504).  Infinities and the default NaN would survive that round trip bit for bit, so
+// non-finite values are refused by their exponent first.
+bool rows_fp16_exact(const float *rows, int64_t n, int64_t d, int64_t stride, int threads) {
+  std::atomic<bool> exact{true};
+  parallel_for(n, threads > 0 ? threads : default_threads(), [&](int64_t r) {
+    if (!exact.load(std::memory_order_relaxed)) return;  // (a row that fails ends the pass: the rows left return at once)
+    const float *p = rows + r * stride;
+    for (int64_t j = 0; j < d; j++) {
+      uint32_t u, v;
+      memcpy(&u, p + j, 4);
+      const float back = half_to_float(float_to_half(p[j]));
+      memcpy(&v, &back, 4);
+      if ((u & 0x7f800000u) == 0x7f800000u || u != v) {
+        exact.store(false, std::memory_order_relaxed);
+        return;
+      }
+    }
+  });
+  return exact.load();
+}
+
 // ------------------------------------------------------------------------------------------------
 // numerics (same evaluation order as the kernels; built with -ffp-contract=off)
 // ------------------------------------------------------------------------------------------------

@@ -59,6 +59,10 @@ struct HostIndex {
 void parallel_for(int64_t n, int threads, const std::function<void(int64_t)> &f);
 int default_threads();
 
+// true if every one of the n x d values (rows `stride` floats apart) is exactly representable in IEEE binary16 and finite:
+// what a float32 index needs to be searched from half rows (wann.h wann_rows_fp16_exact).  threads <= 0: default_threads().
+bool rows_fp16_exact(const float *rows, int64_t n, int64_t d, int64_t stride, int threads);
+
 // metric: bit 0 = inner product, bits 4-5 = element type of the rows behind p / q (0 float32, 1 uint8, 2 int8; float16 point
 // sets are built from their float32 upcast and pass 0)
 float host_distance(int metric, const float *p, const float *q, int d);

@@ -47,7 +47,9 @@ void convert_rows(const HostGraph &g, int rs, int32_t *out) {
 Tuning snapshot_tuning(wann_index &I) {
   std::lock_guard<std::mutex> lk(I.tune_mu);
   if (I.tune.hooks_live) I.tune = Tuning::from_env();
-  return I.tune;
+  Tuning t = I.tune;
+  t.half_rows = I.half_rows_on && I.d_half.p != nullptr;
+  return t;
 }
 
 void upload_index(wann_index &I) {
@@ -92,6 +94,31 @@ void upload_index(wann_index &I) {
     I.d_points.upload(rows);
   } else {
     I.d_points.upload(H.pts);
+  }
+  // float32 points that are all binary16 values, on an index with graphs: a second copy as half rows (the float16 branch's
+  // conversion and padding) for the beam searches, which are bound by the bytes of the rows they score.  Every shape the
+  // float16 k_search serves qualifies -- that is every shape: a float16 index of any kind / metric / R / d runs these kernels.
+  // An index that cannot have the copy (no memory) simply has none.
+  if (s.dtype == WANN_DTYPE_F32 && H.vamana_leaves && rows_fp16_exact(H.pts.data(), s.n, s.d, s.stride, s.threads)) {
+    const int64_t hstride = ((s.d * 2 + 63) / 64) * 16;
+    std::vector<float> rows;
+    try {
+      rows.assign((size_t)s.n * hstride, 0.f);
+      I.d_half.ensure(rows.size());
+    } catch (std::bad_alloc &) {
+      I.d_half.release();
+    } catch (HipError &) {
+      (void)hipGetLastError();  // (the allocation that failed is not left behind as the next call's error)
+      I.d_half.release();
+    }
+    if (I.d_half.p) {
+      parallel_for(s.n, s.threads > 0 ? s.threads : default_threads(), [&](int64_t r) {
+        const float *src = H.pts.data() + r * s.stride;
+        uint16_t *dst = reinterpret_cast<uint16_t *>(rows.data() + r * hstride);
+        for (int64_t j = 0; j < s.d; j++) dst[j] = float_to_half(src[j]);
+      });
+      I.d_half.upload(rows);
+    }
   }
   I.d_labels.upload(H.labels);
   I.d_decoding.upload(H.decoding);
@@ -175,6 +202,14 @@ void upload_index(wann_index &I) {
     v.sup_size = I.d_sup_size.p;
     v.sup_shift = I.d_sup_shift.p;
   }
+  I.search_view = v;
+  if (I.d_half.p) {
+    I.search_view.points = I.d_half.p;
+    I.search_view.stride = (int32_t)(((s.d * 2 + 63) / 64) * 16);
+    I.search_view.dtype = WANN_DTYPE_F16;
+    I.half_rows_on = true;
+  }
+  // (the shadow rows are not in device_bytes, which keeps counting what it always has: wann_half_rows_bytes reports them)
   I.device_bytes = (int64_t)(I.d_points.bytes() + I.d_labels.bytes() + I.d_decoding.bytes() + I.d_graph.bytes() +
                              I.d_parts.bytes() + I.d_fv.bytes() + I.d_fi.bytes() + I.d_wst_off.bytes());
 }
@@ -219,16 +254,16 @@ int ensure_filter_scratch(DevBuf<int32_t> &table, DevBuf<int32_t> &epoch, DevBuf
 constexpr int kLdsGranule = 1280, kLdsPerCu = 160 * 1024;
 inline int lds_blocks_per_cu(int per_block) { return kLdsPerCu / (((per_block + kLdsGranule - 1) / kLdsGranule) * kLdsGranule); }
 
-RoundCfg config_for(const wann_index &I, const Tuning &T, int64_t first_beam, int64_t cap, int64_t work_items, bool big_lds, bool force_table, bool legacy,
-                    int base_pool) {
+RoundCfg config_for(const wann_index &I, const IndexView &V, const Tuning &T, int64_t first_beam, int64_t cap, int64_t work_items, bool big_lds, bool force_table,
+                    bool legacy, int base_pool) {
   RoundCfg rc{};
   const int64_t cap_bytes = ((cap + 1) & ~(int64_t)1) * 8;
   if (cap_bytes > base_pool) big_lds = true;
   // Rows of more than 64 neighbours (64 < R <= 128) are worked in two halves by the first-generation general core only: every
   // search of such an index runs in the one-wave kernel that holds it (k_search<., 2>), eight workgroups per CU.
-  if (I.view.rs > 64) big_lds = legacy = true;
+  if (V.rs > 64) big_lds = legacy = true;
   const int wpb = big_lds ? 1 : kWavesPerBlock;
-  const int common = search_lds_bytes_per_wave(query_words(I.view), 0);
+  const int common = search_lds_bytes_per_wave(query_words(V), 0);
   if (big_lds && !legacy && cap_bytes + 4096 + kScoreBoxBytes > 150 * 1024 - common) legacy = true;
   const int box_bytes = (big_lds && !legacy) ? kScoreBoxBytes : 0;
   if (big_lds && !legacy) force_table = true;
@@ -244,7 +279,7 @@ RoundCfg config_for(const wann_index &I, const Tuning &T, int64_t first_beam, in
   // register budget: the L2 kernel holds two whole 512-B rows per lane pair in flight (2 waves/SIMD)
   // (four-wave kernel: the squared-L2 float kernel needs 232 registers: two waves per SIMD; the inner-product and byte-row
   // kernels are built for three)
-  const int waves_per_cu = (I.view.metric == 1 || byte_rows(I.view)) ? 12 : 8;
+  const int waves_per_cu = three_waves_per_simd(V) ? 12 : 8;
   int blocks_per_cu = std::min((big_lds ? 8 : waves_per_cu) / wpb, lds_blocks_per_cu(per_block));
   blocks_per_cu = std::max(1, blocks_per_cu);
   int64_t blocks = (int64_t)I.num_cus * blocks_per_cu;
@@ -269,9 +304,9 @@ RoundCfg config_for(const wann_index &I, const Tuning &T, int64_t first_beam, in
 // Per-wave pool with which THREE four-wave workgroups share a CU's 160 KiB of LDS (inner-product / byte-row kernels, which
 // fit three waves per SIMD): the in-kernel cap's beam (10 KiB) still fits, the seen-filter of beams up to 90 too.  0: this
 // index can not use it (rows too long).
-int lean_pool_bytes(const wann_index &I, const Tuning &T) {
-  if (!(I.view.metric == 1 || byte_rows(I.view))) return 0;
-  const int common = search_lds_bytes_per_wave(query_words(I.view), 0);
+int lean_pool_bytes(const IndexView &V) {
+  if (!three_waves_per_simd(V)) return 0;
+  const int common = search_lds_bytes_per_wave(query_words(V), 0);
   // 52 KiB per workgroup.  Three workgroups of 53 KiB (159 of the CU's 160 KiB) are NOT co-resident on gfx950, whatever
   // hipOccupancyMaxActiveBlocksPerMultiprocessor says (3): a launch of 768 such workgroups ran at the speed of 512 until round 4
   // measured it (stand-alone inner-product graph, 30 000 searches at beam 80: 6.65 ms at 53 KiB, 5.22 ms at 52.5 KiB and below).
@@ -485,7 +520,7 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
 }
 
 // W / side / last: the lane of this batch (the index's own members for the blocking calls, an AsyncLane's for the asynchronous one)
-void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
+bool run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
                const int64_t *d_qids) {
   if (qp.k <= 0 || qp.k > 1024) throw std::runtime_error("k must be in [1, 1024]");
@@ -516,6 +551,11 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   // stdout in the reference's words after the batch -- a debugging aid: such a call runs plain sequential doubling in the
   // one-wave legacy kernel, which records every search
   const bool verbose_call = qp.verbose != 0 && I.host().vamana_leaves;
+  // The view the beam-search launches (k_search) read: the half-precision shadow rows where the index has them and the switch
+  // is on -- the float16 unit's kernels, which score a row in the float32 kernels' arithmetic and order after an exact
+  // conversion: same rows, same counters, half the vector bytes.  Routing, the exact scans, the dense path and k_finalize keep I.view.
+  const bool use_half = T.half_rows && I.d_half.p != nullptr && I.host().vamana_leaves;
+  const IndexView &SV = use_half ? I.search_view : I.view;
   // (wide rows, R > 64: plain in-kernel doubling in the one-wave kernel, no speculative levels / companion launch)
   const bool spec = I.host().vamana_leaves && T.spec && I.view.rs <= 64 && !verbose_call;
   const int64_t sub_slots = spec ? std::min<int64_t>(nq * (int64_t)maxt * 4 + 1024, (int64_t)1 << 26) : 0;
@@ -528,7 +568,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   // (a sub-task slot's count is -1 until its search has finished: what the pollers' scan goes by)
   if (spec) HIP_CHECK(hipMemsetAsync(W.out_cnt.p + (size_t)nq * maxt, 0xFF, (size_t)sub_slots * sizeof(int32_t), st));
   last = wann_counters{};
-  if (nq == 0) return;
+  if (nq == 0) return use_half;
   HIP_CHECK(hipMemsetAsync(W.ints.p, 0, kInts * sizeof(int32_t), st));
   HIP_CHECK(hipMemsetAsync(W.ctr.p, 0, sizeof(Counters), st));
   HIP_CHECK(hipEventRecord(W.ev[0], st));
@@ -577,7 +617,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   // at 32 MiB per workgroup)
   int32_t big_cap = 0;
   if (spec && T.big) {
-    const int common = search_lds_bytes_per_wave(query_words(I.view), 0);
+    const int common = search_lds_bytes_per_wave(query_words(SV), 0);
     const int64_t big_pool = (int64_t)(common + kSearchPoolBytes) * kWavesPerBlock - common;
     big_cap = (int32_t)std::min<int64_t>(big_pool / 8, 5792);
     if (big_cap <= ra.cap_inkernel || (common + kSearchPoolBytes) * kWavesPerBlock > 160 * 1024) big_cap = 0;
@@ -677,7 +717,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   }
   if (sized && graph_n + big_n > 0) {
     SearchArgs sa{};
-    sa.ix = I.view;
+    sa.ix = SV;
     sa.queries = d_queries;
     sa.qid_base = qid_base;
     sa.raw_qids = reinterpret_cast<const long long *>(d_qids);  // (null unless the caller names every query's own id)
@@ -725,7 +765,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
     const bool scan_on = spec && T.lookahead;
     auto launch = [&](SearchArgs &a, int64_t first_beam, int64_t cap, int64_t items, bool big_lds, int32_t with_big_cap = 0, int32_t deep_pollers = 0,
                       int base_pool = kSearchPoolBytes) {
-      RoundCfg rc = config_for(I, T, first_beam, cap, items, big_lds || verbose_call, a.force_general != 0, a.old_general != 0, base_pool);
+      RoundCfg rc = config_for(I, SV, T, first_beam, cap, items, big_lds || verbose_call, a.force_general != 0, a.old_general != 0, base_pool);
       big_lds = rc.big_lds;
       a.big_list = nullptr;  // (the one-wave kernel then takes ordinary tickets)
       a.helper = (rc.lc.big == 1 && T.helper) ? kHelpers : 0;
@@ -748,7 +788,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
         // companion launch for the speculative levels beyond `cap`: one wave per workgroup, one workgroup per
         // CU, the beam (up to with_big_cap entries) in the LDS, the seen-filter in g_table_big
         with_big = true;
-        const int common = search_lds_bytes_per_wave(query_words(I.view), 0);
+        const int common = search_lds_bytes_per_wave(query_words(SV), 0);
         big = a;
         big_lc.big = a.old_general ? 2 : 1;  // (WANN_OLD_GENERAL: the first-generation core also for the companion's searches)
         big.helper = (big_lc.big == 2 || !T.helper) ? 0 : kHelpers;
@@ -916,7 +956,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
     // Three workgroups per CU (a leaner LDS pool) where the kernel allows it and no companion workgroup has to share a CU with
     // the ordinary ones (the deep-chain pollers book whole CUs of their own)
     int base_pool = kSearchPoolBytes;
-    if (big_n == 0 && !may_continue && cap1 <= kInKernelBeamCap && lean_pool_bytes(I, T) > 0) base_pool = lean_pool_bytes(I, T);
+    if (big_n == 0 && !may_continue && cap1 <= kInKernelBeamCap && lean_pool_bytes(SV) > 0) base_pool = lean_pool_bytes(SV);
     // How many: with two workgroups per CU (squared-L2 float kernel) four -- 16 cost the SIFT-1M 2^-3 batch 2.5 %; with three
     // (twelve waves share a CU's memory path: a third level takes 2.2 ms there, 1.5 ms on a poller) every third-level chain
     // should find one: 16 (deep-10M-like, eight such chains: 5.3 -> 4.5 ms per batch; 12 ... 32 measure alike).
@@ -1200,6 +1240,7 @@ void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   if (W.h_ctr->unsupported)
     throw std::runtime_error(std::to_string((long long)W.h_ctr->unsupported) +
                              " queries need more than " + std::to_string(maxt) + " partition searches; raise the task slot bound");
+  return use_half;
 }
 
 // Graphs missing from the cache: built on the GPU straight into the adjacency pool (with WANN_HOST_BUILD=1:

@@ -132,6 +132,13 @@ struct wann_index {
   int dtype = WANN_DTYPE_F32;  // element type of the caller's points / host queries (device queries are fp32)
   int num_cus = 256;
   DevBuf<float> d_points, d_labels, d_fv;
+  // Shadow rows of a float32 index whose every value is a finite binary16 value (rows_fp16_exact) and that has graphs: the same
+  // points as halves, 64-byte padded -- what a float16 index of these points keeps in d_points.  Only the beam-search launches
+  // (k_search) read them, through search_view; everything else reads d_points.  Empty: no shadow (not eligible, or no memory).
+  DevBuf<float> d_half;
+  IndexView search_view{};     // `view` with points = d_half, the half stride and dtype = WANN_DTYPE_F16 (valid when d_half.p)
+  bool half_rows_on = false;   // wann_set_half_rows (under tune_mu; on when a shadow exists): the next batch searches the shadow
+  std::atomic<int> last_half_rows{0};  // the last finished batch (blocking call / ticket waited for) searched the shadow
   DevBuf<uint32_t> d_decoding;
   DevBuf<int32_t> d_graph, d_fi;
   DevBuf<PartDesc> d_parts;
@@ -205,12 +212,14 @@ struct RoundCfg {
   int table_bits;    // per-slot global seen-filter of 4 << table_bits bytes (0 = none needed)
   int64_t beam_cap;  // per-slot global beam entries (0 = none needed)
 };
-RoundCfg config_for(const wann_index &I, const Tuning &T, int64_t first_beam, int64_t cap, int64_t work_items, bool big_lds = false, bool force_table = false,
+// V: the view the launch's kernel reads (I.view, or I.search_view for a batch that searches the half-precision shadow rows)
+RoundCfg config_for(const wann_index &I, const IndexView &V, const Tuning &T, int64_t first_beam, int64_t cap, int64_t work_items, bool big_lds = false, bool force_table = false,
                     bool legacy = false, int base_pool = kSearchPoolBytes);
-int lean_pool_bytes(const wann_index &I, const Tuning &T);
+int lean_pool_bytes(const IndexView &V);
 int method_code(const char *m);
 // W / side / last: the lane of this batch (the index's own members for the blocking calls, an AsyncLane's for the asynchronous one)
-void run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
+// Returns whether the batch's beam searches read the half-precision shadow rows (T.half_rows on an index with graphs).
+bool run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
                const int64_t *d_qids = nullptr);
 void build_pending(wann_index &I, std::vector<HostPart *> &pending);
@@ -218,8 +227,12 @@ void build_pending(wann_index &I, std::vector<HostPart *> &pending);
 std::vector<float> bytes_to_float(int dtype, const void *src, int64_t count);
 // bytes per element of the caller's points / host queries
 inline int64_t element_bytes(int dtype) { return dtype == WANN_DTYPE_F32 ? 4 : dtype == WANN_DTYPE_F16 ? 2 : 1; }
-// uint8 / int8 rows: scored with v_dot4 by kernels built for more waves per SIMD (float16 rows keep float32's launch shapes)
+// uint8 / int8 rows: scored with v_dot4 by kernels built for more waves per SIMD
 inline bool byte_rows(const IndexView &v) { return v.dtype == WANN_DTYPE_U8 || v.dtype == WANN_DTYPE_I8; }
+// this view's four-wave k_search is built for THREE waves per SIMD (at most 168 registers): the inner-product and byte-row
+// kernels.  The squared-L2 kernels keep two whole rows per lane pair in flight and are built for two: float32 needs 256
+// registers, float16 (k_search<0, 0, 3>) 215 -- see DESIGN.md 3.10.
+inline bool three_waves_per_simd(const IndexView &v) { return v.metric == 1 || byte_rows(v); }
 BuildSpec make_spec(int kind, int metric, int dtype, int64_t n, int64_t d, int32_t cutoff, double split_factor, double shift_factor,
                     const wann_build_params *bp, int threads);
 

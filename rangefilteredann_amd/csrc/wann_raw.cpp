@@ -95,7 +95,7 @@ struct RawGraph {
     const bool old_general = T.old_general || with_cut || wide, force_general = T.force_general || with_cut || wide;
     // (dev / test switches: the large-LDS one-wave configuration; the first-generation cores live in that kernel only)
     const int raw_pool = kSearchPoolBytes;
-    RoundCfg rc = config_for(I, T, beam, beam, nq, T.raw_big_lds || old_general, force_general, old_general, raw_pool);
+    RoundCfg rc = config_for(I, I.view, T, beam, beam, nq, T.raw_big_lds || old_general, force_general, old_general, raw_pool);
     SearchArgs sa{};
     sa.ix = I.view;
     sa.queries = d_q.p;

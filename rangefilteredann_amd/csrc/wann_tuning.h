@@ -48,6 +48,8 @@ struct Tuning {
   bool verbose = false;         // WANN_VERBOSE
   bool profile_phases = false;  // WANN_PROFILE_PHASES (make PROFILE=1 builds)
   std::string task_trace;       // WANN_TASK_TRACE=<file> (make TRACE=1 builds)
+  // not from the environment: the index's wann_set_half_rows state at the moment of the call (snapshot_tuning fills it in)
+  bool half_rows = false;       // this batch's beam searches read the index's half-precision shadow rows
 
   static bool on(const char *name) {
     const char *v = getenv(name);

@@ -186,8 +186,19 @@ class Index {
       rc = wann_wait(h_, ticket, &c);
     }
     if (rc) raise_last("wait failed");
-    return counters_dict(c);
+    py::dict d = counters_dict(c);
+    d["half_rows"] = wann_last_half_rows(h_);
+    return d;
   }
+  // float32 indexes with graphs whose points are all binary16 values: the beam searches read a half-precision copy of the rows
+  // (wann_set_half_rows); returns the setting now in force -- False on an index without such a copy
+  bool set_half_rows(bool on) {
+    const int rc = wann_set_half_rows(h_, on ? 1 : 0);
+    if (rc < 0) raise_last("set_half_rows failed");
+    return rc != 0;
+  }
+  bool half_rows() const { return wann_half_rows(h_) != 0; }
+  int64_t half_rows_bytes() const { return wann_half_rows_bytes(h_); }
 
   // PrefilterIndex only: distinct wide windows on the matrix cores (wann_set_dense_windows); returns the previous setting
   bool set_dense_windows(bool on) {
@@ -230,7 +241,9 @@ class Index {
   py::dict counters() const {
     wann_counters c;
     wann_get_counters(h_, &c);
-    return counters_dict(c);
+    py::dict d = counters_dict(c);
+    d["half_rows"] = wann_last_half_rows(h_);  // 1: the last batch's beam searches read the half-precision shadow rows
+    return d;
   }
   static py::dict counters_dict(const wann_counters &c) {
     py::dict d;
@@ -307,6 +320,9 @@ static void common_defs(py::class_<C> &c) {
       .def("partition_range", &C::partition_range)
       .def("partition_graph", &C::partition_graph, "level"_a, "idx"_a, "max_degree"_a)
       .def("device_bytes", &C::device_bytes)
+      .def("set_half_rows", &C::set_half_rows, "on"_a)
+      .def("half_rows", &C::half_rows)
+      .def("half_rows_bytes", &C::half_rows_bytes)
       .def("max_degree", &C::max_degree)
       .def("num_replicas", &C::num_replicas)
       .def("num_points", &C::num_points)
