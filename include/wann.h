@@ -57,7 +57,8 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * API refuses float16.
  * The MFMA prefilter path (PrefilterIndex batches in which queries share windows, counted in gemm_queries) serves every
  * element type and returns the exact scan's rows: float32 rows of up to 512 elements; float16 rows of up to 128 elements (the
- * float32 kernels on the exact upcast, half loads; longer float16 rows take the exact scan); uint8 / int8 rows of up to 512
+ * float32 kernels on the exact upcast, half loads) -- float16 rows of up to 2048 elements in a process started with
+ * WANN_DENSE_LONG_ROWS=1 (129 .. 2048: the slab kernel, opt-in), longer float16 rows take the exact scan; uint8 / int8 rows of up to 512
  * bytes on the int8 MFMA with exact int32 scores -- up to 2048 bytes in a process started with WANN_DENSE_LONG_ROWS=1 (a kernel
  * that walks the row in slabs; opt-in until it is timed against the scan) -- longer byte rows take the exact scan.  Queries of
  * a byte index become bytes by the exact scan's rule, (int)q & 0xff, on both paths.
@@ -215,7 +216,7 @@ int wann_get_counters(const wann_index *index, wann_counters *out);
  * by the same kernels; candidates outside a query's own window are dropped before the exact re-rank.  Rows are those of the
  * exact scan (same ids, same distance bits: both order by (distance, id)); only the work counters differ: brute_rows no longer
  * counts the rows of the queries taken.  Row lengths the dense path does not take (float16 above 128 elements, bytes above 512 --
- * above 2048 bytes where WANN_DENSE_LONG_ROWS=1 opts in to the long-row kernels) and k > 16 stay on the exact scan.  Applies to every replica of WANN_DEVICES and to every call form.
+ * above 2048 elements or bytes where WANN_DENSE_LONG_ROWS=1 opts in to the long-row kernels) and k > 16 stay on the exact scan.  Applies to every replica of WANN_DEVICES and to every call form.
  * Returns the previous setting (0 / 1) or a NEGATIVE error: -WANN_ERR_UNSUPPORTED for on = 1 on any kind but
  * WANN_KIND_PREFILTER, -WANN_ERR_INVALID for a null index. */
 int wann_set_dense_windows(wann_index *index, int on);

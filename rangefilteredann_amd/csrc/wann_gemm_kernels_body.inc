@@ -28,7 +28,8 @@
 //   float16 rows (WANN_DT = 3)  the narrow k_gemm_scores with half loads: a binary16 value is EXACTLY the sum of its two bf16
 //                    terms (11 significant bits <= 8 + 8; the low term of a subnormal half is a multiple of 2^-24, far above
 //                    bf16's smallest normal number), so scores, selection, proof bound and re-rank are the float32 path's on the
-//                    exact upcast.  Rows of more than 128 elements take the exact scan.
+//                    exact upcast.  Rows of 129 .. 2048 elements: k_gemm_scores_hslab (the float32 unit's K-loop kernel with half
+//                    loads; opt-in), longer ones take the exact scan.
 //   byte rows (WANN_DT = 1 / 2) k_gemm_scores_b on v_mfma_i32_32x32x32_i8: exact int32 sums, one product, no error bound --
 //                    see wann_gemm_kernels_bytes.inc.  Rows of 513 .. 2048 bytes: k_gemm_scores_bslab (both operands staged per
 //                    256-byte slab, quantised keys; opt-in), longer ones take the exact scan.
@@ -1088,7 +1089,24 @@ __global__ void k_split_queries(const float *queries, int64_t nq, int d, int str
   out[q * stride + hw + (c >> 1)] = lo;
 }
 
-__global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
+#endif  // WANN_DT == 0 (wide rows)
+
+#if WANN_DT == 0 || WANN_DT == 3
+// Float16 rows of 129 .. 2048 elements (WANN_DT = 3, two to sixteen slabs) run the same K-loop under a name of their own,
+// k_gemm_scores_hslab.  The rows are halves: a row is `stride` 4-byte words = 2 stride halves (padded to a multiple of 32), while the
+// query operand and the k-steps go by the row length of the float32 upcast, qw = d rounded up to 16 <= 2 stride.  A unit's halves
+// are fetched eight at a time (16 bytes, 32 registers in flight instead of 64) and converted exactly where they are staged, so
+// what the LDS holds is bit for bit what the float32 kernel stages for the upcast row; the queries come split by the float32
+// unit's k_split_queries, qw words a row.
+#if WANN_DT == 3
+#define WANN_KSLAB k_gemm_scores_hslab
+#define WANN_KSLAB_WAVES 2  // (a register cap, not an occupancy: the float16 unit's kernels are held to 256 registers; the LDS admits one workgroup)
+#else
+#define WANN_KSLAB k_gemm_scores_long
+#define WANN_KSLAB_WAVES 1
+#endif
+WANN_GNS_BEGIN
+__global__ __launch_bounds__(256, WANN_KSLAB_WAVES) void WANN_KSLAB(GemmArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const IndexView &ix = A.ix;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -1102,7 +1120,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
   const bool mips = ix.metric == 1;
   const float scale = mips ? -1.f : -2.f;
   const int ntiles = A.plan[P_NTILES];
-  const int stride = ix.stride, nslab = (stride + W - 1) / W;
+  // stride: words of a point row; qw: floats of the (upcast) row = words of a split query = what the k-steps walk (float32: the same)
+  const int stride = ix.stride, qw = qv_words(ix), nslab = (qw + W - 1) / W;
 
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const GemmGroup grp = A.groups[A.tile_group[t]];
@@ -1112,12 +1131,12 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
     const int64_t p_end = (p_begin + kGemmPointChunk < w) ? (p_begin + kGemmPointChunk) : w;
     __syncthreads();  // the previous tile is done with the staging areas and the rows
     if (tid < 128) rid[tid] = window_row(ix, grp.a + min(p_begin + tid, wlast));
-    // this thread's two query rows (64 p + tid / 4), split: stride words, hi pairs then lo pairs (rows beyond the group's last
+    // this thread's two query rows (64 p + tid / 4), split: qw words, hi pairs then lo pairs (rows beyond the group's last
     // query repeat it; their lanes store nothing)
     const unsigned char *qsrc[2];
 #pragma unroll
     for (int p = 0; p < 2; p++)
-      qsrc[p] = reinterpret_cast<const unsigned char *>(A.qsplit + (int64_t)A.gq[grp.qoff + min(q0 + 64 * p + (tid >> 2), grp.qcount - 1)] * stride);
+      qsrc[p] = reinterpret_cast<const unsigned char *>(A.qsplit + (int64_t)A.gq[grp.qoff + min(q0 + 64 * p + (tid >> 2), grp.qcount - 1)] * qw);
     __syncthreads();  // the step's rows are in `rid`
     const int myrow = q0 + 32 * wv + col;
     const bool live = myrow < grp.qcount;
@@ -1126,7 +1145,18 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
     // fetch pipeline: the next (step, slab) travels to registers during the MFMAs of the current one.  `rid` holds the rows of
     // the step being fetched; it moves on to the next step when a step's LAST slab is staged (k_gemm_scores_wide's scheme).
     // Offsets are clamped into the row: a last, partial slab fetches bytes it never multiplies.
+#if WANN_DT == 3
+    constexpr int np = nx / 2;  // point pieces per thread and half slab: eight halves each
+    u32x4 pre[2 * np];
+#define WANN_FETCHL_POINTS(P, SL)                                                                          \
+    _Pragma("unroll") for (int x = 0; x < np; x++)                                                         \
+      pre[(P) * np + x] = *reinterpret_cast<const u32x4 *>(reinterpret_cast<const unsigned short *>(src) + min(W * (SL) + 8 * (tid & 3) + 32 * x, 2 * stride - 8));
+#else
     f32x4 pre[2 * nx];
+#define WANN_FETCHL_POINTS(P, SL)                                                                          \
+    _Pragma("unroll") for (int x = 0; x < nx; x++)                                                         \
+      pre[(P) * nx + x] = *reinterpret_cast<const f32x4 *>(src + min(W * (SL) + 4 * (tid & 3) + 16 * x, stride - 4));
+#endif
     u32x4 qre[2 * nx];  // pieces 0 .. nx/2-1 of a half: hi pairs, the others: lo pairs
     float pre_n = 0.f;
     int pre_rid = 0;
@@ -1134,11 +1164,10 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
   {                                                                                                        \
     _Pragma("unroll") for (int p = 0; p < 2; p++) {                                                        \
       const float *src = ix.points + (int64_t)rid[64 * p + (tid >> 2)] * stride;                           \
-      _Pragma("unroll") for (int x = 0; x < nx; x++)                                                       \
-        pre[p * nx + x] = *reinterpret_cast<const f32x4 *>(src + min(W * (SL) + 4 * (tid & 3) + 16 * x, stride - 4)); \
+      WANN_FETCHL_POINTS(p, SL)                                                                            \
       _Pragma("unroll") for (int x = 0; x < nx; x++) {                                                     \
         const int term = x / (nx / 2), cb = 2 * W * (SL) + 16 * (tid & 3) + 64 * (x % (nx / 2));           \
-        qre[p * nx + x] = *reinterpret_cast<const u32x4 *>(qsrc[p] + term * 2 * stride + min(cb, 2 * stride - 16)); \
+        qre[p * nx + x] = *reinterpret_cast<const u32x4 *>(qsrc[p] + term * 2 * qw + min(cb, 2 * qw - 16)); \
       }                                                                                                    \
     }                                                                                                      \
     if ((NEWSTEP) && tid < 128) {                                                                          \
@@ -1153,6 +1182,21 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
         // (the barrier that ended the previous unit: nobody reads Ps / Qs / base any more)
 #pragma unroll
         for (int p = 0; p < 2; p++) {
+#if WANN_DT == 3
+          unsigned char *dst = Ps + (64 * p + (tid >> 2)) * RB + 16 * (tid & 3);
+#pragma unroll
+          for (int x = 0; x < np; x++) {
+            const u32x4 hw = pre[p * np + x];
+            const float4 v0 = h4_to_f4(make_uint2(hw[0], hw[1])), v1 = h4_to_f4(make_uint2(hw[2], hw[3]));
+            uint32_t h0, l0, h1, l1, h2, l2, h3, l3;
+            split2(v0.x, v0.y, h0, l0);
+            split2(v0.z, v0.w, h1, l1);
+            split2(v1.x, v1.y, h2, l2);
+            split2(v1.z, v1.w, h3, l3);
+            *reinterpret_cast<u32x4 *>(dst + 64 * x) = u32x4{h0, h1, h2, h3};
+            *reinterpret_cast<u32x4 *>(dst + 2 * W + 64 * x) = u32x4{l0, l1, l2, l3};
+          }
+#else
           unsigned char *dst = Ps + (64 * p + (tid >> 2)) * RB + 8 * (tid & 3);
 #pragma unroll
           for (int x = 0; x < nx; x++) {
@@ -1163,6 +1207,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
             *reinterpret_cast<uint2 *>(dst + 32 * x) = make_uint2(h0, h1);
             *reinterpret_cast<uint2 *>(dst + 2 * W + 32 * x) = make_uint2(l0, l1);
           }
+#endif
           unsigned char *qdst = Qs + (64 * p + (tid >> 2)) * RB + 16 * (tid & 3);
 #pragma unroll
           for (int x = 0; x < nx; x++) *reinterpret_cast<u32x4 *>(qdst + (x / (nx / 2)) * 2 * W + 64 * (x % (nx / 2))) = qre[p * nx + x];
@@ -1199,7 +1244,13 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
     _Pragma("unroll") for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[j], a_lo, acc[j], 0, 0, 0); \
     _Pragma("unroll") for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[j], a_hi, acc[j], 0, 0, 0); \
   }
-        const int ks = min(S, (stride - W * sl) >> 4);  // k-steps of this slab (workgroup-uniform)
+        const int ks = min(S, (qw - W * sl) >> 4);  // k-steps of this slab (workgroup-uniform)
+#if WANN_DT == 3
+        // (one loop for full and partial slabs: where an unrolled copy and the loop join, the accumulators live twice -- 63
+        // registers spilled under this unit's cap of 256)
+#pragma unroll 1
+        for (int s = 0; s < ks; s++) WANN_KSTEP(s)
+#else
         if (ks == S) {
 #pragma unroll
           for (int s = 0; s < S; s++) WANN_KSTEP(s)
@@ -1207,6 +1258,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
 #pragma unroll 1
           for (int s = 0; s < ks; s++) WANN_KSTEP(s)
         }
+#endif
 #undef WANN_KSTEP
         if (sl + 1 < nslab) __syncthreads();  // every wave is done with this slab's operands
       }
@@ -1228,10 +1280,14 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_long(GemmArgs A) {
       __syncthreads();  // every wave is done with Ps / Qs / base
     }
 #undef WANN_FETCHL
+#undef WANN_FETCHL_POINTS
   }
 }
+WANN_GNS_END
+#undef WANN_KSLAB
+#undef WANN_KSLAB_WAVES
 
-#endif  // WANN_DT == 0 (wide rows)
+#endif  // WANN_DT == 0 || WANN_DT == 3 (the K-loop)
 
 // One wave per grouped query.  Its window's blocks each handed over their four smallest scores (sorted, position in
 // the low mantissa bits).  The first three of every block are candidates, the fourth bounds everything the block kept
@@ -1647,7 +1703,14 @@ const char *launch_point_norms(const IndexView &ix, float *norm2, unsigned int *
 
 const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream) {
   const int qw = query_words(a.ix);  // the row length of the float32 upcast
-  if (qw > 128) return "float16 rows of more than 128 elements take the exact scan";
+  if (qw > kGemmMaxFloats) return "float16 rows of more than 2048 elements take the exact scan";
+  if (qw > 128) {  // 129 .. 2048 elements: run-time slab count, both operands staged per slab (queries pre-split, qw words a row)
+    if (!a.qsplit) return "k_gemm_scores_hslab needs the split queries";
+    const size_t ldsl = (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4;
+    if (const char *e = gerr_of(hipFuncSetAttribute((const void *)k_gemm_scores_hslab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsl))) return e;
+    hipLaunchKernelGGL(k_gemm_scores_hslab, dim3(num_cus > 0 ? num_cus : 256), dim3(256), ldsl, (hipStream_t)stream, a);
+    return gerr_of(hipGetLastError());
+  }
   const size_t lds = (size_t)128 * (4 * qw + 16) + 3 * 128 * 4;
   void (*kern)(GemmArgs) = nullptr;
   switch (qw) {

@@ -327,14 +327,17 @@ int method_code(const char *m) {
 // never waits.
 // rows the score kernels take, per element type: float32 up to 512 floats (the query operand in registers, RedCaps) -- up to
 // 2048 (kGemmMaxFloats) where WANN_DENSE_LONG_ROWS=1 opts in: k_gemm_scores_long stages both operands slab by slab, and until it
-// is timed against the scan no batch moves to it by default --, float16 up to 128 elements (the narrow kernel only), uint8 / int8
-// up to 512 bytes -- up to 2048 (kGemmMaxBytes, k_gemm_scores_bslab) under the same switch, for the same reason; everything
-// longer (and k > 16) stays on the exact scan
+// is timed against the scan no batch moves to it by default --, float16 up to 128 elements (the narrow kernel) -- up to 2048
+// (k_gemm_scores_hslab, the same K-loop with half loads) under the same switch --, uint8 / int8 up to 512 bytes -- up to 2048
+// (kGemmMaxBytes, k_gemm_scores_bslab) under the same switch, for the same reason; everything longer (and k > 16) stays on the
+// exact scan.  A float16 row counts by query_words: its stride is the half row's word count.
 static bool dense_rows_ok(const wann_index &I, const Tuning &T, int k) {
   const int dtype = I.view.dtype;
   const bool bytes = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8;
   if (k > kSelect / 2 || (I.view.stride & 15)) return false;
-  if (dtype == WANN_DTYPE_F16 ? query_words(I.view) > 128 : I.view.stride > (bytes ? (T.dense_long ? kGemmMaxBytes / 4 : 128) : T.dense_long ? kGemmMaxFloats : 512)) return false;
+  if (dtype == WANN_DTYPE_F16 ? query_words(I.view) > (T.dense_long ? kGemmMaxFloats : 128)
+                              : I.view.stride > (bytes ? (T.dense_long ? kGemmMaxBytes / 4 : 128) : T.dense_long ? kGemmMaxFloats : 512))
+    return false;
   return true;
 }
 
@@ -346,11 +349,13 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   const int dtype = I.view.dtype;
   const bool bytes = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8;
   if (!dense_rows_ok(I, T, k)) return;
-  // rows of more than 512 floats need the batch's queries split into their bf16 terms (nq x stride x 4 bytes, below) before the
-  // device has grouped anything: a batch whose split would exceed 256 MiB (the score buffer's cap) stays on the exact scan.
-  // Byte rows of more than 512 bytes need them packed to bytes (nq x stride words as well): the same buffer, the same cap.
-  const bool long_rows = bytes ? I.view.stride > 128 : (dtype == WANN_DTYPE_F32 && I.view.stride > 512);
-  if (long_rows && (unsigned long long)nq * (unsigned long long)I.view.stride > (64ull << 20)) return;
+  // rows of more than 512 floats (float16: 128 elements) need the batch's queries split into their bf16 terms (nq x qwords x 4
+  // bytes, below) before the device has grouped anything: a batch whose split would exceed 256 MiB (the score buffer's cap) stays
+  // on the exact scan.  Byte rows of more than 512 bytes need them packed to bytes (nq x stride words as well): the same buffer,
+  // the same cap.  qwords: the query's row length in words -- the stride, but for float16 rows, whose stride counts half rows.
+  const int qwords = query_words(I.view);
+  const bool long_rows = bytes ? I.view.stride > 128 : dtype == WANN_DTYPE_F16 ? qwords > 128 : I.view.stride > 512;
+  if (long_rows && (unsigned long long)nq * (unsigned long long)qwords > (64ull << 20)) return;
   if (!I.have_norms) {
     if (bytes) {  // exact integer sums of the rows (wann_gemm_kernels_bytes.inc)
       I.d_pterm.ensure((size_t)I.view.n);
@@ -412,17 +417,17 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   ga.pnorm2_max_bits = I.d_pnorm2_max.p;
   ga.pterm = I.d_pterm.p;
   if (long_rows) {
-    // k_gemm_scores_long takes the queries already split into their bf16 terms: once per batch instead of once per (tile,
-    // step), nq x stride x 4 bytes; k_gemm_scores_bslab takes them packed to biased bytes, the same size.  Counted like the
-    // norms: a PrefilterIndex has never reported its dense buffers.
-    I.g_qsplit.ensure((size_t)nq * (size_t)I.view.stride);
+    // k_gemm_scores_long / _hslab take the queries already split into their bf16 terms: once per batch instead of once per
+    // (tile, step), nq x qwords x 4 bytes; k_gemm_scores_bslab takes them packed to biased bytes, the same size.  Counted like
+    // the norms: a PrefilterIndex has never reported its dense buffers.
+    I.g_qsplit.ensure((size_t)nq * (size_t)qwords);
     if (sorted_exact && (int64_t)I.g_qsplit.bytes() > I.qsplit_counted) {
       I.device_bytes += (int64_t)I.g_qsplit.bytes() - I.qsplit_counted;
       I.qsplit_counted = (int64_t)I.g_qsplit.bytes();
     }
     if (bytes) {
       if (launch_pack_queries(I.view, d_queries, nq, I.g_qsplit.p, st)) throw HipError(std::string("k_pack_queries_b: ") + gemm_launch_last_error());
-    } else if (launch_split_queries(d_queries, nq, I.view.d, I.view.stride, I.g_qsplit.p, st)) {
+    } else if (launch_split_queries(d_queries, nq, I.view.d, qwords, I.g_qsplit.p, st)) {
       throw HipError(std::string("k_split_queries: ") + gemm_launch_last_error());
     }
     ga.qsplit = I.g_qsplit.p;

@@ -161,7 +161,7 @@ struct wann_index {
   DevBuf<int32_t> g_gq, g_tile_group, g_tq_group, g_tq_local, g_slot_count, g_slot_group, g_slot_list, g_q_slot, g_q_rank, g_plan;
   DevBuf<unsigned long long> g_slot_key, g_score_used;
   DevBuf<float> g_scores;
-  DevBuf<uint32_t> g_qsplit;    // rows of more than 512 elements: the batch's queries as bf16 pairs (float32) / packed biased bytes (uint8, int8) (GemmArgs::qsplit)
+  DevBuf<uint32_t> g_qsplit;    // rows of more than 512 elements (float16: 128): the batch's queries as bf16 pairs (float32, float16) / packed biased bytes (uint8, int8) (GemmArgs::qsplit)
   int64_t qsplit_counted = 0;   // bytes of it that device_bytes holds (sorted kinds only, as with the norms)
   DevBuf<unsigned long long> g_prof;
   // cover groups (wann_set_dense_windows): distinct wide windows of a PrefilterIndex batch on the matrix cores, grouped by

@@ -40,7 +40,7 @@ struct Tuning {
   long long deep_min_tasks = 4096;  // WANN_DEEP_MIN_TASKS: graph tasks from which a launch counts as saturated (deep-chain pollers)
   bool serialized = false;     // HIP_LAUNCH_BLOCKING / AMD_SERIALIZE_KERNEL / CUDA_LAUNCH_BLOCKING: launches never overlap
   float proof_factor = 3.f;    // WANN_PROOF_FACTOR, clamped to >= 3 (see dense_prefilter)
-  bool dense_long = false;     // WANN_DENSE_LONG_ROWS=1: float32 rows of 513 .. 2048 floats and uint8 / int8 rows of 513 .. 2048 bytes take the dense path too (opt-in: not yet timed against the scan)
+  bool dense_long = false;     // WANN_DENSE_LONG_ROWS=1: float32 rows of 513 .. 2048 floats, float16 rows of 129 .. 2048 elements and uint8 / int8 rows of 513 .. 2048 bytes take the dense path too (opt-in: not yet timed against the scan)
   // hooks that force rare paths
   bool force_pollers = false, force_poll_timeout = false, la_eager = false, force_general = false, old_general = false,
        raw_big_lds = false;

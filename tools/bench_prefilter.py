@@ -6,14 +6,14 @@ each against the REAL reference at its best thread count (child processes: the r
 --dtype float32 | float16 | uint8 | int8 (default float32) selects the element type of the point set: float16 rounds the same
 set (MIPS), the byte types quantise it -- round(127 x) for int8 (MIPS), + 128 for uint8 (Euclidian), queries likewise -- and run
 on the int8 MFMA with exact scores.  Every leg is timed as the median of repeated calls (min / max beside it: the spread).
---dim D sets the row length (default 100; 512 = RedCaps, 768 / 1024 / 1536 = the long rows of k_gemm_scores_long (float32) and k_gemm_scores_bslab (uint8 / int8)), --clusters C
+--dim D sets the row length (default 100; 512 = RedCaps, 768 / 1024 / 1536 = the long rows of k_gemm_scores_long (float32), k_gemm_scores_hslab (float16) and k_gemm_scores_bslab (uint8 / int8)), --clusters C
 the number of clusters (default 100), --metric l2 | mips the metric of the float types (default mips).  WANN_PF_CACHE=<dir> keeps
 the generated set there for the next run of the same shape; WANN_PF_ONLY=mfma times the dense leg alone (runs under a profiler),
 WANN_PF_ONLY=scan the exact-scan leg alone, twice (the baseline run of a parent build); WANN_PF_NO_REF=1 leaves the CPU reference out.
 Run from the repo root.  Prints one JSON object."""
 import json, os, subprocess, sys, time
 os.environ.setdefault("WANN_TEST_HOOKS", "1")  # this tool flips WANN_* switches between calls on one index
-os.environ.setdefault("WANN_DENSE_LONG_ROWS", "1")  # (float32 / uint8 / int8 rows of 513 .. 2048 elements: the dense leg is the opt-in kernel)
+os.environ.setdefault("WANN_DENSE_LONG_ROWS", "1")  # (float32 / uint8 / int8 rows of 513 .. 2048 elements, float16 rows of 129 .. 2048: the dense leg is the opt-in kernel)
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
 
