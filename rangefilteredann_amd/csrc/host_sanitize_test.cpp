@@ -12,6 +12,7 @@
 
 #include "../../include/wann.h"
 #include "wann_build.h"
+#include "wann_gemm_device.h"
 #include "wann_stdsort.h"
 #include <algorithm>
 
@@ -163,6 +164,30 @@ int main(int argc, char **argv) {
       check(v);
     }
   }
+  // the dense path's row classes (dense_row_class, wann_gemm_device.h) against the table written out as literal boundaries, on the
+  // strides an uploaded index has: float32 d rounded up to 16 words, bytes d rounded up to 64 bytes, float16 2 d bytes likewise
+  for (int dtype : {WANN_DTYPE_F32, WANN_DTYPE_U8, WANN_DTYPE_I8, WANN_DTYPE_F16})
+    for (int d = 1; d <= 2200; d++)
+      for (int dense_long = 0; dense_long < 2; dense_long++) {
+        IndexView v{};
+        v.dtype = dtype;
+        v.d = d;
+        v.stride = dtype == WANN_DTYPE_F32 ? (d + 15) / 16 * 16 : dtype == WANN_DTYPE_F16 ? (2 * d + 63) / 64 * 16 : (d + 63) / 64 * 64 / 4;
+        // elements a row holds after padding: floats and halves to 16, bytes to 64
+        const int len = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8 ? (d + 63) / 64 * 64 : (d + 15) / 16 * 16;
+        DenseRows want;
+        if (dtype == WANN_DTYPE_F32) want = len <= 128 ? kRowsNarrow : len <= 512 ? kRowsWide : len <= 2048 ? kRowsLong : kRowsNone;
+        else if (dtype == WANN_DTYPE_F16) want = len <= 128 ? kRowsNarrow : len <= 2048 ? kRowsLong : kRowsNone;
+        else want = len <= 512 ? kRowsNarrow : len <= 2048 ? kRowsLong : kRowsNone;
+        const DenseRows got = dense_row_class(v);
+        CHECK(got == want);
+        // what the host admits (dense_rows_ok): the long class only where the process has opted in
+        const bool admitted = got != kRowsNone && (got != kRowsLong || dense_long);
+        const int limit = dense_long ? 2048 : dtype == WANN_DTYPE_F16 ? 128 : 512;  // elements: floats, halves, bytes
+        CHECK(admitted == (len <= limit));
+        v.stride += 8;  // not a multiple of 16 words: no kernel takes it
+        CHECK(dense_row_class(v) == kRowsNone);
+      }
   // the C ABI's argument validation (no device needed for these paths) lives in wann_host.cpp and is covered by tests/test_abi.py
   if (fails) {
     fprintf(stderr, "host sanitize test: %d check(s) failed\n", fails);

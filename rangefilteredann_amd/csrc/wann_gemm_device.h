@@ -8,8 +8,8 @@ namespace wann {
 
 constexpr int kSelect = 32;      // candidates kept per query by MFMA score before the exact re-rank
 constexpr int kGemmPointChunk = 2048;  // window positions per tile (multiple of 128)
-constexpr int kGemmMaxFloats = 2048;   // longest padded float32 row the score kernels take (k_gemm_scores_long; 512 without it)
-constexpr int kGemmMaxBytes = 2048;    // longest padded uint8 / int8 row they take (k_gemm_scores_bslab; 512 without it)
+constexpr int kGemmMaxFloats = 2048;   // longest float32 / float16 row, in 32-bit words of the float32 row (dense_row_class only)
+constexpr int kGemmMaxBytes = 2048;    // longest padded uint8 / int8 row, in bytes (dense_row_class only)
 // (a window hands over three candidates per 64 positions: too short a window could never prove a top 10)
 constexpr int kGroupMinQueries = 16, kGroupMinWindow = 1024;
 // cover groups (distinct windows, wann_set_dense_windows): a query is eligible if its window has at least kCoverMinWindow
@@ -106,11 +106,45 @@ struct CoverArgs {
   CoverCounters *cctr;  // of the batch
 };
 
-// (the launchers dispatch on ix.dtype: one set of kernels per element type)
+// Which rows the dense path takes, and on which kind of score kernel: THE table -- the host (dense_rows_ok, dense_prefilter) and
+// the launchers (wann_gemm_launch.inc) ask here and hold no row length of their own.  Lengths in 32-bit words: `stride` for
+// float32 and byte rows, query_words (the row of the float32 upcast; the stride counts half rows) for float16.
+//
+//                  narrow              wide                      long (opt-in: WANN_DENSE_LONG_ROWS=1; queries pre-split / packed)
+//   float32        16 .. 128           129 .. 512                513 .. 2048 (kGemmMaxFloats)
+//                  k_gemm_scores<W>    k_gemm_scores_wide<2|3>   k_gemm_scores_long
+//                                      / k_gemm_scores_wide4
+//   float16        16 .. 128           -                         129 .. 2048 (kGemmMaxFloats)
+//                  k_gemm_scores<W>                              k_gemm_scores_hslab
+//   uint8 / int8   16 .. 128 (512 B)   -                         129 .. 512 (kGemmMaxBytes / 4)
+//                  k_gemm_scores_b<N>                            k_gemm_scores_bslab, quantised keys: k_rerank_bslab
+//
+// Anything longer, and a stride that is not a multiple of 16 words, is kRowsNone: the exact scan.
+enum DenseRows { kRowsNone, kRowsNarrow, kRowsWide, kRowsLong };
+inline DenseRows dense_row_class(const IndexView &ix) {
+  const bool bytes = ix.dtype == 1 || ix.dtype == 2;
+  const int words = query_words(ix);
+  if ((ix.stride & 15) || words < 16 || words > (bytes ? kGemmMaxBytes / 4 : kGemmMaxFloats)) return kRowsNone;
+  if (words <= 128) return kRowsNarrow;
+  return ix.dtype == 0 && words <= 512 ? kRowsWide : kRowsLong;
+}
+
+// One unit's launchers (wann_gemm_launch.inc, compiled once per element type): a null return = launched, otherwise the error
+// text.  Each unit's table is a constant reached through its gemm_unit(): nothing depends on an order of initialisation.
+struct GemmUnit {
+  const char *(*point_sums)(const IndexView &ix, float *norm2, unsigned int *max_bits, int32_t *term, void *stream);  // norms (float types) / terms (bytes)
+  // long rows: the batch's queries split into bf16 terms (the float32 unit's; it serves float16 rows too) / packed to bytes
+  const char *(*prep_queries)(const float *queries, int64_t nq, int d, int words, uint32_t *out, void *stream);
+  const char *(*gemm_scores)(const GemmArgs &a, int num_cus, void *stream);
+  const char *(*select_rerank)(const GemmArgs &a, Counters *ctr, void *stream);
+  const char *(*rerank_cover)(const CoverArgs &c, void *stream);
+};
+
+// entry points (the float32 unit): each looks up ix.dtype's unit, calls it and records the error; 0 = launched
 int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);  // float32 / float16 rows
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream);                         // uint8 / int8 rows
-int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream);  // float32 rows > 512 floats
-int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);  // uint8 / int8 rows > 512 bytes
+int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream);  // long float32 / float16 rows
+int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);  // long uint8 / int8 rows
 int launch_group_windows(const GemmArgs &a, Counters *ctr, void *stream);
 int launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 int launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);

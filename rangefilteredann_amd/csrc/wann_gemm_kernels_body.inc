@@ -24,7 +24,9 @@
 // distance is computed by the reference-order routines.
 //
 // One translation unit per element type of the point set (WANN_DT, set by wann_gemm_kernels.hip / _u8.hip / _i8.hip / _f16.hip
-// before this body is included).  The float32 unit holds the grouping kernels, every float32 kernel and the dispatchers.
+// before this body is included).  The float32 unit holds the grouping kernels and every float32 kernel.  Which rows run on which
+// score kernel is decided in one place, dense_row_class (wann_gemm_device.h); the launchers are one text for all four units,
+// wann_gemm_launch.inc, each unit exposing its own through a constant table (GemmUnit) that the float32 unit's entry points look up.
 //   float16 rows (WANN_DT = 3)  the narrow k_gemm_scores with half loads: a binary16 value is EXACTLY the sum of its two bf16
 //                    terms (11 significant bits <= 8 + 8; the low term of a subnormal half is a multiple of 2^-24, far above
 //                    bf16's smallest normal number), so scores, selection, proof bound and re-rank are the float32 path's on the
@@ -1621,290 +1623,6 @@ __global__ __launch_bounds__(256) void k_rerank_cover_bslab(CoverArgs C) {
 #endif
 WANN_GNS_END
 
-// ------------------------------------------------------------------------------------------------
-// launchers: the float32 unit holds the entry points (wann_gemm_device.h) and hands float16 / byte indexes to their units'
-// (a null return = launched; otherwise the error text)
-// LDS of the selection / re-rank kernels: four waves x (staged query row, candidate arrays, the k-entry merge list)
-static inline size_t rerank_lds_bytes(const IndexView &ix, int k) {
-  return (size_t)4 * (((query_words(ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((k + 1) & ~1) * 8);
-}
-WANN_GNS_BEGIN
-static hipError_t launch_rerank_cover_unit(const CoverArgs &c, void *stream) {  // this unit's k_rerank_cover
-  const GemmArgs &a = c.g;
-  const int blocks = (int)std::min<int64_t>(4096, (a.nq + 3) / 4);
-  const size_t lds = rerank_lds_bytes(a.ix, a.k);
-#if WANN_BYTE_ROWS
-  if (a.ix.stride > 128) {  // (rows of more than 512 bytes: quantised keys)
-    if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank_cover_bslab<1>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
-    else hipLaunchKernelGGL(k_rerank_cover_bslab<0>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
-    return hipGetLastError();
-  }
-#endif
-  if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank_cover<1>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
-  else hipLaunchKernelGGL(k_rerank_cover<0>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, c);
-  return hipGetLastError();
-}
-WANN_GNS_END
-
-#if WANN_DT != 0
-namespace WANN_DT_NS_G {
-static const char *gerr_of(hipError_t e) { return e == hipSuccess ? nullptr : hipGetErrorString(e); }
-
-#if WANN_BYTE_ROWS
-const char *launch_point_terms(const IndexView &ix, int32_t *term, void *stream) {
-  if (ix.n <= 0) return nullptr;
-  const int wpb = 4;
-  hipLaunchKernelGGL(k_point_terms_b, dim3((unsigned)((ix.n + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, ix, term);
-  return gerr_of(hipGetLastError());
-}
-
-const char *launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream) {
-  const int64_t words = nq * ix.stride;
-  if (words <= 0) return nullptr;
-  hipLaunchKernelGGL(k_pack_queries_b, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, queries, nq, ix.d, ix.stride, out);
-  return gerr_of(hipGetLastError());
-}
-
-const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream) {
-  if (a.ix.stride * 4 > kGemmMaxBytes || (a.ix.stride & 15)) return "row too long for the dense prefilter tile";
-  if (a.ix.stride > 128) {  // 513 .. 2048 bytes: run-time slab count, both operands staged per slab (queries pre-packed)
-    if (!a.qsplit) return "k_gemm_scores_bslab needs the packed queries";
-    const size_t ldss = (size_t)2 * 128 * (256 + 16) + 3 * 128 * 4;
-    if (const char *e = gerr_of(hipFuncSetAttribute((const void *)k_gemm_scores_bslab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldss))) return e;
-    hipLaunchKernelGGL(k_gemm_scores_bslab, dim3(2 * (num_cus > 0 ? num_cus : 256)), dim3(256), ldss, (hipStream_t)stream, a);
-    return gerr_of(hipGetLastError());
-  }
-  const int nch = a.ix.stride / 16;
-  const size_t lds = (size_t)128 * (64 * nch + 16) + 3 * 128 * 4;
-  void (*kern)(GemmArgs) = nullptr;
-  switch (nch) {
-    case 1: kern = k_gemm_scores_b<1>; break;
-    case 2: kern = k_gemm_scores_b<2>; break;
-    case 3: kern = k_gemm_scores_b<3>; break;
-    case 4: kern = k_gemm_scores_b<4>; break;
-    case 5: kern = k_gemm_scores_b<5>; break;
-    case 6: kern = k_gemm_scores_b<6>; break;
-    case 7: kern = k_gemm_scores_b<7>; break;
-    default: kern = k_gemm_scores_b<8>; break;
-  }
-  if (lds > 48 * 1024)
-    if (const char *e = gerr_of(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))) return e;
-  const int cus = num_cus > 0 ? num_cus : 256;
-  hipLaunchKernelGGL(kern, dim3(nch > 4 ? cus : 2 * cus), dim3(256), lds, (hipStream_t)stream, a);
-  return gerr_of(hipGetLastError());
-}
-#else
-const char *launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream) {
-  if (ix.n <= 0) return nullptr;
-  const int wpb = 4;
-  hipLaunchKernelGGL(k_point_norms, dim3((unsigned)((ix.n + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, ix, norm2, max_bits);
-  return gerr_of(hipGetLastError());
-}
-
-const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream) {
-  const int qw = query_words(a.ix);  // the row length of the float32 upcast
-  if (qw > kGemmMaxFloats) return "float16 rows of more than 2048 elements take the exact scan";
-  if (qw > 128) {  // 129 .. 2048 elements: run-time slab count, both operands staged per slab (queries pre-split, qw words a row)
-    if (!a.qsplit) return "k_gemm_scores_hslab needs the split queries";
-    const size_t ldsl = (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4;
-    if (const char *e = gerr_of(hipFuncSetAttribute((const void *)k_gemm_scores_hslab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsl))) return e;
-    hipLaunchKernelGGL(k_gemm_scores_hslab, dim3(num_cus > 0 ? num_cus : 256), dim3(256), ldsl, (hipStream_t)stream, a);
-    return gerr_of(hipGetLastError());
-  }
-  const size_t lds = (size_t)128 * (4 * qw + 16) + 3 * 128 * 4;
-  void (*kern)(GemmArgs) = nullptr;
-  switch (qw) {
-    case 16: kern = k_gemm_scores<16>; break;
-    case 32: kern = k_gemm_scores<32>; break;
-    case 48: kern = k_gemm_scores<48>; break;
-    case 64: kern = k_gemm_scores<64>; break;
-    case 80: kern = k_gemm_scores<80>; break;
-    case 96: kern = k_gemm_scores<96>; break;
-    case 112: kern = k_gemm_scores<112>; break;
-    default: kern = k_gemm_scores<128>; break;
-  }
-  if (lds > 48 * 1024)
-    if (const char *e = gerr_of(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))) return e;
-  hipLaunchKernelGGL(kern, dim3(2 * (num_cus > 0 ? num_cus : 256)), dim3(256), lds, (hipStream_t)stream, a);
-  return gerr_of(hipGetLastError());
-}
-#endif
-
-const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int blocks = (int)std::min<int64_t>(4096, (a.nq + 3) / 4);
-  const size_t lds = rerank_lds_bytes(a.ix, a.k);
-#if WANN_BYTE_ROWS
-  if (a.ix.stride > 128) {  // (rows of more than 512 bytes: quantised keys)
-    if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank_bslab<1>, dim3(blocks), dim3(256), lds, s, a, ctr);
-    else hipLaunchKernelGGL(k_rerank_bslab<0>, dim3(blocks), dim3(256), lds, s, a, ctr);
-    return gerr_of(hipGetLastError());
-  }
-#endif
-  if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank<1>, dim3(blocks), dim3(256), lds, s, a, ctr);
-  else hipLaunchKernelGGL(k_rerank<0>, dim3(blocks), dim3(256), lds, s, a, ctr);
-  return gerr_of(hipGetLastError());
-}
-
-const char *launch_rerank_cover(const CoverArgs &c, void *stream) { return gerr_of(launch_rerank_cover_unit(c, stream)); }
-}  // namespace WANN_DT_NS_G
-#else  // WANN_DT == 0
-namespace dt_u8 {
-const char *launch_rerank_cover(const CoverArgs &c, void *stream);
-const char *launch_point_terms(const IndexView &ix, int32_t *term, void *stream);
-const char *launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);
-const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
-const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
-}
-namespace dt_i8 {
-const char *launch_rerank_cover(const CoverArgs &c, void *stream);
-const char *launch_point_terms(const IndexView &ix, int32_t *term, void *stream);
-const char *launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);
-const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
-const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
-}
-namespace dt_f16 {
-const char *launch_rerank_cover(const CoverArgs &c, void *stream);
-const char *launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);
-const char *launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
-const char *launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
-}
-
-static thread_local const char *g_gerr = "";
-const char *gemm_launch_last_error() { return g_gerr; }
-static int gcheck(hipError_t e) {
-  if (e != hipSuccess) {
-    g_gerr = hipGetErrorString(e);
-    return 1;
-  }
-  return 0;
-}
-static int gtyped(const char *err) {  // a per-type unit's launcher
-  if (err) g_gerr = err;
-  return err ? 1 : 0;
-}
-
-int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream) {
-  if (ix.dtype == 3) return gtyped(dt_f16::launch_point_norms(ix, norm2, max_bits, stream));
-  if (ix.n <= 0) return 0;
-  const int wpb = 4;
-  hipLaunchKernelGGL(k_point_norms, dim3((unsigned)((ix.n + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, ix, norm2,
-                     max_bits);
-  return gcheck(hipGetLastError());
-}
-
-int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream) {
-  const int64_t pairs = nq * (stride >> 1);
-  if (pairs <= 0) return 0;
-  hipLaunchKernelGGL(k_split_queries, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, queries, nq, d, stride, out);
-  return gcheck(hipGetLastError());
-}
-
-int launch_point_terms(const IndexView &ix, int32_t *term, void *stream) {
-  return gtyped(ix.dtype == 1 ? dt_u8::launch_point_terms(ix, term, stream) : dt_i8::launch_point_terms(ix, term, stream));
-}
-
-int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream) {
-  return gtyped(ix.dtype == 1 ? dt_u8::launch_pack_queries(ix, queries, nq, out, stream) : dt_i8::launch_pack_queries(ix, queries, nq, out, stream));
-}
-
-int launch_group_windows(const GemmArgs &a, Counters *ctr, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int cap = a.cap_mask + 1;
-  hipLaunchKernelGGL(k_group_clear, dim3((cap + 255) / 256), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_group_insert, dim3((unsigned)((a.nq + 255) / 256)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_group_plan, dim3(1), dim3(1024), 0, s, a, ctr);
-  hipLaunchKernelGGL(k_group_scatter, dim3((unsigned)((a.nq + 255) / 256)), dim3(256), 0, s, a);
-  return gcheck(hipGetLastError());
-}
-
-int launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream) {
-  if (a.ix.dtype == 1) return gtyped(dt_u8::launch_gemm_scores(a, num_cus, stream));
-  if (a.ix.dtype == 2) return gtyped(dt_i8::launch_gemm_scores(a, num_cus, stream));
-  if (a.ix.dtype == 3) return gtyped(dt_f16::launch_gemm_scores(a, num_cus, stream));
-  if (a.ix.stride > 128) {  // 129 .. 512 floats: slabs of 128, A operand in registers, one workgroup per CU
-    if (a.ix.stride > kGemmMaxFloats || (a.ix.stride & 15)) {
-      g_gerr = "dimension too large for the dense prefilter tile";
-      return 1;
-    }
-    if (a.ix.stride > 512) {  // 513 .. 2048 floats: run-time slab count, both operands staged per slab (queries pre-split)
-      if (!a.qsplit) {
-        g_gerr = "k_gemm_scores_long needs the split queries";
-        return 1;
-      }
-      const size_t ldsl = (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4;
-      if (gcheck(hipFuncSetAttribute((const void *)k_gemm_scores_long, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsl))) return 1;
-      hipLaunchKernelGGL(k_gemm_scores_long, dim3(num_cus > 0 ? num_cus : 256), dim3(256), ldsl, (hipStream_t)stream, a);
-      return gcheck(hipGetLastError());
-    }
-    const int slabs = (a.ix.stride + 127) / 128;
-    // (four slabs: + the low halves of the last slab's A operand; the overlapped kernel: + its parity arrays and the raw half slab)
-    const bool wide4 = slabs == 4;
-    const size_t ldsw = (size_t)128 * (4 * 128 + 16) + (wide4 ? 4 : 3) * 128 * 4 + (slabs == 4 ? (size_t)4 * 8 * 64 * 16 : 0) + (wide4 ? (size_t)32 * 1024 : 0);
-    void (*kw)(GemmArgs) = slabs == 2 ? k_gemm_scores_wide<2> : slabs == 3 ? k_gemm_scores_wide<3> : wide4 ? k_gemm_scores_wide4 : k_gemm_scores_wide<4>;
-    if (gcheck(hipFuncSetAttribute((const void *)kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw))) return 1;
-    hipLaunchKernelGGL(kw, dim3(num_cus > 0 ? num_cus : 256), dim3(256), ldsw, (hipStream_t)stream, a);
-    return gcheck(hipGetLastError());
-  }
-  const size_t lds = (size_t)128 * (4 * a.ix.stride + 16) + 3 * 128 * 4;
-  void (*kern)(GemmArgs) = nullptr;
-  switch (a.ix.stride) {
-    case 16: kern = k_gemm_scores<16>; break;
-    case 32: kern = k_gemm_scores<32>; break;
-    case 48: kern = k_gemm_scores<48>; break;
-    case 64: kern = k_gemm_scores<64>; break;
-    case 80: kern = k_gemm_scores<80>; break;
-    case 96: kern = k_gemm_scores<96>; break;
-    case 112: kern = k_gemm_scores<112>; break;
-    case 128: kern = k_gemm_scores<128>; break;
-    default: g_gerr = "row stride is not a multiple of 16 floats"; return 1;
-  }
-  if (lds > 48 * 1024)
-    if (gcheck(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))) return 1;
-  // two workgroups per CU (the LDS allows it): one stores its scores while the other runs its MFMAs
-  hipLaunchKernelGGL(kern, dim3(2 * (num_cus > 0 ? num_cus : 256)), dim3(256), lds, (hipStream_t)stream, a);
-  return gcheck(hipGetLastError());
-}
-
-int launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream) {
-  if (a.ix.dtype == 1) return gtyped(dt_u8::launch_select_rerank(a, ctr, stream));
-  if (a.ix.dtype == 2) return gtyped(dt_i8::launch_select_rerank(a, ctr, stream));
-  if (a.ix.dtype == 3) return gtyped(dt_f16::launch_select_rerank(a, ctr, stream));
-  hipStream_t s = (hipStream_t)stream;
-  const int blocks = (int)std::min<int64_t>(4096, (a.nq + 3) / 4);
-  const size_t lds = rerank_lds_bytes(a.ix, a.k);
-  if (a.ix.metric == 1) hipLaunchKernelGGL(k_rerank<1>, dim3(blocks), dim3(256), lds, s, a, ctr);
-  else hipLaunchKernelGGL(k_rerank<0>, dim3(blocks), dim3(256), lds, s, a, ctr);
-  return gcheck(hipGetLastError());
-}
-
-int launch_cover_plan(const CoverArgs &c, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned qb = (unsigned)((c.g.nq + 255) / 256);
-  hipLaunchKernelGGL(k_cover_count, dim3(qb), dim3(256), 0, s, c);
-  hipLaunchKernelGGL(k_cover_blocks, dim3(1), dim3(1024), 0, s, c);
-  hipLaunchKernelGGL(k_cover_assign, dim3(1), dim3(1024), 0, s, c);
-  hipLaunchKernelGGL(k_cover_plan, dim3((unsigned)c.max_passes), dim3(1024), 0, s, c);
-  hipLaunchKernelGGL(k_cover_scatter, dim3((unsigned)std::min<int64_t>(2048, (c.g.nq + 3) / 4)), dim3(256), 0, s, c);
-  return gcheck(hipGetLastError());
-}
-
-int launch_cover_pass(const CoverArgs &c, int pass, int num_cus, void *stream) {
-  // the pass's plan, groups, tiles and query lists stand where the score kernels look for a batch's
-  GemmArgs a = c.g;
-  a.plan = c.pplan + pass * P_INTS;
-  a.groups = c.groups + (int64_t)pass * c.nblocks;
-  a.tile_group = c.tile_group + (int64_t)pass * c.tile_stride;
-  a.gq = c.gq + (int64_t)pass * c.pair_stride;
-  if (launch_gemm_scores(a, num_cus, stream)) return 1;
-  CoverArgs cp = c;
-  cp.pass = pass;
-  if (c.g.ix.dtype == 1) return gtyped(dt_u8::launch_rerank_cover(cp, stream));
-  if (c.g.ix.dtype == 2) return gtyped(dt_i8::launch_rerank_cover(cp, stream));
-  if (c.g.ix.dtype == 3) return gtyped(dt_f16::launch_rerank_cover(cp, stream));
-  return gcheck(launch_rerank_cover_unit(cp, stream));
-}
-
-#endif  // WANN_DT == 0
+#include "wann_gemm_launch.inc"  // the launchers: one text for every unit, the entry points in the float32 unit
 
 }  // namespace wann

@@ -325,20 +325,11 @@ int method_code(const char *m) {
 // every query whose top-k cannot be proven from the MFMA scores) goes through the exact scan kernel.  Grouping,
 // tile planning and the hand-over to the exact scan all happen on the device: the host enqueues six launches and
 // never waits.
-// rows the score kernels take, per element type: float32 up to 512 floats (the query operand in registers, RedCaps) -- up to
-// 2048 (kGemmMaxFloats) where WANN_DENSE_LONG_ROWS=1 opts in: k_gemm_scores_long stages both operands slab by slab, and until it
-// is timed against the scan no batch moves to it by default --, float16 up to 128 elements (the narrow kernel) -- up to 2048
-// (k_gemm_scores_hslab, the same K-loop with half loads) under the same switch --, uint8 / int8 up to 512 bytes -- up to 2048
-// (kGemmMaxBytes, k_gemm_scores_bslab) under the same switch, for the same reason; everything longer (and k > 16) stays on the
-// exact scan.  A float16 row counts by query_words: its stride is the half row's word count.
+// Which rows the score kernels take: the table above dense_row_class (wann_gemm_device.h).  The long class is opt-in
+// (WANN_DENSE_LONG_ROWS=1: until it is timed against the scan no batch moves to it by default); k > 16 stays on the exact scan.
 static bool dense_rows_ok(const wann_index &I, const Tuning &T, int k) {
-  const int dtype = I.view.dtype;
-  const bool bytes = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8;
-  if (k > kSelect / 2 || (I.view.stride & 15)) return false;
-  if (dtype == WANN_DTYPE_F16 ? query_words(I.view) > (T.dense_long ? kGemmMaxFloats : 128)
-                              : I.view.stride > (bytes ? (T.dense_long ? kGemmMaxBytes / 4 : 128) : T.dense_long ? kGemmMaxFloats : 512))
-    return false;
-  return true;
+  const DenseRows rows = dense_row_class(I.view);
+  return k <= kSelect / 2 && rows != kRowsNone && (rows != kRowsLong || T.dense_long);
 }
 
 // tstride: task slots per query (the dense kernels read a query's slot 0).  sorted_exact: the exact windows of a tree / super
@@ -349,12 +340,12 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   const int dtype = I.view.dtype;
   const bool bytes = dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8;
   if (!dense_rows_ok(I, T, k)) return;
-  // rows of more than 512 floats (float16: 128 elements) need the batch's queries split into their bf16 terms (nq x qwords x 4
-  // bytes, below) before the device has grouped anything: a batch whose split would exceed 256 MiB (the score buffer's cap) stays
-  // on the exact scan.  Byte rows of more than 512 bytes need them packed to bytes (nq x stride words as well): the same buffer,
-  // the same cap.  qwords: the query's row length in words -- the stride, but for float16 rows, whose stride counts half rows.
+  // long float rows need the batch's queries split into their bf16 terms (nq x qwords x 4 bytes, below) before the device has
+  // grouped anything: a batch whose split would exceed 256 MiB (the score buffer's cap) stays on the exact scan.  Long byte rows
+  // need them packed to bytes (nq x stride words as well): the same buffer, the same cap.  qwords: the query's row length in
+  // words -- the stride, but for float16 rows, whose stride counts half rows.
   const int qwords = query_words(I.view);
-  const bool long_rows = bytes ? I.view.stride > 128 : dtype == WANN_DTYPE_F16 ? qwords > 128 : I.view.stride > 512;
+  const bool long_rows = dense_row_class(I.view) == kRowsLong;
   if (long_rows && (unsigned long long)nq * (unsigned long long)qwords > (64ull << 20)) return;
   if (!I.have_norms) {
     if (bytes) {  // exact integer sums of the rows (wann_gemm_kernels_bytes.inc)
