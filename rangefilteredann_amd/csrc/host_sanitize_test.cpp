@@ -1,7 +1,7 @@
 // host_sanitize_test.cpp -- driver of the `make sanitize` target: the CPU-side C++ of the engine (index layout,
 // label sort, window-search-tree / super-tree shapes, the host Vamana builder, graph cache I/O, the
-// insertion permutation) under AddressSanitizer + UndefinedBehaviorSanitizer.  CPU build only: GPU
-// sanitizers are not available on the pool, and nothing here touches HIP.
+// insertion permutation, the reference's printed words of wann_refdump.cpp) under AddressSanitizer +
+// UndefinedBehaviorSanitizer.  CPU build only: GPU sanitizers are not available on the pool, and nothing here touches HIP.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +13,7 @@
 #include "../../include/wann.h"
 #include "wann_build.h"
 #include "wann_gemm_device.h"
+#include "wann_refdump.h"
 #include "wann_stdsort.h"
 #include <algorithm>
 
@@ -34,6 +35,158 @@ static void check_graph(const HostGraph &g, int64_t n, int64_t R) {
     CHECK(r[0] >= 0 && r[0] <= g.maxdeg);
     for (int j = 0; j < r[0]; j++) CHECK(r[1 + j] >= 0 && r[1 + j] < n);
   }
+}
+
+// The reference's words (wann_refdump.cpp) from hand-made records, against strings written out from the formats of
+// tests/golden/verbose_golden.json.  Every array is exactly as long as the dump may read.
+static unsigned long long vrec(long long beam, long long unfiltered, long long frontier) {
+  return ((unsigned long long)beam << 42) | ((unsigned long long)unfiltered << 21) | (unsigned long long)frontier;
+}
+static std::string printed(const wann_host::VerboseDump &d) {
+  char *buf = nullptr;
+  size_t len = 0;
+  FILE *f = open_memstream(&buf, &len);
+  wann_host::print_verbose_dump(f, d);
+  fclose(f);
+  std::string s(buf, len);
+  free(buf);
+  return s;
+}
+static std::string printed_outside(const std::vector<float> &ranges, float first, float last, int digits) {
+  char *buf = nullptr;
+  size_t len = 0;
+  FILE *f = open_memstream(&buf, &len);
+  wann_host::print_outside_range(f, ranges.data(), (int64_t)ranges.size() / 2, first, last, digits);
+  fclose(f);
+  std::string s(buf, len);
+  free(buf);
+  return s;
+}
+static Task task(int query, int mode, int part, int flags) {
+  Task t{};
+  t.query = query;
+  t.mode = mode;
+  t.part = part;
+  t.flags = flags;
+  return t;
+}
+
+static void check_refdump() {
+  std::vector<PartDesc> parts(3);
+  parts[0].n = 2500;
+  parts[1].n = 312;
+  parts[2].n = 156;
+  {  // four queries of three task slots, six records per task, six route entries per query; beam 10 x2, no beam limit in reach
+    const int maxt = 3, cap = 6, rw = 1 + 7 * 6;
+    const std::vector<Task> tasks = {
+        task(0, T_GRAPH, 1, 0), Task{}, Task{},                                        // the super tree's one search
+        task(1, T_GRAPH, 1, 2), task(1, T_BRUTE, 0, 0), task(1, T_GRAPH, 2, 2),        // fenwick: a scan between two searches
+        task(2, T_GRAPH, 0, 0), Task{}, Task{},                                        // the final search's record is missing
+        task(3, T_GRAPH, 0, 0), Task{}, Task{}};                                       // more searches than records fit
+    const std::vector<int32_t> qtask_cnt = {1, 3, 1, 1};
+    std::vector<int32_t> vlog_n = {4, 0, 0, 1, 0, 2, 1, 0, 0, 9, 0, 0};
+    std::vector<unsigned long long> vlog((size_t)4 * maxt * cap, 0);
+    auto put = [&](int ti, std::vector<unsigned long long> r) { std::copy(r.begin(), r.end(), vlog.begin() + (size_t)ti * cap); };
+    put(0, {vrec(10, 10, 3), vrec(20, 20, 7), vrec(40, 40, 12), vrec(80, 80, 25)});  // doubles twice, re-searched at 40 x 2
+    put(3, {vrec(10, 10, 10)});                                                       // flags & 2: multiply 1
+    put(5, {vrec(10, 10, 6), vrec(20, 20, 11)});
+    put(6, {vrec(10, 10, 10)});
+    put(9, {vrec(10, 10, 0), vrec(20, 20, 0), vrec(40, 40, 1), vrec(80, 80, 2), vrec(160, 160, 4), vrec(320, 320, 8)});
+    std::vector<int64_t> vroute((size_t)4 * rw, 0);
+    auto route = [&](int q, std::vector<std::vector<int64_t>> entries) {
+      int64_t *w = vroute.data() + (size_t)q * rw;
+      w[0] = 7 * (int64_t)entries.size();
+      for (size_t i = 0; i < entries.size(); i++) std::copy(entries[i].begin(), entries[i].end(), w + 1 + 7 * i);
+    };
+    // (kind, index of the query's next task, five arguments)
+    route(0, {{1, 0, 28, 0, 0, 0, 0}, {1, 0, 14, 0, 0, 0, 0}, {2, 0, 2239, 2395, 2198, 2500, 313}, {3, 0, 0, 0, 0, 0, 0}});
+    route(1, {{4, 0, 1790, 2415, 0, 0, 0}, {5, 0, 1875, 2188, 0, 0, 0}, {5, 2, 2188, 2344, 0, 0, 0}, {4, 3, 1846, 1875, 0, 0, 0}, {9, 1, 1, 1, 1, 1, 1}});
+    const wann_host::VerboseDump d{4, maxt, tasks.data(), qtask_cnt.data(), vlog_n.data(), vlog.data(), cap, vroute.data(), rw, parts.data(), 1234, 10, 10, 2, 10000};
+    const std::string want =
+        "Testing bucket 28\n"
+        "Testing bucket 14\n"
+        "Query range = (2239,2395), smallest containing range (size 313) = (2198,2500)\n"
+        "Time to find bucket: 0ns\n"
+        "Starting optimized postfiltering, beam size = 10, k = 10, final multiply = 2, n = 312\n"
+        "Unfiltered return = 10\n"
+        "Finished a double, frontier size = 3, beam size = 10\n"
+        "Unfiltered return = 20\n"
+        "Finished a double, frontier size = 7, beam size = 20\n"
+        "Unfiltered return = 40\n"
+        "Finished a double, frontier size = 12, beam size = 40\n"
+        "Unfiltered return = 80\n"
+        "Final frontier size = 25, final beam size 80\n"
+        "Time to do searcht: 1234ns\n"
+        "Query range: 1790 2415\n"
+        "Searching bucket: 1875 2188\n"
+        "Starting optimized postfiltering, beam size = 10, k = 10, final multiply = 1, n = 312\n"
+        "Unfiltered return = 10\n"
+        "Finished a double, frontier size = 10, beam size = 10\n"
+        "Final frontier size = 10, final beam size 10\n"
+        "Searching bucket: 2188 2344\n"
+        "Starting optimized postfiltering, beam size = 10, k = 10, final multiply = 1, n = 156\n"
+        "Unfiltered return = 10\n"
+        "Finished a double, frontier size = 6, beam size = 10\n"
+        "Unfiltered return = 20\n"
+        "Finished a double, frontier size = 11, beam size = 20\n"
+        "Final frontier size = 11, final beam size 20\n"
+        "Query range: 1846 1875\n"  // (belongs to index qtask_cnt: after the last task)
+        "Starting optimized postfiltering, beam size = 10, k = 10, final multiply = 2, n = 2500\n"
+        "Unfiltered return = 10\n"
+        "Finished a double, frontier size = 10, beam size = 10\n"
+        "Final frontier size = 10, final beam size 20\n"  // (no record of the final search: the beam is named all the same)
+        "Starting optimized postfiltering, beam size = 10, k = 10, final multiply = 2, n = 2500\n"
+        "Unfiltered return = 10\n"
+        "Finished a double, frontier size = 0, beam size = 10\n"
+        "Unfiltered return = 20\n"
+        "Finished a double, frontier size = 0, beam size = 20\n"
+        "Unfiltered return = 40\n"
+        "Finished a double, frontier size = 1, beam size = 40\n"
+        "Unfiltered return = 80\n"
+        "Finished a double, frontier size = 2, beam size = 80\n"
+        "Unfiltered return = 160\n"
+        "Finished a double, frontier size = 4, beam size = 160\n"
+        "Unfiltered return = 320\n"
+        "Finished a double, frontier size = 8, beam size = 320\n"
+        "Final frontier size = 8, final beam size 1280\n";
+    CHECK(printed(d) == want);
+  }
+  {  // the beam reaches postfiltering_max_beam: no final search (the golden's postfilter_maxbeam case: beam 8 x3, limit 40)
+    const std::vector<Task> tasks = {task(0, T_GRAPH, 0, 0)};
+    const std::vector<int32_t> qtask_cnt = {1}, vlog_n = {3};
+    const std::vector<unsigned long long> vlog = {vrec(8, 8, 0), vrec(16, 16, 0), vrec(32, 32, 1)};
+    const wann_host::VerboseDump d{1, 1, tasks.data(), qtask_cnt.data(), vlog_n.data(), vlog.data(), 3, nullptr, 0, parts.data(), 0, 10, 8, 3, 40};
+    CHECK(printed(d) ==
+          "Starting optimized postfiltering, beam size = 8, k = 10, final multiply = 3, n = 2500\n"
+          "Unfiltered return = 8\n"
+          "Finished a double, frontier size = 0, beam size = 8\n"
+          "Unfiltered return = 16\n"
+          "Finished a double, frontier size = 0, beam size = 16\n"
+          "Unfiltered return = 32\n"
+          "Finished a double, frontier size = 1, beam size = 32\n"
+          "Final frontier size = 1, final beam size 64\n");
+  }
+  {  // a tree with scan leaves: no records at all, the descent's lines only
+    const int rw = 1 + 7;
+    const std::vector<Task> tasks = {task(0, T_GRAPH, 0, 0), task(1, T_BRUTE, 0, 0)};
+    const std::vector<int32_t> qtask_cnt = {1, 1};
+    const std::vector<int64_t> vroute = {7, 2, 0, 2090, 2402, 1875, 2500, 625, 7, 2, 0, 2155, 2467, 1875, 2500, 625};
+    const wann_host::VerboseDump d{2, 1, tasks.data(), qtask_cnt.data(), nullptr, nullptr, 24, vroute.data(), rw, parts.data(), 77, 10, 10, 1, 10000};
+    CHECK(printed(d) ==
+          "Query range = (2090,2402), smallest containing range (size 625) = (1875,2500)\n"
+          "Query range = (2155,2467), smallest containing range (size 625) = (1875,2500)\n");
+  }
+  // the window outside the index's label range: above, inside, below, straddling the upper end
+  const std::vector<float> ranges = {2.f, 3.5f, 0.3f, 0.4f, -5.f, -0.9998f, 0.9f, 2.f};
+  CHECK(printed_outside(ranges, 0.0002f, 0.9998f, 4) ==
+        "Query range is entirely outside the index range (0.0002, 0.9998) index range vs. (2, 3.5) This shouldn't happen but does not directly impact correctness\n"
+        "Query range is entirely outside the index range (0.0002, 0.9998) index range vs. (-5, -0.9998) This shouldn't happen but does not directly impact correctness\n");
+  const std::vector<float> ranges2 = {0.5f, 0.75f, 1.23456789f, 2.5f};
+  CHECK(printed_outside(ranges2, 0.123456789f, 0.987654321f, 6) ==
+        "Query range is entirely outside the index range (0.123457, 0.987654) index range vs. (1.23457, 2.5) This shouldn't happen but does not directly impact correctness\n");
+  CHECK(printed_outside(ranges2, 0.123456789f, 0.987654321f, 4) ==
+        "Query range is entirely outside the index range (0.1235, 0.9877) index range vs. (1.235, 2.5) This shouldn't happen but does not directly impact correctness\n");
+  CHECK(printed_outside({}, 0.f, 1.f, 4).empty());
 }
 
 int main(int argc, char **argv) {
@@ -188,7 +341,8 @@ int main(int argc, char **argv) {
         v.stride += 8;  // not a multiple of 16 words: no kernel takes it
         CHECK(dense_row_class(v) == kRowsNone);
       }
-  // the C ABI's argument validation (no device needed for these paths) lives in wann_host.cpp and is covered by tests/test_abi.py
+  check_refdump();
+  // the C ABI's argument validation (no device needed for these paths) lives in wann_abi.cpp and is covered by tests/test_abi.py
   if (fails) {
     fprintf(stderr, "host sanitize test: %d check(s) failed\n", fails);
     return 1;

@@ -1,5 +1,7 @@
 // wann_host_internal.h -- what the host side's translation units share (round 5: wann_host.cpp was one 2 100-line file):
-//   wann_host.cpp  device residency of the index, launch geometry, the batch driver (run_batch), the dense prefilter path, GPU build
+//   wann_host.cpp  device residency of the index, launch geometry, GPU build
+//   wann_batch.cpp the batch driver (run_batch, as a list of stages) and the dense prefilter path
+//   wann_refdump.cpp the text printed in the reference's name (outside-range message, QueryParams::verbose dump): no HIP, own header
 //   wann_abi.cpp   the C ABI of include/wann.h: index life cycle, blocking / asynchronous / multi-device search calls, RCCL all-gather
 //   wann_raw.cpp   one graph over one slice of a point set: wann_raw_beam_search and the unfiltered VamanaIndex API
 // Internal: nothing here is part of the boundary (include/wann.h is).

@@ -193,7 +193,7 @@ def main():
     if c["search_kernel_ms"] > 0:
         out["k_search_tb_per_s"] = round(out["algorithmic_gb_per_batch"] / c["search_kernel_ms"], 3)
     if c.get("brute_rows", 0) > 0:
-        # fenwick / three_split: the end scans (k_brute) run BESIDE the graph searches (wann_host.cpp): the call's bytes are both
+        # fenwick / three_split: the end scans (k_brute) run BESIDE the graph searches (wann_batch.cpp): the call's bytes are both
         # kernels', its time is the device time of the call
         out["scan_gb_per_batch"] = round(esz * d * c["brute_rows"] / 1e9, 3)
         out["device_ms"] = round(c["device_ms"], 3)
