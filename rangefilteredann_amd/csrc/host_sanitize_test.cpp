@@ -189,6 +189,52 @@ static void check_refdump() {
   CHECK(printed_outside({}, 0.f, 1.f, 4).empty());
 }
 
+// The exact scan's LDS need (brute_lds_bytes_per_wave, wann_device.h: what k_brute carves, launch_brute asks for and run_batch
+// checks) against byte counts worked out by hand, on the strides an uploaded index has; and k_finalize_multi's.
+static IndexView view_of(int dtype, int d) {
+  IndexView v{};
+  v.dtype = dtype;
+  v.d = d;
+  v.stride = dtype == WANN_DTYPE_F32 ? (d + 15) / 16 * 16 : dtype == WANN_DTYPE_F16 ? (2 * d + 63) / 64 * 16 : (d + 63) / 64 * 64 / 4;
+  return v;
+}
+static int64_t scan_lds(int dtype, int d, int k) { return brute_lds_bytes(query_words(view_of(dtype, d)), k); }
+
+static void check_scan_lds() {
+  static_assert(kWavesPerBlock == 4 && kLdsPerWorkgroup == 163840 && kLdsNoAttribute == 49152 && kMaxK == 1024, "the figures below assume these");
+  // query row + 64 keys + 64 ids + 64 distances + the list: 512 + 512 + 256 + 256 + 80
+  CHECK(brute_lds_bytes_per_wave(128, 10) == 1616);
+  CHECK(scan_lds(WANN_DTYPE_F32, 128, 10) == 4 * 1616);
+  CHECK(scan_lds(WANN_DTYPE_F32, 1024, 1024) == 53248);   // 4 x (4096 + 1024 + 8192): the attribute is needed
+  CHECK(scan_lds(WANN_DTYPE_F32, 3072, 10) == 53568);     // 4 x (12288 + 1024 + 80)
+  CHECK(scan_lds(WANN_DTYPE_F16, 4096, 1024) == 102400);  // the staged query is the float32 upcast: 4 x (16384 + 1024 + 8192)
+  CHECK(scan_lds(WANN_DTYPE_U8, 8192, 1024) == 69632);    // a byte per element: 4 x (8192 + 1024 + 8192)
+  CHECK(scan_lds(WANN_DTYPE_I8, 8192, 65) == 38976);      // the list holds an even number of keys: 4 x (8192 + 1024 + 66 x 8)
+  CHECK(scan_lds(WANN_DTYPE_F32, 2049, 10) == 37440);     // (the longest row of the suite before result widths were tested)
+  // an odd k takes the next even one's list; every count is a multiple of 16
+  for (int k = 1; k <= kMaxK; k++) {
+    CHECK(brute_lds_bytes_per_wave(16, k) == brute_lds_bytes_per_wave(16, (k + 1) & ~1));
+    CHECK(brute_lds_bytes_per_wave(16, k) % 16 == 0 && finalize_lds_bytes_per_wave(k) % 16 == 0);
+    CHECK(brute_lds_bytes_per_wave(16, k) == 64 + 1024 + ((k + 1) / 2) * 16);
+    CHECK(finalize_lds_bytes_per_wave(k) == 512 + ((k + 1) / 2) * 16);
+  }
+  CHECK(finalize_lds_bytes_per_wave(kMaxK) * kWavesPerBlock == 34816);
+  // the first row length past a CU's 160 KiB (40 960 B a wave) for every element type, at a narrow and at the widest k:
+  // 40 960 - 1024 - 80 = 39 856 B of query at k = 10, 40 960 - 1024 - 8192 = 31 744 B at k = 1024, in whole 64-byte rows
+  struct { int dtype, k, last_ok; } edges[] = {{WANN_DTYPE_F32, 10, 9952},  {WANN_DTYPE_F32, 1024, 7936}, {WANN_DTYPE_F16, 10, 9952}, {WANN_DTYPE_F16, 1024, 7936},
+                                               {WANN_DTYPE_U8, 10, 39808},  {WANN_DTYPE_U8, 1024, 31744}, {WANN_DTYPE_I8, 10, 39808},  {WANN_DTYPE_I8, 1024, 31744}};
+  for (auto &e : edges) {
+    CHECK(scan_lds(e.dtype, e.last_ok, e.k) <= kLdsPerWorkgroup);
+    CHECK(scan_lds(e.dtype, e.last_ok + 1, e.k) > kLdsPerWorkgroup);
+    int first_over = 0;  // (and by walking up: the need never decreases with the row length)
+    for (int d = 1; d <= 40000 && !first_over; d++)
+      if (scan_lds(e.dtype, d, e.k) > kLdsPerWorkgroup) first_over = d;
+    CHECK(first_over == e.last_ok + 1);
+  }
+  // no overflow at row lengths far beyond any index: the count stays positive and above the limit
+  CHECK(brute_lds_bytes((int64_t)1 << 31, kMaxK) > kLdsPerWorkgroup);
+}
+
 int main(int argc, char **argv) {
   const std::string tmp = argc > 1 ? argv[1] : "/tmp/wann_sanitize";
   (void)system(("mkdir -p " + tmp).c_str());
@@ -341,6 +387,7 @@ int main(int argc, char **argv) {
         v.stride += 8;  // not a multiple of 16 words: no kernel takes it
         CHECK(dense_row_class(v) == kRowsNone);
       }
+  check_scan_lds();
   check_refdump();
   // the C ABI's argument validation (no device needed for these paths) lives in wann_abi.cpp and is covered by tests/test_abi.py
   if (fails) {

@@ -263,7 +263,7 @@ static BatchPlan plan_batch(const wann_index &I, const Tuning &T, const wann_que
     const int common = search_lds_bytes_per_wave(query_words(*P.SV), 0);
     const int64_t big_pool = (int64_t)(common + kSearchPoolBytes) * kWavesPerBlock - common;
     P.big_cap = (int32_t)std::min<int64_t>(big_pool / 8, 5792);
-    if (P.big_cap <= (int32_t)std::max<int64_t>(P.inkernel_cap, qp.beam_width) || (common + kSearchPoolBytes) * kWavesPerBlock > 160 * 1024) P.big_cap = 0;
+    if (P.big_cap <= (int32_t)std::max<int64_t>(P.inkernel_cap, qp.beam_width) || (common + kSearchPoolBytes) * kWavesPerBlock > kLdsPerWorkgroup) P.big_cap = 0;
   }
   // the list sizes come back while the exact scans run: the beam-search launches are sized by them, and skipped
   // altogether for batches without graph tasks (tiny windows) / without levels beyond the in-kernel cap
@@ -703,20 +703,54 @@ void SearchRounds::follow_up(const SearchArgs &sa, int next_n) {
   int64_t nb = b0;
   while (nb <= cap1) nb *= 2;
   SearchArgs sb = sa;
-  sb.list = W.list_b.p;
-  sb.list_count = W.ints.p + I_NEXT0;
   sb.heavy_list = nullptr;
   sb.heavy_count = nullptr;
   sb.prio_count = nullptr;
   sb.mid_list = nullptr;
   sb.mid_count = nullptr;
-  sb.cursor = W.ints.p + I_CURSOR0 + 1;
-  sb.next_list = W.list_a.p;  // cannot be used: cap = max_beam
-  sb.next_count = W.ints.p + I_NEXT0 + 1;
   sb.start_beam = W.next_beam.p;  // a task resolved from speculative levels may already be past nb
-  launch(sb, nb, qp.postfiltering_max_beam, next_n, true);
-  HIP_CHECK(hipMemcpyAsync(W.h_ints, W.ints.p, kInts * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  // A launch's seen-filter is sized for the largest beam it may run (the reference's: beam squared over four entries), so a
+  // launch up to postfiltering_max_beam = 2^20 would ask for a terabyte whatever its tasks need.  Limits up to kFollowUpStageBeam
+  // run in one launch (cap = the limit: a task never leaves it); beyond, the launches are staged at caps kFollowUpStageBeam,
+  // twice that, ... -- a task that has to double beyond a stage's cap leaves through next_list with its beam in next_beam,
+  // like it left the first launch, and the scratch grows only as far as some task really gets.  The last stage's cap is
+  // kLargestBeam, the largest beam whose filter the kernels can index (2^31 entries, 8 GiB a slot); a task that has to double
+  // beyond it ends the batch with an error (the reference asks for a filter of 32 GiB and more there, per search).
+  const int64_t max_beam = qp.postfiltering_max_beam;
+  const int64_t last_cap = std::min<int64_t>(max_beam, kLargestBeam);
+  int64_t cap = max_beam <= kFollowUpStageBeam ? max_beam : std::min<int64_t>(last_cap, std::max<int64_t>(nb, kFollowUpStageBeam));
+  int64_t first = nb;
+  for (int stage = 0; next_n > 0; stage++) {
+    if (stage >= 24) throw std::runtime_error("too many follow-up launches in one batch");
+    // (lists alternate; stage 0 keeps the slots the one follow-up launch has always used)
+    sb.list = (stage & 1) ? W.list_a.p : W.list_b.p;
+    if (cap == kLargestBeam && cap < max_beam) {  // the one cap that is not twice the last: do all beams of the list fit?
+      bool fits = first <= cap;
+      if (fits) {
+        std::vector<int32_t> tl((size_t)next_n), nbm(W.next_beam.cap);
+        HIP_CHECK(hipMemcpyAsync(tl.data(), sb.list, tl.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(nbm.data(), W.next_beam.p, nbm.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int32_t t : tl) fits = fits && nbm[t] <= cap;
+      }
+      if (!fits)
+        throw std::runtime_error("beam search has to double beyond a beam of " + std::to_string((long long)kLargestBeam) + " (k = " +
+                                 std::to_string(P.k) + ", postfiltering_max_beam = " + std::to_string((long long)max_beam) +
+                                 "): its seen-filter would exceed 2^31 entries");
+    }
+    sb.next_list = (stage & 1) ? W.list_b.p : W.list_a.p;
+    sb.list_count = W.ints.p + (stage == 0 ? I_NEXT0 : I_NEXT0 + 7 + stage);
+    sb.next_count = W.ints.p + (stage == 0 ? I_NEXT0 + 1 : I_NEXT0 + 8 + stage);
+    sb.cursor = W.ints.p + (stage == 0 ? I_CURSOR0 + 1 : I_CURSOR0 + 8 + stage);
+    if (stage == 1) sb.list_count = W.ints.p + I_NEXT0 + 1;
+    launch(sb, first, cap, next_n, true);
+    HIP_CHECK(hipMemcpyAsync(W.h_ints, W.ints.p, kInts * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    next_n = W.h_ints[sb.next_count - W.ints.p];
+    if (cap >= max_beam) break;  // (nothing can have left)
+    first = cap + 1;
+    cap = std::min<int64_t>(last_cap, 2 * cap);
+  }
 }
 
 // final re-searches whose beam exceeded the in-kernel cap: every task at its own beam (next_beam), longest
@@ -969,12 +1003,22 @@ void Batch::copy_counters(const SearchRounds &R, bool tried_dense, float batch_m
 bool run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
                const int64_t *d_qids) {
-  if (qp.k <= 0 || qp.k > 1024) throw std::runtime_error("k must be in [1, 1024]");
+  static_assert(kMaxK == 1024, "the message below names the limit");
+  if (qp.k <= 0 || qp.k > kMaxK) throw std::runtime_error("k must be in [1, 1024]");
   // the brute-force classes ignore the beam (the reference driver passes beam_size = 0 there, run_our_method.py:256)
   if (qp.beam_width <= 0 && I.host().vamana_leaves) throw std::runtime_error("beam_width must be positive");
   if (qp.postfiltering_max_beam > (1 << 20)) throw std::runtime_error("postfiltering_max_beam too large");
   HIP_CHECK(hipSetDevice(I.device));
   const BatchPlan P = plan_batch(I, T, qp, method, nq);
+  // The exact scan keeps a wave's query row and its k-entry list in the LDS (brute_lds_bytes_per_wave): rows too long for a
+  // CU's 160 KiB are refused here, before anything of the batch is queued (config_for says the same of the beam search).
+  if (nq > 0 && P.may_brute) {
+    const int64_t need = brute_lds_bytes(query_words(I.view), P.k);
+    if (need > kLdsPerWorkgroup)
+      throw std::runtime_error("exact-scan LDS footprint exceeds 160 KiB: rows of " + std::to_string((long long)I.view.d) + " elements at k = " +
+                               std::to_string(P.k) + " need " + std::to_string((long long)need) + " bytes per workgroup, the limit is " +
+                               std::to_string(kLdsPerWorkgroup));
+  }
   // the dense path's buffers and counters belong to the index: held until the counters are written
   std::unique_lock<std::mutex> dense_lock(I.dense_mu, std::defer_lock);
   if (P.kind == WANN_KIND_PREFILTER || P.exact_set > 0) dense_lock.lock();

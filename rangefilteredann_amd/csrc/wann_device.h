@@ -331,4 +331,26 @@ constexpr int kSpecExtraLevels = 2;      // RouteArgs::spec_extra (k_route: one 
 constexpr int kHelpers = 3;
 constexpr int kScoreBoxBytes = 9600;
 
+constexpr int kMaxK = 1024;                  // QueryParams::k lies in [1, kMaxK] (run_batch and the C ABI refuse anything else)
+constexpr int kLdsPerWorkgroup = 160 * 1024;  // the LDS of a gfx950 CU: the most one workgroup can be given
+constexpr int kLdsNoAttribute = 48 * 1024;    // dynamic LDS a launch may ask for without raising
+                                              // hipFuncAttributeMaxDynamicSharedMemorySize on the kernel first
+
+// Bytes of LDS one wave of k_brute needs (host and device: the kernel carves, launch_brute sizes and run_batch checks with this
+// one function): the staged query (query_words 32-bit words, rounded up to 16 bytes), 64 candidate keys, ids and distances, and
+// the top[] list of k keys rounded up to an even count -- rounded up to 16 bytes.  A workgroup is kWavesPerBlock waves:
+// 4 x 1616 B at float32 d = 128, k = 10; 53 248 B at float32 d = 1024, k = 1024 (beyond kLdsNoAttribute: launch_brute raises the
+// attribute); beyond kLdsPerWorkgroup from float32 d = 9 953 at k = 10 (run_batch refuses the batch before it queues anything).
+constexpr int64_t brute_lds_bytes_per_wave(int64_t query_words, int k) {
+  return (((query_words * 4 + 15) & ~(int64_t)15) + 64 * 8 + 64 * 4 + 64 * 4 + (int64_t)((k + 1) & ~1) * 8 + 15) & ~(int64_t)15;
+}
+constexpr int64_t brute_lds_bytes(int64_t query_words, int k) { return brute_lds_bytes_per_wave(query_words, k) * kWavesPerBlock; }
+
+// Bytes of LDS one wave of k_finalize_multi needs: 64 candidate keys and the merged list of k keys (rounded up to an even
+// count), rounded up to 16 bytes.  No row length in it: 34 816 B a workgroup at k = kMaxK, so launch_finalize never has to
+// raise the attribute -- the assertion keeps that true if kMaxK ever moves.
+constexpr int finalize_lds_bytes_per_wave(int k) { return (64 * 8 + ((k + 1) & ~1) * 8 + 15) & ~15; }
+static_assert(finalize_lds_bytes_per_wave(kMaxK) * kWavesPerBlock <= kLdsNoAttribute,
+              "k_finalize_multi at k = kMaxK needs more dynamic LDS than a launch gets without the function attribute");
+
 }  // namespace wann

@@ -251,8 +251,8 @@ int ensure_filter_scratch(DevBuf<int32_t> &table, DevBuf<int32_t> &epoch, DevBuf
 // A workgroup's LDS is handed out in granules: 1 280 bytes fits what round 4 measured (three workgroups of 53 KiB = 43 granules each
 // are not co-resident in a CU's 128 granules, three of 52.5 KiB = 42 are; two of 77.5 KiB = 62 are) -- whatever
 // hipOccupancyMaxActiveBlocksPerMultiprocessor says.
-constexpr int kLdsGranule = 1280, kLdsPerCu = 160 * 1024;
-inline int lds_blocks_per_cu(int per_block) { return kLdsPerCu / (((per_block + kLdsGranule - 1) / kLdsGranule) * kLdsGranule); }
+constexpr int kLdsGranule = 1280;  // (of a CU's kLdsPerWorkgroup bytes: wann_device.h)
+inline int lds_blocks_per_cu(int per_block) { return kLdsPerWorkgroup / (((per_block + kLdsGranule - 1) / kLdsGranule) * kLdsGranule); }
 
 RoundCfg config_for(const wann_index &I, const IndexView &V, const Tuning &T, int64_t first_beam, int64_t cap, int64_t work_items, bool big_lds, bool force_table,
                     bool legacy, int base_pool) {
@@ -275,7 +275,7 @@ RoundCfg config_for(const wann_index &I, const IndexView &V, const Tuning &T, in
   rc.pool_bytes = pool;
   const int usable = pool - box_bytes;
   const int per_block = (common + pool) * wpb;
-  if (per_block > 160 * 1024) throw std::runtime_error("beam-search LDS footprint exceeds 160 KiB");
+  if (per_block > kLdsPerWorkgroup) throw std::runtime_error("beam-search LDS footprint exceeds 160 KiB");
   // register budget: the L2 kernel holds two whole 512-B rows per lane pair in flight (2 waves/SIMD)
   // (four-wave kernel: the squared-L2 float kernel needs 232 registers: two waves per SIMD; the inner-product and byte-row
   // kernels are built for three)

@@ -47,6 +47,13 @@ void convert_rows(const HostGraph &g, int rs, int32_t *out);  // reference in-me
 constexpr int kInts = 160;
 enum { I_GRAPH_COUNT = 0, I_BRUTE_COUNT = 1, I_BRUTE_CURSOR = 2, I_HEAVY_COUNT = 3, I_SUB_COUNT = 4, I_BIG_COUNT = 5 /* two ints */, I_BIG_CURSOR = 7, I_DYN_COUNT = 140, I_DYN_CURSOR = 141, I_DONE = 142, I_MID_COUNT = 143, I_RISK = 144, I_BIG_RESIDENT = 145, I_POLL_WAITING = 146, I_PRIO_COUNT = 147, I_SCAN_COUNT = 148, I_CURSOR0 = 8, I_NEXT0 = 72, I_FINAL0 = 104 };
 constexpr int kMaxRounds = 30;
+// follow-up launches (beams beyond the in-kernel cap): a postfiltering_max_beam up to this runs in one launch whose scratch is
+// sized for the limit; a larger limit is reached in stages of doubling caps, sized for what tasks really need (SearchRounds::follow_up)
+constexpr int64_t kFollowUpStageBeam = 16384;
+// the largest beam a search can run: its seen-filter has 2^hash_bits(beam) entries, hash_bits = ceil(log2(beam^2)) - 2, and the
+// kernels index a filter with 32-bit arithmetic (1u << bits): 92 681^2 < 2^33 <= 92 682^2, so 31 bits up to here and 32 beyond
+constexpr int64_t kLargestBeam = 92681;
+static_assert(kLargestBeam * kLargestBeam < ((int64_t)1 << 33) && (kLargestBeam + 1) * (kLargestBeam + 1) >= ((int64_t)1 << 33), "hash_bits(kLargestBeam) == 31");
 constexpr int kVlogCap = 24;  // QueryParams::verbose: records per task (a doubling loop from beam 1 to 2^20 is 21 searches + the final one)
 
 struct Workspace {

@@ -751,8 +751,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_brute(BruteArgs A) {
   const int lane = lane_id();
   const int wib = threadIdx.x >> 6;
   const int K = A.k;
-  int per_wave = ((qv_words(ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((K + 1) & ~1) * 8;
-  per_wave = (per_wave + 15) & ~15;
+  const int per_wave = (int)brute_lds_bytes_per_wave(qv_words(ix), K);
   unsigned char *base = smem + (size_t)wib * per_wave;
   float *qv = reinterpret_cast<float *>(base);
   int off = (qv_words(ix) * 4 + 15) & ~15;
@@ -1444,7 +1443,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_finalize_multi(Finalize
   const int lane = lane_id();
   const int wib = threadIdx.x >> 6;
   const int K = A.k;
-  const int per_wave = (64 * 8 + ((K + 1) & ~1) * 8 + 15) & ~15;
+  const int per_wave = finalize_lds_bytes_per_wave(K);
   u64 *cand_key = reinterpret_cast<u64 *>(smem + (size_t)wib * per_wave);
   u64 *top = cand_key + 64;
   for (int64_t q = (int64_t)blockIdx.x * kWavesPerBlock + wib; q < A.nq; q += (int64_t)gridDim.x * kWavesPerBlock) {
@@ -1623,15 +1622,21 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
   return a.ix.metric == 1 ? launch_search_t<1, 0>(a, grid, block, lds, s) : launch_search_t<0, 0>(a, grid, block, lds, s);
 }
 
+template <int METRIC>
+static int launch_brute_t(const BruteArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+  auto kern = k_brute<METRIC>;
+  if (lds > (size_t)kLdsNoAttribute)
+    if (check(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))) return 1;
+  hipLaunchKernelGGL(kern, grid, block, lds, s, a);
+  return check(hipGetLastError());
+}
+
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   if (blocks <= 0) return 0;
-  int per_wave = ((query_words(a.ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((a.k + 1) & ~1) * 8;
-  per_wave = (per_wave + 15) & ~15;
-  size_t lds = (size_t)per_wave * kWavesPerBlock;
+  // (long rows or a wide k: more than a launch gets unasked -- run_batch has refused what exceeds kLdsPerWorkgroup)
+  const size_t lds = (size_t)brute_lds_bytes(query_words(a.ix), a.k);
   dim3 grid(blocks), block(64 * kWavesPerBlock);
-  if (a.ix.metric == 1) hipLaunchKernelGGL(k_brute<1>, grid, block, lds, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_brute<0>, grid, block, lds, (hipStream_t)stream, a);
-  return check(hipGetLastError());
+  return a.ix.metric == 1 ? launch_brute_t<1>(a, grid, block, lds, (hipStream_t)stream) : launch_brute_t<0>(a, grid, block, lds, (hipStream_t)stream);
 }
 
 }  // namespace WANN_DT_NS
@@ -1669,7 +1674,7 @@ int launch_brute(const BruteArgs &a, int blocks, void *stream) {
 int launch_finalize(const FinalizeArgs &a, void *stream) {
   if (a.nq == 0) return 0;
   if (a.maxt > 1) {
-    int per_wave = (64 * 8 + ((a.k + 1) & ~1) * 8 + 15) & ~15;
+    const int per_wave = finalize_lds_bytes_per_wave(a.k);  // (never beyond kLdsNoAttribute: asserted in wann_device.h)
     int blocks = (int)std::min<int64_t>(2048, (a.nq + kWavesPerBlock - 1) / kWavesPerBlock);
     hipLaunchKernelGGL(k_finalize_multi, dim3(blocks), dim3(64 * kWavesPerBlock), (size_t)per_wave * kWavesPerBlock,
                        (hipStream_t)stream, a);

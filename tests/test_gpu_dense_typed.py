@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
-from util import repeated_labels, sift_like
+from util import clustered_window_batch, repeated_labels, sift_like
 
 pytestmark = pytest.mark.gpu
 
@@ -66,38 +66,30 @@ def _both_paths(pi, wa, monkeypatch, Q, W, k):
     return ids, dists, c
 
 
+def typed_dense_batch(sfx):
+    """X, Q, labels, W of test_typed_dense_prefilter_matches_oracle in the element type of the class of suffix sfx: the float32
+    test's construction (util.clustered_window_batch), quantised"""
+    if sfx.endswith("Euclidian"):
+        X, Q, labels, W = clustered_window_batch(128, "sift")  # integers in [0, 255]
+        if sfx.startswith("Int8"):
+            X, Q = X - 128, Q - 128
+        X, Q = X.astype(_elem(sfx)), Q.astype(_elem(sfx))
+    else:
+        X, Q, labels, W = clustered_window_batch(100, "unit")
+        # (int8 / uint8: scaled so that the largest elements reach the ends of the byte range)
+        s = 1.0 if sfx.startswith("Float16") else 3.0
+        X = _quantise(sfx, s * X / np.linalg.norm(X, axis=1, keepdims=True))
+        Q = _quantise(sfx, s * Q / np.linalg.norm(Q, axis=1, keepdims=True))
+    return np.ascontiguousarray(X), Q, labels, W
+
+
 @pytest.mark.parametrize("sfx", BYTE_CLASSES + HALF_CLASSES)
 def test_typed_dense_prefilter_matches_oracle(oracle, wa, gpu, monkeypatch, sfx):
     """Clustered labels = clustered geometry, 40 queries per cluster window (the construction of the float32 test, quantised):
     most of the batch runs on the matrix cores, and its rows are the exact scan's, the oracle's, and -- for float16 -- the
     float32 index's on the upcast points."""
-    rng = np.random.default_rng(17)
-    nclu, per, qper = 12, 1500, 40
-    n = nclu * per
-    if sfx.endswith("Euclidian"):
-        d = 128
-        X, Q = sift_like(n, d, 3)(n), sift_like(n, d, 3)(nclu * qper)  # integers in [0, 255]
-        if sfx.startswith("Int8"):
-            X, Q = X - 128, Q - 128
-        X, Q = X.astype(_elem(sfx)), Q.astype(_elem(sfx))
-    else:
-        d = 100
-        cent = rng.standard_normal((nclu, d))
-        X = cent[np.repeat(np.arange(nclu), per)] + 0.3 * rng.standard_normal((n, d))
-        Q = cent[np.repeat(np.arange(nclu), qper)] + 0.3 * rng.standard_normal((nclu * qper, d))
-        # (int8 / uint8: scaled so that the largest elements reach the ends of the byte range)
-        s = 1.0 if sfx.startswith("Float16") else 3.0
-        X = _quantise(sfx, s * X / np.linalg.norm(X, axis=1, keepdims=True))
-        Q = _quantise(sfx, s * Q / np.linalg.norm(Q, axis=1, keepdims=True))
-    labels = (np.repeat(np.arange(nclu), per) - 0.5 + rng.random(n)).astype(np.float32)
-    perm = rng.permutation(n)
-    X, labels = np.ascontiguousarray(X[perm]), labels[perm]
+    X, Q, labels, W = typed_dense_batch(sfx)
     nq = Q.shape[0]
-    W = np.zeros((nq, 2))
-    cl = np.repeat(np.arange(nclu), qper)
-    W[:, 0], W[:, 1] = cl - 0.5, cl + 0.5
-    W[::7] = (2.2, 3.9)       # a second family of shared windows
-    W[5::31, 1] += 1e-3 * np.arange(len(W[5::31]))  # and some unique ones (exact scan)
     pi = getattr(wa, "PrefilterIndex" + sfx)(X, labels)
     oi, oq = _oracle_index(oracle, sfx, X, labels)
     ctx = gu.RowContext(X.astype(np.float32), labels, Q.astype(np.float32), W, gu.metric_of(sfx), "prefilter")

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
-from util import repeated_labels
+from util import mixed_positions as _mixed_positions, pos_windows as _pos_windows, random_rows as _random_rows, repeated_labels
 
 pytestmark = pytest.mark.gpu
 
@@ -27,58 +27,10 @@ def _elem(sfx):
     return np.uint8 if sfx.startswith("UInt8") else np.int8 if sfx.startswith("Int8") else np.float16 if sfx.startswith("Float16") else np.float32
 
 
-def _random_rows(sfx, rng, n, d):
-    """well-spread rows: uniform random bytes, unit vectors for the float types"""
-    if sfx.startswith("UInt8"):
-        return rng.integers(0, 256, (n, d)).astype(np.uint8)
-    if sfx.startswith("Int8"):
-        return rng.integers(-128, 128, (n, d)).astype(np.int8)
-    x = rng.standard_normal((n, d)).astype(np.float32)
-    return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(_elem(sfx))
-
-
 def _oracle_index(oracle, sfx, X, labels):
     if sfx.startswith("Float16"):
         return getattr(oracle, "PrefilterIndex" + sfx.replace("Float16", "Float"))(X.astype(np.float32), labels), np.float32
     return getattr(oracle, "PrefilterIndex" + sfx)(X, labels), X.dtype
-
-
-def _pos_windows(a, b):
-    """label windows that hold exactly positions [a, b) of the label order when labels are a permutation of 0 .. n-1"""
-    return np.stack([np.asarray(a, dtype=np.float64) - 0.5, np.asarray(b, dtype=np.float64) - 0.5], 1)
-
-
-def _mixed_positions(rng, n, nq):
-    """window positions [a, b): several fractions of n, edges on and off multiples of 64, 128 and 2 048, the whole set, windows
-    below the minimum width, empty ones, ones with fewer than 16 points and ones outside the label span"""
-    a = np.zeros(nq, dtype=np.int64)
-    b = np.zeros(nq, dtype=np.int64)
-    for i in range(nq):
-        w = int(n * (1 / 32, 1 / 8, 1 / 2, 1 / 16)[i % 4] * (0.6 + 0.8 * rng.random()))
-        w = max(w, MIN_WINDOW + 1)
-        st = int(rng.integers(0, n - w))
-        kind = i % 7
-        if kind == 1:
-            st -= st % 64
-        elif kind == 2:
-            st -= st % 128
-            w -= w % 128
-        elif kind == 3:
-            st -= st % BLOCK
-            w = max(BLOCK, w - w % BLOCK)
-        elif kind == 4:
-            e = (st + w) - (st + w) % BLOCK
-            w = e - st if e - st >= MIN_WINDOW else w
-        a[i], b[i] = st, min(n, st + w)
-    a[0], b[0] = 0, n                       # the whole set
-    a[1], b[1] = 0, n
-    a[10:40] = rng.integers(0, n - 1000, 30)
-    b[10:40] = a[10:40] + rng.integers(17, MIN_WINDOW, 30)    # below the minimum width
-    b[40:50] = a[40:50] + rng.integers(1, 10, 10)              # fewer than k points
-    b[50:55] = a[50:55]                                        # empty
-    a[55:60], b[55:60] = n + 100, n + 5000                     # beyond the label span
-    a[60:62], b[60:62] = n - 1500, n                           # up to the last point
-    return a, b
 
 
 def _eligible(a, b, n, candidates=None):

@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 import golden_util as gu
-from util import REPO, brute_force_gt, recall, repeated_labels, tie_heavy, tie_queries
+from util import REPO, brute_force_gt, pos_windows as _pos_windows, random_rows as _random_rows, recall, repeated_labels, tie_heavy, tie_queries
+from util import wide_window_batch as _used_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -33,20 +34,6 @@ def _qp(mod, k=10, beam=10):
 
 def _elem(sfx):
     return np.uint8 if sfx.startswith("UInt8") else np.int8 if sfx.startswith("Int8") else np.float16 if sfx.startswith("Float16") else np.float32
-
-
-def _random_rows(sfx, rng, n, d):
-    """well-spread rows: uniform random bytes, unit vectors for the float types"""
-    if sfx.startswith("UInt8"):
-        return rng.integers(0, 256, (n, d)).astype(np.uint8)
-    if sfx.startswith("Int8"):
-        return rng.integers(-128, 128, (n, d)).astype(np.int8)
-    x = rng.standard_normal((n, d)).astype(np.float32)
-    return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(_elem(sfx))
-
-
-def _pos_windows(a, b):
-    return np.stack([np.asarray(a, dtype=np.float64) - 0.5, np.asarray(b, dtype=np.float64) - 0.5], 1)
 
 
 @pytest.fixture(scope="module")
@@ -225,21 +212,6 @@ def test_every_method_returns_the_same_exact_rows(wa, gpu, cache, monkeypatch):
 
 # ---- 4. the dense path is really used ------------------------------------------------------------------------------------------
 USED_CASES = [("FloatEuclidian", 64), ("FloatMips", 256), ("Float16Mips", 100), ("UInt8Euclidian", 64)]  # narrow, wide, float16, bytes
-
-
-def _used_batch(n, nq, seed):
-    rng = np.random.default_rng(seed)
-    w = rng.integers(3000, 12000, nq)
-    a = (rng.random(nq) * (n - w - 2)).astype(np.int64) + 1
-    # (both ends of the label order are covered often enough too)
-    a[:40], w[:40] = 1 + np.arange(40), 11000 - 2 * np.arange(40)
-    w[40:80] = 11000 - 2 * np.arange(40)
-    a[40:80] = n - 1 - w[40:80] - np.arange(40)
-    cover = np.zeros(n // BLOCK + 2, dtype=np.int64)
-    for x, y in zip(a, a + w):
-        cover[x // BLOCK:(y - 1) // BLOCK + 1] += 1
-    assert cover[:(n - 1) // BLOCK + 1].min() >= 32
-    return a, w
 
 
 @pytest.mark.parametrize("sfx,d", USED_CASES)

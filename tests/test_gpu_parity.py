@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
-from util import REPO, distinct_labels, sift_like, unit_mixture, windows
+from util import REPO, clustered_window_batch, distinct_labels, sift_like, unit_mixture, windows
 
 pytestmark = pytest.mark.gpu
 FLT_MAX = np.finfo(np.float32).max
@@ -337,6 +337,10 @@ def test_edge_cases(oracle, wa, gpu, tmp_path):
         eids, edists = oi.batch_search(Q, W, nq, "optimized_postfilter", _qp(oracle, 40, 1, k))
         ok, why = gu.same_rows(eids, edists, ids, dists, True, gu.RowContext(X, labels, Q, W, "l2"))
         assert ok, why
+    # k outside [1, 1024] is refused (wider rows are tested in test_gpu_result_width.py)
+    for k in (0, 1025):
+        with pytest.raises(RuntimeError, match=r"k must be in \[1, 1024\]"):
+            pi.batch_search(Q, W, nq, "optimized_postfilter", _qp(wa, 40, 1, k))
     # errors: bad shapes raise RuntimeError like the reference (tree_utils.h:46-60)
     with pytest.raises(RuntimeError):
         wa.VamanaRangeFilterTreeIndexFloatEuclidian(X.reshape(-1), labels)
@@ -1018,31 +1022,21 @@ def test_c_abi_allgather_leaves_device_resident_rows(wa, gpu, tmp_path):
 # dense prefilter path (queries sharing a window -> MFMA GEMM + exact re-rank), adversarial-style data
 # (generate_datasets/generate_advserial_dataset.py:8-69: clusters, labels c - 0.5 + U(0,1), one window per cluster)
 # ------------------------------------------------------------------------------------------
+def dense_prefilter_batch(metric, d):
+    """X, Q, labels, W of test_dense_prefilter_matches_oracle: SIFT-like integer rows for "l2", unit vectors otherwise"""
+    X, Q, labels, W = clustered_window_batch(d, "sift" if metric == "l2" else "unit")
+    if metric != "l2":
+        X = (X / np.linalg.norm(X, axis=1, keepdims=True)).astype(np.float32)
+        Q = (Q / np.linalg.norm(Q, axis=1, keepdims=True)).astype(np.float32)
+    return X, Q, labels, W
+
+
 @pytest.mark.parametrize("metric,sfx,d", [("mips", "FloatMips", 100), ("l2", "FloatEuclidian", 128), ("l2f", "FloatEuclidian", 96),
                                           ("mips", "FloatMips", 512), ("mips", "FloatMips", 300), ("l2f", "FloatEuclidian", 200),
                                           ("l2", "FloatEuclidian", 384)])  # (129 .. 512: the wide kernel, 2 / 3 / 4 slabs, partial last slab)
 def test_dense_prefilter_matches_oracle(oracle, wa, gpu, monkeypatch, metric, sfx, d):
-    rng = np.random.default_rng(17)
-    nclu, per, qper = 12, 1500, 40
-    n = nclu * per
-    if metric == "l2":
-        X = sift_like(n, d, 3)(n)
-        Q = sift_like(n, d, 3)(nclu * qper)
-    else:
-        cent = rng.standard_normal((nclu, d))
-        X = (cent[np.repeat(np.arange(nclu), per)] + 0.3 * rng.standard_normal((n, d)))
-        Q = (cent[np.repeat(np.arange(nclu), qper)] + 0.3 * rng.standard_normal((nclu * qper, d)))
-        X = (X / np.linalg.norm(X, axis=1, keepdims=True)).astype(np.float32)
-        Q = (Q / np.linalg.norm(Q, axis=1, keepdims=True)).astype(np.float32)
-    labels = (np.repeat(np.arange(nclu), per) - 0.5 + rng.random(n)).astype(np.float32)
-    perm = rng.permutation(n)
-    X, labels = X[perm], labels[perm]
+    X, Q, labels, W = dense_prefilter_batch(metric, d)
     nq = Q.shape[0]
-    W = np.zeros((nq, 2))
-    cl = np.repeat(np.arange(nclu), qper)
-    W[:, 0], W[:, 1] = cl - 0.5, cl + 0.5
-    W[::7] = (2.2, 3.9)       # a second family of shared windows
-    W[5::31, 1] += 1e-3 * np.arange(len(W[5::31]))  # and some unique ones (exact scan)
     pi = getattr(wa, "PrefilterIndex" + sfx)(X, labels)
     oi = getattr(oracle, "PrefilterIndex" + sfx)(X, labels)
     for k in (10, 16):

@@ -106,6 +106,31 @@ def recall(gt, ids, k=10):
     return tot / max(cnt, 1)
 
 
+def clustered_window_batch(d, style, seed=17, nclu=12, per=1500, qper=40):
+    """The batch of the dense prefilter tests, shaped like generate_datasets/generate_advserial_dataset.py:8-69: nclu clusters of
+    `per` points whose labels are c - 0.5 + U(0, 1), and qper queries per cluster that share the cluster's window; every seventh
+    query takes a second shared window and a few get a window of their own.  style "sift": integer-valued rows in [0, 255]
+    (sift_like); "unit": cluster centres plus noise, float64 and NOT normalised -- a caller normalises and quantises row by row.
+    Returns X (rows shuffled), Q, labels, W."""
+    rng = np.random.default_rng(seed)
+    n = nclu * per
+    if style == "sift":
+        X, Q = sift_like(n, d, 3)(n), sift_like(n, d, 3)(nclu * qper)
+    else:
+        cent = rng.standard_normal((nclu, d))
+        X = cent[np.repeat(np.arange(nclu), per)] + 0.3 * rng.standard_normal((n, d))
+        Q = cent[np.repeat(np.arange(nclu), qper)] + 0.3 * rng.standard_normal((nclu * qper, d))
+    labels = (np.repeat(np.arange(nclu), per) - 0.5 + rng.random(n)).astype(np.float32)
+    perm = rng.permutation(n)
+    X, labels = X[perm], labels[perm]
+    W = np.zeros((Q.shape[0], 2))
+    cl = np.repeat(np.arange(nclu), qper)
+    W[:, 0], W[:, 1] = cl - 0.5, cl + 0.5
+    W[::7] = (2.2, 3.9)       # a second family of shared windows
+    W[5::31, 1] += 1e-3 * np.arange(len(W[5::31]))  # and some unique ones (exact scan)
+    return X, Q, labels, W
+
+
 def tie_heavy(n, d, seed, lo=0, hi=12, dup_frac=0.15, zero_rows=0):
     """Rows of small integers in [lo, hi) as float32 (exact in fp32, bf16, uint8 / int8): nearly every distance is shared by many
     points.  A dup_frac share of the rows copies other rows, and a block of zero_rows rows in the middle is all zero."""
@@ -157,3 +182,77 @@ def tie_windows(labels, nq, p, seed):
         elif kind == 4:
             out[i] = (s[0] - 1, s[w])
     return out
+
+
+# ---- inputs shared by the dense-window, exact-window and result-width GPU tests ---------------------------------------------
+COVER_MIN_WINDOW, GEMM_POINT_CHUNK = 1024, 2048  # kCoverMinWindow, kGemmPointChunk (csrc/wann_gemm_device.h)
+
+
+def elem_type(sfx):
+    """numpy element type of the index class whose name ends in sfx ("UInt8Euclidian", "Float16Mips", "Float", ...)"""
+    return np.uint8 if sfx.startswith("UInt8") else np.int8 if sfx.startswith("Int8") else np.float16 if sfx.startswith("Float16") else np.float32
+
+
+def random_rows(sfx, rng, n, d):
+    """well-spread rows: uniform random bytes, unit vectors for the float types"""
+    if sfx.startswith("UInt8"):
+        return rng.integers(0, 256, (n, d)).astype(np.uint8)
+    if sfx.startswith("Int8"):
+        return rng.integers(-128, 128, (n, d)).astype(np.int8)
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(elem_type(sfx))
+
+
+def pos_windows(a, b):
+    """label windows that hold exactly positions [a, b) of the label order when labels are a permutation of 0 .. n-1"""
+    return np.stack([np.asarray(a, dtype=np.float64) - 0.5, np.asarray(b, dtype=np.float64) - 0.5], 1)
+
+
+def mixed_positions(rng, n, nq):
+    """window positions [a, b): several fractions of n, edges on and off multiples of 64, 128 and 2 048, the whole set, windows
+    below the minimum width, empty ones, ones with fewer than 16 points and ones outside the label span"""
+    a = np.zeros(nq, dtype=np.int64)
+    b = np.zeros(nq, dtype=np.int64)
+    for i in range(nq):
+        w = int(n * (1 / 32, 1 / 8, 1 / 2, 1 / 16)[i % 4] * (0.6 + 0.8 * rng.random()))
+        w = max(w, COVER_MIN_WINDOW + 1)
+        st = int(rng.integers(0, n - w))
+        kind = i % 7
+        if kind == 1:
+            st -= st % 64
+        elif kind == 2:
+            st -= st % 128
+            w -= w % 128
+        elif kind == 3:
+            st -= st % GEMM_POINT_CHUNK
+            w = max(GEMM_POINT_CHUNK, w - w % GEMM_POINT_CHUNK)
+        elif kind == 4:
+            e = (st + w) - (st + w) % GEMM_POINT_CHUNK
+            w = e - st if e - st >= COVER_MIN_WINDOW else w
+        a[i], b[i] = st, min(n, st + w)
+    a[0], b[0] = 0, n                       # the whole set
+    a[1], b[1] = 0, n
+    a[10:40] = rng.integers(0, n - 1000, 30)
+    b[10:40] = a[10:40] + rng.integers(17, COVER_MIN_WINDOW, 30)    # below the minimum width
+    b[40:50] = a[40:50] + rng.integers(1, 10, 10)              # fewer than k points
+    b[50:55] = a[50:55]                                        # empty
+    a[55:60], b[55:60] = n + 100, n + 5000                     # beyond the label span
+    a[60:62], b[60:62] = n - 1500, n                           # up to the last point
+    return a, b
+
+
+def wide_window_batch(n, nq, seed):
+    """nq windows of 3 000 .. 12 000 positions (start a, width w) that cover every 2 048-point block of the label order at least
+    32 times, both ends included"""
+    rng = np.random.default_rng(seed)
+    w = rng.integers(3000, 12000, nq)
+    a = (rng.random(nq) * (n - w - 2)).astype(np.int64) + 1
+    # (both ends of the label order are covered often enough too)
+    a[:40], w[:40] = 1 + np.arange(40), 11000 - 2 * np.arange(40)
+    w[40:80] = 11000 - 2 * np.arange(40)
+    a[40:80] = n - 1 - w[40:80] - np.arange(40)
+    cover = np.zeros(n // GEMM_POINT_CHUNK + 2, dtype=np.int64)
+    for x, y in zip(a, a + w):
+        cover[x // GEMM_POINT_CHUNK:(y - 1) // GEMM_POINT_CHUNK + 1] += 1
+    assert cover[:(n - 1) // GEMM_POINT_CHUNK + 1].min() >= 32
+    return a, w
