@@ -72,8 +72,19 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * when the index is created; an index that is not eligible (or found no memory for the copy) has no shadow and behaves as before.
  * wann_set_half_rows switches the use of the copy off and on between batches (on by default where the copy exists).
  * wann_device_bytes does NOT count the copy (it reports what it always has: a float32 index and the float16 index of the same
- * points differ there by the bytes of their rows); wann_half_rows_bytes does. */
-enum { WANN_DTYPE_F32 = 0, WANN_DTYPE_U8 = 1, WANN_DTYPE_I8 = 2, WANN_DTYPE_F16 = 3 };
+ * points differ there by the bytes of their rows); wann_half_rows_bytes does.
+ * WANN_DTYPE_BF16 (not a type of the reference): bfloat16 points, rows of uint16_t bit patterns (the top 16 bits of a float32:
+ * float32's exponent range, 8 significant bits).  Everything said of WANN_DTYPE_F16 holds with "bfloat16" for "binary16": the
+ * same row pitch and layout (natural order, zero padded to 32 elements), the widening -- one shift, exact for every pattern,
+ * subnormals, signed zeros, inf and NaN included, integer instructions only -- followed by the float32 path's own arithmetic, so
+ * the float32 index's ids, distance bits and operation counters on the upcast points; the float32 build's graphs and cache
+ * file names on the upcast points; bfloat16 bit patterns as host-buffer queries, fp32 device queries (not rounded), float32
+ * labels; no wann_vamana_* variant.  Its MFMA prefilter path covers rows of up to 128 elements with a kernel of its own (a
+ * bfloat16 row is its own high bf16 term: one staged row per point, two products per step instead of three, the float32
+ * kernel's scores on the upcast row); longer rows take the exact scan, with or without WANN_DENSE_LONG_ROWS.  A bfloat16 index
+ * has no shadow rows (wann_half_rows: 0).
+ * The value is 5: 4 is UNASSIGNED and refused as an unknown dtype, like every other value not listed here. */
+enum { WANN_DTYPE_F32 = 0, WANN_DTYPE_U8 = 1, WANN_DTYPE_I8 = 2, WANN_DTYPE_F16 = 3, WANN_DTYPE_BF16 = 5 };
 /* index classes */
 enum {
   WANN_KIND_PREFILTER = 0,      /* PrefilterIndex                                   */

@@ -133,7 +133,7 @@ int wann_device_count(void) { return usable_devices(); }
 wann_index *wann_index_create(int kind, int metric, int dtype, const void *points, int64_t n, int64_t d,
                               const float *labels, int32_t cutoff, double split_factor, double shift_factor,
                               const wann_build_params *bp, int device, int build_threads) {
-  if (dtype != WANN_DTYPE_F32 && dtype != WANN_DTYPE_U8 && dtype != WANN_DTYPE_I8 && dtype != WANN_DTYPE_F16) {
+  if (!known_dtype(dtype)) {
     fail(WANN_ERR_INVALID, "unknown dtype");
     return nullptr;
   }
@@ -774,7 +774,7 @@ int wann_num_replicas(const wann_index *I) { return I ? 1 + (int)I->replicas.siz
 int wann_build_cache_shard(int kind, int metric, int dtype, const void *points, int64_t n, int64_t d,
                            const float *labels, int32_t cutoff, double split_factor, double shift_factor,
                            const wann_build_params *bp, int shard, int nshards, int build_threads) {
-  if (dtype != WANN_DTYPE_F32 && dtype != WANN_DTYPE_U8 && dtype != WANN_DTYPE_I8 && dtype != WANN_DTYPE_F16)
+  if (!known_dtype(dtype))
     return fail(WANN_ERR_INVALID, "unknown dtype");
   if (!bp || !bp->cache_path || !*bp->cache_path) return fail(WANN_ERR_INVALID, "cache_path required");
   if (nshards <= 0 || shard < 0 || shard >= nshards) return fail(WANN_ERR_INVALID, "bad shard");

@@ -10,6 +10,7 @@
 // whenever no two candidates of a prune / neighbour sort are exactly equidistant (with such ties
 // the reference's order is whatever libstdc++'s std::sort leaves; ours is by id).
 #include "wann_build.h"
+#include "wann_bf16.h"
 #include "wann_half.h"
 
 #include <algorithm>
@@ -677,9 +678,9 @@ void build_host_index(HostIndex &H, const void *points, const float *labels, int
   BuildSpec &s = H.spec;
   if (s.n <= 0 || s.d <= 0) throw std::runtime_error("empty point set");
   if (s.threads <= 0) s.threads = default_threads();
-  // bytes per element of the caller's rows and of the stored rows (float16 points are stored as their exact float32 upcast:
-  // the graphs of a float16 index are those of the float32 index on the upcast points, byte for byte)
-  const bool half = s.dtype == 3;
+  // bytes per element of the caller's rows and of the stored rows (float16 / bfloat16 points are stored as their exact float32
+  // upcast: the graphs of such an index are those of the float32 index on the upcast points, byte for byte)
+  const bool half = s.dtype == 3 || s.dtype == 5;
   const int64_t esz = s.dtype == 0 ? 4 : half ? 2 : 1, ssz = half ? 4 : esz;
   s.stride = ((s.d * ssz + 63) / 64) * 16;      // 64-byte rows (point_range.h:39-44), zero padded; in 32-bit words
   H.sorted = (s.kind == 2 || s.kind == 3 || s.kind == 4);
@@ -696,7 +697,7 @@ void build_host_index(HostIndex &H, const void *points, const float *labels, int
     if (half) {
       const uint16_t *src = (const uint16_t *)points + order[r] * s.d;
       float *dst = H.pts.data() + r * s.stride;
-      for (int64_t j = 0; j < s.d; j++) dst[j] = half_to_float(src[j]);
+      for (int64_t j = 0; j < s.d; j++) dst[j] = two_byte_to_float(s.dtype, src[j]);
     } else {
       memcpy(H.pts.data() + r * s.stride, (const char *)points + order[r] * s.d * esz, (size_t)(s.d * esz));
     }
@@ -829,7 +830,7 @@ void build_pending_on_host(HostIndex &H, std::vector<HostPart *> &pending) {
   std::vector<Job> jobs;
   for (HostPart *P : pending) {
     Job J;
-    const int rows_dt = s.dtype == 3 ? 0 : s.dtype;  // (float16 points: float32 rows, see build_host_index)
+    const int rows_dt = (s.dtype == 3 || s.dtype == 5) ? 0 : s.dtype;  // (float16 / bfloat16 points: float32 rows, see build_host_index)
     J.V = BuildView{H.pts.data(), s.stride, s.d, s.metric | (rows_dt << 4), P->start, P->n, s.R, s.L, s.alpha};
     J.G = &P->g;
     jobs.push_back(std::move(J));

@@ -30,7 +30,7 @@ struct HostPart {
 
 struct BuildSpec {
   int kind = 0, metric = 0;
-  int dtype = 0;  // element type of the caller's rows (wann.h WANN_DTYPE_*): float32, uint8 / int8 bytes, or float16
+  int dtype = 0;  // element type of the caller's rows (wann.h WANN_DTYPE_*): float32, uint8 / int8 bytes, float16 or bfloat16
   int64_t n = 0, d = 0, stride = 0;  // stride: 32-bit words per row of HostIndex::pts
   int32_t cutoff = 1000;
   double split_factor = 2, shift_factor = 0.5;

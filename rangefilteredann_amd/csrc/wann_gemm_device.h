@@ -108,7 +108,7 @@ struct CoverArgs {
 
 // Which rows the dense path takes, and on which kind of score kernel: THE table -- the host (dense_rows_ok, dense_prefilter) and
 // the launchers (wann_gemm_launch.inc) ask here and hold no row length of their own.  Lengths in 32-bit words: `stride` for
-// float32 and byte rows, query_words (the row of the float32 upcast; the stride counts half rows) for float16.
+// float32 and byte rows, query_words (the row of the float32 upcast; the stride counts two-byte rows) for float16 / bfloat16.
 //
 //                  narrow              wide                      long (opt-in: WANN_DENSE_LONG_ROWS=1; queries pre-split / packed)
 //   float32        16 .. 128           129 .. 512                513 .. 2048 (kGemmMaxFloats)
@@ -116,6 +116,8 @@ struct CoverArgs {
 //                                      / k_gemm_scores_wide4
 //   float16        16 .. 128           -                         129 .. 2048 (kGemmMaxFloats)
 //                  k_gemm_scores<W>                              k_gemm_scores_hslab
+//   bfloat16       16 .. 128           -                         -
+//                  k_gemm_scores<W>, two products (the row is its own high bf16 term)
 //   uint8 / int8   16 .. 128 (512 B)   -                         129 .. 512 (kGemmMaxBytes / 4)
 //                  k_gemm_scores_b<N>                            k_gemm_scores_bslab, quantised keys: k_rerank_bslab
 //
@@ -126,6 +128,7 @@ inline DenseRows dense_row_class(const IndexView &ix) {
   const int words = query_words(ix);
   if ((ix.stride & 15) || words < 16 || words > (bytes ? kGemmMaxBytes / 4 : kGemmMaxFloats)) return kRowsNone;
   if (words <= 128) return kRowsNarrow;
+  if (ix.dtype == 5) return kRowsNone;  // bfloat16 rows beyond 128 elements: the exact scan, with or without WANN_DENSE_LONG_ROWS
   return ix.dtype == 0 && words <= 512 ? kRowsWide : kRowsLong;
 }
 
@@ -141,7 +144,7 @@ struct GemmUnit {
 };
 
 // entry points (the float32 unit): each looks up ix.dtype's unit, calls it and records the error; 0 = launched
-int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);  // float32 / float16 rows
+int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);  // float32 / float16 / bfloat16 rows
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream);                         // uint8 / int8 rows
 int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream);  // long float32 / float16 rows
 int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);  // long uint8 / int8 rows

@@ -23,15 +23,19 @@
 // The MFMA scores only SELECT candidates (SURVEY.md A.3: the reference sums in another order); every returned
 // distance is computed by the reference-order routines.
 //
-// One translation unit per element type of the point set (WANN_DT, set by wann_gemm_kernels.hip / _u8.hip / _i8.hip / _f16.hip
+// One translation unit per element type of the point set (WANN_DT, set by wann_gemm_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip
 // before this body is included).  The float32 unit holds the grouping kernels and every float32 kernel.  Which rows run on which
-// score kernel is decided in one place, dense_row_class (wann_gemm_device.h); the launchers are one text for all four units,
+// score kernel is decided in one place, dense_row_class (wann_gemm_device.h); the launchers are one text for all five units,
 // wann_gemm_launch.inc, each unit exposing its own through a constant table (GemmUnit) that the float32 unit's entry points look up.
 //   float16 rows (WANN_DT = 3)  the narrow k_gemm_scores with half loads: a binary16 value is EXACTLY the sum of its two bf16
 //                    terms (11 significant bits <= 8 + 8; the low term of a subnormal half is a multiple of 2^-24, far above
 //                    bf16's smallest normal number), so scores, selection, proof bound and re-rank are the float32 path's on the
 //                    exact upcast.  Rows of 129 .. 2048 elements: k_gemm_scores_hslab (the float32 unit's K-loop kernel with half
 //                    loads; opt-in), longer ones take the exact scan.
+//   bfloat16 rows (WANN_DT = 5) a k_gemm_scores of their own (wann_gemm_kernels_bf16.inc): a bfloat16 row is its own high bf16
+//                    term and has no low term, so a point is staged as one row, copied as it arrives, and a k-step runs two
+//                    products; the scores are the float32 kernel's on the upcast row.  Rows of up to 128 elements; longer
+//                    ones take the exact scan.
 //   byte rows (WANN_DT = 1 / 2) k_gemm_scores_b on v_mfma_i32_32x32x32_i8: exact int32 sums, one product, no error bound --
 //                    see wann_gemm_kernels_bytes.inc.  Rows of 513 .. 2048 bytes: k_gemm_scores_bslab (both operands staged per
 //                    256-byte slab, quantised keys; opt-in), longer ones take the exact scan.
@@ -55,8 +59,10 @@ namespace wann {
 #define WANN_DT_NS_G dt_u8
 #elif WANN_DT == 2
 #define WANN_DT_NS_G dt_i8
-#else
+#elif WANN_DT == 3
 #define WANN_DT_NS_G dt_f16
+#else
+#define WANN_DT_NS_G dt_bf16
 #endif
 #define WANN_GNS_BEGIN namespace WANN_DT_NS_G {
 #define WANN_GNS_END }
@@ -99,6 +105,13 @@ __global__ void k_point_norms(IndexView ix, float *norm2, unsigned int *max_bits
   // (the float32 kernel's arithmetic on the exact upcast: the norms of a float16 index are the float32 index's, bit for bit)
   const unsigned short *ph = reinterpret_cast<const unsigned short *>(p);
   for (int i = lane; i < ix.d; i += 64) s = fmaf(h2f(ph[i]), h2f(ph[i]), s);
+#elif WANN_DT == 5
+  // (likewise: a bfloat16 widens by a shift, and the norms are the float32 index's on the upcast points, bit for bit)
+  const unsigned short *pb = reinterpret_cast<const unsigned short *>(p);
+  for (int i = lane; i < ix.d; i += 64) {
+    const float v = __uint_as_float((uint32_t)pb[i] << 16);
+    s = fmaf(v, v, s);
+  }
 #else
   for (int i = lane; i < ix.d; i += 64) s = fmaf(p[i], p[i], s);
 #endif
@@ -504,6 +517,10 @@ __device__ __forceinline__ void insert4_chain(float &m1, float &m2, float &m3, f
 // all 128 points = 1 x 4 MFMA tiles; a score row of 128 floats leaves as four 128-byte stores.
 // Float16 rows (WANN_DT = 3): STRIDE is the row length of the float32 upcast (d rounded up to 16); the rows themselves are
 // halves (padded to a multiple of 32), fetched as 8-byte blocks of four and converted exactly where they are staged.
+// Bfloat16 rows (WANN_DT = 5) have a kernel body of their own: one staged row per point, two products.
+#if WANN_DT == 5
+#include "wann_gemm_kernels_bf16.inc"
+#else
 WANN_GNS_BEGIN
 template <int STRIDE>  // padded row length in floats: a multiple of 16, <= 128
 __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
@@ -703,6 +720,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
 #endif
 }
 WANN_GNS_END
+#endif  // WANN_DT != 5
 
 #if WANN_DT == 0
 

@@ -6,6 +6,7 @@
 // There is no CPU search path in this library: every compute entry point needs a gfx950 device
 // and fails loudly otherwise.
 #include "wann_host_internal.h"
+#include "wann_bf16.h"
 #include "wann_half.h"
 
 namespace wann_host {
@@ -72,8 +73,8 @@ void upload_index(wann_index &I) {
   IndexView &v = I.view;
   v.n = s.n;
   v.d = (int32_t)s.d;
-  // float16 points: the host rows are their float32 upcast; the device rows are halves again (exact), 64-byte padded
-  v.stride = (int32_t)(s.dtype == WANN_DTYPE_F16 ? ((s.d * 2 + 63) / 64) * 16 : s.stride);
+  // float16 / bfloat16 points: the host rows are their float32 upcast; the device rows are two-byte elements again (exact), 64-byte padded
+  v.stride = (int32_t)(two_byte_rows(s.dtype) ? two_byte_stride_words(s.d) : s.stride);
   v.metric = s.metric;
   v.dtype = s.dtype;
   v.kind = s.kind;
@@ -84,12 +85,12 @@ void upload_index(wann_index &I) {
   v.rs = (int32_t)(((s.R + 15) / 16) * 16);
   v.nlevels = (int32_t)H.levels.size();
 
-  if (s.dtype == WANN_DTYPE_F16) {
+  if (two_byte_rows(s.dtype)) {
     std::vector<float> rows((size_t)s.n * v.stride, 0.f);
     parallel_for(s.n, s.threads > 0 ? s.threads : default_threads(), [&](int64_t r) {
       const float *src = H.pts.data() + r * s.stride;
       uint16_t *dst = reinterpret_cast<uint16_t *>(rows.data() + r * v.stride);
-      for (int64_t j = 0; j < s.d; j++) dst[j] = float_to_half(src[j]);
+      for (int64_t j = 0; j < s.d; j++) dst[j] = float_to_two_byte(s.dtype, src[j]);
     });
     I.d_points.upload(rows);
   } else {
@@ -347,11 +348,11 @@ void build_pending(wann_index &I, std::vector<HostPart *> &pending) {
     build_pending_on_host(H, pending);
     for (auto &t : targets) upload_part_rows(I, *t.part, I.parts[t.part_index]);
   } else {
-    // float16 points are built from their float32 upcast (the host rows) by the float32 build kernels: the graphs are those of
+    // float16 / bfloat16 points are built from their float32 upcast (the host rows) by the float32 build kernels: the graphs are those of
     // the float32 index on the upcast points, byte for byte.  The float32 rows live on the device for the build only.
     IndexView bv = I.view;
     DevBuf<float> rows32;
-    if (s.dtype == WANN_DTYPE_F16) {
+    if (two_byte_rows(s.dtype)) {
       rows32.upload(H.pts);
       bv.points = rows32.p;
       bv.stride = (int32_t)s.stride;
@@ -372,9 +373,9 @@ void build_pending(wann_index &I, std::vector<HostPart *> &pending) {
 
 std::vector<float> bytes_to_float(int dtype, const void *src, int64_t count) {
   std::vector<float> out((size_t)count);
-  if (dtype == WANN_DTYPE_F16) {
+  if (two_byte_rows(dtype)) {
     const uint16_t *p = (const uint16_t *)src;
-    for (int64_t i = 0; i < count; i++) out[(size_t)i] = half_to_float(p[i]);
+    for (int64_t i = 0; i < count; i++) out[(size_t)i] = two_byte_to_float(dtype, p[i]);
   } else if (dtype == WANN_DTYPE_U8) {
     const uint8_t *p = (const uint8_t *)src;
     for (int64_t i = 0; i < count; i++) out[(size_t)i] = (float)p[i];

@@ -24,7 +24,7 @@
 
 namespace wann {
 
-// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip before this body is
+// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip before this body is
 // included): the search and scan kernels and their launchers live in a per-type namespace; the type-independent
 // kernels (routing, finalisation) and the dispatchers are compiled with the float32 unit only.
 #if WANN_DT == 0
@@ -33,8 +33,10 @@ namespace wann {
 #define WANN_DT_NS dt_u8
 #elif WANN_DT == 2
 #define WANN_DT_NS dt_i8
-#else
+#elif WANN_DT == 3
 #define WANN_DT_NS dt_f16
+#else
+#define WANN_DT_NS dt_bf16
 #endif
 // The float16 unit's search kernels carry the element type as a third template argument (k_search<METRIC, KIND, 3>): their
 // symbols differ from the float32 / byte-row kernels' in more than the namespace, and per-type tools and tests that select
@@ -42,6 +44,8 @@ namespace wann {
 // checks the float16 kernels' own register budget).
 #if WANN_DT == 3
 #define WANN_DT_TPARAM , int ROWS_DT = 3
+#elif WANN_DT == 5  // (the bfloat16 unit likewise)
+#define WANN_DT_TPARAM , int ROWS_DT = 5
 #else
 #define WANN_DT_TPARAM
 #endif
@@ -1658,17 +1662,22 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
 int launch_brute(const BruteArgs &a, int blocks, void *stream);
 }
+namespace dt_bf16 {
+int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
+int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
+int launch_brute(const BruteArgs &a, int blocks, void *stream);
+}
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
   return a.ix.dtype == 1 ? dt_u8::search_occupancy(a, cfg) : a.ix.dtype == 2 ? dt_i8::search_occupancy(a, cfg)
-       : a.ix.dtype == 3 ? dt_f16::search_occupancy(a, cfg) : dt_f32::search_occupancy(a, cfg);
+       : a.ix.dtype == 3 ? dt_f16::search_occupancy(a, cfg) : a.ix.dtype == 5 ? dt_bf16::search_occupancy(a, cfg) : dt_f32::search_occupancy(a, cfg);
 }
 int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
   return a.ix.dtype == 1 ? dt_u8::launch_search(a, cfg, stream) : a.ix.dtype == 2 ? dt_i8::launch_search(a, cfg, stream)
-       : a.ix.dtype == 3 ? dt_f16::launch_search(a, cfg, stream) : dt_f32::launch_search(a, cfg, stream);
+       : a.ix.dtype == 3 ? dt_f16::launch_search(a, cfg, stream) : a.ix.dtype == 5 ? dt_bf16::launch_search(a, cfg, stream) : dt_f32::launch_search(a, cfg, stream);
 }
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   return a.ix.dtype == 1 ? dt_u8::launch_brute(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_brute(a, blocks, stream)
-       : a.ix.dtype == 3 ? dt_f16::launch_brute(a, blocks, stream) : dt_f32::launch_brute(a, blocks, stream);
+       : a.ix.dtype == 3 ? dt_f16::launch_brute(a, blocks, stream) : a.ix.dtype == 5 ? dt_bf16::launch_brute(a, blocks, stream) : dt_f32::launch_brute(a, blocks, stream);
 }
 
 int launch_finalize(const FinalizeArgs &a, void *stream) {

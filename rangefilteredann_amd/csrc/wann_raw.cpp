@@ -22,7 +22,7 @@ struct RawGraph {
   DevBuf<unsigned long long> g_beam, d_prof;
   DevBuf<uint32_t> g_seen;
   int64_t layout = -1;
-  // points: (n, d) rows of `dtype` elements (float32, uint8 / int8 bytes: stored as byte rows, or float16: stored as halves)
+  // points: (n, d) rows of `dtype` elements (float32, uint8 / int8 bytes: stored as byte rows, or float16 / bfloat16: stored as two-byte elements)
   void load(int device, int metric, const void *points, int64_t n_, int64_t d_, const int32_t *graph_rows, int64_t maxdeg_,
             int64_t subset_start, int64_t subset_n_, int dtype = WANN_DTYPE_F32) {
     HIP_CHECK(hipSetDevice(device));
@@ -197,7 +197,7 @@ int wann_raw_beam_search_typed(int metric, int dtype, const void *points, int64_
                                const int64_t *query_ids, int64_t beam, int64_t limit, int64_t degree_limit,
                                int32_t *out_ids, float *out_dists, int32_t *out_sizes, int64_t *out_hops,
                                int64_t *out_dist_cmps, int device) {
-  if (dtype < WANN_DTYPE_F32 || dtype > WANN_DTYPE_F16) return fail(WANN_ERR_INVALID, "unknown dtype");
+  if (!known_dtype(dtype)) return fail(WANN_ERR_INVALID, "unknown dtype");
   if (usable_devices() <= device || device < 0)
     return fail(WANN_ERR_NO_DEVICE, "no usable gfx950 device (this library has no CPU search path)");
   if (maxdeg > WANN_MAX_DEGREE) return fail(WANN_ERR_UNSUPPORTED, "max_degree > 128 is not supported");

@@ -84,9 +84,10 @@ __device__ __forceinline__ u64 hash64_2(u64 x) {
 // element type of the point rows: one translation unit per type (wann_kernels.hip, _u8, _i8, _f16)
 // --------------------------------------------------------------------------------------------
 #ifndef WANN_DT
-#define WANN_DT 0  // 0 = float32 rows, 1 = uint8, 2 = int8, 3 = float16
+#define WANN_DT 0  // 0 = float32 rows, 1 = uint8, 2 = int8, 3 = float16, 5 = bfloat16 (4 is unassigned, see wann.h)
 #endif
 #define WANN_BYTE_ROWS (WANN_DT == 1 || WANN_DT == 2)
+#define WANN_HALF_ROWS (WANN_DT == 3 || WANN_DT == 5)  // two-byte float rows (two_byte_rows in wann_device.h is the host side)
 
 // A row BLOCK is four consecutive elements e..e+3 of a row (e a multiple of 4): a float4 of a float32 row, 8 bytes of a
 // float16 row.  Float16 rows (WANN_DT = 3) keep the natural element order, padded with zeros to a multiple of 32 halves
@@ -104,6 +105,16 @@ __device__ __forceinline__ float4 h4_to_f4(uint2 w) {
 }
 #define ld_blk(prow, e) (*reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(prow) + (e)))
 #define cvt_blk(w) h4_to_f4(w)
+#elif WANN_DT == 5
+// bfloat16 rows: the float16 rows' layout and blocks.  A bfloat16 is the top 16 bits of a float32, so the conversion is
+// integer-only -- a shift or a mask, then a bit cast: subnormals, signed zeros, inf and NaN come through whatever the FP mode.
+typedef uint2 rowblk_t;
+__device__ __forceinline__ float4 b4_to_f4(uint2 w) {
+  return make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
+                     __uint_as_float(w.y & 0xffff0000u));
+}
+#define ld_blk(prow, e) (*reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(prow) + (e)))
+#define cvt_blk(w) b4_to_f4(w)
 #else
 typedef float4 rowblk_t;
 // (no parentheses round `e`: `prow + 8 * b + 4 * h` is the address arithmetic the float32 unit has always compiled)
@@ -111,9 +122,9 @@ typedef float4 rowblk_t;
 #define cvt_blk(w) (w)
 #endif
 // 32-bit words of the staged (fp32, zero padded) query and of the LDS reserved for it: `stride` for float32 / byte rows; for
-// float16 rows the float32 row length, d rounded up to 16 -- every routine reads the query up to d rounded up to 8, and the
+// float16 / bfloat16 rows the float32 row length, d rounded up to 16 -- every routine reads the query up to d rounded up to 8, and the
 // LDS layout of a float16 index equals the float32 index's (query_words in wann_device.h is the host side)
-__device__ __forceinline__ int qv_words(const IndexView &ix) { return WANN_DT == 3 ? ((ix.d + 15) & ~15) : ix.stride; }
+__device__ __forceinline__ int qv_words(const IndexView &ix) { return WANN_HALF_ROWS ? ((ix.d + 15) & ~15) : ix.stride; }
 
 // --------------------------------------------------------------------------------------------
 // distances in the reference's evaluation order

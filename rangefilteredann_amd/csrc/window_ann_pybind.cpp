@@ -16,6 +16,7 @@
 #include <cstdio>
 
 #include "../../include/wann.h"
+#include "wann_bf16.h"
 
 namespace py = pybind11;
 using namespace pybind11::literals;
@@ -57,9 +58,22 @@ static const BuildParams &default_build_params() {  // python_bindings.cpp:88
 
 using FArray = py::array_t<float, py::array::c_style | py::array::forcecast>;
 
+// numpy has no bfloat16: any array numpy casts to float32 -> the uint16 bit patterns of its values rounded to bfloat16 (nearest,
+// ties to even: float_to_bf16).  VALUES are rounded, whatever the array's dtype: an integer array is never read as bit patterns.
+static py::array bf16_bits_of(const py::handle &a) {
+  FArray f = FArray::ensure(a);
+  if (!f) return py::array();
+  py::array_t<uint16_t> out(std::vector<py::ssize_t>(f.shape(), f.shape() + f.ndim()));
+  const float *src = f.data();
+  uint16_t *dst = out.mutable_data();
+  for (py::ssize_t i = 0, n = f.size(); i < n; i++) dst[i] = wann::float_to_bf16(src[i]);
+  return std::move(out);
+}
+
 // any array -> a C-contiguous array of the element type `dtype` (py::array_t<T>::ensure semantics; float16, which pybind11 has no
-// C++ type for, through numpy: astype rounds to nearest, ties to even)
+// C++ type for, through numpy: astype rounds to nearest, ties to even; bfloat16: bf16_bits_of)
 static py::array as_elem(int dtype, const py::handle &a) {
+  if (dtype == WANN_DTYPE_BF16) return bf16_bits_of(a);
   if (dtype == WANN_DTYPE_F16) return py::module_::import("numpy").attr("ascontiguousarray")(a, "dtype"_a = "float16");
   if (dtype == WANN_DTYPE_F32) return FArray::ensure(a);
   if (dtype == WANN_DTYPE_U8) return py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(a);
@@ -542,6 +556,10 @@ PYBIND11_MODULE(_window_ann, m) {
   // not a type of the reference: float16 points (wann.h WANN_DTYPE_F16), rows of the float32 index on the upcast points
   add_variant<WANN_METRIC_L2, WANN_DTYPE_F16>(m, "Float16Euclidian");
   add_variant<WANN_METRIC_MIPS, WANN_DTYPE_F16>(m, "Float16Mips");
+  // likewise bfloat16 points (wann.h WANN_DTYPE_BF16): constructors and host batch_search take any array numpy casts to float32
+  // and round its values to bfloat16 (a torch.bfloat16 tensor t passes through t.float().numpy() exactly)
+  add_variant<WANN_METRIC_L2, WANN_DTYPE_BF16>(m, "BFloat16Euclidian");
+  add_variant<WANN_METRIC_MIPS, WANN_DTYPE_BF16>(m, "BFloat16Mips");
 
   // python_bindings.cpp:67-86: builder and index names of the unfiltered Vamana variants
   add_vamana<WANN_METRIC_L2, WANN_DTYPE_F32>(m, "float_euclidian", "VamanaFloatEuclidianIndex");
@@ -558,6 +576,21 @@ PYBIND11_MODULE(_window_ann, m) {
     for (const char *metric : {"Euclidian", "Mips"})
       m.attr((std::string(cls) + "Uint8" + metric).c_str()) = m.attr((std::string(cls) + "UInt8" + metric).c_str());
 
+  // what a bfloat16 index stores of `a`: its values rounded to bfloat16, as uint16 bit patterns / as the float32 values they widen to
+  m.def("bfloat16_bits", [](py::object a) {
+    py::array b = bf16_bits_of(a);
+    if (!b) throw std::runtime_error("bfloat16_bits: not convertible to a float32 array");
+    return b;
+  }, "a"_a);
+  m.def("bfloat16_round", [](py::object a) {
+    FArray f = FArray::ensure(a);
+    if (!f) throw std::runtime_error("bfloat16_round: not convertible to a float32 array");
+    py::array_t<float> out(std::vector<py::ssize_t>(f.shape(), f.shape() + f.ndim()));
+    const float *src = f.data();
+    float *dst = out.mutable_data();
+    for (py::ssize_t i = 0, n = f.size(); i < n; i++) dst[i] = wann::bf16_to_float(wann::float_to_bf16(src[i]));
+    return out;
+  }, "a"_a);
   m.def("device_count", [] { return wann_device_count(); });
   m.def("abi_version", [] { return wann_abi_version(); });
   m.def(
@@ -600,14 +633,17 @@ PYBIND11_MODULE(_window_ann, m) {
       },
       "metric"_a, "points"_a, "graph_rows"_a, "subset_start"_a, "queries"_a, "query_ids"_a, "beam"_a,
       "limit"_a = 10000000, "degree_limit"_a = 10000, "device"_a = 0);
-  // raw_beam_search over points of any element type (dtype: 0 float32, 1 uint8, 2 int8, 3 float16); queries stay float32
+  // raw_beam_search over points of any element type (dtype: 0 float32, 1 uint8, 2 int8, 3 float16, 5 bfloat16 -- there `points` is a
+  // uint16 array of BIT PATTERNS, as float16 takes np.float16); queries stay float32
   m.def(
       "raw_beam_search_typed",
       [](int metric, int dtype, py::array points_in, py::array_t<int32_t, py::array::c_style | py::array::forcecast> graph_rows,
          int64_t subset_start, FArray queries, py::array_t<int64_t, py::array::c_style | py::array::forcecast> query_ids,
          int64_t beam, int64_t limit, int64_t degree_limit, int device) {
-        if (dtype < WANN_DTYPE_F32 || dtype > WANN_DTYPE_F16) throw std::runtime_error("unknown dtype");
-        py::array points = as_elem(dtype, points_in);
+        if ((dtype < WANN_DTYPE_F32 || dtype > WANN_DTYPE_F16) && dtype != WANN_DTYPE_BF16) throw std::runtime_error("unknown dtype");
+        if (dtype == WANN_DTYPE_BF16 && !py::isinstance<py::array_t<uint16_t>>(points_in))
+          throw std::runtime_error("dtype 5 takes the points as a uint16 array of bfloat16 bit patterns");
+        py::array points = dtype == WANN_DTYPE_BF16 ? py::array(py::array_t<uint16_t, py::array::c_style>::ensure(points_in)) : as_elem(dtype, points_in);
         if (points.ndim() != 2 || graph_rows.ndim() != 2 || queries.ndim() != 2) throw std::runtime_error("bad shapes");
         int64_t n = points.shape(0), d = points.shape(1), sn = graph_rows.shape(0), md = graph_rows.shape(1) - 1;
         int64_t nq = queries.shape(0);

@@ -61,8 +61,19 @@ def _module():
 _DTYPES = {"float": "Float", "uint8": "Uint8", "int8": "Int8"}
 # "float16" is not a type of the reference (wrapper.py raises "Invalid data type" for it, and so do these constructors by
 # default): float16 points, rows of the float32 index on the upcast points (include/wann.h WANN_DTYPE_F16).  The --dtype float16
-# experiments ask for it with float16=True.
-_FLOAT16 = {"float16": "Float16"}
+# experiments ask for it with float16=True.  "bfloat16" (WANN_DTYPE_BF16) resolves under the same opt-in and no other.
+_FLOAT16 = {"float16": "Float16", "bfloat16": "BFloat16"}
+_HALF_DTYPES = tuple(_FLOAT16)
+
+
+def round_to_dtype(a, dtype):
+    """What an index of the half-width `dtype` stores of `a`: a float16 array (numpy astype: nearest, ties to even), or -- numpy
+    has no bfloat16 -- the float32 values rounded to bfloat16 (`bfloat16_round`), which the BFloat16 classes take as they are."""
+    if dtype == "float16":
+        return np.asarray(a).astype(np.float16)
+    if dtype == "bfloat16":
+        return _module().bfloat16_round(np.asarray(a))
+    return a
 _METRICS = {"Euclidian": "Euclidian", "mips": "Mips"}
 
 
@@ -240,6 +251,7 @@ class Settings:
     threads: int = os.cpu_count() or 1
     methods: Tuple[str, ...] = ()  # subset of: prefiltering postfiltering vamana_tree optimized_postfiltering smart_combined three_split super_opt_postfiltering
     # "float16": points and queries rounded to float16 (numpy astype: nearest, ties to even) and searched by the Float16 classes;
+    # "bfloat16": rounded to bfloat16 (bfloat16_round) and searched by the BFloat16 classes, cache subdirectory bfloat16/;
     # recall is still taken against the dataset's stored ground truth of the original data.  Graph caches go to a subdirectory
     # of their own: a float16 index's graphs are those of the ROUNDED points, under the same file names as the float32 graphs.
     dtype: str = "float"
@@ -260,13 +272,13 @@ class Experiments:
     def _dataset(self, name):
         if name not in self._dataset_cache:
             data, queries, filter_values, metric = initialize_dataset(self.s.dataset_folder, name)
-            if self.s.dtype == "float16":
-                data, queries = data.astype(np.float16), queries.astype(np.float16)
+            if self.s.dtype in _HALF_DTYPES:
+                data, queries = round_to_dtype(data, self.s.dtype), round_to_dtype(queries, self.s.dtype)
             self._dataset_cache = {name: (data, queries, filter_values, metric)}
         return self._dataset_cache[name]
 
     def _cache(self, sub):
-        path = os.path.join(self.s.cache_root, *(["float16"] if self.s.dtype == "float16" else []), sub)
+        path = os.path.join(self.s.cache_root, *([self.s.dtype] if self.s.dtype in _HALF_DTYPES else []), sub)
         os.makedirs(path if path.endswith("/") else os.path.dirname(path), exist_ok=True)
         return path
 
@@ -364,7 +376,7 @@ class Experiments:
         if not self.s.write_results:
             return None
         os.makedirs(self.s.results_dir, exist_ok=True)
-        half = "float16_" if self.s.dtype == "float16" else ""
+        half = self.s.dtype + "_" if self.s.dtype in _HALF_DTYPES else ""
         exact = f"exact{int(self.s.exact_windows)}_" if self.s.exact_windows else ""
         path = os.path.join(self.s.results_dir, f"{self.s.results_file_prefix}{half}{exact}{dataset_name}_results.csv")
         if not os.path.exists(path):
@@ -427,10 +439,11 @@ def build_for_memory(index_type, data, filter_values, metric, dataset_name, alph
     """Construct the index exactly as all_memories.py:25-83 does and return (index, bytes).  The reference reports the
     growth of the process RSS (its index lives in host memory); this engine's index lives in HBM, so the figure is the
     device footprint (`index.device_bytes()`: vectors + labels + decoding + adjacency pool + partition tables).
-    dtype "float16": the points are rounded to float16 and the Float16 class is built, its graphs in <cache_root>/float16/."""
-    half = dtype == "float16"
+    dtype "float16" / "bfloat16": the points are rounded to that type and the Float16 / BFloat16 class is built, its graphs in
+    <cache_root>/float16/ or <cache_root>/bfloat16/."""
+    half = dtype in _HALF_DTYPES
     if half:
-        data, cache_root = np.asarray(data).astype(np.float16), os.path.join(cache_root, "float16")
+        data, cache_root = round_to_dtype(data, dtype), os.path.join(cache_root, dtype)
     if index_type == "postfiltering":
         cons, kw, sub = (postfilter_vamana_constructor(metric, dtype, float16=True) if half else postfilter_vamana_constructor(metric, "float")), {}, f"{dataset_name}/unsorted-"
     elif index_type == "vamana-tree":
@@ -507,9 +520,9 @@ def main(argv=None):
                          "super-postfiltering} as experiments/all_memories.py, else with --vamana_tree_split_factor as "
                          "experiments/memory_footprint.py")
     ap.add_argument("--index_type", type=str, default=None)
-    ap.add_argument("--dtype", choices=("float", "float16"), default="float",
-                    help="float16: round points and queries to float16 and search the Float16 index classes (own graph cache "
-                         "subdirectory and results prefix; recall against the original data's ground truth)")
+    ap.add_argument("--dtype", choices=("float", "float16", "bfloat16"), default="float",
+                    help="float16 / bfloat16: round points and queries to that type and search the Float16 / BFloat16 index classes "
+                         "(own graph cache subdirectory and results prefix; recall against the original data's ground truth)")
     args = ap.parse_args(argv)
     threads = args.threads or (os.cpu_count() or 1)
     os.environ["PARLAY_NUM_THREADS"] = str(threads)

@@ -8,7 +8,10 @@ then timed ALTERNATELY in this one process (device-resident queries: fp32 rows o
 identical.  Reported per leg: QPS and search_kernel_ms of both, algorithmic bytes (2- or 4-byte elements) and their share of
 8 TB/s, device_bytes of both, and recall@10 against exact ground truth of the UNROUNDED data for the float16 index and for a
 float32 index built on the unrounded points (its own cache) at the same setting -- what a user deciding on float16 needs.
-Prints one JSON object.   python tools/bench_half.py [--configs sift,glove,deep] [--reps 10] [--no-unrounded]"""
+--dtype bfloat16: the same legs for the BFloat16 classes -- points and queries rounded with bfloat16_round (nearest, ties to
+even, 8 significant bits), a cache directory of its own, identical rows required between the bfloat16 index and the float32
+index on the upcast points; the report's keys say "bfloat16" where they say "float16" by default.
+Prints one JSON object.   python tools/bench_half.py [--dtype float16|bfloat16] [--configs sift,glove,deep] [--reps 10] [--no-unrounded]"""
 import argparse
 import json
 import os
@@ -31,6 +34,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="sift,glove,deep")
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16", help="the half-width element type under test")
     ap.add_argument("--cache", default="/tmp/wann_half_cache")
     ap.add_argument("--no-unrounded", dest="unrounded", action="store_false", help="skip the float32 index on the unrounded points")
     ap.add_argument("--setting", default="", help="'beam,mult': skip the sweep (profiling runs)")
@@ -43,6 +47,12 @@ def main():
     import fullsize_configs as fc
 
     dev = torch.device("cuda:0")
+    HALF = args.dtype
+    half_cls = {"float16": "Float16", "bfloat16": "BFloat16"}[HALF]
+
+    def rounded(a):  # what an index of the type stores: a float16 array / the float32 values of the bfloat16 roundings
+        return a.astype(np.float16) if HALF == "float16" else wa.bfloat16_round(a)
+
     K, R, L, ALPHA = fc.K, fc.R, fc.L, fc.ALPHA
     report = dict(tool="tools/bench_half.py", hbm_tb_per_s=HBM_TBPS, legs=[])
 
@@ -54,7 +64,7 @@ def main():
         n, d, nq = cfg["n"], cfg["d"], cfg["nq"]
         l2 = leg["metric"] == "Euclidian"
         X, Q, labels = fc.make_data(name)
-        X16, Q16 = X.astype(np.float16), Q.astype(np.float16)
+        X16, Q16 = rounded(X), rounded(Q)
         W = fc.fraction_windows(labels, nq, leg["frac"], 2000 + leg["frac"]).astype(np.float32)
         method = cfg["method"] or ""
         kw = cfg["kw"]
@@ -92,13 +102,13 @@ def main():
             ids64 = ids_t.to(torch.int64) & 0xFFFFFFFF
             return float((gt[:, :, None] == ids64[:, None, :]).any(2).sum(1).double().mean().item() / K)
 
-        cache = os.path.join(args.cache, f"{name}_float16_n{n}") + "/"
+        cache = os.path.join(args.cache, f"{name}_{HALF}_n{n}") + "/"
         os.makedirs(cache, exist_ok=True)
         t0 = time.time()
-        h = getattr(wa, leg["kind"] + "Float16" + leg["metric"])(X16, labels, build_params=wa.BuildParams(R, L, ALPHA, cache), **kw)
+        h = getattr(wa, leg["kind"] + half_cls + leg["metric"])(X16, labels, build_params=wa.BuildParams(R, L, ALPHA, cache), **kw)
         build_s = time.time() - t0
         f = getattr(wa, leg["kind"] + "Float" + leg["metric"])(X16.astype(np.float32), labels, build_params=wa.BuildParams(R, L, ALPHA, cache), **kw)
-        log(f"{name}: float16 index built in {build_s:.1f}s ({h.device_bytes() / 2**30:.2f} GiB); float32 index on the upcast points "
+        log(f"{name}: {HALF} index built in {build_s:.1f}s ({h.device_bytes() / 2**30:.2f} GiB); float32 index on the upcast points "
             f"opened the same graphs ({f.device_bytes() / 2**30:.2f} GiB)")
 
         sweep = []
@@ -128,29 +138,29 @@ def main():
         rec16_rounded = recall(gt_rounded)
 
         # alternate: f32, f16, f32, f16, ... (each call host-synchronous: its counters are its own)
-        times = {"float32": [], "float16": []}
-        kms = {"float32": [], "float16": []}
+        times = {"float32": [], HALF: []}
+        kms = {"float32": [], HALF: []}
         for _ in range(args.reps):
-            for tag, index in (("float32", f), ("float16", h)):
+            for tag, index in (("float32", f), (HALF, h)):
                 t = time.perf_counter()
                 run(index, *best)
                 times[tag].append((time.perf_counter() - t) * 1e3)
                 kms[tag].append(index.counters()["search_kernel_ms"])
         res = dict(config=name, workload=f"{cfg['cls']} n={n} d={d} {'L2' if l2 else 'MIPS'} R={R} L={L} {kw} window 2^{leg['frac']} nq={nq} k={K}",
-                   float16_build_s=round(build_s, 1), setting=dict(beam=best[0], mult=best[1]), sweep=sweep,
+                   **{HALF + "_build_s": round(build_s, 1)}, setting=dict(beam=best[0], mult=best[1]), sweep=sweep,
                    rows_identical=rows_identical, counters_equal=counters_equal,
                    counters=dict((k, hc[k]) for k in ("beam_searches", "hops", "dist_cmps", "brute_rows", "label_reads", "spec_searches")))
-        for tag, index, esz in (("float32", f, 4), ("float16", h, 2)):
+        for tag, index, esz in (("float32", f, 4), (HALF, h, 2)):
             ms = float(np.median(times[tag]))
             km = float(np.mean(kms[tag]))
             gb = (4 * (R + 1) * hc["hops"] + esz * d * hc["dist_cmps"] + 4 * hc["label_reads"]) / 1e9
             res[tag] = dict(qps=round(nq / ms * 1e3), ms_per_batch=round(ms, 3), search_kernel_ms=round(km, 3),
                             search_kernel_ms_per_call=[round(x, 3) for x in kms[tag]], algorithmic_gb_per_batch=round(gb, 3),
                             hbm_share=round(gb / km / HBM_TBPS, 4) if km > 0 else None, device_bytes=int(index.device_bytes()))
-        res["float16"]["recall_at_10_unrounded_gt"] = round(rec16, 4)
-        res["float16"]["recall_at_10_rounded_gt"] = round(rec16_rounded, 4)
-        res["speedup_qps"] = round(res["float16"]["qps"] / res["float32"]["qps"], 3)
-        res["speedup_search_kernel"] = round(res["float32"]["search_kernel_ms"] / res["float16"]["search_kernel_ms"], 3)
+        res[HALF]["recall_at_10_unrounded_gt"] = round(rec16, 4)
+        res[HALF]["recall_at_10_rounded_gt"] = round(rec16_rounded, 4)
+        res["speedup_qps"] = round(res[HALF]["qps"] / res["float32"]["qps"], 3)
+        res["speedup_search_kernel"] = round(res["float32"]["search_kernel_ms"] / res[HALF]["search_kernel_ms"], 3)
         del f, h
         torch.cuda.empty_cache()
         if args.unrounded:  # the float32 index a user would otherwise run: unrounded points, its own graphs

@@ -1,4 +1,4 @@
-"""Dev tool: VGPR / SGPR / scratch / LDS of every gfx950 kernel inside libwann.so (reads the code objects' notes)."""
+"""Dev tool: VGPR / SGPR / scratch / static LDS of every gfx950 kernel inside libwann.so (reads the code objects' notes)."""
 import os, re, subprocess, sys, tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = os.environ.get("WANN_LIB", os.path.join(REPO, "rangefilteredann_amd", "libwann.so"))
@@ -21,4 +21,4 @@ for i, s in enumerate(starts):
         m = re.match(r":?\s*(\d+)", blk)
         agpr = m.group(1) if m else "?"
         print(f"{name[:60]:60s} vgpr+agpr {g('vgpr_count'):>4} (agpr {agpr:>3}) sgpr {g('sgpr_count'):>4} scratch {g('private_segment_fixed_size'):>5} "
-              f"spill {g('vgpr_spill_count'):>3} sgpr_spill {g('sgpr_spill_count'):>4}")
+              f"spill {g('vgpr_spill_count'):>3} sgpr_spill {g('sgpr_spill_count'):>4} lds {g('group_segment_fixed_size'):>5}")
