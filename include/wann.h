@@ -73,6 +73,17 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * wann_set_half_rows switches the use of the copy off and on between batches (on by default where the copy exists).
  * wann_device_bytes does NOT count the copy (it reports what it always has: a float32 index and the float16 index of the same
  * points differ there by the bytes of their rows); wann_half_rows_bytes does.
+ * ONE-BYTE SHADOW ROWS of a float32 index (opt-in).  Where ALL n x d values of such an index are moreover integers 0 .. 255 --
+ * wann_rows_u8_exact: (float)(uint8_t)x has the bits of x, so +0.0 only; -0.0, negatives, fractions, 256 and above, NaN and the
+ * infinities are refused; SIFT / BIGANN vectors qualify, signed [-128, 127] sets do not -- the index keeps a THIRD copy of its
+ * points as uint8 rows (natural order, zero padded to a multiple of 64 bytes: wann_byte_rows_bytes, a quarter of the float32
+ * bytes) beside the float32 rows and the half rows.  After wann_set_byte_rows(index, 1) the BEAM SEARCHES read that copy: each
+ * byte is widened to the float32 it was made from and scored against the caller's float32 query in the float32 kernels'
+ * arithmetic and order -- the same rows, distance bits and operation counters, queries of any float32 value.  (This is not the
+ * WANN_DTYPE_U8 path, whose queries become bytes.)  OFF by default: a batch reads the one-byte rows if that switch is on, else
+ * the half rows if theirs is on, else the float32 rows; everything the half rows leave to the float32 rows stays there.
+ * wann_device_bytes does not count this copy either.  6, the type of that internal view, is not a WANN_DTYPE_* value and is
+ * refused like any unknown dtype.
  * WANN_DTYPE_BF16 (not a type of the reference): bfloat16 points, rows of uint16_t bit patterns (the top 16 bits of a float32:
  * float32's exponent range, 8 significant bits).  Everything said of WANN_DTYPE_F16 holds with "bfloat16" for "binary16": the
  * same row pitch and layout (natural order, zero padded to 32 elements), the widening -- one shift, exact for every pattern,
@@ -284,7 +295,7 @@ int wann_partition_range(const wann_index *index, int64_t level, int64_t idx, in
 int wann_partition_graph(const wann_index *index, int64_t level, int64_t idx, int32_t *rows, int64_t cap_rows,
                          int64_t max_degree);
 int64_t wann_max_degree(const wann_index *index);
-int64_t wann_device_bytes(const wann_index *index);  /* (without the half-precision shadow rows: wann_half_rows_bytes) */
+int64_t wann_device_bytes(const wann_index *index);  /* (without the shadow rows: wann_half_rows_bytes, wann_byte_rows_bytes) */
 
 /* Half-precision shadow rows (see WANN_DTYPE_*).
  * wann_rows_fp16_exact: 1 if every one of the n x d float32 values (row-major, contiguous) is a finite IEEE binary16 value, else 0;
@@ -300,6 +311,22 @@ int wann_set_half_rows(wann_index *index, int on);
 int wann_half_rows(const wann_index *index);
 int64_t wann_half_rows_bytes(const wann_index *index);
 int wann_last_half_rows(const wann_index *index);
+/* One-byte shadow rows (see WANN_DTYPE_*), the same five calls.
+ * wann_rows_u8_exact: 1 if every one of the n x d float32 values (row-major, contiguous) is an integer 0 .. 255 with the bits of
+ * (float)(uint8_t)x, else 0; 1 for an empty set.  Pure host code: needs no device.
+ * wann_set_byte_rows: whether the beam searches of the NEXT batches read the one-byte rows (a batch submitted earlier keeps what
+ * it was submitted with).  Returns the setting now in force, 0 / 1: asking for 1 on an index without the copy leaves it at 0 and
+ * returns 0.  Allocates and frees nothing; applies to every replica of WANN_DEVICES; a NEGATIVE error for a null index.  The
+ * setting of wann_set_half_rows is kept and counts again once this one is off.
+ * wann_byte_rows: that setting (0 after wann_index_create).  wann_byte_rows_bytes: device bytes of the copy,
+ * n * 64 * ceil(d / 64), or 0 without one.
+ * wann_last_byte_rows: 1 if the beam searches of the last finished batch read the one-byte rows; wann_last_half_rows is then 0
+ * (it keeps its meaning: 1 only when the half rows were read). */
+int wann_rows_u8_exact(const float *rows, int64_t n, int64_t d);
+int wann_set_byte_rows(wann_index *index, int on);
+int wann_byte_rows(const wann_index *index);
+int64_t wann_byte_rows_bytes(const wann_index *index);
+int wann_last_byte_rows(const wann_index *index);
 /* In-process multi-device mode: with WANN_DEVICES=a,b,... in the environment wann_index_create makes the index resident on
  * every listed device (a device may be listed twice) and wann_batch_search -- the host-buffer call, the reference's boundary
  * (src/range_filter_tree.h:62-96: one call parallelises over all queries) -- cuts its batch into contiguous shards, one host

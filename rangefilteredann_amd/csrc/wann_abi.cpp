@@ -11,7 +11,7 @@ struct wann_index::AsyncLane {
   hipStream_t stream = nullptr, side = nullptr;
   hipEvent_t ready = nullptr;  // the caller's inputs (recorded on the caller's stream at submission)
   wann_counters last{};
-  bool last_half = false;  // the lane's last batch searched the half-precision shadow rows (run_batch)
+  int last_store = kStoreRows;  // the row store the lane's last batch searched (run_batch)
   struct Job {
     const float *q, *r;
     int64_t nq, base;
@@ -45,7 +45,7 @@ struct wann_index::AsyncLane {
       try {
         HIP_CHECK(hipSetDevice(I->device));
         HIP_CHECK(hipStreamWaitEvent(stream, ready, 0));
-        last_half = run_batch(*I, ws, side, last, j.q, j.r, j.nq, j.base, j.method.c_str(), j.qp, j.ids, j.dists, stream, j.tune);
+        last_store = run_batch(*I, ws, side, last, j.q, j.r, j.nq, j.base, j.method.c_str(), j.qp, j.ids, j.dists, stream, j.tune);
       } catch (HipError &e) {
         code = WANN_ERR_HIP;
         msg = e.what();
@@ -219,7 +219,7 @@ int wann_batch_search_device(wann_index *I, const void *d_queries, const float *
     // (torch's current stream unless changed), so freshly produced inputs / recycled output blocks are safe
     hipStream_t st = (hipStream_t)hip_stream;
     const Tuning T = snapshot_tuning(*I);  // (WANN_TEST_HOOKS=1 only: tests flip switches between batches)
-    I->last_half_rows = run_batch(*I, I->ws, I->side_stream, I->last, (const float *)d_queries, d_ranges, nq, query_id_base, method, *qp, d_ids, d_dists, st, T);
+    I->note_row_store(run_batch(*I, I->ws, I->side_stream, I->last, (const float *)d_queries, d_ranges, nq, query_id_base, method, *qp, d_ids, d_dists, st, T));
   } catch (HipError &e) {
     return fail(WANN_ERR_HIP, e.what());
   } catch (std::exception &e) {
@@ -234,7 +234,7 @@ int wann_batch_search_device_ids(wann_index *I, const void *d_queries, const flo
   std::lock_guard<std::mutex> lk(I->mu);
   try {
     const Tuning T = snapshot_tuning(*I);
-    I->last_half_rows = run_batch(*I, I->ws, I->side_stream, I->last, (const float *)d_queries, d_ranges, nq, 0, method, *qp, d_ids, d_dists, (hipStream_t)hip_stream, T, d_query_ids);
+    I->note_row_store(run_batch(*I, I->ws, I->side_stream, I->last, (const float *)d_queries, d_ranges, nq, 0, method, *qp, d_ids, d_dists, (hipStream_t)hip_stream, T, d_query_ids));
   } catch (HipError &e) {
     return fail(WANN_ERR_HIP, e.what());
   } catch (std::exception &e) {
@@ -321,7 +321,7 @@ int wann_wait(wann_index *I, int64_t ticket, wann_counters *out) {
   L->cv.wait(ll, [&] { return L->finished >= ticket; });
   if (L->finished != ticket) return fail(WANN_ERR_INVALID, "wann_wait: the ticket's lane has served a later ticket since (wait for ticket t before submitting t + 2)");
   if (out) *out = L->last;
-  I->last_half_rows = L->last_half ? 1 : 0;
+  I->note_row_store(L->last_store);
   if (L->rc != WANN_OK) return fail(L->rc, L->err);
   return WANN_OK;
 }
@@ -400,7 +400,7 @@ int wann_batch_search_allgather(wann_index *I, const void *queries, const float 
             HIP_CHECK(hipMemsetAsync(ids_plane + cnt * k, 0, (size_t)((cap - cnt) * k) * 4, st));
             HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(dist_plane + cnt * k), 0x7f7fffff, (size_t)((cap - cnt) * k), st));
           }
-          T->last_half_rows = run_batch(*T, W, T->side_stream, T->last, W.q_stage.p, W.r_stage.p, cnt, lo, method, *qp, (uint32_t *)ids_plane, (float *)dist_plane, st, tune);
+          T->note_row_store(run_batch(*T, W, T->side_stream, T->last, W.q_stage.p, W.r_stage.p, cnt, lo, method, *qp, (uint32_t *)ids_plane, (float *)dist_plane, st, tune));
         } catch (HipError &e) {
           codes[(size_t)g] = WANN_ERR_HIP;
           errs[(size_t)g] = e.what();
@@ -552,7 +552,7 @@ void search_host_one(wann_index &T, const void *queries, const float *ranges, in
     HIP_CHECK(hipMemcpyAsync(W.q_stage.p, queries, (size_t)nq * d * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(W.r_stage.p, ranges, (size_t)nq * 8, hipMemcpyHostToDevice, st));
   }
-  T.last_half_rows = run_batch(T, W, T.side_stream, T.last, W.q_stage.p, W.r_stage.p, nq, qid_base, method, qp, W.id_stage.p, W.dist_stage.p, st, tune);
+  T.note_row_store(run_batch(T, W, T.side_stream, T.last, W.q_stage.p, W.r_stage.p, nq, qid_base, method, qp, W.id_stage.p, W.dist_stage.p, st, tune));
   if (nq) {
     HIP_CHECK(hipMemcpyAsync(ids, W.id_stage.p, (size_t)nq * qp.k * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(dists, W.dist_stage.p, (size_t)nq * qp.k * 4, hipMemcpyDeviceToHost, st));
@@ -769,6 +769,37 @@ int wann_half_rows(const wann_index *I) {
 
 int64_t wann_half_rows_bytes(const wann_index *I) { return I ? (int64_t)I->d_half.bytes() : -1; }
 int wann_last_half_rows(const wann_index *I) { return I ? I->last_half_rows.load() : 0; }
+
+int wann_rows_u8_exact(const float *rows, int64_t n, int64_t d) {
+  if (n <= 0 || d <= 0) return 1;  // (no value fails the test)
+  if (!rows) return 0;
+  return rows_u8_exact(rows, n, d, d, 0) ? 1 : 0;
+}
+
+int wann_set_byte_rows(wann_index *I, int on) {
+  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
+  // (tune_mu, as wann_set_half_rows: nothing is allocated or freed, a batch in flight keeps its snapshot)
+  int now;
+  {
+    std::lock_guard<std::mutex> lk(I->tune_mu);
+    now = I->byte_rows_on = on != 0 && I->d_bytes.p != nullptr;
+  }
+  for (auto &R : I->replicas) {
+    std::lock_guard<std::mutex> lr(R->tune_mu);
+    R->byte_rows_on = on != 0 && R->d_bytes.p != nullptr;
+  }
+  return now;
+}
+
+int wann_byte_rows(const wann_index *I) {
+  if (!I) return 0;
+  wann_index *M = const_cast<wann_index *>(I);
+  std::lock_guard<std::mutex> lk(M->tune_mu);
+  return I->byte_rows_on ? 1 : 0;
+}
+
+int64_t wann_byte_rows_bytes(const wann_index *I) { return I ? (int64_t)I->d_bytes.bytes() : -1; }
+int wann_last_byte_rows(const wann_index *I) { return I ? I->last_byte_rows.load() : 0; }
 int wann_num_replicas(const wann_index *I) { return I ? 1 + (int)I->replicas.size() : -1; }
 
 int wann_build_cache_shard(int kind, int metric, int dtype, const void *points, int64_t n, int64_t d,

@@ -210,7 +210,7 @@ struct BatchPlan {
   bool exact_dense;     // the dense path takes the exact windows of this batch
   bool verbose_call;    // QueryParams::verbose on an index with graphs: every search is recorded
   bool verbose_route;   // QueryParams::verbose on a tree class: the descent is recorded
-  bool use_half;        // the beam searches read the half-precision shadow rows
+  int store;            // the row store the beam searches read (kStoreRows / kStoreHalf / kStoreBytes)
   const IndexView *SV;  // the view the beam-search launches (k_search) read
   bool spec;            // speculative levels / companion launch
   int64_t sub_slots;    // task slots of the speculative levels and look-aheads
@@ -246,8 +246,11 @@ static BatchPlan plan_batch(const wann_index &I, const Tuning &T, const wann_que
   // The view the beam-search launches (k_search) read: the half-precision shadow rows where the index has them and the switch
   // is on -- the float16 unit's kernels, which score a row in the float32 kernels' arithmetic and order after an exact
   // conversion: same rows, same counters, half the vector bytes.  Routing, the exact scans, the dense path and k_finalize keep I.view.
-  P.use_half = T.half_rows && I.d_half.p != nullptr && H.vamana_leaves;
-  P.SV = P.use_half ? &I.search_view : &I.view;
+  // The one-byte shadow rows (wann_set_byte_rows, opt-in) go before them: the same argument with a quarter of the bytes.
+  P.store = !H.vamana_leaves ? kStoreRows
+          : (T.byte_rows && I.d_bytes.p != nullptr) ? kStoreBytes
+          : (T.half_rows && I.d_half.p != nullptr) ? kStoreHalf : kStoreRows;
+  P.SV = P.store == kStoreBytes ? &I.byte_view : P.store == kStoreHalf ? &I.search_view : &I.view;
   // (wide rows, R > 64: plain in-kernel doubling in the one-wave kernel, no speculative levels / companion launch)
   P.spec = H.vamana_leaves && T.spec && I.view.rs <= 64 && !P.verbose_call;
   P.sub_slots = P.spec ? std::min<int64_t>(nq * (int64_t)P.maxt * 4 + 1024, (int64_t)1 << 26) : 0;
@@ -1000,7 +1003,7 @@ void Batch::copy_counters(const SearchRounds &R, bool tried_dense, float batch_m
 
 // One batch_search call: its stages, in the order the device sees them.
 // W / side / last: the lane of this batch (the index's own members for the blocking calls, an AsyncLane's for the asynchronous one)
-bool run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
+int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
                const int64_t *d_qids) {
   static_assert(kMaxK == 1024, "the message below names the limit");
@@ -1024,7 +1027,7 @@ bool run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   if (P.kind == WANN_KIND_PREFILTER || P.exact_set > 0) dense_lock.lock();
   if (P.exact_set > 0) I.last_exact = wann_exact_window_counters{};
   const Batch B{P, I, W, T, st, side, d_queries, d_ranges, nq, qid_base, qp, d_ids, d_dists, d_qids};
-  if (!B.prepare(last)) return P.use_half;
+  if (!B.prepare(last)) return P.store;
   B.route();
   const bool tried_dense = B.prefilter_dense_gate();
   B.scans();
@@ -1038,7 +1041,7 @@ bool run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &las
   if (W.h_ctr->unsupported)
     throw std::runtime_error(std::to_string((long long)W.h_ctr->unsupported) +
                              " queries need more than " + std::to_string(P.maxt) + " partition searches; raise the task slot bound");
-  return P.use_half;
+  return P.store;
 }
 
 }  // namespace wann_host

@@ -164,6 +164,40 @@ bool rows_fp16_exact(const float *rows, int64_t n, int64_t d, int64_t stride, in
   return exact.load();
 }
 
+// Every value is a uint8 value: (float)(uint8_t)x has the bits of x -- the integers 0 .. 255 with +0.0 only.  The conversion
+// to uint8_t is defined for values in [0, 256) only, so everything else (NaN included: both comparisons fail) is refused
+// first; -0.0 passes the comparisons and fails on its bits.
+bool rows_u8_exact(const float *rows, int64_t n, int64_t d, int64_t stride, int threads) {
+  std::atomic<bool> exact{true};
+  parallel_for(n, threads > 0 ? threads : default_threads(), [&](int64_t r) {
+    if (!exact.load(std::memory_order_relaxed)) return;  // (a row that fails ends the pass: the rows left return at once)
+    const float *p = rows + r * stride;
+    for (int64_t j = 0; j < d; j++) {
+      uint32_t u = 0, v = 1;
+      if (p[j] >= 0.f && p[j] <= 255.f) {
+        const float back = (float)(uint8_t)p[j];
+        memcpy(&u, p + j, 4);
+        memcpy(&v, &back, 4);
+      }
+      if (u != v) {
+        exact.store(false, std::memory_order_relaxed);
+        return;
+      }
+    }
+  });
+  return exact.load();
+}
+
+// The one-byte rows of a point set that passed rows_u8_exact: row r's d values as bytes in their natural order at word
+// r * out_words of `out` (out_words 32-bit words per row, at least d bytes); the caller hands over zeroed rows, so the padding stays zero.
+void pack_u8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64_t out_words, int threads, float *out) {
+  parallel_for(n, threads > 0 ? threads : default_threads(), [&](int64_t r) {
+    const float *src = rows + r * stride;
+    uint8_t *dst = reinterpret_cast<uint8_t *>(out + r * out_words);
+    for (int64_t j = 0; j < d; j++) dst[j] = (uint8_t)src[j];
+  });
+}
+
 // ------------------------------------------------------------------------------------------------
 // numerics (same evaluation order as the kernels; built with -ffp-contract=off)
 // ------------------------------------------------------------------------------------------------

@@ -62,6 +62,12 @@ int default_threads();
 // true if every one of the n x d values (rows `stride` floats apart) is exactly representable in IEEE binary16 and finite:
 // what a float32 index needs to be searched from half rows (wann.h wann_rows_fp16_exact).  threads <= 0: default_threads().
 bool rows_fp16_exact(const float *rows, int64_t n, int64_t d, int64_t stride, int threads);
+// true if every one of the n x d values is an integer 0 .. 255 with the bits of (float)(uint8_t)x (no -0.0): what a float32
+// index needs to be searched from one-byte rows (wann.h wann_rows_u8_exact).  threads <= 0: default_threads().
+bool rows_u8_exact(const float *rows, int64_t n, int64_t d, int64_t stride, int threads);
+// such a point set as one-byte rows: the d values of row r as bytes, natural order, at word r * out_words of the ZEROED buffer
+// `out` (n * out_words 32-bit words; out_words * 4 >= d -- u8_widened_stride_words(d) in wann_device.h)
+void pack_u8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64_t out_words, int threads, float *out);
 
 // metric: bit 0 = inner product, bits 4-5 = element type of the rows behind p / q (0 float32, 1 uint8, 2 int8; float16 point
 // sets are built from their float32 upcast and pass 0)

@@ -44,7 +44,7 @@ struct IndexView {
   int32_t d, stride, rs, maxdeg, metric, kind, nlevels, cutoff, split, vamana_leaves;
   int32_t dtype;  // element type of `points` (wann.h WANN_DTYPE_*): float32 rows, uint8 / int8 rows of d bytes padded to a
                   // multiple of 64, or float16 / bfloat16 rows of d two-byte elements padded to a multiple of 32 -- `stride` counts 32-bit words in every
-                  // case and `points` is addressed in words
+                  // case and `points` is addressed in words.  6 (kRowsU8Widened, below) only in the view of a float32 index's one-byte shadow rows
 };
 
 // two-byte float rows: float16 (3) and bfloat16 (5) share the row pitch and layout rules -- d elements in natural order, zero
@@ -52,9 +52,18 @@ struct IndexView {
 constexpr bool two_byte_rows(int dtype) { return dtype == 3 || dtype == 5; }
 constexpr int64_t two_byte_stride_words(int64_t d) { return ((d * 2 + 63) / 64) * 16; }
 
+// One-byte shadow rows of a float32 index (dtype 6: an INTERNAL view type, never a WANN_DTYPE_* the C ABI accepts): every value
+// is an integer 0 .. 255 stored as a uint8 -- d bytes in natural order, zero padded to a multiple of 64 -- and the beam-search
+// kernels of wann_kernels_w8.hip widen each byte exactly to the float32 it stands for.  Only k_search is ever launched on such a view.
+constexpr int kRowsU8Widened = 6;
+constexpr int64_t u8_widened_stride_words(int64_t d) { return ((d + 63) / 64) * 16; }
+// rows narrower than float32 that are scored as their exact float32 upcast against an fp32 query: the two-byte float rows and
+// the one-byte shadow rows (WANN_WIDENED_ROWS in wann_wave.h is the device side)
+constexpr bool widened_rows(int dtype) { return two_byte_rows(dtype) || dtype == kRowsU8Widened; }
+
 // 32-bit words of a staged query (fp32, zero padded; the LDS the kernels reserve for it): `stride` for float32 / byte rows, the
-// float32 row length (d rounded up to 16) for two-byte float rows -- the same LDS layout as the float32 index (host side of qv_words)
-inline int query_words(const IndexView &v) { return two_byte_rows(v.dtype) ? ((v.d + 15) & ~15) : v.stride; }
+// float32 row length (d rounded up to 16) for widened rows -- the same LDS layout as the float32 index (host side of qv_words)
+inline int query_words(const IndexView &v) { return widened_rows(v.dtype) ? ((v.d + 15) & ~15) : v.stride; }
 
 enum { T_EMPTY = 0, T_GRAPH = 1, T_BRUTE = 2, T_BRUTE_GATHER = 3, T_PARENT = 4 };
 // Task::flags: 1 = heavy (schedule first), 2 = final_beam_multiply forced to 1, 4 = speculative sub-task, 8 = mid priority

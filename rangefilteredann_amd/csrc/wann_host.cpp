@@ -50,6 +50,7 @@ Tuning snapshot_tuning(wann_index &I) {
   if (I.tune.hooks_live) I.tune = Tuning::from_env();
   Tuning t = I.tune;
   t.half_rows = I.half_rows_on && I.d_half.p != nullptr;
+  t.byte_rows = I.byte_rows_on && I.d_bytes.p != nullptr;
   return t;
 }
 
@@ -119,6 +120,26 @@ void upload_index(wann_index &I) {
         for (int64_t j = 0; j < s.d; j++) dst[j] = float_to_half(src[j]);
       });
       I.d_half.upload(rows);
+    }
+  }
+  // ... and where they are all integers 0 .. 255 (SIFT / BIGANN are), a third copy as one-byte rows: a quarter of the float32
+  // bytes, scored by the kernels of wann_kernels_w8.hip.  Beside the half copy, not instead of it: wann_set_byte_rows chooses
+  // between batches without allocating anything, and the copy is off until it is asked for.
+  if (s.dtype == WANN_DTYPE_F32 && H.vamana_leaves && rows_u8_exact(H.pts.data(), s.n, s.d, s.stride, s.threads)) {
+    const int64_t bstride = u8_widened_stride_words(s.d);
+    std::vector<float> rows;
+    try {
+      rows.assign((size_t)s.n * bstride, 0.f);
+      I.d_bytes.ensure(rows.size());
+    } catch (std::bad_alloc &) {
+      I.d_bytes.release();
+    } catch (HipError &) {
+      (void)hipGetLastError();  // (the allocation that failed is not left behind as the next call's error)
+      I.d_bytes.release();
+    }
+    if (I.d_bytes.p) {
+      pack_u8_rows(H.pts.data(), s.n, s.d, s.stride, bstride, s.threads, rows.data());
+      I.d_bytes.upload(rows);
     }
   }
   I.d_labels.upload(H.labels);
@@ -210,7 +231,13 @@ void upload_index(wann_index &I) {
     I.search_view.dtype = WANN_DTYPE_F16;
     I.half_rows_on = true;
   }
-  // (the shadow rows are not in device_bytes, which keeps counting what it always has: wann_half_rows_bytes reports them)
+  I.byte_view = v;
+  if (I.d_bytes.p) {  // (byte_rows_on stays false: the one-byte rows are opt-in, wann_set_byte_rows)
+    I.byte_view.points = I.d_bytes.p;
+    I.byte_view.stride = (int32_t)u8_widened_stride_words(s.d);
+    I.byte_view.dtype = kRowsU8Widened;
+  }
+  // (neither shadow copy is in device_bytes, which keeps counting what it always has: wann_half_rows_bytes / wann_byte_rows_bytes report them)
   I.device_bytes = (int64_t)(I.d_points.bytes() + I.d_labels.bytes() + I.d_decoding.bytes() + I.d_graph.bytes() +
                              I.d_parts.bytes() + I.d_fv.bytes() + I.d_fi.bytes() + I.d_wst_off.bytes());
 }

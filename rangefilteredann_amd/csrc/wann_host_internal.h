@@ -127,6 +127,9 @@ struct Workspace {
 };
 
 
+// the row store a batch's beam searches read: the index's own rows, the half-precision shadow rows, the one-byte shadow rows
+enum { kStoreRows = 0, kStoreHalf = 1, kStoreBytes = 2 };
+
 }  // namespace wann_host
 
 struct wann_index {
@@ -148,6 +151,19 @@ struct wann_index {
   IndexView search_view{};     // `view` with points = d_half, the half stride and dtype = WANN_DTYPE_F16 (valid when d_half.p)
   bool half_rows_on = false;   // wann_set_half_rows (under tune_mu; on when a shadow exists): the next batch searches the shadow
   std::atomic<int> last_half_rows{0};  // the last finished batch (blocking call / ticket waited for) searched the shadow
+  // One-byte shadow rows of a float32 index whose every value is an integer 0 .. 255 (rows_u8_exact) and that has graphs: the
+  // same points as uint8, 64-byte padded, read by the beam-search launches through byte_view (dtype kRowsU8Widened: the
+  // kernels of wann_kernels_w8.hip).  Beside d_half, not instead of it; off until wann_set_byte_rows asks for it, and then it
+  // goes before the half rows.  Empty: no copy (not eligible, or no memory).
+  DevBuf<float> d_bytes;
+  IndexView byte_view{};       // `view` with points = d_bytes, the byte stride and dtype = kRowsU8Widened (valid when d_bytes.p)
+  bool byte_rows_on = false;   // wann_set_byte_rows (under tune_mu; off by default): the next batch searches the one-byte rows
+  std::atomic<int> last_byte_rows{0};  // the last finished batch searched the one-byte rows
+  // which row store a finished batch's beam searches read (run_batch's result)
+  void note_row_store(int store) {
+    last_half_rows = store == wann_host::kStoreHalf ? 1 : 0;
+    last_byte_rows = store == wann_host::kStoreBytes ? 1 : 0;
+  }
   DevBuf<uint32_t> d_decoding;
   DevBuf<int32_t> d_graph, d_fi;
   DevBuf<PartDesc> d_parts;
@@ -221,14 +237,15 @@ struct RoundCfg {
   int table_bits;    // per-slot global seen-filter of 4 << table_bits bytes (0 = none needed)
   int64_t beam_cap;  // per-slot global beam entries (0 = none needed)
 };
-// V: the view the launch's kernel reads (I.view, or I.search_view for a batch that searches the half-precision shadow rows)
+// V: the view the launch's kernel reads (I.view, or I.search_view / I.byte_view for a batch that searches a shadow copy of the rows)
 RoundCfg config_for(const wann_index &I, const IndexView &V, const Tuning &T, int64_t first_beam, int64_t cap, int64_t work_items, bool big_lds = false, bool force_table = false,
                     bool legacy = false, int base_pool = kSearchPoolBytes);
 int lean_pool_bytes(const IndexView &V);
 int method_code(const char *m);
 // W / side / last: the lane of this batch (the index's own members for the blocking calls, an AsyncLane's for the asynchronous one)
-// Returns whether the batch's beam searches read the half-precision shadow rows (T.half_rows on an index with graphs).
-bool run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
+// Returns the row store the batch's beam searches read (kStore*): the one-byte rows if T.byte_rows, else the half rows if
+// T.half_rows, else the index's own rows.
+int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
                const int64_t *d_qids = nullptr);
 void build_pending(wann_index &I, std::vector<HostPart *> &pending);

@@ -24,7 +24,7 @@
 
 namespace wann {
 
-// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip before this body is
+// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip / _w8.hip before this body is
 // included): the search and scan kernels and their launchers live in a per-type namespace; the type-independent
 // kernels (routing, finalisation) and the dispatchers are compiled with the float32 unit only.
 #if WANN_DT == 0
@@ -35,8 +35,10 @@ namespace wann {
 #define WANN_DT_NS dt_i8
 #elif WANN_DT == 3
 #define WANN_DT_NS dt_f16
-#else
+#elif WANN_DT == 5
 #define WANN_DT_NS dt_bf16
+#else
+#define WANN_DT_NS dt_w8  // (the one-byte shadow rows of a float32 index: only its k_search is ever launched)
 #endif
 // The float16 unit's search kernels carry the element type as a third template argument (k_search<METRIC, KIND, 3>): their
 // symbols differ from the float32 / byte-row kernels' in more than the namespace, and per-type tools and tests that select
@@ -46,6 +48,8 @@ namespace wann {
 #define WANN_DT_TPARAM , int ROWS_DT = 3
 #elif WANN_DT == 5  // (the bfloat16 unit likewise)
 #define WANN_DT_TPARAM , int ROWS_DT = 5
+#elif WANN_DT == 6  // (and the one-byte shadow rows' unit)
+#define WANN_DT_TPARAM , int ROWS_DT = 6
 #else
 #define WANN_DT_TPARAM
 #endif
@@ -747,7 +751,9 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
 // --------------------------------------------------------------------------------------------
 // k_brute: exact top-k over rows [a,b) of the sorted order (T_BRUTE) or over the label-argsort
 // positions [a,b) of an unsorted point set (T_BRUTE_GATHER, prefiltering.h:189-194)
+// (not in the unit of the one-byte shadow rows: the exact scans keep the index's own rows)
 // --------------------------------------------------------------------------------------------
+#if WANN_DT != 6
 template <int METRIC>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_brute(BruteArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -859,6 +865,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_brute(BruteArgs A) {
   }
   if (lane == 0 && rows_done) atomicAdd(&A.ctr->brute_rows, rows_done);
 }
+
+#endif  // WANN_DT != 6 (k_brute)
 
 }  // namespace WANN_DT_NS
 
@@ -1626,6 +1634,7 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
   return a.ix.metric == 1 ? launch_search_t<1, 0>(a, grid, block, lds, s) : launch_search_t<0, 0>(a, grid, block, lds, s);
 }
 
+#if WANN_DT != 6
 template <int METRIC>
 static int launch_brute_t(const BruteArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
   auto kern = k_brute<METRIC>;
@@ -1642,6 +1651,7 @@ int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   dim3 grid(blocks), block(64 * kWavesPerBlock);
   return a.ix.metric == 1 ? launch_brute_t<1>(a, grid, block, lds, (hipStream_t)stream) : launch_brute_t<0>(a, grid, block, lds, (hipStream_t)stream);
 }
+#endif  // WANN_DT != 6
 
 }  // namespace WANN_DT_NS
 
@@ -1667,13 +1677,19 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
 int launch_brute(const BruteArgs &a, int blocks, void *stream);
 }
+namespace dt_w8 {  // (a view of one-byte shadow rows goes to the beam search only: no scan is dispatched on it)
+int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
+int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
+}
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
   return a.ix.dtype == 1 ? dt_u8::search_occupancy(a, cfg) : a.ix.dtype == 2 ? dt_i8::search_occupancy(a, cfg)
-       : a.ix.dtype == 3 ? dt_f16::search_occupancy(a, cfg) : a.ix.dtype == 5 ? dt_bf16::search_occupancy(a, cfg) : dt_f32::search_occupancy(a, cfg);
+       : a.ix.dtype == 3 ? dt_f16::search_occupancy(a, cfg) : a.ix.dtype == 5 ? dt_bf16::search_occupancy(a, cfg)
+       : a.ix.dtype == kRowsU8Widened ? dt_w8::search_occupancy(a, cfg) : dt_f32::search_occupancy(a, cfg);
 }
 int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
   return a.ix.dtype == 1 ? dt_u8::launch_search(a, cfg, stream) : a.ix.dtype == 2 ? dt_i8::launch_search(a, cfg, stream)
-       : a.ix.dtype == 3 ? dt_f16::launch_search(a, cfg, stream) : a.ix.dtype == 5 ? dt_bf16::launch_search(a, cfg, stream) : dt_f32::launch_search(a, cfg, stream);
+       : a.ix.dtype == 3 ? dt_f16::launch_search(a, cfg, stream) : a.ix.dtype == 5 ? dt_bf16::launch_search(a, cfg, stream)
+       : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_search(a, cfg, stream) : dt_f32::launch_search(a, cfg, stream);
 }
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   return a.ix.dtype == 1 ? dt_u8::launch_brute(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_brute(a, blocks, stream)

@@ -84,10 +84,13 @@ __device__ __forceinline__ u64 hash64_2(u64 x) {
 // element type of the point rows: one translation unit per type (wann_kernels.hip, _u8, _i8, _f16)
 // --------------------------------------------------------------------------------------------
 #ifndef WANN_DT
-#define WANN_DT 0  // 0 = float32 rows, 1 = uint8, 2 = int8, 3 = float16, 5 = bfloat16 (4 is unassigned, see wann.h)
+#define WANN_DT 0  // 0 = float32 rows, 1 = uint8, 2 = int8, 3 = float16, 5 = bfloat16 (4 is unassigned, see wann.h),
+                   // 6 = the one-byte shadow rows of a float32 index (internal: kRowsU8Widened in wann_device.h)
 #endif
 #define WANN_BYTE_ROWS (WANN_DT == 1 || WANN_DT == 2)
 #define WANN_HALF_ROWS (WANN_DT == 3 || WANN_DT == 5)  // two-byte float rows (two_byte_rows in wann_device.h is the host side)
+// rows narrower than float32, scored as their exact float32 upcast against the fp32 query (widened_rows is the host side)
+#define WANN_WIDENED_ROWS (WANN_HALF_ROWS || WANN_DT == 6)
 
 // A row BLOCK is four consecutive elements e..e+3 of a row (e a multiple of 4): a float4 of a float32 row, 8 bytes of a
 // float16 row.  Float16 rows (WANN_DT = 3) keep the natural element order, padded with zeros to a multiple of 32 halves
@@ -115,6 +118,17 @@ __device__ __forceinline__ float4 b4_to_f4(uint2 w) {
 }
 #define ld_blk(prow, e) (*reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(prow) + (e)))
 #define cvt_blk(w) b4_to_f4(w)
+#elif WANN_DT == 6
+// one-byte shadow rows of a float32 index whose values are all integers 0 .. 255: a block is ONE aligned 32-bit word, bytes
+// e .. e+3 of the row (rows keep the natural element order, zero padded to a multiple of 64 bytes).  Each byte widens UNSIGNED
+// to the float32 it was made from (v_cvt_f32_ubyte0..3: exact), and the float32 arithmetic follows in its own order against the
+// fp32 query in the float32 LDS layout.  A block held across a round trip stays its packed word: a quarter of a float32 block.
+typedef uint32_t rowblk_t;
+__device__ __forceinline__ float4 u4_to_f4(uint32_t w) {
+  return make_float4((float)(w & 0xffu), (float)((w >> 8) & 0xffu), (float)((w >> 16) & 0xffu), (float)(w >> 24));
+}
+#define ld_blk(prow, e) (*reinterpret_cast<const uint32_t *>(reinterpret_cast<const unsigned char *>(prow) + (e)))
+#define cvt_blk(w) u4_to_f4(w)
 #else
 typedef float4 rowblk_t;
 // (no parentheses round `e`: `prow + 8 * b + 4 * h` is the address arithmetic the float32 unit has always compiled)
@@ -122,9 +136,9 @@ typedef float4 rowblk_t;
 #define cvt_blk(w) (w)
 #endif
 // 32-bit words of the staged (fp32, zero padded) query and of the LDS reserved for it: `stride` for float32 / byte rows; for
-// float16 / bfloat16 rows the float32 row length, d rounded up to 16 -- every routine reads the query up to d rounded up to 8, and the
-// LDS layout of a float16 index equals the float32 index's (query_words in wann_device.h is the host side)
-__device__ __forceinline__ int qv_words(const IndexView &ix) { return WANN_HALF_ROWS ? ((ix.d + 15) & ~15) : ix.stride; }
+// widened rows (float16 / bfloat16 / one-byte shadow rows) the float32 row length, d rounded up to 16 -- every routine reads the
+// query up to d rounded up to 8, and the LDS layout of such a view equals the float32 index's (query_words in wann_device.h is the host side)
+__device__ __forceinline__ int qv_words(const IndexView &ix) { return WANN_WIDENED_ROWS ? ((ix.d + 15) & ~15) : ix.stride; }
 
 // --------------------------------------------------------------------------------------------
 // distances in the reference's evaluation order

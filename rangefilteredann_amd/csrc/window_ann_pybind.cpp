@@ -202,6 +202,7 @@ class Index {
     if (rc) raise_last("wait failed");
     py::dict d = counters_dict(c);
     d["half_rows"] = wann_last_half_rows(h_);
+    d["byte_rows"] = wann_last_byte_rows(h_);
     return d;
   }
   // float32 indexes with graphs whose points are all binary16 values: the beam searches read a half-precision copy of the rows
@@ -213,6 +214,15 @@ class Index {
   }
   bool half_rows() const { return wann_half_rows(h_) != 0; }
   int64_t half_rows_bytes() const { return wann_half_rows_bytes(h_); }
+  // ... and whose points are all integers 0 .. 255: the beam searches read a one-byte copy of the rows instead, once asked to
+  // (wann_set_byte_rows, off by default); returns the setting now in force -- False on an index without such a copy
+  bool set_byte_rows(bool on) {
+    const int rc = wann_set_byte_rows(h_, on ? 1 : 0);
+    if (rc < 0) raise_last("set_byte_rows failed");
+    return rc != 0;
+  }
+  bool byte_rows() const { return wann_byte_rows(h_) != 0; }
+  int64_t byte_rows_bytes() const { return wann_byte_rows_bytes(h_); }
 
   // PrefilterIndex only: distinct wide windows on the matrix cores (wann_set_dense_windows); returns the previous setting
   bool set_dense_windows(bool on) {
@@ -257,6 +267,7 @@ class Index {
     wann_get_counters(h_, &c);
     py::dict d = counters_dict(c);
     d["half_rows"] = wann_last_half_rows(h_);  // 1: the last batch's beam searches read the half-precision shadow rows
+    d["byte_rows"] = wann_last_byte_rows(h_);  // 1: they read the one-byte shadow rows (then half_rows is 0)
     return d;
   }
   static py::dict counters_dict(const wann_counters &c) {
@@ -337,6 +348,9 @@ static void common_defs(py::class_<C> &c) {
       .def("set_half_rows", &C::set_half_rows, "on"_a)
       .def("half_rows", &C::half_rows)
       .def("half_rows_bytes", &C::half_rows_bytes)
+      .def("set_byte_rows", &C::set_byte_rows, "on"_a)
+      .def("byte_rows", &C::byte_rows)
+      .def("byte_rows_bytes", &C::byte_rows_bytes)
       .def("max_degree", &C::max_degree)
       .def("num_replicas", &C::num_replicas)
       .def("num_points", &C::num_points)
