@@ -67,8 +67,8 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * of x, which keeps -0.0 and the binary16 subnormals and drops NaN, the infinities and |x| > 65504; SIFT / BIGANN vectors, integers
  * in [0, 255], qualify -- keeps a second copy of its points as half rows (64-byte padded, wann_half_rows_bytes) and its BEAM
  * SEARCHES read that copy through the float16 kernels: the same rows, distance bits and operation counters (see above), half the
- * vector bytes per scored row.  Everything else -- routing, the exact scans, the dense path, the GPU builder, the raw-search
- * hooks, the unfiltered wann_vamana_* API -- reads the float32 rows, which stay where they were.  The property is tested once,
+ * vector bytes per scored row.  Everything else -- routing, the exact scans (unless wann_set_scan_rows is on, below), the dense
+ * path, the GPU builder, the raw-search hooks, the unfiltered wann_vamana_* API -- reads the float32 rows, which stay where they were.  The property is tested once,
  * when the index is created; an index that is not eligible (or found no memory for the copy) has no shadow and behaves as before.
  * wann_set_half_rows switches the use of the copy off and on between batches (on by default where the copy exists).
  * wann_device_bytes does NOT count the copy (it reports what it always has: a float32 index and the float16 index of the same
@@ -84,6 +84,13 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * the half rows if theirs is on, else the float32 rows; everything the half rows leave to the float32 rows stays there.
  * wann_device_bytes does not count this copy either.  6, the type of that internal view, is not a WANN_DTYPE_* value and is
  * refused like any unknown dtype.
+ * EXACT SCANS FROM THE SHADOW ROWS (opt-in).  After wann_set_scan_rows(index, 1) the exact scans of a batch (k_brute: the tiny
+ * windows, the end scans of fenwick / three_split, the scanned queries of wann_set_exact_windows, what the dense path could not
+ * prove) read the copy that the same batch's beam searches read -- the one-byte rows if wann_set_byte_rows is on, else the half
+ * rows if wann_set_half_rows is on, else the index's own rows -- widened exactly and scored in the float32 scan's arithmetic and
+ * order: the same ids, distance bits and operation counters (brute_rows included) with a quarter or half of the row bytes.  OFF
+ * by default.  The dense path (exact-window batches included), routing, the finalisation, the GPU builder and the raw hooks keep
+ * the float32 rows.
  * WANN_DTYPE_BF16 (not a type of the reference): bfloat16 points, rows of uint16_t bit patterns (the top 16 bits of a float32:
  * float32's exponent range, 8 significant bits).  Everything said of WANN_DTYPE_F16 holds with "bfloat16" for "binary16": the
  * same row pitch and layout (natural order, zero padded to 32 elements), the widening -- one shift, exact for every pattern,
@@ -327,6 +334,18 @@ int wann_set_byte_rows(wann_index *index, int on);
 int wann_byte_rows(const wann_index *index);
 int64_t wann_byte_rows_bytes(const wann_index *index);
 int wann_last_byte_rows(const wann_index *index);
+/* Exact scans from the shadow rows (see WANN_DTYPE_*).
+ * wann_set_scan_rows: whether the exact scans of the NEXT batches read the shadow copy that the same batch's beam searches read
+ * (a batch submitted earlier keeps what it was submitted with, the asynchronous lanes included).  Returns the setting now in
+ * force, 0 / 1: asking for 1 on an index that has no shadow copy at all (a PrefilterIndex, the prefilter-leaf tree, points that
+ * are not eligible, byte / float16 / bfloat16 indexes) leaves it at 0 and returns 0.  Allocates and frees nothing; applies to
+ * every replica of WANN_DEVICES; a NEGATIVE error for a null index.
+ * wann_scan_rows: that setting (0 after wann_index_create).
+ * wann_last_scan_rows: which rows the exact-scan launch of the last finished batch read -- 0 the index's own rows, 1 the half
+ * rows, 2 the one-byte rows; 0 when the batch launched no scan. */
+int wann_set_scan_rows(wann_index *index, int on);
+int wann_scan_rows(const wann_index *index);
+int wann_last_scan_rows(const wann_index *index);
 /* In-process multi-device mode: with WANN_DEVICES=a,b,... in the environment wann_index_create makes the index resident on
  * every listed device (a device may be listed twice) and wann_batch_search -- the host-buffer call, the reference's boundary
  * (src/range_filter_tree.h:62-96: one call parallelises over all queries) -- cuts its batch into contiguous shards, one host

@@ -212,6 +212,7 @@ struct BatchPlan {
   bool verbose_route;   // QueryParams::verbose on a tree class: the descent is recorded
   int store;            // the row store the beam searches read (kStoreRows / kStoreHalf / kStoreBytes)
   const IndexView *SV;  // the view the beam-search launches (k_search) read
+  int scan_store;       // the row store the exact scans (k_brute) read: `store` under wann_set_scan_rows, else kStoreRows
   bool spec;            // speculative levels / companion launch
   int64_t sub_slots;    // task slots of the speculative levels and look-aheads
   int32_t big_cap;      // largest beam of the companion launch's searches (0: none)
@@ -245,7 +246,8 @@ static BatchPlan plan_batch(const wann_index &I, const Tuning &T, const wann_que
   P.verbose_route = qp.verbose != 0 && (tree || P.kind == WANN_KIND_SUPER);
   // The view the beam-search launches (k_search) read: the half-precision shadow rows where the index has them and the switch
   // is on -- the float16 unit's kernels, which score a row in the float32 kernels' arithmetic and order after an exact
-  // conversion: same rows, same counters, half the vector bytes.  Routing, the exact scans, the dense path and k_finalize keep I.view.
+  // conversion: same rows, same counters, half the vector bytes.  Routing, the dense path and k_finalize keep I.view; so do the
+  // exact scans unless wann_set_scan_rows is on (scan_store, below).
   // The one-byte shadow rows (wann_set_byte_rows, opt-in) go before them: the same argument with a quarter of the bytes.
   P.store = !H.vamana_leaves ? kStoreRows
           : (T.byte_rows && I.d_bytes.p != nullptr) ? kStoreBytes
@@ -278,6 +280,11 @@ static BatchPlan plan_batch(const wann_index &I, const Tuning &T, const wann_que
   // for both.  Batches of the one-task methods keep the single stream (their scans are the tiny windows' and mostly absent) --
   // unless exact windows are on: those scans and the dense launches in front of them run beside the searches too.
   P.scans_aside = P.may_brute && (P.maxt > 1 || P.exact_limit > 0) && P.sized;
+  // wann_set_scan_rows: k_brute reads the copy the beam searches of this batch read -- the unit of that view scores a row to the
+  // bits of its float32 upcast, so the scans return the same keys.  Only an index with graphs owns a copy, and every scan task
+  // of such an index is T_BRUTE (contiguous rows of the sorted order; k_route emits T_BRUTE_GATHER for the PrefilterIndex alone).
+  // k_exact_rows, the dense path and what it hands back are routed as before; the tasks handed back are scanned from this store.
+  P.scan_store = (T.scan_rows && P.may_brute) ? P.store : kStoreRows;
   return P;
 }
 
@@ -397,6 +404,17 @@ bool Batch::prefilter_dense_gate() const {
   return tried_dense;
 }
 
+// Workgroups of a scan over a shadow view (wann_set_scan_rows) that a CU holds at once; a workgroup puts one wave on each SIMD.
+// By the registers of the compiled kernels, 512 / VGPRs (profiles/scan_rows_kernel_resources.txt): the float16 unit's k_brute on
+// the half rows 160 (squared L2) / 117 (inner product); k_brute_staged on the one-byte rows 148 / 128 -- and there by the LDS of
+// the staged rows too, whichever is fewer.
+static int scan_rows_per_cu(const IndexView &V, int k) {
+  const bool mips = V.metric == 1;
+  if (V.dtype != kRowsU8Widened) return mips ? 4 : 3;
+  const int by_lds = (int)(kLdsPerWorkgroup / brute_staged_lds_bytes(V.stride, query_words(V), k));
+  return std::max(1, std::min(mips ? 4 : 3, by_lds));
+}
+
 // Stage: the exact scans (k_brute, k_exact_rows) and, in front of them, the dense path of a batch with exact windows -- on the
 // batch's stream, or beside the searches on the lane's scan stream (BatchPlan::scans_aside).
 void Batch::scans() const {
@@ -410,7 +428,7 @@ void Batch::scans() const {
   if (P.exact_dense) dense_prefilter(I, T, W, d_queries, nq, P.k, scan_st, P.maxt, true);
   if (!P.may_brute) return;
   BruteArgs ba{};
-  ba.ix = I.view;
+  ba.ix = P.scan_store == kStoreRows ? I.view : *P.SV;
   ba.queries = d_queries;
   ba.tasks = W.tasks.p;
   ba.list = W.list_brute.p;
@@ -436,7 +454,8 @@ void Batch::scans() const {
   }
   // (as many waves as the chip holds at once -- by the registers: two per SIMD for squared-L2 float rows (two 512-byte rows
   // per lane pair in flight), three for inner-product float rows, five for byte rows -- deal the tickets among themselves)
-  const int brute_per_cu = byte_rows(I.view) ? 5 : (I.view.metric == 1 ? 3 : 2);
+  int brute_per_cu = byte_rows(I.view) ? 5 : (I.view.metric == 1 ? 3 : 2);
+  if (P.scan_store != kStoreRows) brute_per_cu = scan_rows_per_cu(ba.ix, P.k);
   int blocks = (int)std::min<int64_t>((int64_t)I.num_cus * brute_per_cu, (nq * std::min(P.maxt, 2) + kWavesPerBlock - 1) / kWavesPerBlock);
   if (launch_brute(ba, blocks, scan_st)) throw HipError(std::string("k_brute: ") + launch_last_error());
   if (P.exact_limit > 0 && launch_exact_rows(ba, nq * std::min(P.maxt, 2), scan_st)) throw HipError(std::string("k_exact_rows: ") + launch_last_error());
@@ -1016,7 +1035,8 @@ int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last
   // The exact scan keeps a wave's query row and its k-entry list in the LDS (brute_lds_bytes_per_wave): rows too long for a
   // CU's 160 KiB are refused here, before anything of the batch is queued (config_for says the same of the beam search).
   if (nq > 0 && P.may_brute) {
-    const int64_t need = brute_lds_bytes(query_words(I.view), P.k);
+    const int64_t need = P.scan_store == kStoreBytes ? brute_staged_lds_bytes(P.SV->stride, query_words(*P.SV), P.k)
+                                                     : brute_lds_bytes(query_words(I.view), P.k);  // (a half view stages the same query words)
     if (need > kLdsPerWorkgroup)
       throw std::runtime_error("exact-scan LDS footprint exceeds 160 KiB: rows of " + std::to_string((long long)I.view.d) + " elements at k = " +
                                std::to_string(P.k) + " need " + std::to_string((long long)need) + " bytes per workgroup, the limit is " +
@@ -1027,7 +1047,7 @@ int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last
   if (P.kind == WANN_KIND_PREFILTER || P.exact_set > 0) dense_lock.lock();
   if (P.exact_set > 0) I.last_exact = wann_exact_window_counters{};
   const Batch B{P, I, W, T, st, side, d_queries, d_ranges, nq, qid_base, qp, d_ids, d_dists, d_qids};
-  if (!B.prepare(last)) return P.store;
+  if (!B.prepare(last)) return P.store;  // (nothing was launched: no scan either)
   B.route();
   const bool tried_dense = B.prefilter_dense_gate();
   B.scans();
@@ -1041,7 +1061,7 @@ int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last
   if (W.h_ctr->unsupported)
     throw std::runtime_error(std::to_string((long long)W.h_ctr->unsupported) +
                              " queries need more than " + std::to_string(P.maxt) + " partition searches; raise the task slot bound");
-  return P.store;
+  return P.store | (P.scan_store << 8);
 }
 
 }  // namespace wann_host

@@ -54,7 +54,7 @@ constexpr int64_t two_byte_stride_words(int64_t d) { return ((d * 2 + 63) / 64) 
 
 // One-byte shadow rows of a float32 index (dtype 6: an INTERNAL view type, never a WANN_DTYPE_* the C ABI accepts): every value
 // is an integer 0 .. 255 stored as a uint8 -- d bytes in natural order, zero padded to a multiple of 64 -- and the beam-search
-// kernels of wann_kernels_w8.hip widen each byte exactly to the float32 it stands for.  Only k_search is ever launched on such a view.
+// kernels of wann_kernels_w8.hip widen each byte exactly to the float32 it stands for.  k_search is launched on such a view, and k_brute under wann_set_scan_rows.
 constexpr int kRowsU8Widened = 6;
 constexpr int64_t u8_widened_stride_words(int64_t d) { return ((d + 63) / 64) * 16; }
 // rows narrower than float32 that are scored as their exact float32 upcast against an fp32 query: the two-byte float rows and
@@ -325,6 +325,7 @@ int launch_gate(const int32_t *resident, int need, void *stream);
 int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
 // workgroups of that launch the runtime expects to be resident per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor); -1 on error
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
+// (a view of a float32 index's one-byte shadow rows, wann_set_scan_rows: the launch is k_brute_staged)
 int launch_brute(const BruteArgs &a, int blocks, void *stream);
 // wann_set_exact_windows: adds the widths of the flagged tasks on k_brute's list to Counters::exact_rows (nq sizes the launch)
 int launch_exact_rows(const BruteArgs &a, int64_t nq, void *stream);
@@ -359,6 +360,42 @@ constexpr int64_t brute_lds_bytes_per_wave(int64_t query_words, int k) {
   return (((query_words * 4 + 15) & ~(int64_t)15) + 64 * 8 + 64 * 4 + 64 * 4 + (int64_t)((k + 1) & ~1) * 8 + 15) & ~(int64_t)15;
 }
 constexpr int64_t brute_lds_bytes(int64_t query_words, int k) { return brute_lds_bytes_per_wave(query_words, k) * kWavesPerBlock; }
+
+// The STAGED row fetch of k_brute_staged (wann_set_scan_rows: the exact scans of a float32 index read its ONE-BYTE shadow rows;
+// the half rows keep the plain fetch).  A pass of a T_BRUTE scan scores `cnt` CONTIGUOUS rows: one span of
+// cnt x pitch bytes (pitch = 4 x stride, a multiple of 64).  The wave copies the span into its LDS with 16-byte loads, lane after
+// lane -- step s of lane l moves bytes [16 (64 s + l), + 16) of the span -- and the lane pairs then read their 4-byte blocks from
+// there.  In the LDS a row is followed by kScanStagePad = 8 bytes, so that the 16 pairs of one ds_read_b32 group (banks modulo
+// 32) start 2 banks apart -- whatever the pitch, since pitch / 4 is a multiple of 16.  scan_fetch is the whole mapping, host and
+// device: the kernel loads and stores by it and scan_rows_sanitize_test.cpp plays it over exact-size buffers (every byte of the
+// span once, none outside, no two chunks on the same LDS bytes).
+struct ScanFetch {
+  int32_t src;  // byte offset into the span (from row r0's first byte)
+  int32_t dst;  // byte offset into the wave's staging area
+  bool valid;   // false: this (lane, step) moves nothing
+};
+constexpr ScanFetch scan_fetch(int lane, int step, int cnt, int pitch, int pad) {
+  const int src = (step * 64 + lane) * 16;
+  return ScanFetch{src, src + (src / pitch) * pad, src < cnt * pitch};
+}
+constexpr int scan_fetch_steps(int cnt, int pitch) { return (cnt * pitch + 1023) / 1024; }
+constexpr int kScanStagePad = 8;
+// Rows a wave stages per pass: 64 where they fit kScanStageBytes (64 rows of up to 256 bytes) and what the workgroup's 160 KiB
+// leave beside brute_lds_bytes_per_wave -- fewer, never none, where they do not (a pass of fewer rows merges the same keys).
+constexpr int kScanStageBytes = 64 * (256 + kScanStagePad);
+constexpr int scan_stage_rows(int pitch, int pad, int64_t query_words, int k) {
+  const int64_t left = (kLdsPerWorkgroup / kWavesPerBlock - brute_lds_bytes_per_wave(query_words, k)) & ~(int64_t)15;
+  const int64_t rows = (left < kScanStageBytes ? left : kScanStageBytes) / (pitch + pad);
+  return rows > 64 ? 64 : rows < 1 ? 1 : (int)rows;
+}
+constexpr int64_t scan_stage_bytes_per_wave(int pitch, int pad, int64_t query_words, int k) {
+  return ((int64_t)scan_stage_rows(pitch, pad, query_words, k) * (pitch + pad) + 15) & ~(int64_t)15;
+}
+// LDS of a k_brute_staged workgroup: what k_brute carves per wave, then the wave's staging area (the kernel, launch_brute and
+// run_batch's 160 KiB refusal use this one function; beyond the limit only when not even one row fits beside the rest)
+constexpr int64_t brute_staged_lds_bytes(int stride_words, int64_t query_words, int k) {
+  return (brute_lds_bytes_per_wave(query_words, k) + scan_stage_bytes_per_wave(stride_words * 4, kScanStagePad, query_words, k)) * kWavesPerBlock;
+}
 
 // Bytes of LDS one wave of k_finalize_multi needs: 64 candidate keys and the merged list of k keys (rounded up to an even
 // count), rounded up to 16 bytes.  No row length in it: 34 816 B a workgroup at k = kMaxK, so launch_finalize never has to

@@ -51,6 +51,7 @@ Tuning snapshot_tuning(wann_index &I) {
   Tuning t = I.tune;
   t.half_rows = I.half_rows_on && I.d_half.p != nullptr;
   t.byte_rows = I.byte_rows_on && I.d_bytes.p != nullptr;
+  t.scan_rows = I.scan_rows_on && (I.d_half.p != nullptr || I.d_bytes.p != nullptr);
   return t;
 }
 

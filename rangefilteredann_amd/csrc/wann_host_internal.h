@@ -159,10 +159,16 @@ struct wann_index {
   IndexView byte_view{};       // `view` with points = d_bytes, the byte stride and dtype = kRowsU8Widened (valid when d_bytes.p)
   bool byte_rows_on = false;   // wann_set_byte_rows (under tune_mu; off by default): the next batch searches the one-byte rows
   std::atomic<int> last_byte_rows{0};  // the last finished batch searched the one-byte rows
-  // which row store a finished batch's beam searches read (run_batch's result)
-  void note_row_store(int store) {
+  // wann_set_scan_rows (under tune_mu; off by default, only ever on where a shadow copy exists): the exact scans of the next
+  // batch read the copy its beam searches read
+  bool scan_rows_on = false;
+  std::atomic<int> last_scan_rows{0};  // the store (kStore*) the k_brute launch of the last finished batch read
+  // which row stores a finished batch read (run_batch's result: the beam searches' store, the scan's in the next byte)
+  void note_row_store(int stores) {
+    const int store = stores & 0xff;
     last_half_rows = store == wann_host::kStoreHalf ? 1 : 0;
     last_byte_rows = store == wann_host::kStoreBytes ? 1 : 0;
+    last_scan_rows = stores >> 8;
   }
   DevBuf<uint32_t> d_decoding;
   DevBuf<int32_t> d_graph, d_fi;
@@ -244,7 +250,8 @@ int lean_pool_bytes(const IndexView &V);
 int method_code(const char *m);
 // W / side / last: the lane of this batch (the index's own members for the blocking calls, an AsyncLane's for the asynchronous one)
 // Returns the row store the batch's beam searches read (kStore*): the one-byte rows if T.byte_rows, else the half rows if
-// T.half_rows, else the index's own rows.
+// T.half_rows, else the index's own rows -- and, shifted left by 8, the store its k_brute launch read (the same one if
+// T.scan_rows, else kStoreRows; kStoreRows too for a batch that launched no scan).
 int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
                const int64_t *d_qids = nullptr);

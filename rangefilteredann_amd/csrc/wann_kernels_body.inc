@@ -38,7 +38,7 @@ namespace wann {
 #elif WANN_DT == 5
 #define WANN_DT_NS dt_bf16
 #else
-#define WANN_DT_NS dt_w8  // (the one-byte shadow rows of a float32 index: only its k_search is ever launched)
+#define WANN_DT_NS dt_w8  // (the one-byte shadow rows of a float32 index: its k_search and, under wann_set_scan_rows, its scan)
 #endif
 // The float16 unit's search kernels carry the element type as a third template argument (k_search<METRIC, KIND, 3>): their
 // symbols differ from the float32 / byte-row kernels' in more than the namespace, and per-type tools and tests that select
@@ -751,122 +751,28 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
 // --------------------------------------------------------------------------------------------
 // k_brute: exact top-k over rows [a,b) of the sorted order (T_BRUTE) or over the label-argsort
 // positions [a,b) of an unsorted point set (T_BRUTE_GATHER, prefiltering.h:189-194)
-// (not in the unit of the one-byte shadow rows: the exact scans keep the index's own rows)
+// The unit of the one-byte shadow rows and the float16 unit serve the shadow views of a float32 index under wann_set_scan_rows:
+// the half view takes the float16 unit's k_brute as it is.
+// k_brute_staged (the one-byte unit): the rows of a pass -- contiguous in a T_BRUTE task -- reach the lane pairs through the
+// LDS: scan_fetch (wann_device.h) copies the span with 16-byte loads, and wave_distances scores a view of the staging area, the
+// same routines on the same blocks in the same order.  (On the half view the same fetch lost to the plain one: DESIGN.md 3.4.)
 // --------------------------------------------------------------------------------------------
-#if WANN_DT != 6
+#define WANN_SCAN_STAGED (WANN_DT == 6)
+#if !WANN_SCAN_STAGED
 template <int METRIC>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_brute(BruteArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const IndexView &ix = A.ix;
-  const int lane = lane_id();
-  const int wib = threadIdx.x >> 6;
-  const int K = A.k;
-  const int per_wave = (int)brute_lds_bytes_per_wave(qv_words(ix), K);
-  unsigned char *base = smem + (size_t)wib * per_wave;
-  float *qv = reinterpret_cast<float *>(base);
-  int off = (qv_words(ix) * 4 + 15) & ~15;
-  u64 *cand_key = reinterpret_cast<u64 *>(base + off);
-  off += 64 * 8;
-  int32_t *cand_id = reinterpret_cast<int32_t *>(base + off);
-  off += 64 * 4;
-  float *cand_dist = reinterpret_cast<float *>(base + off);
-  off += 64 * 4;
-  u64 *top = reinterpret_cast<u64 *>(base + off);
-  const int total = *A.list_count;
-  if (total == 0) return;  // (the list is sized on the device; an empty one must not cost a ticket per wave)
-  const int step = (METRIC == 1) ? 64 : 64;
-  // scans are short and uniform: a wave takes four tickets at a time and reports its row count once (ten thousand
-  // same-address atomics per batch were most of a tiny-window batch)
-  // A short list (a few queries, or the handful the dense path could not prove) would leave the chip to `total` waves,
-  // each walking its whole window alone: such scans are cut into S slices, one wave per slice; the slice that finishes
-  // last merges the others' partial results (they are in memory; a counter per task tells who is last).
-  int S = 1, lgS = 0;
-  if (A.part_key) {
-    const int64_t waves = (int64_t)gridDim.x * kWavesPerBlock, kpad = (K + 1) & ~1;
-    while (S < 64 && (int64_t)total * S * 4 <= waves && (int64_t)total * S * 2 * kpad <= A.part_cap && (int64_t)total * S * 2 <= A.part_slots) {
-      S <<= 1;
-      lgS++;
-    }
-  }
-  const int ntickets = total << lgS;
-  // Tickets are dealt, not drawn: wave w takes tickets w, w + W, w + 2 W, ... (W = the waves of the launch, sized to what the
-  // chip holds at once).  Scans of one batch are about equally long, and a few long ones are cut into slices above; drawing
-  // tickets from a counter cost ten thousand same-address atomics per tiny-window batch, and drawing four at a time (round 1)
-  // left a 10 000-query batch to 2 500 waves of four scans in a row.
-  const int nwaves = (int)gridDim.x * kWavesPerBlock;
-  unsigned long long rows_done = 0;
-
-  for (int t = (int)blockIdx.x * kWavesPerBlock + wib; t < ntickets; t += nwaves) {
-    const int li = t >> lgS, part = t & (S - 1);
-    const int ti = A.list[li];
-    const Task task = A.tasks[ti];
-    const int64_t qrow = task.query;
-    for (int i = lane; i < qv_words(ix); i += 64) qv[i] = stage_query_word(A.queries, qrow, i, ix.d);
-    WAVE_SYNC();
-    int64_t ra = task.a, rb = task.b;
-    if (S > 1) {
-      const int64_t len = (((task.b - task.a + S - 1) >> lgS) + 63) & ~(int64_t)63;
-      ra = task.a + part * len;
-      rb = (ra + len < task.b) ? ra + len : task.b;
-    }
-    int m = 0;
-    for (int64_t r0 = ra; r0 < rb; r0 += step) {
-      int cnt = (int)((rb - r0) < step ? (rb - r0) : step);
-      int64_t row = r0 + lane;
-      int rid = 0;
-      if (lane < cnt) rid = (task.mode == T_BRUTE_GATHER) ? ix.fi_sorted[row] : (int)row;
-      cand_id[lane] = rid;
-      WAVE_SYNC();
-      float dist = wave_distances<METRIC, true, true>(ix, cand_id, cand_dist, qv, cnt, 0);
-      u64 key = ((u64)fkey(dist) << 32) | ((u64)(uint32_t)rid << 1);
-      bool pass = lane < cnt;
-      if (m >= K) pass = pass && ((key | 1ull) < (top[K - 1] | 1ull));
-      int p0;
-      m = wave_merge(top, m, K, pass, key, cand_key, &p0);
-    }
-    rows_done += (unsigned long long)(rb > ra ? rb - ra : 0);
-    bool last = true;
-    if (S > 1) {
-      const size_t kpad = (size_t)((K + 1) & ~1);
-      u64 *mine = A.part_key + ((size_t)li * S + part) * kpad;
-      for (int x = lane; x < m; x += 64) mine[x] = top[x];
-      if (lane == 0) A.part_cnt[li * S + part] = m;
-      __threadfence();
-      int old = 0;
-      if (lane == 0) old = atomicAdd(&A.part_done[li], 1);
-      last = __builtin_amdgcn_readfirstlane(old) == S - 1;
-      if (last) {
-        __threadfence();
-        // the other slices' lists, 64 slots at a time (a slot = (slice, place); most lists are short)
-        const u64 *all = A.part_key + (size_t)li * S * kpad;
-        for (int x0 = 0; x0 < S * (int)kpad; x0 += 64) {
-          const int x = x0 + lane, p = x / (int)kpad, off = x - p * (int)kpad;
-          bool pass = p < S && p != part;
-          if (pass) pass = off < __hip_atomic_load(&A.part_cnt[li * S + p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          u64 key = 0;
-          if (pass) key = __hip_atomic_load(&all[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (m >= K) pass = pass && ((key | 1ull) < (top[K - 1] | 1ull));
-          if (ballot64(pass)) {
-            int p0;
-            m = wave_merge(top, m, K, pass, key, cand_key, &p0);
-          }
-        }
-        if (lane == 0) A.part_done[li] = 0;  // ready for the next batch
-      }
-    }
-    if (last) {
-      for (int x = lane; x < m; x += 64) {
-        u64 e = top[x];
-        A.out_key[(size_t)ti * K + x] = (e & 0xffffffff00000000ull) | (uint32_t)((uint32_t)e >> 1);
-      }
-      if (lane == 0) A.out_cnt[ti] = m;
-    }
-    WAVE_SYNC();
-  }
-  if (lane == 0 && rows_done) atomicAdd(&A.ctr->brute_rows, rows_done);
+#define WANN_BRUTE_STAGED 0
+#include "wann_brute_body.inc"
+#undef WANN_BRUTE_STAGED
 }
-
-#endif  // WANN_DT != 6 (k_brute)
+#else
+template <int METRIC>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_brute_staged(BruteArgs A) {
+#define WANN_BRUTE_STAGED 1
+#include "wann_brute_body.inc"
+#undef WANN_BRUTE_STAGED
+}
+#endif
 
 }  // namespace WANN_DT_NS
 
@@ -1634,10 +1540,13 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
   return a.ix.metric == 1 ? launch_search_t<1, 0>(a, grid, block, lds, s) : launch_search_t<0, 0>(a, grid, block, lds, s);
 }
 
-#if WANN_DT != 6
 template <int METRIC>
 static int launch_brute_t(const BruteArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+#if WANN_SCAN_STAGED
+  auto kern = k_brute_staged<METRIC>;  // (the one scan kernel of this unit)
+#else
   auto kern = k_brute<METRIC>;
+#endif
   if (lds > (size_t)kLdsNoAttribute)
     if (check(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))) return 1;
   hipLaunchKernelGGL(kern, grid, block, lds, s, a);
@@ -1647,11 +1556,14 @@ static int launch_brute_t(const BruteArgs &a, dim3 grid, dim3 block, size_t lds,
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   if (blocks <= 0) return 0;
   // (long rows or a wide k: more than a launch gets unasked -- run_batch has refused what exceeds kLdsPerWorkgroup)
+#if WANN_SCAN_STAGED
+  const size_t lds = (size_t)brute_staged_lds_bytes(a.ix.stride, query_words(a.ix), a.k);
+#else
   const size_t lds = (size_t)brute_lds_bytes(query_words(a.ix), a.k);
+#endif
   dim3 grid(blocks), block(64 * kWavesPerBlock);
   return a.ix.metric == 1 ? launch_brute_t<1>(a, grid, block, lds, (hipStream_t)stream) : launch_brute_t<0>(a, grid, block, lds, (hipStream_t)stream);
 }
-#endif  // WANN_DT != 6
 
 }  // namespace WANN_DT_NS
 
@@ -1677,9 +1589,10 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
 int launch_brute(const BruteArgs &a, int blocks, void *stream);
 }
-namespace dt_w8 {  // (a view of one-byte shadow rows goes to the beam search only: no scan is dispatched on it)
+namespace dt_w8 {  // (a view of one-byte shadow rows: the beam search, and the exact scan under wann_set_scan_rows)
 int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
+int launch_brute(const BruteArgs &a, int blocks, void *stream);
 }
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
   return a.ix.dtype == 1 ? dt_u8::search_occupancy(a, cfg) : a.ix.dtype == 2 ? dt_i8::search_occupancy(a, cfg)
@@ -1693,7 +1606,8 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
 }
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   return a.ix.dtype == 1 ? dt_u8::launch_brute(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_brute(a, blocks, stream)
-       : a.ix.dtype == 3 ? dt_f16::launch_brute(a, blocks, stream) : a.ix.dtype == 5 ? dt_bf16::launch_brute(a, blocks, stream) : dt_f32::launch_brute(a, blocks, stream);
+       : a.ix.dtype == 3 ? dt_f16::launch_brute(a, blocks, stream) : a.ix.dtype == 5 ? dt_bf16::launch_brute(a, blocks, stream)
+       : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_brute(a, blocks, stream) : dt_f32::launch_brute(a, blocks, stream);
 }
 
 int launch_finalize(const FinalizeArgs &a, void *stream) {

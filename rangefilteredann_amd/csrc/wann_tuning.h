@@ -51,6 +51,7 @@ struct Tuning {
   // not from the environment: the index's wann_set_half_rows state at the moment of the call (snapshot_tuning fills it in)
   bool half_rows = false;       // this batch's beam searches read the index's half-precision shadow rows
   bool byte_rows = false;       // wann_set_byte_rows likewise: they read the one-byte shadow rows (which go before the half rows)
+  bool scan_rows = false;       // wann_set_scan_rows: this batch's exact scans (k_brute) read the shadow copy its beam searches read
 
   static bool on(const char *name) {
     const char *v = getenv(name);

@@ -203,6 +203,7 @@ class Index {
     py::dict d = counters_dict(c);
     d["half_rows"] = wann_last_half_rows(h_);
     d["byte_rows"] = wann_last_byte_rows(h_);
+    d["scan_rows"] = wann_last_scan_rows(h_);
     return d;
   }
   // float32 indexes with graphs whose points are all binary16 values: the beam searches read a half-precision copy of the rows
@@ -223,6 +224,14 @@ class Index {
   }
   bool byte_rows() const { return wann_byte_rows(h_) != 0; }
   int64_t byte_rows_bytes() const { return wann_byte_rows_bytes(h_); }
+  // the exact scans read the shadow copy the beam searches read (wann_set_scan_rows, off by default); returns the setting now
+  // in force -- False on an index without a shadow copy
+  bool set_scan_rows(bool on) {
+    const int rc = wann_set_scan_rows(h_, on ? 1 : 0);
+    if (rc < 0) raise_last("set_scan_rows failed");
+    return rc != 0;
+  }
+  bool scan_rows() const { return wann_scan_rows(h_) != 0; }
 
   // PrefilterIndex only: distinct wide windows on the matrix cores (wann_set_dense_windows); returns the previous setting
   bool set_dense_windows(bool on) {
@@ -268,6 +277,7 @@ class Index {
     py::dict d = counters_dict(c);
     d["half_rows"] = wann_last_half_rows(h_);  // 1: the last batch's beam searches read the half-precision shadow rows
     d["byte_rows"] = wann_last_byte_rows(h_);  // 1: they read the one-byte shadow rows (then half_rows is 0)
+    d["scan_rows"] = wann_last_scan_rows(h_);  // the rows its k_brute launch read: 0 the index's own, 1 the half rows, 2 the one-byte rows
     return d;
   }
   static py::dict counters_dict(const wann_counters &c) {
@@ -351,6 +361,8 @@ static void common_defs(py::class_<C> &c) {
       .def("set_byte_rows", &C::set_byte_rows, "on"_a)
       .def("byte_rows", &C::byte_rows)
       .def("byte_rows_bytes", &C::byte_rows_bytes)
+      .def("set_scan_rows", &C::set_scan_rows, "on"_a)
+      .def("scan_rows", &C::scan_rows)
       .def("max_degree", &C::max_degree)
       .def("num_replicas", &C::num_replicas)
       .def("num_points", &C::num_points)
