@@ -76,7 +76,7 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * ONE-BYTE SHADOW ROWS of a float32 index (opt-in).  Where ALL n x d values of such an index are moreover integers 0 .. 255 --
  * wann_rows_u8_exact: (float)(uint8_t)x has the bits of x, so +0.0 only; -0.0, negatives, fractions, 256 and above, NaN and the
  * infinities are refused; SIFT / BIGANN vectors qualify, signed [-128, 127] sets do not -- the index keeps a THIRD copy of its
- * points as uint8 rows (natural order, zero padded to a multiple of 64 bytes: wann_byte_rows_bytes, a quarter of the float32
+ * points as uint8 rows (zero padded to a multiple of 64 bytes, elements interleaved inside groups of 32 -- wann_byte_row_position: wann_byte_rows_bytes, a quarter of the float32
  * bytes) beside the float32 rows and the half rows.  After wann_set_byte_rows(index, 1) the BEAM SEARCHES read that copy: each
  * byte is widened to the float32 it was made from and scored against the caller's float32 query in the float32 kernels'
  * arithmetic and order -- the same rows, distance bits and operation counters, queries of any float32 value.  (This is not the
@@ -328,8 +328,14 @@ int wann_last_half_rows(const wann_index *index);
  * wann_byte_rows: that setting (0 after wann_index_create).  wann_byte_rows_bytes: device bytes of the copy,
  * n * 64 * ceil(d / 64), or 0 without one.
  * wann_last_byte_rows: 1 if the beam searches of the last finished batch read the one-byte rows; wann_last_half_rows is then 0
- * (it keeps its meaning: 1 only when the half rows were read). */
+ * (it keeps its meaning: 1 only when the half rows were read).
+ * wann_byte_row_position: the LAYOUT of the device copy, as a pure function (no device, no index): the byte position inside a
+ * one-byte shadow row at which element `element` of the row is stored,
+ *     32 (e >> 5) + 16 ((e >> 2) & 1) + 4 ((e >> 3) & 3) + (e & 3)
+ * -- a permutation inside every aligned group of 32 elements that lets a lane of the search kernels fetch four of its 4-element
+ * blocks with one 16-byte load; -1 for a negative argument.  The row pitch and wann_byte_rows_bytes do not depend on it. */
 int wann_rows_u8_exact(const float *rows, int64_t n, int64_t d);
+int64_t wann_byte_row_position(int64_t element);
 int wann_set_byte_rows(wann_index *index, int on);
 int wann_byte_rows(const wann_index *index);
 int64_t wann_byte_rows_bytes(const wann_index *index);

@@ -776,6 +776,8 @@ int wann_rows_u8_exact(const float *rows, int64_t n, int64_t d) {
   return rows_u8_exact(rows, n, d, d, 0) ? 1 : 0;
 }
 
+int64_t wann_byte_row_position(int64_t element) { return element < 0 ? -1 : u8_row_position(element); }
+
 int wann_set_byte_rows(wann_index *I, int on) {
   if (!I) return -fail(WANN_ERR_INVALID, "null argument");
   // (tune_mu, as wann_set_half_rows: nothing is allocated or freed, a batch in flight keeps its snapshot)

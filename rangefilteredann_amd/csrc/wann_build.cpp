@@ -10,6 +10,7 @@
 // whenever no two candidates of a prune / neighbour sort are exactly equidistant (with such ties
 // the reference's order is whatever libstdc++'s std::sort leaves; ours is by id).
 #include "wann_build.h"
+#include "wann_device.h"
 #include "wann_bf16.h"
 #include "wann_half.h"
 
@@ -195,6 +196,20 @@ void pack_u8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64
     const float *src = rows + r * stride;
     uint8_t *dst = reinterpret_cast<uint8_t *>(out + r * out_words);
     for (int64_t j = 0; j < d; j++) dst[j] = (uint8_t)src[j];
+  });
+}
+
+// The packed rows in the layout the device copy has (u8_row_position, wann_device.h), in place: a permutation of the bytes of
+// every aligned group of 32, padding included -- a row is `words` 32-bit words, a whole number of groups.
+void interleave_u8_rows(float *rows, int64_t n, int64_t words, int threads) {
+  if (words <= 0 || words % 8 != 0) throw std::runtime_error("interleave_u8_rows: a row is a whole number of 32-byte groups");
+  parallel_for(n, threads > 0 ? threads : default_threads(), [&](int64_t r) {
+    uint8_t *row = reinterpret_cast<uint8_t *>(rows + r * words);
+    for (int64_t g = 0; g < words * 4; g += 32) {
+      uint8_t t[32];
+      for (int e = 0; e < 32; e++) t[u8_row_position(e)] = row[g + e];
+      memcpy(row + g, t, 32);
+    }
   });
 }
 

@@ -68,6 +68,9 @@ bool rows_u8_exact(const float *rows, int64_t n, int64_t d, int64_t stride, int 
 // such a point set as one-byte rows: the d values of row r as bytes, natural order, at word r * out_words of the ZEROED buffer
 // `out` (n * out_words 32-bit words; out_words * 4 >= d -- u8_widened_stride_words(d) in wann_device.h)
 void pack_u8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64_t out_words, int threads, float *out);
+// packed rows (natural order) into the device copy's layout, in place: the byte at position e of a row moves to position
+// u8_row_position(e) (wann_device.h: a permutation inside every aligned 32 bytes).  `words` 32-bit words per row, a multiple of 8.
+void interleave_u8_rows(float *rows, int64_t n, int64_t words, int threads);
 
 // metric: bit 0 = inner product, bits 4-5 = element type of the rows behind p / q (0 float32, 1 uint8, 2 int8; float16 point
 // sets are built from their float32 upcast and pass 0)

@@ -53,10 +53,18 @@ constexpr bool two_byte_rows(int dtype) { return dtype == 3 || dtype == 5; }
 constexpr int64_t two_byte_stride_words(int64_t d) { return ((d * 2 + 63) / 64) * 16; }
 
 // One-byte shadow rows of a float32 index (dtype 6: an INTERNAL view type, never a WANN_DTYPE_* the C ABI accepts): every value
-// is an integer 0 .. 255 stored as a uint8 -- d bytes in natural order, zero padded to a multiple of 64 -- and the beam-search
+// is an integer 0 .. 255 stored as a uint8 -- d bytes, zero padded to a multiple of 64 -- and the beam-search
 // kernels of wann_kernels_w8.hip widen each byte exactly to the float32 it stands for.  k_search is launched on such a view, and k_brute under wann_set_scan_rows.
 constexpr int kRowsU8Widened = 6;
 constexpr int64_t u8_widened_stride_words(int64_t d) { return ((d + 63) / 64) * 16; }
+// THE LAYOUT of the device copy (wann_index::d_bytes, byte_view), stated once: a row keeps its pitch, and inside every aligned
+// group of 32 elements the bytes are permuted -- element e of a row sits at byte u8_row_position(e) of it.  A row BLOCK is four
+// consecutive elements (wann_wave.h); lane h of a lane pair owns the blocks 8 b + 4 h, and for b = 4 c .. 4 c + 3 those four
+// blocks are the 16 contiguous bytes at 32 c + 16 h: one 16-byte load per lane brings four blocks (a QUAD), a lane pair covers 32
+// contiguous bytes per load instruction.  The padded row is a whole number of quads and its padding is zero, so a whole quad
+// may always be loaded.  pack_u8_rows (wann_build.h) writes the natural order, interleave_u8_rows turns it into this one
+// before the upload; wann_byte_row_position (wann.h) is this function.
+constexpr int64_t u8_row_position(int64_t e) { return 32 * (e >> 5) + 16 * ((e >> 2) & 1) + 4 * ((e >> 3) & 3) + (e & 3); }
 // rows narrower than float32 that are scored as their exact float32 upcast against an fp32 query: the two-byte float rows and
 // the one-byte shadow rows (WANN_WIDENED_ROWS in wann_wave.h is the device side)
 constexpr bool widened_rows(int dtype) { return two_byte_rows(dtype) || dtype == kRowsU8Widened; }

@@ -140,6 +140,7 @@ void upload_index(wann_index &I) {
     }
     if (I.d_bytes.p) {
       pack_u8_rows(H.pts.data(), s.n, s.d, s.stride, bstride, s.threads, rows.data());
+      interleave_u8_rows(rows.data(), s.n, bstride, s.threads);  // (the copy's layout: u8_row_position, wann_device.h)
       I.d_bytes.upload(rows);
     }
   }

@@ -119,15 +119,26 @@ __device__ __forceinline__ float4 b4_to_f4(uint2 w) {
 #define ld_blk(prow, e) (*reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(prow) + (e)))
 #define cvt_blk(w) b4_to_f4(w)
 #elif WANN_DT == 6
-// one-byte shadow rows of a float32 index whose values are all integers 0 .. 255: a block is ONE aligned 32-bit word, bytes
-// e .. e+3 of the row (rows keep the natural element order, zero padded to a multiple of 64 bytes).  Each byte widens UNSIGNED
+// one-byte shadow rows of a float32 index whose values are all integers 0 .. 255: a block is ONE aligned 32-bit word, the
+// elements e .. e+3 of the row (rows zero padded to a multiple of 64 bytes).  Each byte widens UNSIGNED
 // to the float32 it was made from (v_cvt_f32_ubyte0..3: exact), and the float32 arithmetic follows in its own order against the
 // fp32 query in the float32 LDS layout.  A block held across a round trip stays its packed word: a quarter of a float32 block.
+// The rows are INTERLEAVED (u8_row_position, wann_device.h): the blocks 8 b + 4 h of lane h, b = 4 c .. 4 c + 3, are the 16
+// contiguous bytes at 32 c + 16 h of the row -- a QUAD, one 16-byte load (ld_quad); quad_blk(q, i) is block b = 4 c + i of it.
+// Every routine of this unit fetches quads (in quad order) and consumes blocks in the float32 routines' order; a block at or
+// beyond the row's block count is never consumed (the quad's padding is zero, but the staged query ends with the row).  In the
+// run-time routines `i` is a compile-time constant of an unrolled loop, and the one last block of an odd count is a select
+// between the four words (never a register index).  A quad is typed with 8-byte alignment: rows in HBM start on multiples
+// of 64 (one global_load_dwordx4), rows staged in the LDS (k_brute_staged) on multiples of 8 (two 8-byte reads).  (The unit has
+// no ld_blk: a single block's address would follow the natural order, and no routine fetches single blocks any more.)
 typedef uint32_t rowblk_t;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 rowquad_t __attribute__((aligned(8)));
 __device__ __forceinline__ float4 u4_to_f4(uint32_t w) {
   return make_float4((float)(w & 0xffu), (float)((w >> 8) & 0xffu), (float)((w >> 16) & 0xffu), (float)(w >> 24));
 }
-#define ld_blk(prow, e) (*reinterpret_cast<const uint32_t *>(reinterpret_cast<const unsigned char *>(prow) + (e)))
+#define ld_quad(prow, c, h) (*reinterpret_cast<const rowquad_t *>(reinterpret_cast<const unsigned char *>(prow) + 32 * (c) + 16 * (h)))
+__device__ __forceinline__ uint32_t quad_blk(const u32x4 &q, int i) { return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w; }
 #define cvt_blk(w) u4_to_f4(w)
 #else
 typedef float4 rowblk_t;
@@ -150,6 +161,45 @@ template <int NB>
 __device__ __forceinline__ float l2_pair(const float *__restrict__ prow, const float *qv, int D8,
                                          int h, bool active) {
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#if WANN_DT == 6
+  if (active) {
+    const int nfull = D8 & ~1;  // the blocks 0 .. nfull - 1 in index order, after the last block of an odd count
+    if (D8 & 1) {
+      const int b = D8 - 1;
+      const u32x4 last = ld_quad(prow, b >> 2, h);
+      const uint32_t w = quad_blk(last, b & 3);  // (wave-uniform selects)
+      float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
+      float t;
+      t = cvt_blk(w).x - q.x; a0 = fmaf(t, t, a0);
+      t = cvt_blk(w).y - q.y; a1 = fmaf(t, t, a1);
+      t = cvt_blk(w).z - q.z; a2 = fmaf(t, t, a2);
+      t = cvt_blk(w).w - q.w; a3 = fmaf(t, t, a3);
+    }
+    constexpr int NQ = NB / 4;  // quads in flight
+    for (int c0 = 0; 4 * c0 < nfull; c0 += NQ) {
+      u32x4 buf[NQ];
+#pragma unroll
+      for (int j = 0; j < NQ; j++)
+        if (4 * (c0 + j) < nfull) buf[j] = ld_quad(prow, c0 + j, h);
+#pragma unroll
+      for (int j = 0; j < NQ; j++) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int b = 4 * (c0 + j) + i;
+          if (b < nfull) {
+            float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
+            const uint32_t w = quad_blk(buf[j], i);
+            float t;
+            t = cvt_blk(w).x - q.x; a0 = fmaf(t, t, a0);
+            t = cvt_blk(w).y - q.y; a1 = fmaf(t, t, a1);
+            t = cvt_blk(w).z - q.z; a2 = fmaf(t, t, a2);
+            t = cvt_blk(w).w - q.w; a3 = fmaf(t, t, a3);
+          }
+        }
+      }
+    }
+  }
+#else
   if (active) {
     const bool odd = D8 & 1;
     for (int i0 = 0; i0 < D8; i0 += NB) {
@@ -177,6 +227,7 @@ __device__ __forceinline__ float l2_pair(const float *__restrict__ prow, const f
       }
     }
   }
+#endif
   float s = ((a0 + a1) + a2) + a3;          // even lane: ((l0+l1)+l2)+l3
   float other = __shfl_xor(s, 1);           // odd lane receives the even lane's partial
   return (((other + a0) + a1) + a2) + a3;   // odd lane: ((((s+l4)+l5)+l6)+l7)
@@ -202,6 +253,18 @@ __device__ __forceinline__ float l2_pair_ct(const float *__restrict__ prow, cons
   (void)active;
   constexpr bool odd = D8C & 1;
   f32x2 alo = {0.f, 0.f}, ahi = {0.f, 0.f};
+#if WANN_DT == 6
+  constexpr int NQ = (D8C + 3) / 4;  // the loads in quad order, the blocks consumed in the order below
+  u32x4 buf[NQ];
+#pragma unroll
+  for (int c = 0; c < NQ; c++) buf[c] = ld_quad(prow, c, h);
+#pragma unroll
+  for (int i = 0; i < D8C; i++) {
+    const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
+    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
+    sq_acc(alo, ahi, cvt_blk(quad_blk(buf[b >> 2], b & 3)), q);
+  }
+#else
   rowblk_t buf[D8C];
 #pragma unroll
   for (int i = 0; i < D8C; i++) {
@@ -214,6 +277,7 @@ __device__ __forceinline__ float l2_pair_ct(const float *__restrict__ prow, cons
     const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
     sq_acc(alo, ahi, cvt_blk(buf[i]), q);
   }
+#endif
   float s = ((alo.x + alo.y) + ahi.x) + ahi.y;
   float other = __shfl_xor(s, 1);
   return (((other + alo.x) + alo.y) + ahi.x) + ahi.y;
@@ -225,6 +289,22 @@ template <int D8C>
 __device__ __forceinline__ void l2_pair2_ct(const float *__restrict__ prow0, const float *__restrict__ prow1,
                                             const float *qv, int h, float &d0, float &d1) {
   constexpr bool odd = D8C & 1;
+#if WANN_DT == 6
+  constexpr int NQ = (D8C + 3) / 4;
+  u32x4 b0[NQ], b1[NQ];
+#pragma unroll
+  for (int c = 0; c < NQ; c++) b0[c] = ld_quad(prow0, c, h);
+#pragma unroll
+  for (int c = 0; c < NQ; c++) b1[c] = ld_quad(prow1, c, h);
+  f32x2 alo = {0.f, 0.f}, ahi = {0.f, 0.f}, clo = {0.f, 0.f}, chi = {0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < D8C; i++) {
+    const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
+    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
+    sq_acc(alo, ahi, cvt_blk(quad_blk(b0[b >> 2], b & 3)), q);
+    sq_acc(clo, chi, cvt_blk(quad_blk(b1[b >> 2], b & 3)), q);
+  }
+#else
   rowblk_t b0[D8C], b1[D8C];
 #pragma unroll
   for (int i = 0; i < D8C; i++) {
@@ -244,6 +324,7 @@ __device__ __forceinline__ void l2_pair2_ct(const float *__restrict__ prow0, con
     sq_acc(alo, ahi, cvt_blk(b0[i]), q);
     sq_acc(clo, chi, cvt_blk(b1[i]), q);
   }
+#endif
   float s = ((alo.x + alo.y) + ahi.x) + ahi.y;
   float other = __shfl_xor(s, 1);
   d0 = (((other + alo.x) + alo.y) + ahi.x) + ahi.y;
@@ -294,6 +375,18 @@ __device__ __forceinline__ float mips_step(float r, const float4 &p, const float
 template <int NP>
 __device__ __forceinline__ float mips_pair_ct(const float *__restrict__ prow, const float *qv, int d, int h) {
   const int tail_from = (d & ~7) >> 3;  // first fused step
+#if WANN_DT == 6
+  constexpr int NQ = (NP + 3) / 4;
+  u32x4 buf[NQ];
+#pragma unroll
+  for (int c = 0; c < NQ; c++) buf[c] = ld_quad(prow, c, h);
+  float r = 0.f;
+#pragma unroll
+  for (int t = 0; t < NP; t++) {
+    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
+    r = mips_step(r, cvt_blk(quad_blk(buf[t >> 2], t & 3)), q, t >= tail_from);
+  }
+#else
   rowblk_t buf[NP];
 #pragma unroll
   for (int t = 0; t < NP; t++) buf[t] = ld_blk(prow, 8 * t + 4 * h);
@@ -303,6 +396,7 @@ __device__ __forceinline__ float mips_pair_ct(const float *__restrict__ prow, co
     const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
     r = mips_step(r, cvt_blk(buf[t]), q, t >= tail_from);
   }
+#endif
   return -r;
 }
 
@@ -311,6 +405,22 @@ template <int NP>
 __device__ __forceinline__ void mips_pair2_ct(const float *__restrict__ prow0, const float *__restrict__ prow1,
                                               const float *qv, int d, int h, float &d0, float &d1) {
   const int tail_from = (d & ~7) >> 3;
+#if WANN_DT == 6
+  constexpr int NQ = (NP + 3) / 4;
+  u32x4 b0[NQ], b1[NQ];
+#pragma unroll
+  for (int c = 0; c < NQ; c++) b0[c] = ld_quad(prow0, c, h);
+#pragma unroll
+  for (int c = 0; c < NQ; c++) b1[c] = ld_quad(prow1, c, h);
+  float r0 = 0.f, r1 = 0.f;
+#pragma unroll
+  for (int t = 0; t < NP; t++) {
+    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
+    const bool tail = t >= tail_from;
+    r0 = mips_step(r0, cvt_blk(quad_blk(b0[t >> 2], t & 3)), q, tail);
+    r1 = mips_step(r1, cvt_blk(quad_blk(b1[t >> 2], t & 3)), q, tail);
+  }
+#else
   rowblk_t b0[NP], b1[NP];
 #pragma unroll
   for (int t = 0; t < NP; t++) b0[t] = ld_blk(prow0, 8 * t + 4 * h);
@@ -324,6 +434,7 @@ __device__ __forceinline__ void mips_pair2_ct(const float *__restrict__ prow0, c
     r0 = mips_step(r0, cvt_blk(b0[t]), q, tail);
     r1 = mips_step(r1, cvt_blk(b1[t]), q, tail);
   }
+#endif
   d0 = -r0;
   d1 = -r1;
 }
@@ -332,6 +443,20 @@ __device__ __forceinline__ void mips_pair2_ct(const float *__restrict__ prow0, c
 __device__ __forceinline__ float mips_pair(const float *__restrict__ prow, const float *qv, int d, int h) {
   const int np = (((d + 3) >> 2) + 1) >> 1, tail_from = (d & ~7) >> 3;
   float r = 0.f;
+#if WANN_DT == 6
+  for (int t0 = 0; t0 < np; t0 += 8) {  // (two quads in flight)
+    u32x4 buf[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+      if (t0 + 4 * j < np) buf[j] = ld_quad(prow, (t0 >> 2) + j, h);
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      if (t0 + j < np) {
+        const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * (t0 + j) + 4 * h);
+        r = mips_step(r, cvt_blk(quad_blk(buf[j >> 2], j & 3)), q, t0 + j >= tail_from);
+      }
+  }
+#else
   for (int t0 = 0; t0 < np; t0 += 8) {
     rowblk_t buf[8];
 #pragma unroll
@@ -344,6 +469,7 @@ __device__ __forceinline__ float mips_pair(const float *__restrict__ prow, const
         r = mips_step(r, cvt_blk(buf[j]), q, t0 + j >= tail_from);
       }
   }
+#endif
   return -r;
 }
 
@@ -1854,8 +1980,18 @@ constexpr int kRowRegsL2 = 16, kRowRegsMips = 0;
 #endif
 template <int NR>
 struct RowRegs {
+#if WANN_DT == 6
+  u32x4 q[NR > 0 ? (NR + 3) / 4 : 1];  // (one-byte shadow rows: QUADS stay quads across the round trip -- four registers for 16 blocks)
+#else
   rowblk_t v[NR > 0 ? NR : 1];  // (float16 rows: the blocks stay halves until they are scored)
+#endif
 };
+// block i of the held row (i a compile-time constant of an unrolled loop)
+#if WANN_DT == 6
+#define rr_blk(rr, i) quad_blk((rr).q[(i) >> 2], (i) & 3)
+#else
+#define rr_blk(rr, i) (rr).v[i]
+#endif
 template <int METRIC>
 struct RowRegsFor {
 #if WANN_BYTE_ROWS
@@ -1890,9 +2026,15 @@ __device__ __forceinline__ int row_regs_blocks(const IndexView &ix) {
 // for them one by one); NBC = 0: `nblk` decides at run time
 template <int NR, int NBC = 0>
 __device__ __forceinline__ void row_regs_load(RowRegs<NR> &rr, const float *__restrict__ prow, int h, int nblk) {
+#if WANN_DT == 6
+#pragma unroll
+  for (int c = 0; c < (NR + 3) / 4; c++)  // (one-byte shadow rows: the quads that hold a block below the count)
+    if (NBC > 0 ? 4 * c < NBC : 4 * c < nblk) rr.q[c] = ld_quad(prow, c, h);
+#else
 #pragma unroll
   for (int j = 0; j < NR; j++)
     if (NBC > 0 ? j < NBC : j < nblk) rr.v[j] = ld_blk(prow, 8 * j + 4 * h);
+#endif
 }
 
 template <int METRIC, int NR, int NBC = 0>
@@ -1932,7 +2074,7 @@ __device__ __forceinline__ float row_regs_score(const RowRegs<NR> &rr, const flo
     for (int t = 0; t < NR; t++)
       if (t < nblk) {
         const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
-        r = mips_step(r, cvt_blk(rr.v[t]), q, t >= tail_from);
+        r = mips_step(r, cvt_blk(rr_blk(rr, t)), q, t >= tail_from);
       }
     return -r;
   }
@@ -1941,14 +2083,14 @@ __device__ __forceinline__ float row_regs_score(const RowRegs<NR> &rr, const flo
   int nfull = nblk;
   if (NR > 12 && nblk == 13) {
     const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * 12 + 4 * h);
-    sq_acc(alo, ahi, cvt_blk(rr.v[NR > 12 ? 12 : 0]), q);
+    sq_acc(alo, ahi, cvt_blk(rr_blk(rr, NR > 12 ? 12 : 0)), q);
     nfull = 12;
   }
 #pragma unroll
   for (int i = 0; i < NR; i++)
     if (i < nfull) {
       const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * i + 4 * h);
-      sq_acc(alo, ahi, cvt_blk(rr.v[i]), q);
+      sq_acc(alo, ahi, cvt_blk(rr_blk(rr, i)), q);
     }
   const float s = ((alo.x + alo.y) + ahi.x) + ahi.y;
   const float other = __shfl_xor(s, 1);
