@@ -94,11 +94,12 @@ __device__ __forceinline__ u64 hash64_2(u64 x) {
 
 // A row BLOCK is four consecutive elements e..e+3 of a row (e a multiple of 4): a float4 of a float32 row, 8 bytes of a
 // float16 row.  Float16 rows (WANN_DT = 3) keep the natural element order, padded with zeros to a multiple of 32 halves
-// (64 B); `stride` still counts 32-bit words, so element e of a row sits at half e of its first word.  ld_blk issues the load,
-// cvt_blk turns a block into the float32 values the float32 routines work on: every half is converted EXACTLY (v_cvt_f32_f16;
-// f16 denormals are preserved by the kernels' default FP mode), and the arithmetic that follows is the float32 path's own,
-// in its own order -- a float16 row scores to the bits of its float32 upcast.  Blocks held across a memory round trip stay
-// halves (half the registers of a float32 block); the conversion happens where the block is consumed.
+// (64 B); `stride` still counts 32-bit words, so element e of a row sits at half e of its first word.  cvt_blk turns a block
+// into the float32 values the float32 routines work on: every half is converted EXACTLY (v_cvt_f32_f16; f16 denormals are
+// preserved by the kernels' default FP mode), and the arithmetic that follows is the float32 path's own, in its own order -- a
+// float16 row scores to the bits of its float32 upcast.  The distance routines hold a row's blocks in RowBlks (below): as they
+// were fetched (halves: half the registers of a float32 block), converted where a block is consumed.  Only RowBlks' loaders
+// know how a unit fetches: ld_blk, one load per block, here and for float32 / bfloat16 / byte rows.
 // (macros: the float32 and byte-row units compile exactly the expressions they compiled before the float16 unit existed)
 #if WANN_DT == 3
 typedef uint2 rowblk_t;
@@ -122,15 +123,16 @@ __device__ __forceinline__ float4 b4_to_f4(uint2 w) {
 // one-byte shadow rows of a float32 index whose values are all integers 0 .. 255: a block is ONE aligned 32-bit word, the
 // elements e .. e+3 of the row (rows zero padded to a multiple of 64 bytes).  Each byte widens UNSIGNED
 // to the float32 it was made from (v_cvt_f32_ubyte0..3: exact), and the float32 arithmetic follows in its own order against the
-// fp32 query in the float32 LDS layout.  A block held across a round trip stays its packed word: a quarter of a float32 block.
+// fp32 query in the float32 LDS layout.  A held block stays its packed word: a quarter of a float32 block.
 // The rows are INTERLEAVED (u8_row_position, wann_device.h): the blocks 8 b + 4 h of lane h, b = 4 c .. 4 c + 3, are the 16
 // contiguous bytes at 32 c + 16 h of the row -- a QUAD, one 16-byte load (ld_quad); quad_blk(q, i) is block b = 4 c + i of it.
-// Every routine of this unit fetches quads (in quad order) and consumes blocks in the float32 routines' order; a block at or
-// beyond the row's block count is never consumed (the quad's padding is zero, but the staged query ends with the row).  In the
-// run-time routines `i` is a compile-time constant of an unrolled loop, and the one last block of an odd count is a select
-// between the four words (never a register index).  A quad is typed with 8-byte alignment: rows in HBM start on multiples
-// of 64 (one global_load_dwordx4), rows staged in the LDS (k_brute_staged) on multiples of 8 (two 8-byte reads).  (The unit has
-// no ld_blk: a single block's address would follow the natural order, and no routine fetches single blocks any more.)
+// RowBlks' loaders of this unit fetch quads, in quad order, and RowBlks keeps them quads; the routines consume blocks in the
+// float32 order through the same accessor as every unit.  A block at or beyond the row's block count is never consumed (the
+// quad's padding is zero, but the staged query ends with the row).  A block's number is a compile-time constant of an unrolled
+// loop wherever it is consumed; the one last block of an odd run-time count is a select between the four words (never a
+// register index).  A quad is typed with 8-byte alignment: rows in HBM start on multiples of 64 (one global_load_dwordx4),
+// rows staged in the LDS (k_brute_staged) on multiples of 8 (two 8-byte reads).  (The unit has no ld_blk: a single block's
+// address would follow the natural order.)
 typedef uint32_t rowblk_t;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 rowquad_t __attribute__((aligned(8)));
@@ -140,11 +142,19 @@ __device__ __forceinline__ float4 u4_to_f4(uint32_t w) {
 #define ld_quad(prow, c, h) (*reinterpret_cast<const rowquad_t *>(reinterpret_cast<const unsigned char *>(prow) + 32 * (c) + 16 * (h)))
 __device__ __forceinline__ uint32_t quad_blk(const u32x4 &q, int i) { return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w; }
 #define cvt_blk(w) u4_to_f4(w)
+typedef u32x4 rowheld_t;  // what a lane holds of a row: quads
+constexpr int kHeldBlks = 4;
+#define held_blk(w, i) quad_blk(w, i)
 #else
 typedef float4 rowblk_t;
 // (no parentheses round `e`: `prow + 8 * b + 4 * h` is the address arithmetic the float32 unit has always compiled)
 #define ld_blk(prow, e) (*reinterpret_cast<const float4 *>(prow + e))
 #define cvt_blk(w) (w)
+#endif
+#ifndef held_blk  // every unit but the quad one: what a lane holds of a row is its blocks, one by one
+typedef rowblk_t rowheld_t;
+constexpr int kHeldBlks = 1;
+#define held_blk(w, i) (w)
 #endif
 // 32-bit words of the staged (fp32, zero padded) query and of the LDS reserved for it: `stride` for float32 / byte rows; for
 // widened rows (float16 / bfloat16 / one-byte shadow rows) the float32 row length, d rounded up to 16 -- every routine reads the
@@ -154,133 +164,142 @@ __device__ __forceinline__ int qv_words(const IndexView &ix) { return WANN_WIDEN
 // --------------------------------------------------------------------------------------------
 // distances in the reference's evaluation order
 // --------------------------------------------------------------------------------------------
-// Squared L2 (NSGDist.h:33-69): 8 accumulators (the AVX lanes); a lane PAIR owns one candidate:
-// lane h = lane&1 carries accumulators 4h..4h+3 and walks the 8-float blocks in the reference's
-// order (odd block count: last block first).  Returns the full distance in the odd lane.
-template <int NB>
-__device__ __forceinline__ float l2_pair(const float *__restrict__ prow, const float *qv, int D8,
-                                         int h, bool active) {
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+// Step i of a squared-L2 walk over n 8-float blocks scores this block: the reference's order (NSGDist.h:40-47; odd block
+// count: last block first).
+__device__ __forceinline__ constexpr int l2_order(int i, int n) { return (n & 1) ? (i == 0 ? n - 1 : i - 1) : i; }
+// lane h's part of the staged query that goes with block b of a row.  (A macro, like row_blk below, and read into a local
+// before the step: a function that returns the float4 by value costs the one-byte kernels 40 % more waits.)
+#define q_blk(qv, b, h) (*reinterpret_cast<const float4 *>((qv) + 8 * (b) + 4 * (h)))
+
+// The blocks of a row that a lane holds, however its unit fetched them: lane h of a pair holds the 16-byte blocks 2 b + h of
+// its row (the elements 8 b + 4 h .. + 3), b < N.  RowBlks<N> and its loaders are where the units differ -- every distance
+// routine below loads a RowBlks and consumes row_blk(rb, b), so each routine's arithmetic and its order exist once:
+//  * float32 / float16 / bfloat16 / byte rows keep one rowblk_t per block (halves stay halves until row_blk converts them);
+//  * the one-byte shadow rows keep QUADS, a register per four blocks (the mid core holds four registers across a hop's round
+//    trip where a float32 row takes 64); row_blk picks word b & 3 of quad b >> 2 and widens it.
+// A plain array and free functions, not a struct with members: as a struct the compiler no longer kept both rows of the
+// two-row routines in flight (16 loads before the first wait where there had been 32).  N = 0: nothing held.
+template <int N>
+using RowBlks = rowheld_t[N > 0 ? (N + kHeldBlks - 1) / kHeldBlks : 1];
+// the float4 of block b, b a compile-time constant of an unrolled loop (the array stays registers)
+#define row_blk(rb, b) cvt_blk(held_blk((rb)[(b) / kHeldBlks], (b) % kHeldBlks))
+
+// The loader: slot j of `rb` receives block b0 + j of the row.  NBC > 0: the blocks 0 .. NBC - 1, a compile-time count (no branch
+// per block, the loads go out back to back and the scoring waits for them one by one); NBC = 0: the blocks below `nblk`, at
+// run time.  The one-byte shadow rows issue the quads that hold a block below the count, in quad order (b0 a
+// multiple of 4).  Every other unit issues one ld_blk per block -- the same addresses for float32 rows under either metric
+// and for byte rows -- in index order, or, LAST_FIRST, in the order a squared-L2 routine consumes them.
+template <int N, int NBC = 0, bool LAST_FIRST = false>
+__device__ __forceinline__ void row_blks_load(RowBlks<N> &rb, const float *__restrict__ prow, int h, int nblk = 0, int b0 = 0) {
 #if WANN_DT == 6
-  if (active) {
-    const int nfull = D8 & ~1;  // the blocks 0 .. nfull - 1 in index order, after the last block of an odd count
-    if (D8 & 1) {
-      const int b = D8 - 1;
-      const u32x4 last = ld_quad(prow, b >> 2, h);
-      const uint32_t w = quad_blk(last, b & 3);  // (wave-uniform selects)
-      float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
-      float t;
-      t = cvt_blk(w).x - q.x; a0 = fmaf(t, t, a0);
-      t = cvt_blk(w).y - q.y; a1 = fmaf(t, t, a1);
-      t = cvt_blk(w).z - q.z; a2 = fmaf(t, t, a2);
-      t = cvt_blk(w).w - q.w; a3 = fmaf(t, t, a3);
-    }
-    constexpr int NQ = NB / 4;  // quads in flight
-    for (int c0 = 0; 4 * c0 < nfull; c0 += NQ) {
-      u32x4 buf[NQ];
 #pragma unroll
-      for (int j = 0; j < NQ; j++)
-        if (4 * (c0 + j) < nfull) buf[j] = ld_quad(prow, c0 + j, h);
-#pragma unroll
-      for (int j = 0; j < NQ; j++) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const int b = 4 * (c0 + j) + i;
-          if (b < nfull) {
-            float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
-            const uint32_t w = quad_blk(buf[j], i);
-            float t;
-            t = cvt_blk(w).x - q.x; a0 = fmaf(t, t, a0);
-            t = cvt_blk(w).y - q.y; a1 = fmaf(t, t, a1);
-            t = cvt_blk(w).z - q.z; a2 = fmaf(t, t, a2);
-            t = cvt_blk(w).w - q.w; a3 = fmaf(t, t, a3);
-          }
-        }
-      }
-    }
-  }
+  for (int c = 0; c < (N + 3) / 4; c++)
+    if (NBC > 0 ? 4 * c < NBC : b0 + 4 * c < nblk) rb[c] = ld_quad(prow, (b0 >> 2) + c, h);
 #else
-  if (active) {
-    const bool odd = D8 & 1;
-    for (int i0 = 0; i0 < D8; i0 += NB) {
-      rowblk_t buf[NB];
 #pragma unroll
-      for (int j = 0; j < NB; j++) {
-        int i = i0 + j;
-        if (i < D8) {
-          int b = odd ? (i == 0 ? D8 - 1 : i - 1) : i;
-          buf[j] = ld_blk(prow, 8 * b + 4 * h);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < NB; j++) {
-        int i = i0 + j;
-        if (i < D8) {
-          int b = odd ? (i == 0 ? D8 - 1 : i - 1) : i;
-          float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
-          float t;
-          t = cvt_blk(buf[j]).x - q.x; a0 = fmaf(t, t, a0);
-          t = cvt_blk(buf[j]).y - q.y; a1 = fmaf(t, t, a1);
-          t = cvt_blk(buf[j]).z - q.z; a2 = fmaf(t, t, a2);
-          t = cvt_blk(buf[j]).w - q.w; a3 = fmaf(t, t, a3);
-        }
-      }
-    }
+  for (int i = 0; i < N; i++) {
+    const int j = LAST_FIRST ? l2_order(i, NBC) : i;
+    if (NBC > 0 ? j < NBC : b0 + j < nblk) rb[j] = ld_blk(prow, 8 * (b0 + j) + 4 * h);
   }
 #endif
-  float s = ((a0 + a1) + a2) + a3;          // even lane: ((l0+l1)+l2)+l3
-  float other = __shfl_xor(s, 1);           // odd lane receives the even lane's partial
-  return (((other + a0) + a1) + a2) + a3;   // odd lane: ((((s+l4)+l5)+l6)+l7)
 }
 
-// Same arithmetic with the block count known at compile time: no branches, the row's loads, then the
-// query's LDS reads, are issued back to back (the hot path for d = 128 / 96 / 100 / 64 / 32).
+// Squared L2 (NSGDist.h:33-69): 8 accumulators (the AVX lanes); a lane PAIR owns one candidate:
+// lane h = lane&1 carries accumulators 4h..4h+3 (lo.x lo.y hi.x hi.y) and walks the 8-float blocks in the reference's
+// order (l2_order).  The full distance arrives in the odd lane.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// acc += (p - q)^2 element-wise with one rounding per element (fma): packed fp32 instructions
-// (v_pk_add_f32 / v_pk_fma_f32) compute exactly what two scalar ops compute.
-__device__ __forceinline__ void sq_acc(f32x2 &lo, f32x2 &hi, const float4 &p, const float4 &q) {
+// acc += (p - q)^2 element-wise with one rounding per element (fma), in two forms that compute the same bits: on pairs --
+// packed fp32 instructions (v_pk_add_f32 / v_pk_fma_f32) compute exactly what two scalar ops compute -- for the compile-time
+// routines, on four scalars for the run-time routine.  (Each routine keeps the form it has always compiled to: the run-time
+// routine written on the components of two pairs took four more registers in the one-wave kernel.)
+__device__ __forceinline__ void l2_step(f32x2 &lo, f32x2 &hi, const float4 &p, const float4 &q) {
   f32x2 t0 = f32x2{p.x, p.y} - f32x2{q.x, q.y};
   f32x2 t1 = f32x2{p.z, p.w} - f32x2{q.z, q.w};
   lo = __builtin_elementwise_fma(t0, t0, lo);
   hi = __builtin_elementwise_fma(t1, t1, hi);
 }
+__device__ __forceinline__ void l2_step(float &a0, float &a1, float &a2, float &a3, const float4 &p, const float4 &q) {
+  float t;
+  t = p.x - q.x; a0 = fmaf(t, t, a0);
+  t = p.y - q.y; a1 = fmaf(t, t, a1);
+  t = p.z - q.z; a2 = fmaf(t, t, a2);
+  t = p.w - q.w; a3 = fmaf(t, t, a3);
+}
 
+// the pair's eight accumulators summed in the reference's order; the result is the odd lane's
+__device__ __forceinline__ float l2_reduce(const f32x2 &lo, const f32x2 &hi) {
+  const float s = ((lo.x + lo.y) + hi.x) + hi.y;     // even lane: ((l0+l1)+l2)+l3
+  const float other = __shfl_xor(s, 1);              // odd lane receives the even lane's partial
+  return (((other + lo.x) + lo.y) + hi.x) + hi.y;    // odd lane: ((((s+l4)+l5)+l6)+l7)
+}
+
+// Any block count: batches of up to NB blocks in flight.  The step is the one l2_step; the fetch loop round it is kept in
+// two forms, because no single one holds both of these (a common loop with a one-block first batch for the quads moved the
+// registers of four of the one-byte kernels):
+//  * one load per block: a batch is NB steps in the walk's order, so the last block of an odd count travels with the first
+//    batch -- no load that is waited for on its own;
+//  * quads: a batch in the walk's order would span NB / 4 + 1 quads whenever the count is odd.  The last block of an odd
+//    count comes from a load of its own (its quad, the word picked by wave-uniform selects), and the batches behind it
+//    walk the blocks below it in index order from quad boundaries: NB / 4 quads in flight.
+template <int NB>
+__device__ __forceinline__ float l2_pair(const float *__restrict__ prow, const float *qv, int D8,
+                                         int h, bool active) {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  if (active) {
+#if WANN_DT == 6
+    const int nfull = D8 & ~1;
+    if (D8 & 1) {
+      const int b = D8 - 1;
+      const u32x4 last = ld_quad(prow, b >> 2, h);
+      const float4 q = q_blk(qv, b, h);
+      l2_step(a0, a1, a2, a3, cvt_blk(quad_blk(last, b & 3)), q);
+    }
+    for (int b0 = 0; b0 < nfull; b0 += NB) {
+      RowBlks<NB> buf;
+      row_blks_load<NB>(buf, prow, h, nfull, b0);
+#pragma unroll
+      for (int j = 0; j < NB; j++)
+        if (b0 + j < nfull) {
+          const float4 q = q_blk(qv, b0 + j, h);
+          l2_step(a0, a1, a2, a3, row_blk(buf, j), q);
+        }
+    }
+#else
+    for (int i0 = 0; i0 < D8; i0 += NB) {
+      RowBlks<NB> buf;
+#pragma unroll
+      for (int j = 0; j < NB; j++)
+        if (i0 + j < D8) buf[j] = ld_blk(prow, 8 * l2_order(i0 + j, D8) + 4 * h);
+#pragma unroll
+      for (int j = 0; j < NB; j++)
+        if (i0 + j < D8) {
+          const float4 q = q_blk(qv, l2_order(i0 + j, D8), h);
+          l2_step(a0, a1, a2, a3, row_blk(buf, j), q);
+        }
+    }
+#endif
+  }
+  return l2_reduce(f32x2{a0, a1}, f32x2{a2, a3});
+}
+
+// Same arithmetic with the block count known at compile time: no branches, the row's loads, then the
+// query's LDS reads, are issued back to back (the hot path for d = 128 / 96 / 100 / 64 / 32).
 template <int D8C>
 __device__ __forceinline__ float l2_pair_ct(const float *__restrict__ prow, const float *qv, int h, bool active) {
   // inactive lanes are handed a valid row (node 0 of the partition) and compute a value nobody
   // reads: no per-load exec-mask branches
   (void)active;
-  constexpr bool odd = D8C & 1;
+  RowBlks<D8C> buf;
+  row_blks_load<D8C, D8C, true>(buf, prow, h);
   f32x2 alo = {0.f, 0.f}, ahi = {0.f, 0.f};
-#if WANN_DT == 6
-  constexpr int NQ = (D8C + 3) / 4;  // the loads in quad order, the blocks consumed in the order below
-  u32x4 buf[NQ];
-#pragma unroll
-  for (int c = 0; c < NQ; c++) buf[c] = ld_quad(prow, c, h);
 #pragma unroll
   for (int i = 0; i < D8C; i++) {
-    const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
-    sq_acc(alo, ahi, cvt_blk(quad_blk(buf[b >> 2], b & 3)), q);
+    const int b = l2_order(i, D8C);
+    const float4 q = q_blk(qv, b, h);
+    l2_step(alo, ahi, row_blk(buf, b), q);
   }
-#else
-  rowblk_t buf[D8C];
-#pragma unroll
-  for (int i = 0; i < D8C; i++) {
-    const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    buf[i] = ld_blk(prow, 8 * b + 4 * h);
-  }
-#pragma unroll
-  for (int i = 0; i < D8C; i++) {
-    const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
-    sq_acc(alo, ahi, cvt_blk(buf[i]), q);
-  }
-#endif
-  float s = ((alo.x + alo.y) + ahi.x) + ahi.y;
-  float other = __shfl_xor(s, 1);
-  return (((other + alo.x) + alo.y) + ahi.x) + ahi.y;
+  return l2_reduce(alo, ahi);
 }
 
 // Two candidates per lane pair (s and s + 32) with every block of BOTH rows in flight before the
@@ -288,49 +307,19 @@ __device__ __forceinline__ float l2_pair_ct(const float *__restrict__ prow, cons
 template <int D8C>
 __device__ __forceinline__ void l2_pair2_ct(const float *__restrict__ prow0, const float *__restrict__ prow1,
                                             const float *qv, int h, float &d0, float &d1) {
-  constexpr bool odd = D8C & 1;
-#if WANN_DT == 6
-  constexpr int NQ = (D8C + 3) / 4;
-  u32x4 b0[NQ], b1[NQ];
-#pragma unroll
-  for (int c = 0; c < NQ; c++) b0[c] = ld_quad(prow0, c, h);
-#pragma unroll
-  for (int c = 0; c < NQ; c++) b1[c] = ld_quad(prow1, c, h);
+  RowBlks<D8C> b0, b1;
+  row_blks_load<D8C, D8C, true>(b0, prow0, h);
+  row_blks_load<D8C, D8C, true>(b1, prow1, h);
   f32x2 alo = {0.f, 0.f}, ahi = {0.f, 0.f}, clo = {0.f, 0.f}, chi = {0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < D8C; i++) {
-    const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
-    sq_acc(alo, ahi, cvt_blk(quad_blk(b0[b >> 2], b & 3)), q);
-    sq_acc(clo, chi, cvt_blk(quad_blk(b1[b >> 2], b & 3)), q);
+    const int b = l2_order(i, D8C);
+    const float4 q = q_blk(qv, b, h);
+    l2_step(alo, ahi, row_blk(b0, b), q);
+    l2_step(clo, chi, row_blk(b1, b), q);
   }
-#else
-  rowblk_t b0[D8C], b1[D8C];
-#pragma unroll
-  for (int i = 0; i < D8C; i++) {
-    const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    b0[i] = ld_blk(prow0, 8 * b + 4 * h);
-  }
-#pragma unroll
-  for (int i = 0; i < D8C; i++) {
-    const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    b1[i] = ld_blk(prow1, 8 * b + 4 * h);
-  }
-  f32x2 alo = {0.f, 0.f}, ahi = {0.f, 0.f}, clo = {0.f, 0.f}, chi = {0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < D8C; i++) {
-    const int b = odd ? (i == 0 ? D8C - 1 : i - 1) : i;
-    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * b + 4 * h);
-    sq_acc(alo, ahi, cvt_blk(b0[i]), q);
-    sq_acc(clo, chi, cvt_blk(b1[i]), q);
-  }
-#endif
-  float s = ((alo.x + alo.y) + ahi.x) + ahi.y;
-  float other = __shfl_xor(s, 1);
-  d0 = (((other + alo.x) + alo.y) + ahi.x) + ahi.y;
-  s = ((clo.x + clo.y) + chi.x) + chi.y;
-  other = __shfl_xor(s, 1);
-  d1 = (((other + clo.x) + clo.y) + chi.x) + chi.y;
+  d0 = l2_reduce(alo, ahi);
+  d1 = l2_reduce(clo, chi);
 }
 
 // Negative inner product (mips_point.h:60-66 as compiled): ONE running scalar per candidate, products rounded
@@ -375,28 +364,14 @@ __device__ __forceinline__ float mips_step(float r, const float4 &p, const float
 template <int NP>
 __device__ __forceinline__ float mips_pair_ct(const float *__restrict__ prow, const float *qv, int d, int h) {
   const int tail_from = (d & ~7) >> 3;  // first fused step
-#if WANN_DT == 6
-  constexpr int NQ = (NP + 3) / 4;
-  u32x4 buf[NQ];
-#pragma unroll
-  for (int c = 0; c < NQ; c++) buf[c] = ld_quad(prow, c, h);
+  RowBlks<NP> buf;
+  row_blks_load<NP, NP>(buf, prow, h);
   float r = 0.f;
 #pragma unroll
   for (int t = 0; t < NP; t++) {
-    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
-    r = mips_step(r, cvt_blk(quad_blk(buf[t >> 2], t & 3)), q, t >= tail_from);
+    const float4 q = q_blk(qv, t, h);
+    r = mips_step(r, row_blk(buf, t), q, t >= tail_from);
   }
-#else
-  rowblk_t buf[NP];
-#pragma unroll
-  for (int t = 0; t < NP; t++) buf[t] = ld_blk(prow, 8 * t + 4 * h);
-  float r = 0.f;
-#pragma unroll
-  for (int t = 0; t < NP; t++) {
-    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
-    r = mips_step(r, cvt_blk(buf[t]), q, t >= tail_from);
-  }
-#endif
   return -r;
 }
 
@@ -405,74 +380,39 @@ template <int NP>
 __device__ __forceinline__ void mips_pair2_ct(const float *__restrict__ prow0, const float *__restrict__ prow1,
                                               const float *qv, int d, int h, float &d0, float &d1) {
   const int tail_from = (d & ~7) >> 3;
-#if WANN_DT == 6
-  constexpr int NQ = (NP + 3) / 4;
-  u32x4 b0[NQ], b1[NQ];
-#pragma unroll
-  for (int c = 0; c < NQ; c++) b0[c] = ld_quad(prow0, c, h);
-#pragma unroll
-  for (int c = 0; c < NQ; c++) b1[c] = ld_quad(prow1, c, h);
+  RowBlks<NP> b0, b1;
+  row_blks_load<NP, NP>(b0, prow0, h);
+  row_blks_load<NP, NP>(b1, prow1, h);
   float r0 = 0.f, r1 = 0.f;
 #pragma unroll
   for (int t = 0; t < NP; t++) {
-    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
+    const float4 q = q_blk(qv, t, h);
     const bool tail = t >= tail_from;
-    r0 = mips_step(r0, cvt_blk(quad_blk(b0[t >> 2], t & 3)), q, tail);
-    r1 = mips_step(r1, cvt_blk(quad_blk(b1[t >> 2], t & 3)), q, tail);
+    r0 = mips_step(r0, row_blk(b0, t), q, tail);
+    r1 = mips_step(r1, row_blk(b1, t), q, tail);
   }
-#else
-  rowblk_t b0[NP], b1[NP];
-#pragma unroll
-  for (int t = 0; t < NP; t++) b0[t] = ld_blk(prow0, 8 * t + 4 * h);
-#pragma unroll
-  for (int t = 0; t < NP; t++) b1[t] = ld_blk(prow1, 8 * t + 4 * h);
-  float r0 = 0.f, r1 = 0.f;
-#pragma unroll
-  for (int t = 0; t < NP; t++) {
-    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
-    const bool tail = t >= tail_from;
-    r0 = mips_step(r0, cvt_blk(b0[t]), q, tail);
-    r1 = mips_step(r1, cvt_blk(b1[t]), q, tail);
-  }
-#endif
   d0 = -r0;
   d1 = -r1;
 }
 
-// any dimension: blocks of 8 pair steps
+// any dimension: batches of 8 pair steps (the one-byte shadow rows: two quads in flight)
 __device__ __forceinline__ float mips_pair(const float *__restrict__ prow, const float *qv, int d, int h) {
   const int np = (((d + 3) >> 2) + 1) >> 1, tail_from = (d & ~7) >> 3;
   float r = 0.f;
-#if WANN_DT == 6
-  for (int t0 = 0; t0 < np; t0 += 8) {  // (two quads in flight)
-    u32x4 buf[2];
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-      if (t0 + 4 * j < np) buf[j] = ld_quad(prow, (t0 >> 2) + j, h);
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-      if (t0 + j < np) {
-        const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * (t0 + j) + 4 * h);
-        r = mips_step(r, cvt_blk(quad_blk(buf[j >> 2], j & 3)), q, t0 + j >= tail_from);
-      }
-  }
-#else
   for (int t0 = 0; t0 < np; t0 += 8) {
-    rowblk_t buf[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-      if (t0 + j < np) buf[j] = ld_blk(prow, 8 * (t0 + j) + 4 * h);
+    RowBlks<8> buf;
+    row_blks_load<8>(buf, prow, h, np, t0);
 #pragma unroll
     for (int j = 0; j < 8; j++)
       if (t0 + j < np) {
-        const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * (t0 + j) + 4 * h);
-        r = mips_step(r, cvt_blk(buf[j]), q, t0 + j >= tail_from);
+        const float4 q = q_blk(qv, t0 + j, h);
+        r = mips_step(r, row_blk(buf, j), q, t0 + j >= tail_from);
       }
   }
-#endif
   return -r;
 }
 
+// --------------------------------------------------------------------------------------------
 // --------------------------------------------------------------------------------------------
 // uint8 / int8 point sets (WANN_DT = 1 / 2: one translation unit per element type, see wann_kernels_u8.hip):
 // rows are BYTES (d elements, zero padded to a multiple of 64), `stride` still counts 32-bit words, distances
@@ -490,6 +430,32 @@ __device__ __forceinline__ int dot4_acc(uint32_t a, uint32_t b, int c) {
 #endif
 }
 
+// one 16-byte chunk of row (p) and query (q) into the three running sums (exact integers: any order)
+template <int METRIC>
+__device__ __forceinline__ void byte_chunk_acc(int &ab, int &aa, int &qq, const uint4 &p, const uint4 &q) {
+  ab = dot4_acc(p.x, q.x, ab);
+  ab = dot4_acc(p.y, q.y, ab);
+  ab = dot4_acc(p.z, q.z, ab);
+  ab = dot4_acc(p.w, q.w, ab);
+  if (METRIC == 0) {
+    aa = dot4_acc(p.x, p.x, aa);
+    aa = dot4_acc(p.y, p.y, aa);
+    aa = dot4_acc(p.z, p.z, aa);
+    aa = dot4_acc(p.w, p.w, aa);
+    qq = dot4_acc(q.x, q.x, qq);
+    qq = dot4_acc(q.y, q.y, qq);
+    qq = dot4_acc(q.z, q.z, qq);
+    qq = dot4_acc(q.w, q.w, qq);
+  }
+}
+// ... and the pair's distance from each lane's sums
+template <int METRIC>
+__device__ __forceinline__ float byte_reduce(int ab, int aa, int qq) {
+  const int mine = METRIC == 0 ? (aa + qq - 2 * ab) : ab;
+  const int both = mine + __shfl_xor(mine, 1);
+  return METRIC == 0 ? (float)both : -(float)both;
+}
+
 template <int METRIC>
 __device__ __forceinline__ float byte_pair(const float *__restrict__ prow, const float *qv, int stride_words, int h) {
   const int chunks = stride_words >> 3;  // 16-byte chunks per lane (the row has stride_words / 4 of them)
@@ -501,28 +467,10 @@ __device__ __forceinline__ float byte_pair(const float *__restrict__ prow, const
       if (t0 + j < chunks) buf[j] = *reinterpret_cast<const uint4 *>(prow + 4 * (2 * (t0 + j) + h));
 #pragma unroll
     for (int j = 0; j < 8; j++)
-      if (t0 + j < chunks) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(qv + 4 * (2 * (t0 + j) + h));
-        const uint4 p = buf[j];
-        ab = dot4_acc(p.x, q.x, ab);
-        ab = dot4_acc(p.y, q.y, ab);
-        ab = dot4_acc(p.z, q.z, ab);
-        ab = dot4_acc(p.w, q.w, ab);
-        if (METRIC == 0) {
-          aa = dot4_acc(p.x, p.x, aa);
-          aa = dot4_acc(p.y, p.y, aa);
-          aa = dot4_acc(p.z, p.z, aa);
-          aa = dot4_acc(p.w, p.w, aa);
-          qq = dot4_acc(q.x, q.x, qq);
-          qq = dot4_acc(q.y, q.y, qq);
-          qq = dot4_acc(q.z, q.z, qq);
-          qq = dot4_acc(q.w, q.w, qq);
-        }
-      }
+      if (t0 + j < chunks)
+        byte_chunk_acc<METRIC>(ab, aa, qq, buf[j], *reinterpret_cast<const uint4 *>(qv + 4 * (2 * (t0 + j) + h)));
   }
-  const int mine = METRIC == 0 ? (aa + qq - 2 * ab) : ab;
-  const int both = mine + __shfl_xor(mine, 1);
-  return METRIC == 0 ? (float)both : -(float)both;
+  return byte_reduce<METRIC>(ab, aa, qq);
 }
 
 // the query's elements (integer-valued floats) packed four to a word, as the rows are
@@ -560,6 +508,39 @@ __device__ __forceinline__ void wave_touch_rows(const IndexView &ix, const int32
   }
 }
 
+// One row per lane pair: the routine for the index's row shape (a wave-uniform choice).  Compile-time routines exist for
+// d = 128 / 96 / 100 / 64 under squared L2 and for d = 96 / 100 under the inner product.  `active`: see l2_pair_ct.
+template <int METRIC>
+__device__ __forceinline__ float pair_distance(const IndexView &ix, const float *__restrict__ prow, const float *qv, int h, bool active) {
+#if WANN_BYTE_ROWS
+  return byte_pair<METRIC>(prow, qv, ix.stride, h);
+#else
+  if (METRIC == 1) {
+    switch ((((ix.d + 3) >> 2) + 1) >> 1) {
+      case 12: return mips_pair_ct<12>(prow, qv, ix.d, h);  // d = 96
+      case 13: return mips_pair_ct<13>(prow, qv, ix.d, h);  // d = 100
+      default: return mips_pair(prow, qv, ix.d, h);
+    }
+  }
+  const int D8 = (ix.d + 7) >> 3;
+  switch (D8) {
+    case 16: return l2_pair_ct<16>(prow, qv, h, active);  // d = 128
+    case 12: return l2_pair_ct<12>(prow, qv, h, active);  // d = 96
+    case 13: return l2_pair_ct<13>(prow, qv, h, active);  // d = 100
+    case 8: return l2_pair_ct<8>(prow, qv, h, active);    // d = 64
+    default: return l2_pair<16>(prow, qv, D8, h, active);
+  }
+#endif
+}
+
+// the distances that the lanes holding them published to scratch_lds[0..cnt): lane s < cnt reads row s's
+__device__ __forceinline__ float wave_read_back(const float *scratch_lds, int cnt, int lane) {
+  WAVE_SYNC();
+  const float r = (lane < cnt) ? scratch_lds[lane] : 0.f;
+  WAVE_SYNC();
+  return r;
+}
+
 // Distances of `cnt` rows whose (sorted-order) row numbers sit in ids_lds[0..cnt): afterwards lane
 // s < cnt holds the distance of row s.  scratch_lds: 64 floats.
 // MIPS_TWO: the inner-product routine that keeps two rows per lane pair in flight (the exact scans: rows stream, registers
@@ -576,13 +557,10 @@ __device__ __forceinline__ float wave_distances(const IndexView &ix, const int32
       const int s = base + (lane >> 1);
       const bool act = s < cnt;
       const int id = act ? ids_lds[s] : 0;
-      const float dd = byte_pair<METRIC>(ix.points + (row_off + id) * (int64_t)ix.stride, qv, ix.stride, h);
+      const float dd = pair_distance<METRIC>(ix, ix.points + (row_off + id) * (int64_t)ix.stride, qv, h, act);
       if (act && h) scratch_lds[s] = dd;
     }
-    WAVE_SYNC();
-    const float r = (lane < cnt) ? scratch_lds[lane] : 0.f;
-    WAVE_SYNC();
-    return r;
+    return wave_read_back(scratch_lds, cnt, lane);
   }
 #endif
   if (METRIC == 1) {
@@ -603,10 +581,7 @@ __device__ __forceinline__ float wave_distances(const IndexView &ix, const int32
       else mips_pair2_ct<13>(p0, p1, qv, ix.d, h, d0, d1);
       if (h) scratch_lds[s0] = d0;
       if (act1 && h) scratch_lds[s1] = d1;
-      WAVE_SYNC();
-      float r = (lane < cnt) ? scratch_lds[lane] : 0.f;
-      WAVE_SYNC();
-      return r;
+      return wave_read_back(scratch_lds, cnt, lane);
     }
     if (cnt > 32) wave_touch_rows(ix, ids_lds, 32, cnt - 32, row_off);
     for (int base = 0; base < cnt; base += 32) {
@@ -614,18 +589,10 @@ __device__ __forceinline__ float wave_distances(const IndexView &ix, const int32
       const bool act = s < cnt;
       const int id = act ? ids_lds[s] : 0;  // idle pairs score node 0: no branches
       const float *prow = ix.points + (row_off + id) * (int64_t)ix.stride;
-      float dd;
-      switch (np) {
-        case 12: dd = mips_pair_ct<12>(prow, qv, ix.d, h); break;  // d = 96
-        case 13: dd = mips_pair_ct<13>(prow, qv, ix.d, h); break;  // d = 100
-        default: dd = mips_pair(prow, qv, ix.d, h); break;
-      }
+      const float dd = pair_distance<METRIC>(ix, prow, qv, h, act);
       if (act && h) scratch_lds[s] = dd;
     }
-    WAVE_SYNC();
-    float r = (lane < cnt) ? scratch_lds[lane] : 0.f;
-    WAVE_SYNC();
-    return r;
+    return wave_read_back(scratch_lds, cnt, lane);
   } else {
     const int D8 = (ix.d + 7) >> 3;
     const int h = lane & 1;
@@ -652,21 +619,11 @@ __device__ __forceinline__ float wave_distances(const IndexView &ix, const int32
         bool act = s < cnt;
         int id = act ? ids_lds[s] : 0;
         const float *prow = ix.points + (row_off + id) * (int64_t)ix.stride;
-        float dist;
-        switch (D8) {  // wave-uniform
-          case 16: dist = l2_pair_ct<16>(prow, qv, h, act); break;  // d = 128 (TWO_ROWS = false)
-          case 12: dist = l2_pair_ct<12>(prow, qv, h, act); break;  // d = 96
-          case 13: dist = l2_pair_ct<13>(prow, qv, h, act); break;  // d = 100
-          case 8: dist = l2_pair_ct<8>(prow, qv, h, act); break;    // d = 64
-          default: dist = l2_pair<16>(prow, qv, D8, h, act); break;
-        }
+        const float dist = pair_distance<METRIC>(ix, prow, qv, h, act);
         if (act && h) scratch_lds[s] = dist;
       }
     }
-    WAVE_SYNC();
-    float r = (lane < cnt) ? scratch_lds[lane] : 0.f;
-    WAVE_SYNC();
-    return r;
+    return wave_read_back(scratch_lds, cnt, lane);
   }
 }
 
@@ -1305,30 +1262,12 @@ __device__ __forceinline__ float wave_distances_own(const IndexView &ix, int a, 
     const int id = (base + s < nt) ? ev : 0;  // idle pairs score node 0: no branches
     const float *prow = ix.points + (row_off + id) * (int64_t)ix.stride;
     float dd;
-#if WANN_BYTE_ROWS
-    dd = byte_pair<METRIC>(prow, qv, ix.stride, h);
-#else
-    if (LEAN) {
+    if (!WANN_BYTE_ROWS && LEAN) {
       if (METRIC == 1) dd = mips_pair(prow, qv, ix.d, h);
       else dd = l2_pair<8>(prow, qv, (ix.d + 7) >> 3, h, true);
-    } else if (METRIC == 1) {
-      const int np = (((ix.d + 3) >> 2) + 1) >> 1;
-      switch (np) {  // wave-uniform
-        case 12: dd = mips_pair_ct<12>(prow, qv, ix.d, h); break;
-        case 13: dd = mips_pair_ct<13>(prow, qv, ix.d, h); break;
-        default: dd = mips_pair(prow, qv, ix.d, h); break;
-      }
     } else {
-      const int D8 = (ix.d + 7) >> 3;
-      switch (D8) {  // wave-uniform
-        case 16: dd = l2_pair_ct<16>(prow, qv, h, true); break;
-        case 12: dd = l2_pair_ct<12>(prow, qv, h, true); break;
-        case 13: dd = l2_pair_ct<13>(prow, qv, h, true); break;
-        case 8: dd = l2_pair_ct<8>(prow, qv, h, true); break;
-        default: dd = l2_pair<16>(prow, qv, D8, h, true); break;
-      }
+      dd = pair_distance<METRIC>(ix, prow, qv, h, true);
     }
-#endif
     // the result sits in the odd lane of the pair (in both for the inner product): the owner pulls it
     const float back = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((((r - base) << 1) | 1) << 2, __builtin_bit_cast(int, dd)));
     if (now) mine = back;
@@ -1961,7 +1900,7 @@ __device__ __forceinline__ void wave_beam_search_big(const IndexView &ix, const 
 //    a hop WITH shared slots is united on its own, at once, with the multiset rule.
 //  * A HOP'S REQUESTS GO OUT TOGETHER, the vectors first; expectations, probes and the pending buffer are worked on while
 //    they travel.  The steady-state hop is one memory round trip + distance arithmetic + ~350 instructions.
-//  * Vectors are requested at one point of the hop and consumed at another (RowRegs: half a row per lane, one row per
+//  * Vectors are requested at one point of the hop and consumed at another (RowBlks: half a row per lane, one row per
 //    lane pair and pass, ids and results through the cross-lane network as in wave_distances_own) where the kernel's
 //    register budget allows (elsewhere they are fetched where they are scored); a second pass's rows are TOUCHED at request
 //    time (one dword per 128-byte line) so that their round trip ends in the L2.
@@ -1978,20 +1917,6 @@ constexpr int kRowRegs = 4;  // byte rows of up to 128 elements (8 cost the byte
 #else
 constexpr int kRowRegsL2 = 16, kRowRegsMips = 0;
 #endif
-template <int NR>
-struct RowRegs {
-#if WANN_DT == 6
-  u32x4 q[NR > 0 ? (NR + 3) / 4 : 1];  // (one-byte shadow rows: QUADS stay quads across the round trip -- four registers for 16 blocks)
-#else
-  rowblk_t v[NR > 0 ? NR : 1];  // (float16 rows: the blocks stay halves until they are scored)
-#endif
-};
-// block i of the held row (i a compile-time constant of an unrolled loop)
-#if WANN_DT == 6
-#define rr_blk(rr, i) quad_blk((rr).q[(i) >> 2], (i) & 3)
-#else
-#define rr_blk(rr, i) (rr).v[i]
-#endif
 template <int METRIC>
 struct RowRegsFor {
 #if WANN_BYTE_ROWS
@@ -1999,10 +1924,10 @@ struct RowRegsFor {
 #else
   static constexpr int NR = METRIC == 1 ? kRowRegsMips : kRowRegsL2;
 #endif
-  typedef RowRegs<NR> type;
+  typedef RowBlks<NR> type;
 };
 
-// how many 16-byte blocks of a row a lane holds in RowRegs (wave-uniform); 0: this row shape is fetched where it is scored.
+// how many 16-byte blocks of a row a lane holds across a hop (wave-uniform); 0: this row shape is fetched where it is scored.
 // (ONE loader and one scoring routine per metric, blocks predicated by the count: a switch over compile-time routines made
 // hipcc merge the cases' loads into one block with an address register pair per load -- 270 registers.)
 template <int METRIC>
@@ -2020,52 +1945,17 @@ __device__ __forceinline__ int row_regs_blocks(const IndexView &ix) {
 #endif
 }
 
-// lane h of a pair holds the 16-byte blocks 2 j + h of its row, j < nblk -- the same addresses for float32 rows under either
-// metric and for byte rows
-// NBC > 0: the block count is a compile-time constant (no branch per block, the loads go out back to back and the scoring waits
-// for them one by one); NBC = 0: `nblk` decides at run time
-template <int NR, int NBC = 0>
-__device__ __forceinline__ void row_regs_load(RowRegs<NR> &rr, const float *__restrict__ prow, int h, int nblk) {
-#if WANN_DT == 6
-#pragma unroll
-  for (int c = 0; c < (NR + 3) / 4; c++)  // (one-byte shadow rows: the quads that hold a block below the count)
-    if (NBC > 0 ? 4 * c < NBC : 4 * c < nblk) rr.q[c] = ld_quad(prow, c, h);
-#else
-#pragma unroll
-  for (int j = 0; j < NR; j++)
-    if (NBC > 0 ? j < NBC : j < nblk) rr.v[j] = ld_blk(prow, 8 * j + 4 * h);
-#endif
-}
-
+// the distance of the row a lane pair holds (row_blks_load<NR, NBC>, blocks in index order): the routines' own steps
 template <int METRIC, int NR, int NBC = 0>
-__device__ __forceinline__ float row_regs_score(const RowRegs<NR> &rr, const float *qv, const IndexView &ix, int h, int nblk) {
+__device__ __forceinline__ float row_regs_score(const RowBlks<NR> &rr, const float *qv, const IndexView &ix, int h, int nblk) {
   if (NR == 0) return 0.f;
   if (NBC > 0) nblk = NBC;
 #if WANN_BYTE_ROWS
-  int ab = 0, aa = 0, qq = 0;  // byte_pair's arithmetic (exact integer sums: any order)
+  int ab = 0, aa = 0, qq = 0;  // byte_pair's arithmetic
 #pragma unroll
   for (int j = 0; j < NR; j++)
-    if (j < nblk) {
-      const uint4 q = *reinterpret_cast<const uint4 *>(qv + 8 * j + 4 * h);
-      const uint4 p = __builtin_bit_cast(uint4, rr.v[j]);
-      ab = dot4_acc(p.x, q.x, ab);
-      ab = dot4_acc(p.y, q.y, ab);
-      ab = dot4_acc(p.z, q.z, ab);
-      ab = dot4_acc(p.w, q.w, ab);
-      if (METRIC == 0) {
-        aa = dot4_acc(p.x, p.x, aa);
-        aa = dot4_acc(p.y, p.y, aa);
-        aa = dot4_acc(p.z, p.z, aa);
-        aa = dot4_acc(p.w, p.w, aa);
-        qq = dot4_acc(q.x, q.x, qq);
-        qq = dot4_acc(q.y, q.y, qq);
-        qq = dot4_acc(q.z, q.z, qq);
-        qq = dot4_acc(q.w, q.w, qq);
-      }
-    }
-  const int mine = METRIC == 0 ? (aa + qq - 2 * ab) : ab;
-  const int both = mine + __shfl_xor(mine, 1);
-  return METRIC == 0 ? (float)both : -(float)both;
+    if (j < nblk) byte_chunk_acc<METRIC>(ab, aa, qq, __builtin_bit_cast(uint4, rr[j]), __builtin_bit_cast(uint4, q_blk(qv, j, h)));
+  return byte_reduce<METRIC>(ab, aa, qq);
 #else
   if (METRIC == 1) {  // mips_pair_ct's arithmetic: one running scalar, products rounded then added in index order, fused tail
     const int tail_from = (ix.d & ~7) >> 3;
@@ -2073,30 +1963,29 @@ __device__ __forceinline__ float row_regs_score(const RowRegs<NR> &rr, const flo
 #pragma unroll
     for (int t = 0; t < NR; t++)
       if (t < nblk) {
-        const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * t + 4 * h);
-        r = mips_step(r, cvt_blk(rr_blk(rr, t)), q, t >= tail_from);
+        const float4 q = q_blk(qv, t, h);
+        r = mips_step(r, row_blk(rr, t), q, t >= tail_from);
       }
     return -r;
   }
-  // l2_pair_ct's arithmetic: blocks in the reference's order (an odd count: last block first)
+  // l2_pair_ct's arithmetic: blocks in the reference's order (an odd count -- 13 is the only one held -- last block first)
   f32x2 alo = {0.f, 0.f}, ahi = {0.f, 0.f};
   int nfull = nblk;
   if (NR > 12 && nblk == 13) {
-    const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * 12 + 4 * h);
-    sq_acc(alo, ahi, cvt_blk(rr_blk(rr, NR > 12 ? 12 : 0)), q);
+    const float4 q = q_blk(qv, 12, h);
+    l2_step(alo, ahi, row_blk(rr, NR > 12 ? 12 : 0), q);
     nfull = 12;
   }
 #pragma unroll
   for (int i = 0; i < NR; i++)
     if (i < nfull) {
-      const float4 q = *reinterpret_cast<const float4 *>(qv + 8 * i + 4 * h);
-      sq_acc(alo, ahi, cvt_blk(rr_blk(rr, i)), q);
+      const float4 q = q_blk(qv, i, h);
+      l2_step(alo, ahi, row_blk(rr, i), q);
     }
-  const float s = ((alo.x + alo.y) + ahi.x) + ahi.y;
-  const float other = __shfl_xor(s, 1);
-  return (((other + alo.x) + alo.y) + ahi.x) + ahi.y;
+  return l2_reduce(alo, ahi);
 #endif
 }
+
 
 // Request the rows of a hop's kept neighbours (lanes flagged `take`, entry `a`): the r-th flagged lane pushes its id to lane
 // pair r (first pass: r < 32), the pair's lanes request half a row each.  r / nt: rank of this lane among the flagged, their number.
@@ -2128,7 +2017,7 @@ __device__ __forceinline__ void mid_request_rows(const IndexView &ix, int a, boo
   const int got = __builtin_amdgcn_ds_permute(now ? (r << 3) : 4, a);
   const int ev = pair_even_value(got);
   const int id = ((lane >> 1) < nt) ? ev : 0;  // idle pairs fetch node 0: no branches
-  row_regs_load<RowRegsFor<METRIC>::NR, NBC>(rr, ix.points + (row_off + id) * (int64_t)ix.stride, lane & 1, mode);
+  row_blks_load<RowRegsFor<METRIC>::NR, NBC>(rr, ix.points + (row_off + id) * (int64_t)ix.stride, lane & 1, mode);
 }
 
 // ... and their distances: every flagged lane receives the distance of its entry
@@ -2139,7 +2028,7 @@ __device__ __forceinline__ float mid_take_distances(const IndexView &ix, int a, 
   if (nt == 0) return 0.f;
   // (no registers held across the hop: the compile-time routines where the row shape has one -- a whole row per lane pair in flight,
   // one round trip per pass)
-  // (a kernel that holds RowRegs for other row shapes has no room for a second whole row: the lean routines there)
+  // (a kernel that holds rows across the hop for other row shapes has no room for a second whole row: the lean routines there)
   if (RowRegsFor<METRIC>::NR == 0 || mode == 0) return wave_distances_own<METRIC, (RowRegsFor<METRIC>::NR != 0)>(ix, a, take, qv, row_off);
   const int lane = lane_id(), h = lane & 1;
   float mine = 0.f;
@@ -2154,7 +2043,7 @@ __device__ __forceinline__ float mid_take_distances(const IndexView &ix, int a, 
     const int ev = pair_even_value(got);
     const int id = (32 + (lane >> 1) < nt) ? ev : 0;
     typename RowRegsFor<METRIC>::type r2;  // (registers of its own: `rr` has ONE definition per hop, or the compiler copies it around)
-    row_regs_load<RowRegsFor<METRIC>::NR, NBC>(r2, ix.points + (row_off + id) * (int64_t)ix.stride, h, mode);
+    row_blks_load<RowRegsFor<METRIC>::NR, NBC>(r2, ix.points + (row_off + id) * (int64_t)ix.stride, h, mode);
     const float dd = row_regs_score<METRIC, RowRegsFor<METRIC>::NR, NBC>(r2, qv, ix, h, mode);
     const float back = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((((r - 32) << 1) | 1) << 2, __builtin_bit_cast(int, dd)));
     if (now) mine = back;

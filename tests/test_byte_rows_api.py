@@ -118,3 +118,22 @@ def test_six_is_not_a_public_dtype(wa, lib):
                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int,
                                       ctypes.c_int]
     assert lib.wann_index_create(0, 0, 6, x.ctypes.data, 8, 4, labels.ctypes.data, 4, 2.0, 0.5, None, 0, 1) is None
+
+
+def test_byte_rows_kernels_register_budget(wa):
+    """the one-byte unit's k_search<METRIC, KIND, 6> kernels (3 kernels x 2 metrics) and k_brute_staged for both metrics: no
+    scratch segment, and within the register budget of the float32 launch shapes they reuse (at most 256 registers: two
+    four-wave workgroups per CU)"""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(REPO, "tools", "kernel_resources.py"), "dt_w8"], capture_output=True, text=True,
+                         timeout=300)
+    if out.returncode != 0 or not out.stdout.strip():
+        pytest.skip("ROCm llvm tools not present")
+    lines = out.stdout.splitlines()
+    search = [l for l in lines if "k_search" in l]
+    assert len(search) == 6 and all("ELi6EEEv" in l for l in search)
+    assert len(lines) >= 8  # (+ k_brute_staged for both metrics)
+    for l in lines:
+        assert int(l.split("vgpr+agpr")[1].split()[0]) <= 256, l
+        assert int(l.split("scratch")[1].split()[0]) == 0, l
