@@ -65,8 +65,9 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * HALF-PRECISION SHADOW ROWS of a float32 index.  A WANN_DTYPE_F32 index that has graphs (the post filter, the graph-backed tree,
  * the super tree) and whose n x d values are ALL finite binary16 values -- wann_rows_fp16_exact: half(x) converts back to the bits
  * of x, which keeps -0.0 and the binary16 subnormals and drops NaN, the infinities and |x| > 65504; SIFT / BIGANN vectors, integers
- * in [0, 255], qualify -- keeps a second copy of its points as half rows (64-byte padded, wann_half_rows_bytes) and its BEAM
- * SEARCHES read that copy through the float16 kernels: the same rows, distance bits and operation counters (see above), half the
+ * in [0, 255], qualify -- keeps a second copy of its points as half rows (64-byte padded, elements paired inside groups of 16 --
+ * wann_half_row_position: wann_half_rows_bytes) and its BEAM
+ * SEARCHES read that copy through the float16 kernels' arithmetic (a kernel unit of its own for the paired rows): the same rows, distance bits and operation counters (see above), half the
  * vector bytes per scored row.  Everything else -- routing, the exact scans (unless wann_set_scan_rows is on, below), the dense
  * path, the GPU builder, the raw-search hooks, the unfiltered wann_vamana_* API -- reads the float32 rows, which stay where they were.  The property is tested once,
  * when the index is created; an index that is not eligible (or found no memory for the copy) has no shadow and behaves as before.
@@ -312,8 +313,15 @@ int64_t wann_device_bytes(const wann_index *index);  /* (without the shadow rows
  * returns 0.  Allocates and frees nothing; applies to every replica of WANN_DEVICES; a NEGATIVE error for a null index.
  * wann_half_rows: that setting.  wann_half_rows_bytes: device bytes of the shadow rows, n * 64 * ceil(2 d / 64), or 0 without one.
  * wann_last_half_rows: 1 if the beam searches of the last finished batch -- the last blocking call, or the ticket last waited
- * for -- read the shadow rows (wann_counters keeps its ABI 5 layout, so this is a call of its own). */
+ * for -- read the shadow rows (wann_counters keeps its ABI 5 layout, so this is a call of its own).
+ * wann_half_row_position: the LAYOUT of the device copy, as a pure function (no device, no index): the position, counted in
+ * halves, inside a half shadow row at which element `element` of the row is stored,
+ *     16 (e >> 4) + 8 ((e >> 2) & 1) + 4 ((e >> 3) & 1) + (e & 3)
+ * -- a permutation inside every aligned group of 16 elements that lets a lane of the search kernels fetch two of its 4-element
+ * blocks with one 16-byte load; -1 for a negative argument.  The row pitch and wann_half_rows_bytes do not depend on it, and
+ * float16 / bfloat16 indexes keep the natural order. */
 int wann_rows_fp16_exact(const float *rows, int64_t n, int64_t d);
+int64_t wann_half_row_position(int64_t element);
 int wann_set_half_rows(wann_index *index, int on);
 int wann_half_rows(const wann_index *index);
 int64_t wann_half_rows_bytes(const wann_index *index);

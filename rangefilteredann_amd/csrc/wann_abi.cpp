@@ -768,6 +768,8 @@ int wann_half_rows(const wann_index *I) {
 }
 
 int64_t wann_half_rows_bytes(const wann_index *I) { return I ? (int64_t)I->d_half.bytes() : -1; }
+
+int64_t wann_half_row_position(int64_t element) { return element < 0 ? -1 : h16_row_position(element); }
 int wann_last_half_rows(const wann_index *I) { return I ? I->last_half_rows.load() : 0; }
 
 int wann_rows_u8_exact(const float *rows, int64_t n, int64_t d) {

@@ -245,7 +245,7 @@ static BatchPlan plan_batch(const wann_index &I, const Tuning &T, const wann_que
   P.verbose_call = qp.verbose != 0 && H.vamana_leaves;
   P.verbose_route = qp.verbose != 0 && (tree || P.kind == WANN_KIND_SUPER);
   // The view the beam-search launches (k_search) read: the half-precision shadow rows where the index has them and the switch
-  // is on -- the float16 unit's kernels, which score a row in the float32 kernels' arithmetic and order after an exact
+  // is on -- the float16 kernels in their unit for paired rows (wann_kernels_h16.hip), which score a row in the float32 kernels' arithmetic and order after an exact
   // conversion: same rows, same counters, half the vector bytes.  Routing, the dense path and k_finalize keep I.view; so do the
   // exact scans unless wann_set_scan_rows is on (scan_store, below).
   // The one-byte shadow rows (wann_set_byte_rows, opt-in) go before them: the same argument with a quarter of the bytes.
@@ -407,7 +407,8 @@ bool Batch::prefilter_dense_gate() const {
 // Workgroups of a scan over a shadow view (wann_set_scan_rows) that a CU holds at once; a workgroup puts one wave on each SIMD.
 // By the registers of the compiled kernels, 512 / VGPRs (profiles/scan_rows_kernel_resources.txt): the float16 unit's k_brute on
 // the half rows 160 (squared L2) / 117 (inner product); k_brute_staged on the one-byte rows 148 / 128 -- and there by the LDS of
-// the staged rows too, whichever is fewer.
+// the staged rows too, whichever is fewer.  (The paired half rows' own k_brute, wann_kernels_h16.hip, has 122 / 116 registers;
+// it keeps the float16 unit's launch shape.)
 static int scan_rows_per_cu(const IndexView &V, int k) {
   const bool mips = V.metric == 1;
   if (V.dtype != kRowsU8Widened) return mips ? 4 : 3;

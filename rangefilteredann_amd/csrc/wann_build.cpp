@@ -213,6 +213,21 @@ void interleave_u8_rows(float *rows, int64_t n, int64_t words, int threads) {
   });
 }
 
+// Half rows in natural order into the layout the half shadow rows' device copy has (h16_row_position, wann_device.h), in
+// place: a permutation of the halves of every aligned group of 16, padding included -- a row is `words` 32-bit words, a whole
+// number of groups.
+void interleave_h16_rows(float *rows, int64_t n, int64_t words, int threads) {
+  if (words <= 0 || words % 8 != 0) throw std::runtime_error("interleave_h16_rows: a row is a whole number of 32-byte groups");
+  parallel_for(n, threads > 0 ? threads : default_threads(), [&](int64_t r) {
+    uint16_t *row = reinterpret_cast<uint16_t *>(rows + r * words);
+    for (int64_t g = 0; g < words * 2; g += 16) {
+      uint16_t t[16];
+      for (int e = 0; e < 16; e++) t[h16_row_position(e)] = row[g + e];
+      memcpy(row + g, t, 32);
+    }
+  });
+}
+
 // ------------------------------------------------------------------------------------------------
 // numerics (same evaluation order as the kernels; built with -ffp-contract=off)
 // ------------------------------------------------------------------------------------------------

@@ -71,6 +71,10 @@ void pack_u8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64
 // packed rows (natural order) into the device copy's layout, in place: the byte at position e of a row moves to position
 // u8_row_position(e) (wann_device.h: a permutation inside every aligned 32 bytes).  `words` 32-bit words per row, a multiple of 8.
 void interleave_u8_rows(float *rows, int64_t n, int64_t words, int threads);
+// half rows (natural order, zero padded) into the half shadow rows' device layout, in place: the half at position e of a row
+// moves to position h16_row_position(e) (wann_device.h: a permutation inside every aligned 16 halves).  `words` 32-bit words
+// per row, a multiple of 8.
+void interleave_h16_rows(float *rows, int64_t n, int64_t words, int threads);
 
 // metric: bit 0 = inner product, bits 4-5 = element type of the rows behind p / q (0 float32, 1 uint8, 2 int8; float16 point
 // sets are built from their float32 upcast and pass 0)

@@ -44,13 +44,27 @@ struct IndexView {
   int32_t d, stride, rs, maxdeg, metric, kind, nlevels, cutoff, split, vamana_leaves;
   int32_t dtype;  // element type of `points` (wann.h WANN_DTYPE_*): float32 rows, uint8 / int8 rows of d bytes padded to a
                   // multiple of 64, or float16 / bfloat16 rows of d two-byte elements padded to a multiple of 32 -- `stride` counts 32-bit words in every
-                  // case and `points` is addressed in words.  6 (kRowsU8Widened, below) only in the view of a float32 index's one-byte shadow rows
+                  // case and `points` is addressed in words.  6 (kRowsU8Widened, below) only in the view of a float32 index's one-byte shadow rows,
+                  // 7 (kRowsF16Paired) only in the view of its half shadow rows
 };
 
 // two-byte float rows: float16 (3) and bfloat16 (5) share the row pitch and layout rules -- d elements in natural order, zero
-// padded to a multiple of 32 (64 B) -- and the staged query's length (WANN_HALF_ROWS in wann_wave.h is the device side)
-constexpr bool two_byte_rows(int dtype) { return dtype == 3 || dtype == 5; }
+// padded to a multiple of 32 (64 B) -- and the staged query's length (WANN_HALF_ROWS in wann_wave.h is the device side); the
+// half shadow rows of a float32 index (7, below) share all of it but the order of the elements inside a group of 16
+// Half shadow rows of a float32 index (dtype 7: an INTERNAL view type like 6 below, never a WANN_DTYPE_* the C ABI accepts): the
+// float16 rows' values, pitch and padding with the halves of every aligned group of 16 elements PAIRED (h16_row_position); the
+// kernels of wann_kernels_h16.hip read them, and every predicate treats such a view as a float16 one.
+constexpr int kRowsF16Paired = 7;
+constexpr bool two_byte_rows(int dtype) { return dtype == 3 || dtype == 5 || dtype == kRowsF16Paired; }
 constexpr int64_t two_byte_stride_words(int64_t d) { return ((d * 2 + 63) / 64) * 16; }
+// THE LAYOUT of the half shadow rows' device copy (wann_index::d_half, search_view), stated once: a row keeps its pitch, and
+// inside every aligned group of 16 elements the halves are permuted -- element e of a row sits at half h16_row_position(e) of
+// it.  Lane h of a lane pair owns the blocks 8 b + 4 h (wann_wave.h), and its two blocks b = 2 c and 2 c + 1 are the 16
+// contiguous bytes at byte 32 c + 16 h of the row: one 16-byte load per lane brings two blocks (a PAIR).  Rows stay padded with
+// zeros to 64 bytes, so every pair exists and is 16-byte aligned.  interleave_h16_rows (wann_build.h) turns natural-order rows
+// into this order before the upload; wann_half_row_position (wann.h) is this function.  Native float16 / bfloat16 indexes keep
+// the natural order: the dense path, the build kernels and finalisation read those rows.
+constexpr int64_t h16_row_position(int64_t e) { return 16 * (e >> 4) + 8 * ((e >> 2) & 1) + 4 * ((e >> 3) & 1) + (e & 3); }
 
 // One-byte shadow rows of a float32 index (dtype 6: an INTERNAL view type, never a WANN_DTYPE_* the C ABI accepts): every value
 // is an integer 0 .. 255 stored as a uint8 -- d bytes, zero padded to a multiple of 64 -- and the beam-search

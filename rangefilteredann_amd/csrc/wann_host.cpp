@@ -120,6 +120,7 @@ void upload_index(wann_index &I) {
         uint16_t *dst = reinterpret_cast<uint16_t *>(rows.data() + r * hstride);
         for (int64_t j = 0; j < s.d; j++) dst[j] = float_to_half(src[j]);
       });
+      interleave_h16_rows(rows.data(), s.n, hstride, s.threads);  // (the copy's layout: h16_row_position, wann_device.h)
       I.d_half.upload(rows);
     }
   }
@@ -230,7 +231,7 @@ void upload_index(wann_index &I) {
   if (I.d_half.p) {
     I.search_view.points = I.d_half.p;
     I.search_view.stride = (int32_t)(((s.d * 2 + 63) / 64) * 16);
-    I.search_view.dtype = WANN_DTYPE_F16;
+    I.search_view.dtype = kRowsF16Paired;
     I.half_rows_on = true;
   }
   I.byte_view = v;

@@ -148,7 +148,7 @@ struct wann_index {
   // points as halves, 64-byte padded -- what a float16 index of these points keeps in d_points.  Only the beam-search launches
   // (k_search) read them, through search_view; everything else reads d_points.  Empty: no shadow (not eligible, or no memory).
   DevBuf<float> d_half;
-  IndexView search_view{};     // `view` with points = d_half, the half stride and dtype = WANN_DTYPE_F16 (valid when d_half.p)
+  IndexView search_view{};     // `view` with points = d_half (paired: h16_row_position), the half stride and dtype = kRowsF16Paired (valid when d_half.p)
   bool half_rows_on = false;   // wann_set_half_rows (under tune_mu; on when a shadow exists): the next batch searches the shadow
   std::atomic<int> last_half_rows{0};  // the last finished batch (blocking call / ticket waited for) searched the shadow
   // One-byte shadow rows of a float32 index whose every value is an integer 0 .. 255 (rows_u8_exact) and that has graphs: the
@@ -268,7 +268,7 @@ inline bool known_dtype(int dtype) {
 inline bool byte_rows(const IndexView &v) { return v.dtype == WANN_DTYPE_U8 || v.dtype == WANN_DTYPE_I8; }
 // this view's four-wave k_search is built for THREE waves per SIMD (at most 168 registers): the inner-product and byte-row
 // kernels.  The squared-L2 kernels keep two whole rows per lane pair in flight and are built for two: float32 needs 256
-// registers, float16 (k_search<0, 0, 3>) 215 -- see DESIGN.md 3.10.
+// registers, float16 (k_search<0, 0, 3>) 215, the paired half shadow rows (k_search<0, 0, 7>) 189 -- see DESIGN.md 3.10.
 inline bool three_waves_per_simd(const IndexView &v) { return v.metric == 1 || byte_rows(v); }
 BuildSpec make_spec(int kind, int metric, int dtype, int64_t n, int64_t d, int32_t cutoff, double split_factor, double shift_factor,
                     const wann_build_params *bp, int threads);

@@ -24,7 +24,7 @@
 
 namespace wann {
 
-// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip / _w8.hip before this body is
+// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip / _w8.hip / _h16.hip before this body is
 // included): the search and scan kernels and their launchers live in a per-type namespace; the type-independent
 // kernels (routing, finalisation) and the dispatchers are compiled with the float32 unit only.
 #if WANN_DT == 0
@@ -37,6 +37,8 @@ namespace wann {
 #define WANN_DT_NS dt_f16
 #elif WANN_DT == 5
 #define WANN_DT_NS dt_bf16
+#elif WANN_DT == 7
+#define WANN_DT_NS dt_h16  // (the half shadow rows of a float32 index, paired: its k_search and, under wann_set_scan_rows, its plain k_brute)
 #else
 #define WANN_DT_NS dt_w8  // (the one-byte shadow rows of a float32 index: its k_search and, under wann_set_scan_rows, its scan)
 #endif
@@ -50,6 +52,8 @@ namespace wann {
 #define WANN_DT_TPARAM , int ROWS_DT = 5
 #elif WANN_DT == 6  // (and the one-byte shadow rows' unit)
 #define WANN_DT_TPARAM , int ROWS_DT = 6
+#elif WANN_DT == 7  // (and the paired half shadow rows')
+#define WANN_DT_TPARAM , int ROWS_DT = 7
 #else
 #define WANN_DT_TPARAM
 #endif
@@ -752,7 +756,7 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
 // k_brute: exact top-k over rows [a,b) of the sorted order (T_BRUTE) or over the label-argsort
 // positions [a,b) of an unsorted point set (T_BRUTE_GATHER, prefiltering.h:189-194)
 // The unit of the one-byte shadow rows and the float16 unit serve the shadow views of a float32 index under wann_set_scan_rows:
-// the half view takes the float16 unit's k_brute as it is.
+// the half view takes the plain k_brute of its own unit (wann_kernels_h16.hip: the float16 unit's, on paired rows).
 // k_brute_staged (the one-byte unit): the rows of a pass -- contiguous in a T_BRUTE task -- reach the lane pairs through the
 // LDS: scan_fetch (wann_device.h) copies the span with 16-byte loads, and wave_distances scores a view of the staging area, the
 // same routines on the same blocks in the same order.  (On the half view the same fetch lost to the plain one: DESIGN.md 3.4.)
@@ -1594,20 +1598,28 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
 int launch_brute(const BruteArgs &a, int blocks, void *stream);
 }
+namespace dt_h16 {  // (a view of paired half shadow rows, likewise)
+int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
+int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
+int launch_brute(const BruteArgs &a, int blocks, void *stream);
+}
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
   return a.ix.dtype == 1 ? dt_u8::search_occupancy(a, cfg) : a.ix.dtype == 2 ? dt_i8::search_occupancy(a, cfg)
        : a.ix.dtype == 3 ? dt_f16::search_occupancy(a, cfg) : a.ix.dtype == 5 ? dt_bf16::search_occupancy(a, cfg)
-       : a.ix.dtype == kRowsU8Widened ? dt_w8::search_occupancy(a, cfg) : dt_f32::search_occupancy(a, cfg);
+       : a.ix.dtype == kRowsU8Widened ? dt_w8::search_occupancy(a, cfg) : a.ix.dtype == kRowsF16Paired ? dt_h16::search_occupancy(a, cfg)
+       : dt_f32::search_occupancy(a, cfg);
 }
 int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
   return a.ix.dtype == 1 ? dt_u8::launch_search(a, cfg, stream) : a.ix.dtype == 2 ? dt_i8::launch_search(a, cfg, stream)
        : a.ix.dtype == 3 ? dt_f16::launch_search(a, cfg, stream) : a.ix.dtype == 5 ? dt_bf16::launch_search(a, cfg, stream)
-       : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_search(a, cfg, stream) : dt_f32::launch_search(a, cfg, stream);
+       : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_search(a, cfg, stream) : a.ix.dtype == kRowsF16Paired ? dt_h16::launch_search(a, cfg, stream)
+       : dt_f32::launch_search(a, cfg, stream);
 }
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   return a.ix.dtype == 1 ? dt_u8::launch_brute(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_brute(a, blocks, stream)
        : a.ix.dtype == 3 ? dt_f16::launch_brute(a, blocks, stream) : a.ix.dtype == 5 ? dt_bf16::launch_brute(a, blocks, stream)
-       : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_brute(a, blocks, stream) : dt_f32::launch_brute(a, blocks, stream);
+       : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_brute(a, blocks, stream) : a.ix.dtype == kRowsF16Paired ? dt_h16::launch_brute(a, blocks, stream)
+       : dt_f32::launch_brute(a, blocks, stream);
 }
 
 int launch_finalize(const FinalizeArgs &a, void *stream) {

@@ -85,10 +85,11 @@ __device__ __forceinline__ u64 hash64_2(u64 x) {
 // --------------------------------------------------------------------------------------------
 #ifndef WANN_DT
 #define WANN_DT 0  // 0 = float32 rows, 1 = uint8, 2 = int8, 3 = float16, 5 = bfloat16 (4 is unassigned, see wann.h),
-                   // 6 = the one-byte shadow rows of a float32 index (internal: kRowsU8Widened in wann_device.h)
+                   // 6 = the one-byte shadow rows of a float32 index (internal: kRowsU8Widened in wann_device.h),
+                   // 7 = its half shadow rows, paired (internal: kRowsF16Paired)
 #endif
 #define WANN_BYTE_ROWS (WANN_DT == 1 || WANN_DT == 2)
-#define WANN_HALF_ROWS (WANN_DT == 3 || WANN_DT == 5)  // two-byte float rows (two_byte_rows in wann_device.h is the host side)
+#define WANN_HALF_ROWS (WANN_DT == 3 || WANN_DT == 5 || WANN_DT == 7)  // two-byte float rows (two_byte_rows in wann_device.h is the host side)
 // rows narrower than float32, scored as their exact float32 upcast against the fp32 query (widened_rows is the host side)
 #define WANN_WIDENED_ROWS (WANN_HALF_ROWS || WANN_DT == 6)
 
@@ -99,7 +100,8 @@ __device__ __forceinline__ u64 hash64_2(u64 x) {
 // preserved by the kernels' default FP mode), and the arithmetic that follows is the float32 path's own, in its own order -- a
 // float16 row scores to the bits of its float32 upcast.  The distance routines hold a row's blocks in RowBlks (below): as they
 // were fetched (halves: half the registers of a float32 block), converted where a block is consumed.  Only RowBlks' loaders
-// know how a unit fetches: ld_blk, one load per block, here and for float32 / bfloat16 / byte rows.
+// know how a unit fetches: ld_blk, one load per block, here and for float32 / bfloat16 / byte rows (the two shadow-row units
+// of a float32 index, 6 and 7, permute the elements inside a row and fetch 16 bytes at a time: below).
 // (macros: the float32 and byte-row units compile exactly the expressions they compiled before the float16 unit existed)
 #if WANN_DT == 3
 typedef uint2 rowblk_t;
@@ -108,6 +110,23 @@ __device__ __forceinline__ float4 h4_to_f4(uint2 w) {
   return make_float4(h2f(w.x & 0xffffu), h2f(w.x >> 16), h2f(w.y & 0xffffu), h2f(w.y >> 16));
 }
 #define ld_blk(prow, e) (*reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(prow) + (e)))
+#define cvt_blk(w) h4_to_f4(w)
+#elif WANN_DT == 7
+// the half shadow rows of a float32 index: the float16 unit's blocks and conversion, and so its arithmetic, block order, lane
+// pairing and accumulators.  Only the fetch differs.  The rows are PAIRED (h16_row_position, wann_device.h): the blocks
+// 8 b + 4 h of lane h, b = 2 c and 2 c + 1, are the 16 contiguous bytes at 32 c + 16 h of the row -- one 16-byte load
+// (ld_pair), split at once into the two blocks' slots: RowBlks stays one uint2 per block, as in the float16 unit (held as
+// 16-byte pairs the four-wave kernel spilled).  The loaders issue the pairs that hold a block below the count, in pair order; a
+// block at or beyond the row's count is never consumed (the padding is zero, but the staged query ends with the row).  Rows
+// start on multiples of 64 bytes, so every pair is 16-byte aligned.  (Like the one-byte unit this one has no ld_blk: a single
+// block's address would follow the natural order.)
+typedef uint2 rowblk_t;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float h2f(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
+__device__ __forceinline__ float4 h4_to_f4(uint2 w) {
+  return make_float4(h2f(w.x & 0xffffu), h2f(w.x >> 16), h2f(w.y & 0xffffu), h2f(w.y >> 16));
+}
+#define ld_pair(prow, c, h) (*reinterpret_cast<const u32x4 *>(reinterpret_cast<const unsigned char *>(prow) + 32 * (c) + 16 * (h)))
 #define cvt_blk(w) h4_to_f4(w)
 #elif WANN_DT == 5
 // bfloat16 rows: the float16 rows' layout and blocks.  A bfloat16 is the top 16 bits of a float32, so the conversion is
@@ -187,7 +206,8 @@ using RowBlks = rowheld_t[N > 0 ? (N + kHeldBlks - 1) / kHeldBlks : 1];
 // The loader: slot j of `rb` receives block b0 + j of the row.  NBC > 0: the blocks 0 .. NBC - 1, a compile-time count (no branch
 // per block, the loads go out back to back and the scoring waits for them one by one); NBC = 0: the blocks below `nblk`, at
 // run time.  The one-byte shadow rows issue the quads that hold a block below the count, in quad order (b0 a
-// multiple of 4).  Every other unit issues one ld_blk per block -- the same addresses for float32 rows under either metric
+// multiple of 4), the paired half shadow rows the pairs that do, each split into its two slots (b0 even).  Every other unit
+// issues one ld_blk per block -- the same addresses for float32 rows under either metric
 // and for byte rows -- in index order, or, LAST_FIRST, in the order a squared-L2 routine consumes them.
 template <int N, int NBC = 0, bool LAST_FIRST = false>
 __device__ __forceinline__ void row_blks_load(RowBlks<N> &rb, const float *__restrict__ prow, int h, int nblk = 0, int b0 = 0) {
@@ -195,6 +215,14 @@ __device__ __forceinline__ void row_blks_load(RowBlks<N> &rb, const float *__res
 #pragma unroll
   for (int c = 0; c < (N + 3) / 4; c++)
     if (NBC > 0 ? 4 * c < NBC : b0 + 4 * c < nblk) rb[c] = ld_quad(prow, (b0 >> 2) + c, h);
+#elif WANN_DT == 7
+#pragma unroll
+  for (int c = 0; c < (N + 1) / 2; c++)  // (b0 even; the second block of a last pair may lie beyond the count: never consumed)
+    if (NBC > 0 ? 2 * c < NBC : b0 + 2 * c < nblk) {
+      const u32x4 p = ld_pair(prow, (b0 >> 1) + c, h);
+      rb[2 * c] = make_uint2(p.x, p.y);
+      if (2 * c + 1 < N) rb[2 * c + 1] = make_uint2(p.z, p.w);
+    }
 #else
 #pragma unroll
   for (int i = 0; i < N; i++) {
@@ -241,19 +269,26 @@ __device__ __forceinline__ float l2_reduce(const f32x2 &lo, const f32x2 &hi) {
 //    batch -- no load that is waited for on its own;
 //  * quads: a batch in the walk's order would span NB / 4 + 1 quads whenever the count is odd.  The last block of an odd
 //    count comes from a load of its own (its quad, the word picked by wave-uniform selects), and the batches behind it
-//    walk the blocks below it in index order from quad boundaries: NB / 4 quads in flight.
+//    walk the blocks below it in index order from quad boundaries: NB / 4 quads in flight.  The paired half shadow rows
+//    take this form with pairs: the last block of an odd count is the first half of its pair, NB / 2 pairs in flight.
 template <int NB>
 __device__ __forceinline__ float l2_pair(const float *__restrict__ prow, const float *qv, int D8,
                                          int h, bool active) {
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   if (active) {
-#if WANN_DT == 6
+#if WANN_DT == 6 || WANN_DT == 7
     const int nfull = D8 & ~1;
     if (D8 & 1) {
       const int b = D8 - 1;
+#if WANN_DT == 6
       const u32x4 last = ld_quad(prow, b >> 2, h);
       const float4 q = q_blk(qv, b, h);
       l2_step(a0, a1, a2, a3, cvt_blk(quad_blk(last, b & 3)), q);
+#else
+      const u32x4 last = ld_pair(prow, b >> 1, h);  // (b is even: the first block of its pair, the second is padding)
+      const float4 q = q_blk(qv, b, h);
+      l2_step(a0, a1, a2, a3, cvt_blk(make_uint2(last.x, last.y)), q);
+#endif
     }
     for (int b0 = 0; b0 < nfull; b0 += NB) {
       RowBlks<NB> buf;

@@ -621,6 +621,8 @@ PYBIND11_MODULE(_window_ann, m) {
   m.def("abi_version", [] { return wann_abi_version(); });
   // the byte of a one-byte shadow row (the device copy) at which element `e` of the row is stored; -1 for a negative e
   m.def("byte_row_position", [](int64_t e) { return wann_byte_row_position(e); }, py::arg("element"));
+  // the half of a half shadow row (the device copy) at which element `e` of the row is stored; -1 for a negative e
+  m.def("half_row_position", [](int64_t e) { return wann_half_row_position(e); }, py::arg("element"));
   m.def(
       "build_cache_shard",
       [](int kind, int metric, FArray points, FArray labels, int32_t cutoff, double split, double shift,
