@@ -92,6 +92,21 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * order: the same ids, distance bits and operation counters (brute_rows included) with a quarter or half of the row bytes.  OFF
  * by default.  The dense path (exact-window batches included), routing, the finalisation, the GPU builder and the raw hooks keep
  * the float32 rows.
+ * DENSE SCORES FROM ONE-BYTE ROWS (opt-in).  After wann_set_dense_rows(index, 1) the SCORE launches of the MFMA prefilter path
+ * (k_gemm_scores: shared windows, the cover groups of wann_set_dense_windows, the exact windows of wann_set_exact_windows) read
+ * a one-byte copy of the rows instead of the float32 rows: a quarter of the bytes fetched.  An integer 0 .. 255 is exactly one
+ * bfloat16 value, so the kernel is the bfloat16 index's (one staged row per point, two products per step) behind a fetch that
+ * widens each byte, and its scores are the float32 kernel's.  Only those launches change their source: the point norms, the
+ * selection, the proof bound, the exact re-rank and the finalisation read the float32 rows as before -- the same ids, distance
+ * bits and dense counters (gemm_queries / gemm_unproven / gemm_rescued, wann_dense_window_counters, wann_exact_window_counters).
+ * Which indexes have such a copy: the graph-backed tree and the super tree read their one-byte shadow rows (nothing more is
+ * allocated); a WANN_DTYPE_F32 PrefilterIndex whose points pass wann_rows_u8_exact keeps a copy of its own in the same layout
+ * (wann_byte_row_position) and the row order of its points -- not a shadow of the kind above: wann_byte_rows_bytes stays 0 and
+ * wann_set_byte_rows / wann_set_scan_rows stay refused there.  Rows of up to 128 elements only (the score kernel's narrow
+ * class): longer rows have no copy for this path.  The post filter, the prefilter-leaf tree, byte / float16 / bfloat16 indexes
+ * and points that are not eligible have none either.  wann_device_bytes does not count the copy.  OFF by default, and
+ * independent of wann_set_byte_rows / wann_set_scan_rows.  The contract is for FINITE queries: the float32 score kernels
+ * already assume finite scores, and so does this one.
  * WANN_DTYPE_BF16 (not a type of the reference): bfloat16 points, rows of uint16_t bit patterns (the top 16 bits of a float32:
  * float32's exponent range, 8 significant bits).  Everything said of WANN_DTYPE_F16 holds with "bfloat16" for "binary16": the
  * same row pitch and layout (natural order, zero padded to 32 elements), the widening -- one shift, exact for every pattern,
@@ -360,6 +375,21 @@ int wann_last_byte_rows(const wann_index *index);
 int wann_set_scan_rows(wann_index *index, int on);
 int wann_scan_rows(const wann_index *index);
 int wann_last_scan_rows(const wann_index *index);
+/* Dense scores from one-byte rows (see WANN_DTYPE_*).
+ * wann_set_dense_rows: whether the score launches of the dense path of the NEXT batches read the one-byte copy of the rows (a
+ * batch submitted earlier keeps what it was submitted with, the asynchronous lanes included).  Returns the setting now in
+ * force, 0 / 1: asking for 1 on an index without a copy this path can read (see above) leaves it at 0 and returns 0.  Allocates
+ * and frees nothing; applies to every replica of WANN_DEVICES; a NEGATIVE error for a null index.  Independent of
+ * wann_set_byte_rows and wann_set_scan_rows.
+ * wann_dense_rows: that setting (0 after wann_index_create).
+ * wann_dense_rows_bytes: device bytes of the copy the dense path would read, n * 64 * ceil(d / 64) -- on a tree index the bytes
+ * wann_byte_rows_bytes reports, the same buffer -- or 0 without one; -1 for a null index.
+ * wann_last_dense_rows: 1 if a score launch of the last finished batch read the copy; 0 for a batch whose dense path scored no
+ * query (or launched nothing). */
+int wann_set_dense_rows(wann_index *index, int on);
+int wann_dense_rows(const wann_index *index);
+int64_t wann_dense_rows_bytes(const wann_index *index);
+int wann_last_dense_rows(const wann_index *index);
 /* In-process multi-device mode: with WANN_DEVICES=a,b,... in the environment wann_index_create makes the index resident on
  * every listed device (a device may be listed twice) and wann_batch_search -- the host-buffer call, the reference's boundary
  * (src/range_filter_tree.h:62-96: one call parallelises over all queries) -- cuts its batch into contiguous shards, one host

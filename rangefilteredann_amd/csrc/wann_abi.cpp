@@ -828,6 +828,31 @@ int wann_scan_rows(const wann_index *I) {
 }
 
 int wann_last_scan_rows(const wann_index *I) { return I ? I->last_scan_rows.load() : 0; }
+
+int wann_set_dense_rows(wann_index *I, int on) {
+  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
+  // (tune_mu, as wann_set_half_rows: nothing is allocated or freed, a batch in flight keeps its snapshot)
+  int now;
+  {
+    std::lock_guard<std::mutex> lk(I->tune_mu);
+    now = I->dense_rows_on = on != 0 && I->has_dense_copy();
+  }
+  for (auto &R : I->replicas) {
+    std::lock_guard<std::mutex> lr(R->tune_mu);
+    R->dense_rows_on = on != 0 && R->has_dense_copy();
+  }
+  return now;
+}
+
+int wann_dense_rows(const wann_index *I) {
+  if (!I) return 0;
+  wann_index *M = const_cast<wann_index *>(I);
+  std::lock_guard<std::mutex> lk(M->tune_mu);
+  return I->dense_rows_on ? 1 : 0;
+}
+
+int64_t wann_dense_rows_bytes(const wann_index *I) { return I ? I->dense_copy_bytes() : -1; }
+int wann_last_dense_rows(const wann_index *I) { return I ? I->last_dense_rows.load() : 0; }
 int wann_num_replicas(const wann_index *I) { return I ? 1 + (int)I->replicas.size() : -1; }
 
 int wann_build_cache_shard(int kind, int metric, int dtype, const void *points, int64_t n, int64_t d,

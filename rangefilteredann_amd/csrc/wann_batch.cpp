@@ -19,6 +19,14 @@ static bool dense_rows_ok(const wann_index &I, const Tuning &T, int k) {
   return k <= kSelect / 2 && rows != kRowsNone && (rows != kRowsLong || T.dense_long);
 }
 
+// wann_set_dense_rows: the view the score launches of this call's dense path read instead of I.view -- the one-byte copy of a
+// float32 index of byte-exact points, scored by the unit of wann_gemm_kernels_w8.hip to the float32 kernel's values -- or null:
+// switch off, no copy, or rows the copy's kernel does not take.  Everything else on the dense path keeps I.view.
+static const IndexView *dense_score_view(const wann_index &I, const Tuning &T) {
+  const bool use = T.dense_rows && I.has_dense_copy() && dense_row_class(I.view) == kRowsNarrow && dense_row_class(I.dense_view) == kRowsNarrow;
+  return use ? &I.dense_view : nullptr;
+}
+
 // tstride: task slots per query (the dense kernels read a query's slot 0).  sorted_exact: the exact windows of a tree / super
 // index (wann_set_exact_windows) -- rows in label order (no argsort table), cover groups always on, and an exact-scan list that
 // also holds other tasks: it is appended to, never rebuilt.
@@ -187,11 +195,16 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
     ca.cctr = &W.ctr.p->cover;
     if (launch_cover_plan(ca, st)) throw HipError(std::string("k_cover_*: ") + gemm_launch_last_error());
   }
-  if (launch_gemm_scores(ga, I.num_cus, st)) throw HipError(std::string("k_gemm_scores: ") + gemm_launch_last_error());
+  // the score launches alone may read the one-byte copy (a copy of the arguments whose view is the copy's): same tiles, same
+  // hand-over, the float32 kernel's accumulators
+  const IndexView *score_view = dense_score_view(I, T);
+  GemmArgs gs = ga;
+  if (score_view) gs.ix = *score_view;
+  if (launch_gemm_scores(gs, I.num_cus, st)) throw HipError(std::string("k_gemm_scores: ") + gemm_launch_last_error());
   if (launch_select_rerank(ga, W.ctr.p, st)) throw HipError(std::string("k_rerank: ") + gemm_launch_last_error());
   if (cover)
     for (int p = 0; p < ca.max_passes; p++)
-      if (launch_cover_pass(ca, p, I.num_cus, st)) throw HipError(std::string("cover pass: ") + gemm_launch_last_error());
+      if (launch_cover_pass(ca, p, I.num_cus, st, score_view)) throw HipError(std::string("cover pass: ") + gemm_launch_last_error());
 #ifdef WANN_GEMM_PROF
   unsigned long long h[8];
   HIP_CHECK(hipMemcpyAsync(h, I.g_prof.p, 64, hipMemcpyDeviceToHost, st));
@@ -1062,7 +1075,10 @@ int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last
   if (W.h_ctr->unsupported)
     throw std::runtime_error(std::to_string((long long)W.h_ctr->unsupported) +
                              " queries need more than " + std::to_string(P.maxt) + " partition searches; raise the task slot bound");
-  return P.store | (P.scan_store << 8);
+  // (wann_last_dense_rows: the dense launches were enqueued with the one-byte view, and their plans held at least one query --
+  // a score launch over an empty plan reads no row)
+  const bool dense_copy = (tried_dense || P.exact_dense) && dense_score_view(I, T) != nullptr && W.h_ctr->gemm_queries + W.h_ctr->cover.queries > 0;
+  return P.store | (P.scan_store << 8) | ((dense_copy ? 1 : 0) << 16);
 }
 
 }  // namespace wann_host

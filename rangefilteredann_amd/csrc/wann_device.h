@@ -68,7 +68,8 @@ constexpr int64_t h16_row_position(int64_t e) { return 16 * (e >> 4) + 8 * ((e >
 
 // One-byte shadow rows of a float32 index (dtype 6: an INTERNAL view type, never a WANN_DTYPE_* the C ABI accepts): every value
 // is an integer 0 .. 255 stored as a uint8 -- d bytes, zero padded to a multiple of 64 -- and the beam-search
-// kernels of wann_kernels_w8.hip widen each byte exactly to the float32 it stands for.  k_search is launched on such a view, and k_brute under wann_set_scan_rows.
+// kernels of wann_kernels_w8.hip widen each byte exactly to the float32 it stands for.  k_search is launched on such a view, and k_brute under wann_set_scan_rows;
+// under wann_set_dense_rows the dense path's k_gemm_scores too (wann_gemm_kernels_w8.hip: each byte widened to the bfloat16 it also is).
 constexpr int kRowsU8Widened = 6;
 constexpr int64_t u8_widened_stride_words(int64_t d) { return ((d + 63) / 64) * 16; }
 // THE LAYOUT of the device copy (wann_index::d_bytes, byte_view), stated once: a row keeps its pitch, and inside every aligned

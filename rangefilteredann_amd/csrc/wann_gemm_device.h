@@ -118,6 +118,9 @@ struct CoverArgs {
 //                  k_gemm_scores<W>                              k_gemm_scores_hslab
 //   bfloat16       16 .. 128           -                         -
 //                  k_gemm_scores<W>, two products (the row is its own high bf16 term)
+//   one-byte shadow rows of a float32 index (internal view type 6, wann_set_dense_rows)
+//                  16 .. 128           -                         -
+//                  k_gemm_scores<W> of wann_gemm_kernels_w8.inc: the bfloat16 kernel, a quarter of the float32 bytes fetched
 //   uint8 / int8   16 .. 128 (512 B)   -                         129 .. 512 (kGemmMaxBytes / 4)
 //                  k_gemm_scores_b<N>                            k_gemm_scores_bslab, quantised keys: k_rerank_bslab
 //
@@ -129,6 +132,9 @@ inline DenseRows dense_row_class(const IndexView &ix) {
   if ((ix.stride & 15) || words < 16 || words > (bytes ? kGemmMaxBytes / 4 : kGemmMaxFloats)) return kRowsNone;
   if (words <= 128) return kRowsNarrow;
   if (ix.dtype == 5) return kRowsNone;  // bfloat16 rows beyond 128 elements: the exact scan, with or without WANN_DENSE_LONG_ROWS
+  // (the view of a float32 index's one-byte shadow rows, wann_set_dense_rows: its score kernel is the bfloat16 one with a byte
+  // fetch and covers the narrow class alone -- longer rows are scored from the float32 rows)
+  if (ix.dtype == kRowsU8Widened) return kRowsNone;
   return ix.dtype == 0 && words <= 512 ? kRowsWide : kRowsLong;
 }
 
@@ -152,7 +158,8 @@ int launch_group_windows(const GemmArgs &a, Counters *ctr, void *stream);
 int launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream);
 int launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream);
 int launch_cover_plan(const CoverArgs &c, void *stream);     // after launch_group_windows, before launch_select_rerank
-int launch_cover_pass(const CoverArgs &c, int pass, int num_cus, void *stream);  // score kernel + selection / re-rank of one pass
+// score kernel + selection / re-rank of one pass; score_ix: the view the score kernel reads instead of c.g.ix (null: c.g.ix)
+int launch_cover_pass(const CoverArgs &c, int pass, int num_cus, void *stream, const IndexView *score_ix = nullptr);
 const char *gemm_launch_last_error();
 
 }  // namespace wann

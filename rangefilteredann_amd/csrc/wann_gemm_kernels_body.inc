@@ -39,6 +39,10 @@
 //   byte rows (WANN_DT = 1 / 2) k_gemm_scores_b on v_mfma_i32_32x32x32_i8: exact int32 sums, one product, no error bound --
 //                    see wann_gemm_kernels_bytes.inc.  Rows of 513 .. 2048 bytes: k_gemm_scores_bslab (both operands staged per
 //                    256-byte slab, quantised keys; opt-in), longer ones take the exact scan.
+//   one-byte shadow rows of a float32 index (WANN_DT = 6, wann_gemm_kernels_w8.hip; opt-in: wann_set_dense_rows) the bfloat16
+//                    unit's k_gemm_scores with another point fetch (wann_gemm_kernels_w8.inc): an integer 0 .. 255 is one
+//                    bfloat16 value, so a row widened byte by byte is its own high term.  The unit holds that kernel alone:
+//                    norms, selection and re-rank stay the float32 unit's, on the float32 rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -61,8 +65,10 @@ namespace wann {
 #define WANN_DT_NS_G dt_i8
 #elif WANN_DT == 3
 #define WANN_DT_NS_G dt_f16
-#else
+#elif WANN_DT == 5
 #define WANN_DT_NS_G dt_bf16
+#else
+#define WANN_DT_NS_G dt_w8  // (the one-byte shadow rows of a float32 index: the unit holds a score kernel and nothing else)
 #endif
 #define WANN_GNS_BEGIN namespace WANN_DT_NS_G {
 #define WANN_GNS_END }
@@ -93,7 +99,7 @@ __device__ __forceinline__ int window_row(const IndexView &ix, int64_t pos) { re
 // a task the dense path may take: a PrefilterIndex window, or the exact window of a query of a sorted kind
 __device__ __forceinline__ bool dense_task(const Task &t) { return t.mode == T_BRUTE_GATHER || (t.mode == T_BRUTE && (t.flags & kTaskExactWindow)); }
 
-#if !WANN_BYTE_ROWS
+#if !WANN_BYTE_ROWS && WANN_DT != 6  // (the one-byte shadow rows: the norms are the float32 rows', computed by the float32 unit)
 WANN_GNS_BEGIN
 __global__ void k_point_norms(IndexView ix, float *norm2, unsigned int *max_bits) {
   const int lane = lane_id();
@@ -520,6 +526,8 @@ __device__ __forceinline__ void insert4_chain(float &m1, float &m2, float &m3, f
 // Bfloat16 rows (WANN_DT = 5) have a kernel body of their own: one staged row per point, two products.
 #if WANN_DT == 5
 #include "wann_gemm_kernels_bf16.inc"
+#elif WANN_DT == 6
+#include "wann_gemm_kernels_w8.inc"
 #else
 WANN_GNS_BEGIN
 template <int STRIDE>  // padded row length in floats: a multiple of 16, <= 128
@@ -720,7 +728,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
 #endif
 }
 WANN_GNS_END
-#endif  // WANN_DT != 5
+#endif  // WANN_DT != 5, 6
 
 #if WANN_DT == 0
 
@@ -1308,6 +1316,10 @@ WANN_GNS_END
 #undef WANN_KSLAB_WAVES
 
 #endif  // WANN_DT == 0 || WANN_DT == 3 (the K-loop)
+#endif  // !WANN_BYTE_ROWS (the score kernels of the float types)
+
+#if WANN_DT != 6  // (selection and re-rank read the float32 rows: the unit of the one-byte shadow rows has none)
+#if !WANN_BYTE_ROWS
 
 // One wave per grouped query.  Its window's blocks each handed over their four smallest scores (sorted, position in
 // the low mantissa bits).  The first three of every block are candidates, the fourth bounds everything the block kept
@@ -1640,6 +1652,7 @@ __global__ __launch_bounds__(256) void k_rerank_cover_bslab(CoverArgs C) {
 }
 #endif
 WANN_GNS_END
+#endif  // WANN_DT != 6
 
 #include "wann_gemm_launch.inc"  // the launchers: one text for every unit, the entry points in the float32 unit
 

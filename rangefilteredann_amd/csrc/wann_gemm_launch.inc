@@ -1,5 +1,5 @@
 // wann_gemm_launch.inc -- the launchers of the dense prefilter path, included at the end of wann_gemm_kernels_body.inc: one text,
-// compiled in every unit (float32, uint8, int8, float16, bfloat16) against that unit's kernels.  A unit picks its kernels by the row class
+// compiled in every unit (float32, uint8, int8, float16, bfloat16, one-byte shadow rows) against that unit's kernels.  A unit picks its kernels by the row class
 // (dense_row_class, wann_gemm_device.h: the only place that knows a row length) and exposes its launchers as one constant table,
 // gemm_unit(); the float32 unit also holds the entry points of wann_gemm_device.h, which look the table up by ix.dtype (unit_of).
 // Every launcher returns null when it has launched, otherwise the error text.
@@ -22,6 +22,7 @@ static size_t rerank_lds_bytes(const IndexView &ix, int k) {
   return (size_t)4 * (((query_words(ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((k + 1) & ~1) * 8);
 }
 
+#if WANN_DT != 6  // (the unit of the one-byte shadow rows holds score kernels only)
 static const char *unit_rerank_cover(const CoverArgs &c, void *stream) {
   void (*kern)(CoverArgs) = nullptr;
 #if WANN_BYTE_ROWS
@@ -31,6 +32,7 @@ static const char *unit_rerank_cover(const CoverArgs &c, void *stream) {
   hipLaunchKernelGGL(kern, rerank_grid(c.g), dim3(256), rerank_lds_bytes(c.g.ix, c.g.k), (hipStream_t)stream, c);
   return gerr_of(hipGetLastError());
 }
+#endif
 
 static ScoreKernel pick_score_kernel(const IndexView &ix) {
   const DenseRows rows = dense_row_class(ix);
@@ -57,8 +59,8 @@ static ScoreKernel pick_score_kernel(const IndexView &ix) {
   // long: run-time slab count, both operands staged per slab (queries pre-split, `words` words a row), one workgroup per CU
 #if WANN_DT == 3
   if (rows == kRowsLong) return {k_gemm_scores_hslab, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
-#elif WANN_DT == 5
-  // (bfloat16 rows: narrow only; dense_row_class names no other class for them)
+#elif WANN_DT == 5 || WANN_DT == 6
+  // (bfloat16 rows, and the one-byte shadow rows of a float32 index: narrow only; dense_row_class names no other class for them)
 #else
   if (rows == kRowsLong) return {k_gemm_scores_long, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
   if (rows == kRowsWide) {  // slabs of 128, A operand in registers, one workgroup per CU
@@ -81,7 +83,8 @@ static ScoreKernel pick_score_kernel(const IndexView &ix) {
     default: kern = k_gemm_scores<128>; break;
   }
   // two workgroups per CU (the LDS allows it): one stores its scores while the other runs its MFMAs
-  // (bfloat16 rows: the same bytes -- the float32 query tile passes through the staging area, see wann_gemm_kernels_bf16.inc)
+  // (bfloat16 rows and one-byte shadow rows: the same bytes -- the float32 query tile passes through the staging area, see
+  // wann_gemm_kernels_bf16.inc)
   return {kern, (size_t)128 * (4 * words + 16) + 3 * 128 * 4, 2, false};
 #endif
 }
@@ -96,6 +99,7 @@ static const char *unit_gemm_scores(const GemmArgs &a, int num_cus, void *stream
   return gerr_of(hipGetLastError());
 }
 
+#if WANN_DT != 6
 static const char *unit_point_sums(const IndexView &ix, float *norm2, unsigned int *max_bits, int32_t *term, void *stream) {
   if (ix.n <= 0) return nullptr;
   const int wpb = 4;  // a wave per row
@@ -135,10 +139,13 @@ static const char *unit_select_rerank(const GemmArgs &a, Counters *ctr, void *st
   hipLaunchKernelGGL(kern, rerank_grid(a), dim3(256), rerank_lds_bytes(a.ix, a.k), (hipStream_t)stream, a, ctr);
   return gerr_of(hipGetLastError());
 }
+#endif  // WANN_DT != 6
 
 // (reached through a function: host code only, and no order of initialisation to depend on)
 const GemmUnit &gemm_unit() {
-#if WANN_HALF_ROWS
+#if WANN_DT == 6
+  static constexpr GemmUnit unit = {nullptr, nullptr, unit_gemm_scores, nullptr, nullptr};  // (only ever asked for gemm_scores: dense_prefilter)
+#elif WANN_HALF_ROWS
   static constexpr GemmUnit unit = {unit_point_sums, nullptr, unit_gemm_scores, unit_select_rerank, unit_rerank_cover};
 #else
   static constexpr GemmUnit unit = {unit_point_sums, unit_prep_queries, unit_gemm_scores, unit_select_rerank, unit_rerank_cover};
@@ -154,9 +161,10 @@ namespace dt_u8 { const GemmUnit &gemm_unit(); }
 namespace dt_i8 { const GemmUnit &gemm_unit(); }
 namespace dt_f16 { const GemmUnit &gemm_unit(); }
 namespace dt_bf16 { const GemmUnit &gemm_unit(); }
+namespace dt_w8 { const GemmUnit &gemm_unit(); }
 static const GemmUnit &unit_of(const IndexView &ix) {
   return ix.dtype == 1 ? dt_u8::gemm_unit() : ix.dtype == 2 ? dt_i8::gemm_unit() : ix.dtype == 3 ? dt_f16::gemm_unit()
-       : ix.dtype == 5 ? dt_bf16::gemm_unit() : gemm_unit();
+       : ix.dtype == 5 ? dt_bf16::gemm_unit() : ix.dtype == kRowsU8Widened ? dt_w8::gemm_unit() : gemm_unit();
 }
 
 static thread_local const char *g_gerr = "";
@@ -194,17 +202,17 @@ int launch_cover_plan(const CoverArgs &c, void *stream) {
   return record(gerr_of(hipGetLastError()));
 }
 
-int launch_cover_pass(const CoverArgs &c, int pass, int num_cus, void *stream) {
+int launch_cover_pass(const CoverArgs &c, int pass, int num_cus, void *stream, const IndexView *score_ix) {
   // the pass's plan, groups, tiles and query lists stand where the score kernels look for a batch's
   GemmArgs a = c.g;
+  if (score_ix) a.ix = *score_ix;  // (wann_set_dense_rows: the score kernel reads the one-byte copy, the re-rank the float32 rows)
   a.plan = c.pplan + pass * P_INTS;
   a.groups = c.groups + (int64_t)pass * c.nblocks;
   a.tile_group = c.tile_group + (int64_t)pass * c.tile_stride;
   a.gq = c.gq + (int64_t)pass * c.pair_stride;
-  const GemmUnit &u = unit_of(c.g.ix);
-  if (record(u.gemm_scores(a, num_cus, stream))) return 1;
+  if (record(unit_of(a.ix).gemm_scores(a, num_cus, stream))) return 1;
   CoverArgs cp = c;
   cp.pass = pass;
-  return record(u.rerank_cover(cp, stream));
+  return record(unit_of(c.g.ix).rerank_cover(cp, stream));
 }
 #endif  // WANN_DT == 0

@@ -52,6 +52,7 @@ Tuning snapshot_tuning(wann_index &I) {
   t.half_rows = I.half_rows_on && I.d_half.p != nullptr;
   t.byte_rows = I.byte_rows_on && I.d_bytes.p != nullptr;
   t.scan_rows = I.scan_rows_on && (I.d_half.p != nullptr || I.d_bytes.p != nullptr);
+  t.dense_rows = I.dense_rows_on && I.has_dense_copy();
   return t;
 }
 
@@ -143,6 +144,28 @@ void upload_index(wann_index &I) {
       pack_u8_rows(H.pts.data(), s.n, s.d, s.stride, bstride, s.threads, rows.data());
       interleave_u8_rows(rows.data(), s.n, bstride, s.threads);  // (the copy's layout: u8_row_position, wann_device.h)
       I.d_bytes.upload(rows);
+    }
+  }
+  // A float32 PrefilterIndex of such points keeps the same one-byte rows for the score kernel of its dense path
+  // (wann_set_dense_rows, off by default), where that kernel takes them: rows of the narrow class.  The layout of d_bytes, the
+  // row order of d_points, a buffer of its own: the index has no beam searches and no byte rows to switch on.
+  if (s.dtype == WANN_DTYPE_F32 && s.kind == WANN_KIND_PREFILTER && dense_row_class(v) == kRowsNarrow &&
+      rows_u8_exact(H.pts.data(), s.n, s.d, s.stride, s.threads)) {
+    const int64_t bstride = u8_widened_stride_words(s.d);
+    std::vector<float> rows;
+    try {
+      rows.assign((size_t)s.n * bstride, 0.f);
+      I.d_dense.ensure(rows.size());
+    } catch (std::bad_alloc &) {
+      I.d_dense.release();
+    } catch (HipError &) {
+      (void)hipGetLastError();  // (the allocation that failed is not left behind as the next call's error)
+      I.d_dense.release();
+    }
+    if (I.d_dense.p) {
+      pack_u8_rows(H.pts.data(), s.n, s.d, s.stride, bstride, s.threads, rows.data());
+      interleave_u8_rows(rows.data(), s.n, bstride, s.threads);
+      I.d_dense.upload(rows);
     }
   }
   I.d_labels.upload(H.labels);
@@ -239,6 +262,18 @@ void upload_index(wann_index &I) {
     I.byte_view.points = I.d_bytes.p;
     I.byte_view.stride = (int32_t)u8_widened_stride_words(s.d);
     I.byte_view.dtype = kRowsU8Widened;
+  }
+  // the copy the dense path's score launches read under wann_set_dense_rows: the PrefilterIndex's own, or the one-byte shadow
+  // rows of the kinds whose exact windows take the dense path -- where the float32 rows are in the score kernel's narrow class
+  I.dense_view = v;
+  {
+    const bool exact_kind = s.kind == WANN_KIND_TREE_VAMANA || s.kind == WANN_KIND_SUPER;
+    const float *copy = I.d_dense.p ? I.d_dense.p : (exact_kind && dense_row_class(v) == kRowsNarrow) ? I.d_bytes.p : nullptr;
+    if (copy) {
+      I.dense_view.points = copy;
+      I.dense_view.stride = (int32_t)u8_widened_stride_words(s.d);
+      I.dense_view.dtype = kRowsU8Widened;
+    }
   }
   // (neither shadow copy is in device_bytes, which keeps counting what it always has: wann_half_rows_bytes / wann_byte_rows_bytes report them)
   I.device_bytes = (int64_t)(I.d_points.bytes() + I.d_labels.bytes() + I.d_decoding.bytes() + I.d_graph.bytes() +

@@ -163,12 +163,26 @@ struct wann_index {
   // batch read the copy its beam searches read
   bool scan_rows_on = false;
   std::atomic<int> last_scan_rows{0};  // the store (kStore*) the k_brute launch of the last finished batch read
-  // which row stores a finished batch read (run_batch's result: the beam searches' store, the scan's in the next byte)
+  // wann_set_dense_rows (under tune_mu; off by default, only ever on where dense_view is a one-byte view): the score launches of
+  // the dense path (k_gemm_scores; float32 rows of the narrow class, d <= 128) read the one-byte copy of the rows through
+  // dense_view.  Norms, selection, re-rank and finalisation keep the float32 rows.  The copy is d_bytes for the kinds whose
+  // exact windows take the dense path (tree-of-graphs, super tree) and d_dense, a buffer of its own with the same layout and
+  // the row order of d_points, for a float32 PrefilterIndex of byte-exact points -- which has no d_bytes: its
+  // wann_byte_rows_bytes stays 0.  Neither is counted in device_bytes.
+  DevBuf<float> d_dense;
+  IndexView dense_view{};      // `view` with points = the copy, the byte stride and dtype = kRowsU8Widened (dtype as `view`'s: no copy)
+  bool dense_rows_on = false;
+  std::atomic<int> last_dense_rows{0};  // a score launch of the last finished batch read the copy
+  bool has_dense_copy() const { return dense_view.dtype == kRowsU8Widened && dense_view.points != nullptr; }
+  int64_t dense_copy_bytes() const { return !has_dense_copy() ? 0 : (int64_t)(d_dense.p ? d_dense.bytes() : d_bytes.bytes()); }
+  // which row stores a finished batch read (run_batch's result: the beam searches' store, the scan's in the next byte, whether
+  // a dense score launch read the one-byte copy in the byte after that)
   void note_row_store(int stores) {
     const int store = stores & 0xff;
     last_half_rows = store == wann_host::kStoreHalf ? 1 : 0;
     last_byte_rows = store == wann_host::kStoreBytes ? 1 : 0;
-    last_scan_rows = stores >> 8;
+    last_scan_rows = (stores >> 8) & 0xff;
+    last_dense_rows = (stores >> 16) & 1;
   }
   DevBuf<uint32_t> d_decoding;
   DevBuf<int32_t> d_graph, d_fi;
@@ -251,7 +265,8 @@ int method_code(const char *m);
 // W / side / last: the lane of this batch (the index's own members for the blocking calls, an AsyncLane's for the asynchronous one)
 // Returns the row store the batch's beam searches read (kStore*): the one-byte rows if T.byte_rows, else the half rows if
 // T.half_rows, else the index's own rows -- and, shifted left by 8, the store its k_brute launch read (the same one if
-// T.scan_rows, else kStoreRows; kStoreRows too for a batch that launched no scan).
+// T.scan_rows, else kStoreRows; kStoreRows too for a batch that launched no scan) -- and, shifted left by 16, 1 if a score launch
+// of its dense path read the one-byte copy (T.dense_rows) for at least one query.
 int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
                const int64_t *d_qids = nullptr);

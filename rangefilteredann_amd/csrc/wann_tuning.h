@@ -52,6 +52,7 @@ struct Tuning {
   bool half_rows = false;       // this batch's beam searches read the index's half-precision shadow rows
   bool byte_rows = false;       // wann_set_byte_rows likewise: they read the one-byte shadow rows (which go before the half rows)
   bool scan_rows = false;       // wann_set_scan_rows: this batch's exact scans (k_brute) read the shadow copy its beam searches read
+  bool dense_rows = false;      // wann_set_dense_rows: this batch's dense score launches (k_gemm_scores) read the one-byte copy of the rows
 
   static bool on(const char *name) {
     const char *v = getenv(name);

@@ -204,6 +204,7 @@ class Index {
     d["half_rows"] = wann_last_half_rows(h_);
     d["byte_rows"] = wann_last_byte_rows(h_);
     d["scan_rows"] = wann_last_scan_rows(h_);
+    d["dense_rows"] = wann_last_dense_rows(h_);
     return d;
   }
   // float32 indexes with graphs whose points are all binary16 values: the beam searches read a half-precision copy of the rows
@@ -232,6 +233,15 @@ class Index {
     return rc != 0;
   }
   bool scan_rows() const { return wann_scan_rows(h_) != 0; }
+  // the score launches of the dense path read the one-byte copy of a float32 index of byte-exact points (wann_set_dense_rows, off
+  // by default); returns the setting now in force -- False on an index without a copy that path can read
+  bool set_dense_rows(bool on) {
+    const int rc = wann_set_dense_rows(h_, on ? 1 : 0);
+    if (rc < 0) raise_last("set_dense_rows failed");
+    return rc != 0;
+  }
+  bool dense_rows() const { return wann_dense_rows(h_) != 0; }
+  int64_t dense_rows_bytes() const { return wann_dense_rows_bytes(h_); }
 
   // PrefilterIndex only: distinct wide windows on the matrix cores (wann_set_dense_windows); returns the previous setting
   bool set_dense_windows(bool on) {
@@ -278,6 +288,7 @@ class Index {
     d["half_rows"] = wann_last_half_rows(h_);  // 1: the last batch's beam searches read the half-precision shadow rows
     d["byte_rows"] = wann_last_byte_rows(h_);  // 1: they read the one-byte shadow rows (then half_rows is 0)
     d["scan_rows"] = wann_last_scan_rows(h_);  // the rows its k_brute launch read: 0 the index's own, 1 the half rows, 2 the one-byte rows
+    d["dense_rows"] = wann_last_dense_rows(h_);  // 1: a score launch of its dense path read the one-byte copy of the rows
     return d;
   }
   static py::dict counters_dict(const wann_counters &c) {
@@ -363,6 +374,9 @@ static void common_defs(py::class_<C> &c) {
       .def("byte_rows_bytes", &C::byte_rows_bytes)
       .def("set_scan_rows", &C::set_scan_rows, "on"_a)
       .def("scan_rows", &C::scan_rows)
+      .def("set_dense_rows", &C::set_dense_rows, "on"_a)
+      .def("dense_rows", &C::dense_rows)
+      .def("dense_rows_bytes", &C::dense_rows_bytes)
       .def("max_degree", &C::max_degree)
       .def("num_replicas", &C::num_replicas)
       .def("num_points", &C::num_points)

@@ -10,6 +10,15 @@ on the int8 MFMA with exact scores.  Every leg is timed as the median of repeate
 the number of clusters (default 100), --metric l2 | mips the metric of the float types (default mips).  WANN_PF_CACHE=<dir> keeps
 the generated set there for the next run of the same shape; WANN_PF_ONLY=mfma times the dense leg alone (runs under a profiler),
 WANN_PF_ONLY=scan the exact-scan leg alone, twice (the baseline run of a parent build); WANN_PF_NO_REF=1 leaves the CPU reference out.
+--byte-exact: the float32 index is fed the integer values of the uint8 leg, round(127 x) + 128, as float32 (d = 128 and the
+Euclidian metric unless --dim / --metric say otherwise; the queries keep their fractions: 127 q + 128), and the dense call is
+timed with wann_set_dense_rows off and on -- the same index, one process, the legs alternating (off, on, off, on), 21 calls per
+leg, device time from the HIP events around the batch (counters()["device_ms"]), ids and distance bits compared between the
+legs.  Nothing else runs in that mode; WANN_PF_ONLY=on / off runs one leg alone (under a kernel trace).  Those values are unit
+vectors around a common offset of 128, which the squared-L2 proof cannot settle: every query goes on to the exact
+scan and the call is the scan's.  --rows sift (with --byte-exact) keeps the shape -- 100 windows of 10 000 points, 99 queries
+each -- and takes SIFT-like rows instead (tests/util.sift_like: integers 0 .. 255 of low intrinsic dimension; queries the same
+plus a fraction), whose queries the dense path proves.
 Run from the repo root.  Prints one JSON object."""
 import json, os, subprocess, sys, time
 os.environ.setdefault("WANN_TEST_HOOKS", "1")  # this tool flips WANN_* switches between calls on one index
@@ -22,10 +31,11 @@ def _opt(name, default):
     return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
 
 
-DTYPE = _opt("--dtype", "float32")
-DIM = int(_opt("--dim", os.environ.get("WANN_PF_DIM", "100")))  # (WANN_PF_DIM: the option's older spelling)
+BYTE_EXACT = "--byte-exact" in sys.argv
+DTYPE = "float32" if BYTE_EXACT else _opt("--dtype", "float32")
+DIM = int(_opt("--dim", os.environ.get("WANN_PF_DIM", "128" if BYTE_EXACT else "100")))  # (WANN_PF_DIM: the option's older spelling)
 NCLU = int(_opt("--clusters", "100"))
-METRIC = _opt("--metric", "mips")
+METRIC = _opt("--metric", "l2" if BYTE_EXACT else "mips")
 CLASS = {"float32": "FloatMips", "float16": "Float16Mips", "int8": "Int8Mips", "uint8": "UInt8Euclidian"}[DTYPE]
 if METRIC == "l2" and DTYPE in ("float32", "float16"):
     CLASS = CLASS.replace("Mips", "Euclidian")
@@ -110,6 +120,15 @@ import torch
 import window_ann as wa
 
 X, Q, labels, W1, W2, per, w = make()
+if BYTE_EXACT:  # the uint8 leg's values (as_elem), as float32; the queries are not rounded
+    X = (np.rint(127.0 * X) + 128).astype(np.float32)
+    Q = (127.0 * Q + 128).astype(np.float32)
+    if _opt("--rows", "uint8-leg") == "sift":
+        from util import sift_like
+        g = sift_like(X.shape[0], X.shape[1], 3)
+        X = g(X.shape[0]) + np.float32(0)  # (+ 0: clip keeps the -0.0 that rint makes, and the one-byte rule is on bits)
+        Q = (g(Q.shape[0]) + np.random.default_rng(4).random(Q.shape, dtype=np.float32) - np.float32(0.5)).astype(np.float32)
+    assert X.min() >= 0 and X.max() <= 255 and X.dtype == np.float32
 d = X.shape[1]
 nq = Q.shape[0]
 idx = getattr(wa, "PrefilterIndex" + CLASS)(X, labels)
@@ -140,6 +159,36 @@ def timed(Wt, env):
 
 
 W1t, W2t = torch.from_numpy(W1).to(dev), torch.from_numpy(W2).to(dev)
+if BYTE_EXACT:
+    assert idx.dense_rows_bytes() == X.shape[0] * 64 * ((d + 63) // 64), "the index has no one-byte copy for its dense path"
+
+    def leg(on):
+        assert idx.set_dense_rows(on) is on
+        r = timed(W1t, None)
+        assert r["counters"]["dense_rows"] == (1 if on else 0) and r["counters"]["gemm_queries"] > 0, r["counters"]
+        return r
+
+    only = os.environ.get("WANN_PF_ONLY")
+    if only in ("on", "off"):  # under a kernel trace: one leg alone
+        r = leg(only == "on")
+        print(json.dumps(dict(leg=only, ms=r["ms"], device_ms=r["counters"]["device_ms"], gemm_queries=int(r["counters"]["gemm_queries"]), calls=REPS + 3)))
+        sys.exit(0)
+    legs = [("off", leg(False)), ("on", leg(True)), ("off", leg(False)), ("on", leg(True))]
+    idx.set_dense_rows(False)
+    ref = legs[0][1]
+    same = all(np.array_equal(r["ids"], ref["ids"]) and np.array_equal(r["d"].view(np.uint32), ref["d"].view(np.uint32)) for _, r in legs)
+    dev_ms = {name: [round(r["counters"]["device_ms"], 4) for n2, r in legs if n2 == name] for name in ("off", "on")}
+    dev_rng = {name: [[r["device_ms_min"], r["device_ms_max"]] for n2, r in legs if n2 == name] for name in ("off", "on")}
+    ratios = [round(a / b, 4) for a in dev_ms["off"] for b in dev_ms["on"]]
+    print(json.dumps(dict(workload=f"adversarial {NCLU}x10000 d={d} float32 rows of integers 0 .. 255 ({_opt('--rows', 'uint8-leg')} values), {'Euclidian' if CLASS.endswith('Euclidian') else 'MIPS'}, {nq} queries, window = 1 cluster",
+                          legs="wann_set_dense_rows off / on, alternating (off, on, off, on), one index, one process", timed_calls_per_leg=REPS,
+                          device_ms_median=dev_ms, device_ms_min_max=dev_rng, wall_ms_median={name: [r["ms"] for n2, r in legs if n2 == name] for name in ("off", "on")},
+                          off_over_on=dict(all_pairs=ratios, min=min(ratios), max=max(ratios)),
+                          repeat_spread=dict(off=round(max(dev_ms["off"]) / min(dev_ms["off"]), 4), on=round(max(dev_ms["on"]) / min(dev_ms["on"]), 4)),
+                          ids_and_distance_bits_equal=bool(same), gemm_queries=int(ref["counters"]["gemm_queries"]),
+                          gemm_unproven=[int(r["counters"]["gemm_unproven"]) for _, r in legs], gemm_rescued=[int(r["counters"]["gemm_rescued"]) for _, r in legs],
+                          row_bytes=dict(float32=64 * ((4 * d + 63) // 64), one_byte=64 * ((d + 63) // 64)))))
+    sys.exit(0)
 if os.environ.get("WANN_PF_ONLY") == "p12":  # dev runs under a profiler: the synthetic windows alone
     r = timed(W2t, None)
     print(json.dumps(dict(ms=r["ms"], device_ms=r["counters"]["device_ms"], brute_rows=int(r["counters"]["brute_rows"]))))
