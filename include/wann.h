@@ -117,8 +117,28 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * bfloat16 row is its own high bf16 term: one staged row per point, two products per step instead of three, the float32
  * kernel's scores on the upcast row); longer rows take the exact scan, with or without WANN_DENSE_LONG_ROWS.  A bfloat16 index
  * has no shadow rows (wann_half_rows: 0).
- * The value is 5: 4 is UNASSIGNED and refused as an unknown dtype, like every other value not listed here. */
-enum { WANN_DTYPE_F32 = 0, WANN_DTYPE_U8 = 1, WANN_DTYPE_I8 = 2, WANN_DTYPE_F16 = 3, WANN_DTYPE_BF16 = 5 };
+ * The value is 5: 4 is UNASSIGNED and refused as an unknown dtype, like every other value not listed here.
+ * WANN_DTYPE_F8 (not a type of the reference): float8 points, rows of uint8_t bit patterns of OCP E4M3 ("e4m3fn": 1 sign bit, 4
+ * exponent bits with bias 7, 3 mantissa bits; no infinities, 0x7f / 0xff are NaN, the largest finite value is 448, subnormals
+ * are M * 2^-9) -- a quarter of the float32 vector bytes for REAL-VALUED sets.  Everything said of WANN_DTYPE_BF16 holds with
+ * "float8" for "bfloat16", except: (1) the device rows are d bytes zero padded to a multiple of 64, and inside every aligned
+ * group of 32 elements the bytes sit in wann_byte_row_position order, the layout of the one-byte shadow rows (host arrays and
+ * cache inputs stay in natural order; wann_device_bytes counts n * 64 * ceil(d / 64) for them); (2) the widening is the
+ * hardware's two-at-a-time E4M3 -> float32 conversion, exact for all 254 finite patterns whatever the FP mode (every one is a
+ * normal float32 value; -0.0 and the subnormals are ordinary values); (3) NaN patterns are REFUSED, not scored:
+ * wann_index_create, wann_build_cache_shard and a host-buffer wann_batch_search fail with WANN_ERR_INVALID, the message naming
+ * the first offending row, if any point (or host query) element is 0x7f or 0xff, and nothing is written to the cache before
+ * that check.  Rounding to float8 (the Python classes, window_ann.float8_bits) is to nearest, ties to even, on the value; a
+ * magnitude that rounds above 448 (464 ties down to 448, anything larger does not), an infinity or a NaN becomes the NaN pattern of
+ * its sign -- so out-of-range data is an error when the index is created, never silently saturated.  A caller may scale points
+ * and queries by a power of two without changing any ordering.  Host-buffer calls take float8 bit patterns as queries,
+ * device-buffer calls fp32 queries (not rounded); labels stay float32; no wann_vamana_* variant; wann_raw_beam_search_typed
+ * accepts the type.  The MFMA prefilter path covers rows of up to 128 elements (each byte is also exactly one bfloat16 value: the
+ * bfloat16 kernel behind a byte fetch, norms and re-rank on the float8 rows); longer rows take the exact scan, with or without
+ * WANN_DENSE_LONG_ROWS.  A float8 index has no shadow copies: wann_half_rows, wann_byte_rows and wann_dense_rows are 0 and the
+ * four setters return 0 as on any index without a copy.
+ * The value is 8: 6 and 7 are INTERNAL view types (the shadow rows above) and stay refused, like 4. */
+enum { WANN_DTYPE_F32 = 0, WANN_DTYPE_U8 = 1, WANN_DTYPE_I8 = 2, WANN_DTYPE_F16 = 3, WANN_DTYPE_BF16 = 5, WANN_DTYPE_F8 = 8 };
 /* index classes */
 enum {
   WANN_KIND_PREFILTER = 0,      /* PrefilterIndex                                   */

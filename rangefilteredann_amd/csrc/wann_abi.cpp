@@ -2,6 +2,7 @@
 // calls, the RCCL all-gather of per-shard rows, cost prediction, introspection.  Every compute entry point needs a gfx950 device
 // and fails loudly otherwise: there is no CPU search path in this library.
 #include "wann_host_internal.h"
+#include "wann_f8.h"
 
 // One batch in flight beside the others: its own workspace, streams and worker thread.  The worker runs the same run_batch
 // the blocking call runs (host-side waits included) -- on ITS stream, so the kernels of two consecutive batches share the GPU:
@@ -126,6 +127,17 @@ wann_index::~wann_index() {
 
 extern "C" {
 
+// float8 (wann.h WANN_DTYPE_F8): NaN patterns are refused, not scored.  True (and the error recorded, naming the first offending
+// row) if any of the n x d elements is 0x7f / 0xff; false for every other element type.
+static bool f8_nan_refused(int dtype, const void *rows, int64_t n, int64_t d, const char *what) {
+  if (dtype != WANN_DTYPE_F8 || !rows) return false;
+  const int64_t bad = wann::f8_first_nan_row((const uint8_t *)rows, n, d);
+  if (bad < 0) return false;
+  fail(WANN_ERR_INVALID, "float8 NaN pattern (0x7f / 0xff) in " + std::string(what) + " row " + std::to_string(bad) +
+                             ": a value out of the E4M3 range (|x| rounds above 448), an infinity or a NaN");
+  return true;
+}
+
 int wann_abi_version(void) { return WANN_ABI_VERSION; }
 const char *wann_last_error(void) { return g_err.c_str(); }
 int wann_device_count(void) { return usable_devices(); }
@@ -145,6 +157,7 @@ wann_index *wann_index_create(int kind, int metric, int dtype, const void *point
     fail(WANN_ERR_UNSUPPORTED, "point sets of 2^31 or more rows are not supported");
     return nullptr;
   }
+  if (f8_nan_refused(dtype, points, n, d, "point")) return nullptr;
   // uint8 / int8 point sets (euclidian_point.h:44-60, mips_point.h:44-58: int32 accumulation, cast to float) are kept as
   // BYTE rows on the device and scored with v_dot4 into exact int32 sums: any dimension, a quarter of the vector traffic.
   if (usable_devices() <= device || device < 0) {
@@ -565,6 +578,7 @@ int wann_batch_search(wann_index *I, const void *queries, const float *ranges, i
                       const wann_query_params *qp, uint32_t *ids, float *dists) {
   if (!I || !qp || nq < 0 || (nq > 0 && (!queries || !ranges || !ids || !dists)))
     return fail(WANN_ERR_INVALID, "invalid argument to wann_batch_search");
+  if (f8_nan_refused(I->dtype, queries, nq, I->H.spec.d, "query")) return WANN_ERR_INVALID;
   const int G = 1 + (int)I->replicas.size();
   if (G == 1 || nq < G) {
     try {
@@ -862,6 +876,8 @@ int wann_build_cache_shard(int kind, int metric, int dtype, const void *points, 
     return fail(WANN_ERR_INVALID, "unknown dtype");
   if (!bp || !bp->cache_path || !*bp->cache_path) return fail(WANN_ERR_INVALID, "cache_path required");
   if (nshards <= 0 || shard < 0 || shard >= nshards) return fail(WANN_ERR_INVALID, "bad shard");
+  if (!points || n <= 0 || d <= 0) return fail(WANN_ERR_INVALID, "invalid argument to wann_build_cache_shard");
+  if (f8_nan_refused(dtype, points, n, d, "point")) return WANN_ERR_INVALID;  // (before anything is written to the cache)
   try {
     HostIndex H;
     H.spec = make_spec(kind, metric, dtype, n, d, cutoff, split_factor, shift_factor, bp, build_threads);

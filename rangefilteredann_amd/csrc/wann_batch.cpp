@@ -424,9 +424,11 @@ bool Batch::prefilter_dense_gate() const {
 // it keeps the float16 unit's launch shape.)
 static int scan_rows_per_cu(const IndexView &V, int k) {
   const bool mips = V.metric == 1;
-  if (V.dtype != kRowsU8Widened) return mips ? 4 : 3;
+  // (float8 rows, profiles/float8_kernel_resources.txt: k_brute 186 / 93, k_brute_staged 216 / 129 -- two workgroups under squared L2)
+  const int by_regs = mips ? 4 : V.dtype == kRowsF8 ? 2 : 3;
+  if (!scan_staged(V, k)) return by_regs;
   const int by_lds = (int)(kLdsPerWorkgroup / brute_staged_lds_bytes(V.stride, query_words(V), k));
-  return std::max(1, std::min(mips ? 4 : 3, by_lds));
+  return std::max(1, std::min(by_regs, by_lds));
 }
 
 // Stage: the exact scans (k_brute, k_exact_rows) and, in front of them, the dense path of a batch with exact windows -- on the
@@ -469,7 +471,8 @@ void Batch::scans() const {
   // (as many waves as the chip holds at once -- by the registers: two per SIMD for squared-L2 float rows (two 512-byte rows
   // per lane pair in flight), three for inner-product float rows, five for byte rows -- deal the tickets among themselves)
   int brute_per_cu = byte_rows(I.view) ? 5 : (I.view.metric == 1 ? 3 : 2);
-  if (P.scan_store != kStoreRows) brute_per_cu = scan_rows_per_cu(ba.ix, P.k);
+  // (float8 rows: the one-byte shadow rows' kernels and launch shape -- by their registers, and the staged rows' LDS)
+  if (P.scan_store != kStoreRows || ba.ix.dtype == kRowsF8) brute_per_cu = scan_rows_per_cu(ba.ix, P.k);
   int blocks = (int)std::min<int64_t>((int64_t)I.num_cus * brute_per_cu, (nq * std::min(P.maxt, 2) + kWavesPerBlock - 1) / kWavesPerBlock);
   if (launch_brute(ba, blocks, scan_st)) throw HipError(std::string("k_brute: ") + launch_last_error());
   if (P.exact_limit > 0 && launch_exact_rows(ba, nq * std::min(P.maxt, 2), scan_st)) throw HipError(std::string("k_exact_rows: ") + launch_last_error());

@@ -12,6 +12,7 @@
 #include "wann_build.h"
 #include "wann_device.h"
 #include "wann_bf16.h"
+#include "wann_f8.h"
 #include "wann_half.h"
 
 #include <algorithm>
@@ -196,6 +197,16 @@ void pack_u8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64
     const float *src = rows + r * stride;
     uint8_t *dst = reinterpret_cast<uint8_t *>(out + r * out_words);
     for (int64_t j = 0; j < d; j++) dst[j] = (uint8_t)src[j];
+  });
+}
+
+// The float8 rows of a float8 index (wann.h WANN_DTYPE_F8): `rows` are the exact float32 upcast of the caller's patterns
+// (build_host_index), so float_to_f8 gives every pattern back -- natural order, the layout pack_u8_rows writes.
+void pack_f8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64_t out_words, int threads, float *out) {
+  parallel_for(n, threads > 0 ? threads : default_threads(), [&](int64_t r) {
+    const float *src = rows + r * stride;
+    uint8_t *dst = reinterpret_cast<uint8_t *>(out + r * out_words);
+    for (int64_t j = 0; j < d; j++) dst[j] = float_to_f8(src[j]);
   });
 }
 
@@ -742,10 +753,10 @@ void build_host_index(HostIndex &H, const void *points, const float *labels, int
   BuildSpec &s = H.spec;
   if (s.n <= 0 || s.d <= 0) throw std::runtime_error("empty point set");
   if (s.threads <= 0) s.threads = default_threads();
-  // bytes per element of the caller's rows and of the stored rows (float16 / bfloat16 points are stored as their exact float32
-  // upcast: the graphs of such an index are those of the float32 index on the upcast points, byte for byte)
-  const bool half = s.dtype == 3 || s.dtype == 5;
-  const int64_t esz = s.dtype == 0 ? 4 : half ? 2 : 1, ssz = half ? 4 : esz;
+  // bytes per element of the caller's rows and of the stored rows (float16 / bfloat16 / float8 points are stored as their exact
+  // float32 upcast: the graphs of such an index are those of the float32 index on the upcast points, byte for byte)
+  const bool half = s.dtype == 3 || s.dtype == 5, f8 = s.dtype == kRowsF8;
+  const int64_t esz = s.dtype == 0 ? 4 : half ? 2 : 1, ssz = (half || f8) ? 4 : esz;
   s.stride = ((s.d * ssz + 63) / 64) * 16;      // 64-byte rows (point_range.h:39-44), zero padded; in 32-bit words
   H.sorted = (s.kind == 2 || s.kind == 3 || s.kind == 4);
   H.vamana_leaves = (s.kind == 1 || s.kind == 3 || s.kind == 4);
@@ -762,6 +773,10 @@ void build_host_index(HostIndex &H, const void *points, const float *labels, int
       const uint16_t *src = (const uint16_t *)points + order[r] * s.d;
       float *dst = H.pts.data() + r * s.stride;
       for (int64_t j = 0; j < s.d; j++) dst[j] = two_byte_to_float(s.dtype, src[j]);
+    } else if (f8) {
+      const uint8_t *src = (const uint8_t *)points + order[r] * s.d;
+      float *dst = H.pts.data() + r * s.stride;
+      for (int64_t j = 0; j < s.d; j++) dst[j] = f8_to_float(src[j]);
     } else {
       memcpy(H.pts.data() + r * s.stride, (const char *)points + order[r] * s.d * esz, (size_t)(s.d * esz));
     }
@@ -894,7 +909,7 @@ void build_pending_on_host(HostIndex &H, std::vector<HostPart *> &pending) {
   std::vector<Job> jobs;
   for (HostPart *P : pending) {
     Job J;
-    const int rows_dt = (s.dtype == 3 || s.dtype == 5) ? 0 : s.dtype;  // (float16 / bfloat16 points: float32 rows, see build_host_index)
+    const int rows_dt = upcast_built(s.dtype) ? 0 : s.dtype;  // (float16 / bfloat16 / float8 points: float32 rows, see build_host_index)
     J.V = BuildView{H.pts.data(), s.stride, s.d, s.metric | (rows_dt << 4), P->start, P->n, s.R, s.L, s.alpha};
     J.G = &P->g;
     jobs.push_back(std::move(J));

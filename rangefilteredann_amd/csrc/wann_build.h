@@ -30,7 +30,7 @@ struct HostPart {
 
 struct BuildSpec {
   int kind = 0, metric = 0;
-  int dtype = 0;  // element type of the caller's rows (wann.h WANN_DTYPE_*): float32, uint8 / int8 bytes, float16 or bfloat16
+  int dtype = 0;  // element type of the caller's rows (wann.h WANN_DTYPE_*): float32, uint8 / int8 bytes, float16, bfloat16 or float8
   int64_t n = 0, d = 0, stride = 0;  // stride: 32-bit words per row of HostIndex::pts
   int32_t cutoff = 1000;
   double split_factor = 2, shift_factor = 0.5;
@@ -68,6 +68,8 @@ bool rows_u8_exact(const float *rows, int64_t n, int64_t d, int64_t stride, int 
 // such a point set as one-byte rows: the d values of row r as bytes, natural order, at word r * out_words of the ZEROED buffer
 // `out` (n * out_words 32-bit words; out_words * 4 >= d -- u8_widened_stride_words(d) in wann_device.h)
 void pack_u8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64_t out_words, int threads, float *out);
+// the rows of a float8 index (`rows`: the exact float32 upcast of its E4M3 patterns) as those patterns again, the same way
+void pack_f8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64_t out_words, int threads, float *out);
 // packed rows (natural order) into the device copy's layout, in place: the byte at position e of a row moves to position
 // u8_row_position(e) (wann_device.h: a permutation inside every aligned 32 bytes).  `words` 32-bit words per row, a multiple of 8.
 void interleave_u8_rows(float *rows, int64_t n, int64_t words, int threads);

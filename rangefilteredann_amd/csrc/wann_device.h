@@ -45,7 +45,8 @@ struct IndexView {
   int32_t dtype;  // element type of `points` (wann.h WANN_DTYPE_*): float32 rows, uint8 / int8 rows of d bytes padded to a
                   // multiple of 64, or float16 / bfloat16 rows of d two-byte elements padded to a multiple of 32 -- `stride` counts 32-bit words in every
                   // case and `points` is addressed in words.  6 (kRowsU8Widened, below) only in the view of a float32 index's one-byte shadow rows,
-                  // 7 (kRowsF16Paired) only in the view of its half shadow rows
+                  // 7 (kRowsF16Paired) only in the view of its half shadow rows.  8 (kRowsF8): float8 rows of d bytes padded to a multiple
+                  // of 64, in the one-byte shadow rows' interleaved order
 };
 
 // two-byte float rows: float16 (3) and bfloat16 (5) share the row pitch and layout rules -- d elements in natural order, zero
@@ -82,7 +83,16 @@ constexpr int64_t u8_widened_stride_words(int64_t d) { return ((d + 63) / 64) * 
 constexpr int64_t u8_row_position(int64_t e) { return 32 * (e >> 5) + 16 * ((e >> 2) & 1) + 4 * ((e >> 3) & 3) + (e & 3); }
 // rows narrower than float32 that are scored as their exact float32 upcast against an fp32 query: the two-byte float rows and
 // the one-byte shadow rows (WANN_WIDENED_ROWS in wann_wave.h is the device side)
-constexpr bool widened_rows(int dtype) { return two_byte_rows(dtype) || dtype == kRowsU8Widened; }
+// Float8 rows (wann.h WANN_DTYPE_F8 = 8, OCP E4M3 bit patterns): an element type of the C ABI whose device rows have the one-byte
+// shadow rows' pitch (u8_widened_stride_words) and LAYOUT (u8_row_position inside every aligned group of 32 elements); the
+// kernels of wann_kernels_f8.hip / wann_gemm_kernels_f8.hip widen each byte exactly to the float32 (bfloat16) it stands for.
+// Host arrays and cache inputs keep the natural order: interleave_u8_rows runs before the upload.
+constexpr int kRowsF8 = 8;
+// one-byte rows in the interleaved layout, fetched 16 bytes at a time (WANN_QUAD_ROWS in wann_wave.h is the device side)
+constexpr bool one_byte_widened_rows(int dtype) { return dtype == kRowsU8Widened || dtype == kRowsF8; }
+constexpr bool widened_rows(int dtype) { return two_byte_rows(dtype) || one_byte_widened_rows(dtype); }
+// element types whose host rows (HostIndex::pts) are the exact float32 upcast of the caller's: both builders build from those
+constexpr bool upcast_built(int dtype) { return dtype == 3 || dtype == 5 || dtype == kRowsF8; }
 
 // 32-bit words of a staged query (fp32, zero padded; the LDS the kernels reserve for it): `stride` for float32 / byte rows, the
 // float32 row length (d rounded up to 16) for widened rows -- the same LDS layout as the float32 index (host side of qv_words)
@@ -418,6 +428,18 @@ constexpr int64_t scan_stage_bytes_per_wave(int pitch, int pad, int64_t query_wo
 // run_batch's 160 KiB refusal use this one function; beyond the limit only when not even one row fits beside the rest)
 constexpr int64_t brute_staged_lds_bytes(int stride_words, int64_t query_words, int k) {
   return (brute_lds_bytes_per_wave(query_words, k) + scan_stage_bytes_per_wave(stride_words * 4, kScanStagePad, query_words, k)) * kWavesPerBlock;
+}
+
+// Which scan kernel a view takes (launch_brute, run_batch's LDS check and its launch shape ask here): the one-byte shadow rows
+// always the staged one (their unit has no other); float8 rows the staged one where every task is T_BRUTE -- every kind but the
+// PrefilterIndex, whose T_BRUTE_GATHER rows are not contiguous -- and a row fits beside the rest; otherwise the plain k_brute,
+// so the scan admits the row lengths it admits for the other widened types.
+inline bool scan_staged(const IndexView &v, int k) {
+  if (v.dtype == kRowsU8Widened) return true;
+  return v.dtype == kRowsF8 && v.kind != 0 && brute_staged_lds_bytes(v.stride, query_words(v), k) <= kLdsPerWorkgroup;
+}
+inline int64_t scan_lds_bytes(const IndexView &v, int k) {
+  return scan_staged(v, k) ? brute_staged_lds_bytes(v.stride, query_words(v), k) : brute_lds_bytes(query_words(v), k);
 }
 
 // Bytes of LDS one wave of k_finalize_multi needs: 64 candidate keys and the merged list of k keys (rounded up to an even

@@ -121,6 +121,8 @@ struct CoverArgs {
 //   one-byte shadow rows of a float32 index (internal view type 6, wann_set_dense_rows)
 //                  16 .. 128           -                         -
 //                  k_gemm_scores<W> of wann_gemm_kernels_w8.inc: the bfloat16 kernel, a quarter of the float32 bytes fetched
+//   float8         16 .. 128           -                         -
+//                  k_gemm_scores<W> of the one-byte rows (each E4M3 byte is one bf16: the bfloat16 kernel behind a byte fetch)
 //   uint8 / int8   16 .. 128 (512 B)   -                         129 .. 512 (kGemmMaxBytes / 4)
 //                  k_gemm_scores_b<N>                            k_gemm_scores_bslab, quantised keys: k_rerank_bslab
 //
@@ -131,7 +133,7 @@ inline DenseRows dense_row_class(const IndexView &ix) {
   const int words = query_words(ix);
   if ((ix.stride & 15) || words < 16 || words > (bytes ? kGemmMaxBytes / 4 : kGemmMaxFloats)) return kRowsNone;
   if (words <= 128) return kRowsNarrow;
-  if (ix.dtype == 5) return kRowsNone;  // bfloat16 rows beyond 128 elements: the exact scan, with or without WANN_DENSE_LONG_ROWS
+  if (ix.dtype == 5 || ix.dtype == kRowsF8) return kRowsNone;  // bfloat16 / float8 rows beyond 128 elements: the exact scan, with or without WANN_DENSE_LONG_ROWS
   // (the view of a float32 index's one-byte shadow rows, wann_set_dense_rows: its score kernel is the bfloat16 one with a byte
   // fetch and covers the narrow class alone -- longer rows are scored from the float32 rows)
   if (ix.dtype == kRowsU8Widened) return kRowsNone;

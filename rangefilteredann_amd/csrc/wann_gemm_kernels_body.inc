@@ -23,7 +23,7 @@
 // The MFMA scores only SELECT candidates (SURVEY.md A.3: the reference sums in another order); every returned
 // distance is computed by the reference-order routines.
 //
-// One translation unit per element type of the point set (WANN_DT, set by wann_gemm_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip
+// One translation unit per element type of the point set (WANN_DT, set by wann_gemm_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip / _w8.hip / _f8.hip
 // before this body is included).  The float32 unit holds the grouping kernels and every float32 kernel.  Which rows run on which
 // score kernel is decided in one place, dense_row_class (wann_gemm_device.h); the launchers are one text for all five units,
 // wann_gemm_launch.inc, each unit exposing its own through a constant table (GemmUnit) that the float32 unit's entry points look up.
@@ -43,6 +43,9 @@
 //                    unit's k_gemm_scores with another point fetch (wann_gemm_kernels_w8.inc): an integer 0 .. 255 is one
 //                    bfloat16 value, so a row widened byte by byte is its own high term.  The unit holds that kernel alone:
 //                    norms, selection and re-rank stay the float32 unit's, on the float32 rows.
+//   float8 rows (WANN_DT = 8, wann_gemm_kernels_f8.hip) that same kernel and fetch, each E4M3 byte widened to the bfloat16 it
+//                    also is (four significant bits, exponents 2^-9 .. 2^8).  A FULL unit: k_point_norms, k_rerank,
+//                    k_rerank_cover and the rescue read the float8 rows.  Rows of up to 128 elements; longer ones take the scan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -67,6 +70,8 @@ namespace wann {
 #define WANN_DT_NS_G dt_f16
 #elif WANN_DT == 5
 #define WANN_DT_NS_G dt_bf16
+#elif WANN_DT == 8
+#define WANN_DT_NS_G dt_f8
 #else
 #define WANN_DT_NS_G dt_w8  // (the one-byte shadow rows of a float32 index: the unit holds a score kernel and nothing else)
 #endif
@@ -116,6 +121,14 @@ __global__ void k_point_norms(IndexView ix, float *norm2, unsigned int *max_bits
   const unsigned short *pb = reinterpret_cast<const unsigned short *>(p);
   for (int i = lane; i < ix.d; i += 64) {
     const float v = __uint_as_float((uint32_t)pb[i] << 16);
+    s = fmaf(v, v, s);
+  }
+#elif WANN_DT == 8
+  // (likewise: element i of a float8 row is byte u8_row_position(i) of it, widened exactly -- the lane's elements and their order
+  // are the float32 kernel's, and so are the norms on the upcast points, bit for bit)
+  const unsigned char *p8 = reinterpret_cast<const unsigned char *>(p);
+  for (int i = lane; i < ix.d; i += 64) {
+    const float v = __builtin_amdgcn_cvt_pk_f32_fp8((int)p8[u8_row_position(i)], false)[0];
     s = fmaf(v, v, s);
   }
 #else
@@ -526,7 +539,7 @@ __device__ __forceinline__ void insert4_chain(float &m1, float &m2, float &m3, f
 // Bfloat16 rows (WANN_DT = 5) have a kernel body of their own: one staged row per point, two products.
 #if WANN_DT == 5
 #include "wann_gemm_kernels_bf16.inc"
-#elif WANN_DT == 6
+#elif WANN_DT == 6 || WANN_DT == 8  // (float8 rows: the same kernel, another widening)
 #include "wann_gemm_kernels_w8.inc"
 #else
 WANN_GNS_BEGIN
@@ -728,7 +741,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
 #endif
 }
 WANN_GNS_END
-#endif  // WANN_DT != 5, 6
+#endif  // WANN_DT != 5, 6, 8
 
 #if WANN_DT == 0
 

@@ -18,11 +18,22 @@
 //     of 16 ends in half a group: its 16 elements are the blocks 0 .. 3, the first two slots of both chunks.
 // |p|^2 is the float32 rows' (GemmArgs::pnorm2: k_point_norms of the float32 unit); selection, proof bound and re-rank run in
 // the float32 unit on the float32 rows.
+// Float8 rows (WANN_DT = 8, wann_gemm_kernels_f8.hip) take this kernel with another widen4_bf16: an OCP E4M3 value has four
+// significant bits and an exponent of 2^-9 .. 2^8, so it too IS one bfloat16 value -- v_cvt_pk_f32_fp8 gives the float32, exact
+// for every finite pattern in any FP mode (its results are normal numbers), and the top half of that is the bf16.  There the rows
+// are the index's own (wann_index::d_points, the same layout), |p|^2 comes from this unit's k_point_norms, and selection, proof
+// bound and re-rank run in this unit on the float8 rows: the float32 kernel's scores on the upcast row all the same.
 WANN_GNS_BEGIN
 // four bytes of a row -> the four bf16 they stand for, in element order
 __device__ __forceinline__ uint2 widen4_bf16(uint32_t w) {
+#if WANN_DT == 8
+  typedef float f8pair_g __attribute__((ext_vector_type(2)));
+  const f8pair_g lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  const uint32_t f0 = __float_as_uint(lo.x), f1 = __float_as_uint(lo.y), f2 = __float_as_uint(hi.x), f3 = __float_as_uint(hi.y);
+#else
   const uint32_t f0 = __float_as_uint((float)(w & 0xffu)), f1 = __float_as_uint((float)((w >> 8) & 0xffu));
   const uint32_t f2 = __float_as_uint((float)((w >> 16) & 0xffu)), f3 = __float_as_uint((float)(w >> 24));
+#endif
   return make_uint2((f0 >> 16) | (f1 & 0xffff0000u), (f2 >> 16) | (f3 & 0xffff0000u));
 }
 

@@ -1,5 +1,5 @@
 // wann_gemm_launch.inc -- the launchers of the dense prefilter path, included at the end of wann_gemm_kernels_body.inc: one text,
-// compiled in every unit (float32, uint8, int8, float16, bfloat16, one-byte shadow rows) against that unit's kernels.  A unit picks its kernels by the row class
+// compiled in every unit (float32, uint8, int8, float16, bfloat16, one-byte shadow rows, float8) against that unit's kernels.  A unit picks its kernels by the row class
 // (dense_row_class, wann_gemm_device.h: the only place that knows a row length) and exposes its launchers as one constant table,
 // gemm_unit(); the float32 unit also holds the entry points of wann_gemm_device.h, which look the table up by ix.dtype (unit_of).
 // Every launcher returns null when it has launched, otherwise the error text.
@@ -59,8 +59,8 @@ static ScoreKernel pick_score_kernel(const IndexView &ix) {
   // long: run-time slab count, both operands staged per slab (queries pre-split, `words` words a row), one workgroup per CU
 #if WANN_DT == 3
   if (rows == kRowsLong) return {k_gemm_scores_hslab, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
-#elif WANN_DT == 5 || WANN_DT == 6
-  // (bfloat16 rows, and the one-byte shadow rows of a float32 index: narrow only; dense_row_class names no other class for them)
+#elif WANN_DT == 5 || WANN_DT == 6 || WANN_DT == 8
+  // (bfloat16 and float8 rows, and the one-byte shadow rows of a float32 index: narrow only; dense_row_class names no other class for them)
 #else
   if (rows == kRowsLong) return {k_gemm_scores_long, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
   if (rows == kRowsWide) {  // slabs of 128, A operand in registers, one workgroup per CU
@@ -112,7 +112,7 @@ static const char *unit_point_sums(const IndexView &ix, float *norm2, unsigned i
   return gerr_of(hipGetLastError());
 }
 
-#if !WANN_HALF_ROWS  // (float16 rows: the float32 unit's k_split_queries; bfloat16 rows have no long class)
+#if !WANN_HALF_ROWS && WANN_DT != 8  // (float16 rows: the float32 unit's k_split_queries; bfloat16 / float8 rows have no long class)
 static const char *unit_prep_queries(const float *queries, int64_t nq, int d, int words, uint32_t *out, void *stream) {
 #if WANN_BYTE_ROWS
   const int64_t items = nq * words;  // a thread per packed word
@@ -145,7 +145,7 @@ static const char *unit_select_rerank(const GemmArgs &a, Counters *ctr, void *st
 const GemmUnit &gemm_unit() {
 #if WANN_DT == 6
   static constexpr GemmUnit unit = {nullptr, nullptr, unit_gemm_scores, nullptr, nullptr};  // (only ever asked for gemm_scores: dense_prefilter)
-#elif WANN_HALF_ROWS
+#elif WANN_HALF_ROWS || WANN_DT == 8
   static constexpr GemmUnit unit = {unit_point_sums, nullptr, unit_gemm_scores, unit_select_rerank, unit_rerank_cover};
 #else
   static constexpr GemmUnit unit = {unit_point_sums, unit_prep_queries, unit_gemm_scores, unit_select_rerank, unit_rerank_cover};
@@ -162,9 +162,10 @@ namespace dt_i8 { const GemmUnit &gemm_unit(); }
 namespace dt_f16 { const GemmUnit &gemm_unit(); }
 namespace dt_bf16 { const GemmUnit &gemm_unit(); }
 namespace dt_w8 { const GemmUnit &gemm_unit(); }
+namespace dt_f8 { const GemmUnit &gemm_unit(); }
 static const GemmUnit &unit_of(const IndexView &ix) {
   return ix.dtype == 1 ? dt_u8::gemm_unit() : ix.dtype == 2 ? dt_i8::gemm_unit() : ix.dtype == 3 ? dt_f16::gemm_unit()
-       : ix.dtype == 5 ? dt_bf16::gemm_unit() : ix.dtype == kRowsU8Widened ? dt_w8::gemm_unit() : gemm_unit();
+       : ix.dtype == 5 ? dt_bf16::gemm_unit() : ix.dtype == kRowsU8Widened ? dt_w8::gemm_unit() : ix.dtype == kRowsF8 ? dt_f8::gemm_unit() : gemm_unit();
 }
 
 static thread_local const char *g_gerr = "";

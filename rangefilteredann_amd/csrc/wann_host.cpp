@@ -7,6 +7,7 @@
 // and fails loudly otherwise.
 #include "wann_host_internal.h"
 #include "wann_bf16.h"
+#include "wann_f8.h"
 #include "wann_half.h"
 
 namespace wann_host {
@@ -77,7 +78,8 @@ void upload_index(wann_index &I) {
   v.n = s.n;
   v.d = (int32_t)s.d;
   // float16 / bfloat16 points: the host rows are their float32 upcast; the device rows are two-byte elements again (exact), 64-byte padded
-  v.stride = (int32_t)(two_byte_rows(s.dtype) ? two_byte_stride_words(s.d) : s.stride);
+  // float8 points: likewise one-byte patterns again, d bytes zero padded to a multiple of 64, in the one-byte shadow rows' layout
+  v.stride = (int32_t)(two_byte_rows(s.dtype) ? two_byte_stride_words(s.d) : s.dtype == WANN_DTYPE_F8 ? u8_widened_stride_words(s.d) : s.stride);
   v.metric = s.metric;
   v.dtype = s.dtype;
   v.kind = s.kind;
@@ -95,6 +97,11 @@ void upload_index(wann_index &I) {
       uint16_t *dst = reinterpret_cast<uint16_t *>(rows.data() + r * v.stride);
       for (int64_t j = 0; j < s.d; j++) dst[j] = float_to_two_byte(s.dtype, src[j]);
     });
+    I.d_points.upload(rows);
+  } else if (s.dtype == WANN_DTYPE_F8) {
+    std::vector<float> rows((size_t)s.n * v.stride, 0.f);
+    pack_f8_rows(H.pts.data(), s.n, s.d, s.stride, v.stride, s.threads, rows.data());
+    interleave_u8_rows(rows.data(), s.n, v.stride, s.threads);  // (the device layout: u8_row_position, wann_device.h)
     I.d_points.upload(rows);
   } else {
     I.d_points.upload(H.pts);
@@ -413,11 +420,11 @@ void build_pending(wann_index &I, std::vector<HostPart *> &pending) {
     build_pending_on_host(H, pending);
     for (auto &t : targets) upload_part_rows(I, *t.part, I.parts[t.part_index]);
   } else {
-    // float16 / bfloat16 points are built from their float32 upcast (the host rows) by the float32 build kernels: the graphs are those of
+    // float16 / bfloat16 / float8 points are built from their float32 upcast (the host rows) by the float32 build kernels: the graphs are those of
     // the float32 index on the upcast points, byte for byte.  The float32 rows live on the device for the build only.
     IndexView bv = I.view;
     DevBuf<float> rows32;
-    if (two_byte_rows(s.dtype)) {
+    if (upcast_built(s.dtype)) {
       rows32.upload(H.pts);
       bv.points = rows32.p;
       bv.stride = (int32_t)s.stride;
@@ -441,6 +448,9 @@ std::vector<float> bytes_to_float(int dtype, const void *src, int64_t count) {
   if (two_byte_rows(dtype)) {
     const uint16_t *p = (const uint16_t *)src;
     for (int64_t i = 0; i < count; i++) out[(size_t)i] = two_byte_to_float(dtype, p[i]);
+  } else if (dtype == WANN_DTYPE_F8) {
+    const uint8_t *p = (const uint8_t *)src;
+    for (int64_t i = 0; i < count; i++) out[(size_t)i] = f8_to_float(p[i]);
   } else if (dtype == WANN_DTYPE_U8) {
     const uint8_t *p = (const uint8_t *)src;
     for (int64_t i = 0; i < count; i++) out[(size_t)i] = (float)p[i];

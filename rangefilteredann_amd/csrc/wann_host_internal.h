@@ -271,14 +271,16 @@ int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
                const int64_t *d_qids = nullptr);
 void build_pending(wann_index &I, std::vector<HostPart *> &pending);
-// host queries of the index's element type (uint8 / int8 / float16) -> the fp32 rows every kernel stages (exact)
+// host queries of the index's element type (uint8 / int8 / float16 / bfloat16 / float8) -> the fp32 rows every kernel stages (exact)
 std::vector<float> bytes_to_float(int dtype, const void *src, int64_t count);
 // bytes per element of the caller's points / host queries
 inline int64_t element_bytes(int dtype) { return dtype == WANN_DTYPE_F32 ? 4 : two_byte_rows(dtype) ? 2 : 1; }
 // the element types the C ABI accepts (wann.h: 4 is unassigned)
 inline bool known_dtype(int dtype) {
-  return dtype == WANN_DTYPE_F32 || dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8 || dtype == WANN_DTYPE_F16 || dtype == WANN_DTYPE_BF16;
+  return dtype == WANN_DTYPE_F32 || dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8 || dtype == WANN_DTYPE_F16 || dtype == WANN_DTYPE_BF16 ||
+         dtype == WANN_DTYPE_F8;
 }
+static_assert(WANN_DTYPE_F8 == kRowsF8, "the float8 element type is its own view type");
 // uint8 / int8 rows: scored with v_dot4 by kernels built for more waves per SIMD
 inline bool byte_rows(const IndexView &v) { return v.dtype == WANN_DTYPE_U8 || v.dtype == WANN_DTYPE_I8; }
 // this view's four-wave k_search is built for THREE waves per SIMD (at most 168 registers): the inner-product and byte-row

@@ -24,7 +24,7 @@
 
 namespace wann {
 
-// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip / _w8.hip / _h16.hip before this body is
+// One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip / _w8.hip / _h16.hip / _f8.hip before this body is
 // included): the search and scan kernels and their launchers live in a per-type namespace; the type-independent
 // kernels (routing, finalisation) and the dispatchers are compiled with the float32 unit only.
 #if WANN_DT == 0
@@ -39,6 +39,8 @@ namespace wann {
 #define WANN_DT_NS dt_bf16
 #elif WANN_DT == 7
 #define WANN_DT_NS dt_h16  // (the half shadow rows of a float32 index, paired: its k_search and, under wann_set_scan_rows, its plain k_brute)
+#elif WANN_DT == 8
+#define WANN_DT_NS dt_f8  // (float8 rows: k_search, the staged scan for sorted rows and the plain k_brute for the PrefilterIndex's gathered ones)
 #else
 #define WANN_DT_NS dt_w8  // (the one-byte shadow rows of a float32 index: its k_search and, under wann_set_scan_rows, its scan)
 #endif
@@ -54,6 +56,8 @@ namespace wann {
 #define WANN_DT_TPARAM , int ROWS_DT = 6
 #elif WANN_DT == 7  // (and the paired half shadow rows')
 #define WANN_DT_TPARAM , int ROWS_DT = 7
+#elif WANN_DT == 8  // (and the float8 unit)
+#define WANN_DT_TPARAM , int ROWS_DT = 8
 #else
 #define WANN_DT_TPARAM
 #endif
@@ -761,15 +765,20 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
 // LDS: scan_fetch (wann_device.h) copies the span with 16-byte loads, and wave_distances scores a view of the staging area, the
 // same routines on the same blocks in the same order.  (On the half view the same fetch lost to the plain one: DESIGN.md 3.4.)
 // --------------------------------------------------------------------------------------------
-#define WANN_SCAN_STAGED (WANN_DT == 6)
-#if !WANN_SCAN_STAGED
+// The float8 unit holds both: the staged kernel for the sorted kinds, whose T_BRUTE rows are contiguous, and the plain one for
+// the PrefilterIndex, whose T_BRUTE_GATHER rows are not (scan_staged, wann_device.h, chooses) -- the same routines on the
+// same blocks either way.
+#define WANN_SCAN_STAGED (WANN_DT == 6 || WANN_DT == 8)
+#define WANN_SCAN_PLAIN (WANN_DT != 6)
+#if WANN_SCAN_PLAIN
 template <int METRIC>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_brute(BruteArgs A) {
 #define WANN_BRUTE_STAGED 0
 #include "wann_brute_body.inc"
 #undef WANN_BRUTE_STAGED
 }
-#else
+#endif
+#if WANN_SCAN_STAGED
 template <int METRIC>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_brute_staged(BruteArgs A) {
 #define WANN_BRUTE_STAGED 1
@@ -1545,12 +1554,15 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
 }
 
 template <int METRIC>
-static int launch_brute_t(const BruteArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-#if WANN_SCAN_STAGED
+static int launch_brute_t(const BruteArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t s, bool staged) {
+#if WANN_SCAN_STAGED && WANN_SCAN_PLAIN
+  auto kern = staged ? k_brute_staged<METRIC> : k_brute<METRIC>;
+#elif WANN_SCAN_STAGED
   auto kern = k_brute_staged<METRIC>;  // (the one scan kernel of this unit)
 #else
   auto kern = k_brute<METRIC>;
 #endif
+  (void)staged;
   if (lds > (size_t)kLdsNoAttribute)
     if (check(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))) return 1;
   hipLaunchKernelGGL(kern, grid, block, lds, s, a);
@@ -1560,13 +1572,11 @@ static int launch_brute_t(const BruteArgs &a, dim3 grid, dim3 block, size_t lds,
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   if (blocks <= 0) return 0;
   // (long rows or a wide k: more than a launch gets unasked -- run_batch has refused what exceeds kLdsPerWorkgroup)
-#if WANN_SCAN_STAGED
-  const size_t lds = (size_t)brute_staged_lds_bytes(a.ix.stride, query_words(a.ix), a.k);
-#else
-  const size_t lds = (size_t)brute_lds_bytes(query_words(a.ix), a.k);
-#endif
+  const bool staged = scan_staged(a.ix, a.k);  // (wann_device.h: by the view's type and kind -- this unit's kernel for it)
+  const size_t lds = (size_t)scan_lds_bytes(a.ix, a.k);
   dim3 grid(blocks), block(64 * kWavesPerBlock);
-  return a.ix.metric == 1 ? launch_brute_t<1>(a, grid, block, lds, (hipStream_t)stream) : launch_brute_t<0>(a, grid, block, lds, (hipStream_t)stream);
+  return a.ix.metric == 1 ? launch_brute_t<1>(a, grid, block, lds, (hipStream_t)stream, staged)
+                          : launch_brute_t<0>(a, grid, block, lds, (hipStream_t)stream, staged);
 }
 
 }  // namespace WANN_DT_NS
@@ -1603,23 +1613,28 @@ int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
 int launch_brute(const BruteArgs &a, int blocks, void *stream);
 }
+namespace dt_f8 {
+int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
+int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
+int launch_brute(const BruteArgs &a, int blocks, void *stream);
+}
 int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
   return a.ix.dtype == 1 ? dt_u8::search_occupancy(a, cfg) : a.ix.dtype == 2 ? dt_i8::search_occupancy(a, cfg)
        : a.ix.dtype == 3 ? dt_f16::search_occupancy(a, cfg) : a.ix.dtype == 5 ? dt_bf16::search_occupancy(a, cfg)
        : a.ix.dtype == kRowsU8Widened ? dt_w8::search_occupancy(a, cfg) : a.ix.dtype == kRowsF16Paired ? dt_h16::search_occupancy(a, cfg)
-       : dt_f32::search_occupancy(a, cfg);
+       : a.ix.dtype == kRowsF8 ? dt_f8::search_occupancy(a, cfg) : dt_f32::search_occupancy(a, cfg);
 }
 int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
   return a.ix.dtype == 1 ? dt_u8::launch_search(a, cfg, stream) : a.ix.dtype == 2 ? dt_i8::launch_search(a, cfg, stream)
        : a.ix.dtype == 3 ? dt_f16::launch_search(a, cfg, stream) : a.ix.dtype == 5 ? dt_bf16::launch_search(a, cfg, stream)
        : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_search(a, cfg, stream) : a.ix.dtype == kRowsF16Paired ? dt_h16::launch_search(a, cfg, stream)
-       : dt_f32::launch_search(a, cfg, stream);
+       : a.ix.dtype == kRowsF8 ? dt_f8::launch_search(a, cfg, stream) : dt_f32::launch_search(a, cfg, stream);
 }
 int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   return a.ix.dtype == 1 ? dt_u8::launch_brute(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_brute(a, blocks, stream)
        : a.ix.dtype == 3 ? dt_f16::launch_brute(a, blocks, stream) : a.ix.dtype == 5 ? dt_bf16::launch_brute(a, blocks, stream)
        : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_brute(a, blocks, stream) : a.ix.dtype == kRowsF16Paired ? dt_h16::launch_brute(a, blocks, stream)
-       : dt_f32::launch_brute(a, blocks, stream);
+       : a.ix.dtype == kRowsF8 ? dt_f8::launch_brute(a, blocks, stream) : dt_f32::launch_brute(a, blocks, stream);
 }
 
 int launch_finalize(const FinalizeArgs &a, void *stream) {

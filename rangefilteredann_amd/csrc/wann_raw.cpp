@@ -22,7 +22,7 @@ struct RawGraph {
   DevBuf<unsigned long long> g_beam, d_prof;
   DevBuf<uint32_t> g_seen;
   int64_t layout = -1;
-  // points: (n, d) rows of `dtype` elements (float32, uint8 / int8 bytes: stored as byte rows, or float16 / bfloat16: stored as two-byte elements)
+  // points: (n, d) rows of `dtype` elements (float32, uint8 / int8 bytes: stored as byte rows, float16 / bfloat16: stored as two-byte elements, or float8: stored as interleaved one-byte rows)
   void load(int device, int metric, const void *points, int64_t n_, int64_t d_, const int32_t *graph_rows, int64_t maxdeg_,
             int64_t subset_start, int64_t subset_n_, int dtype = WANN_DTYPE_F32) {
     HIP_CHECK(hipSetDevice(device));
@@ -39,6 +39,7 @@ struct RawGraph {
     const int64_t stride = ((d * esz + 63) / 64) * 16;  // 32-bit words per row
     std::vector<float> pts((size_t)n * stride, 0.f);
     for (int64_t i = 0; i < n; i++) memcpy(pts.data() + i * stride, (const char *)points + i * d * esz, (size_t)(d * esz));
+    if (dtype == WANN_DTYPE_F8) interleave_u8_rows(pts.data(), n, stride, 0);  // (float8 rows: the device layout, u8_row_position)
     const int rs = (int)(((maxdeg_ + 15) / 16) * 16);
     HostGraph g;
     g.n = subset_n;

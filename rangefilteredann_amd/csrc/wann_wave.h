@@ -86,12 +86,14 @@ __device__ __forceinline__ u64 hash64_2(u64 x) {
 #ifndef WANN_DT
 #define WANN_DT 0  // 0 = float32 rows, 1 = uint8, 2 = int8, 3 = float16, 5 = bfloat16 (4 is unassigned, see wann.h),
                    // 6 = the one-byte shadow rows of a float32 index (internal: kRowsU8Widened in wann_device.h),
-                   // 7 = its half shadow rows, paired (internal: kRowsF16Paired)
+                   // 7 = its half shadow rows, paired (internal: kRowsF16Paired),
+                   // 8 = float8 (OCP E4M3) rows, in the one-byte shadow rows' layout
 #endif
 #define WANN_BYTE_ROWS (WANN_DT == 1 || WANN_DT == 2)
 #define WANN_HALF_ROWS (WANN_DT == 3 || WANN_DT == 5 || WANN_DT == 7)  // two-byte float rows (two_byte_rows in wann_device.h is the host side)
 // rows narrower than float32, scored as their exact float32 upcast against the fp32 query (widened_rows is the host side)
-#define WANN_WIDENED_ROWS (WANN_HALF_ROWS || WANN_DT == 6)
+#define WANN_QUAD_ROWS (WANN_DT == 6 || WANN_DT == 8)  // one-byte rows, interleaved and fetched 16 bytes (a quad of blocks) at a time
+#define WANN_WIDENED_ROWS (WANN_HALF_ROWS || WANN_QUAD_ROWS)
 
 // A row BLOCK is four consecutive elements e..e+3 of a row (e a multiple of 4): a float4 of a float32 row, 8 bytes of a
 // float16 row.  Float16 rows (WANN_DT = 3) keep the natural element order, padded with zeros to a multiple of 32 halves
@@ -164,6 +166,27 @@ __device__ __forceinline__ uint32_t quad_blk(const u32x4 &q, int i) { return i =
 typedef u32x4 rowheld_t;  // what a lane holds of a row: quads
 constexpr int kHeldBlks = 4;
 #define held_blk(w, i) quad_blk(w, i)
+#elif WANN_DT == 8
+// float8 rows (OCP E4M3, wann.h WANN_DTYPE_F8): the one-byte shadow rows' layout, blocks, quads, loaders and lane pairing --
+// a block is one aligned 32-bit word, rows are interleaved (u8_row_position), a lane fetches a QUAD with one 16-byte load.
+// Only the widening differs: v_cvt_pk_f32_fp8 turns two E4M3 bytes of the word into two float32, two instructions a block.
+// It is exact for every finite pattern whatever the FP mode: an E4M3 value has four significant bits and an exponent of
+// 2^-9 .. 2^8, so even its subnormals are NORMAL float32 values -- no multiply, nothing the float32 denormal mode can flush.
+// (The NaN patterns 0x7f / 0xff never reach a row: the host refuses them.)  The float32 arithmetic follows in its own order.
+typedef uint32_t rowblk_t;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 rowquad_t __attribute__((aligned(8)));
+typedef float f8pair_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float4 f8x4_to_f4(uint32_t w) {
+  const f8pair_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  return make_float4(lo.x, lo.y, hi.x, hi.y);
+}
+#define ld_quad(prow, c, h) (*reinterpret_cast<const rowquad_t *>(reinterpret_cast<const unsigned char *>(prow) + 32 * (c) + 16 * (h)))
+__device__ __forceinline__ uint32_t quad_blk(const u32x4 &q, int i) { return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w; }
+#define cvt_blk(w) f8x4_to_f4(w)
+typedef u32x4 rowheld_t;  // what a lane holds of a row: quads
+constexpr int kHeldBlks = 4;
+#define held_blk(w, i) quad_blk(w, i)
 #else
 typedef float4 rowblk_t;
 // (no parentheses round `e`: `prow + 8 * b + 4 * h` is the address arithmetic the float32 unit has always compiled)
@@ -211,7 +234,7 @@ using RowBlks = rowheld_t[N > 0 ? (N + kHeldBlks - 1) / kHeldBlks : 1];
 // and for byte rows -- in index order, or, LAST_FIRST, in the order a squared-L2 routine consumes them.
 template <int N, int NBC = 0, bool LAST_FIRST = false>
 __device__ __forceinline__ void row_blks_load(RowBlks<N> &rb, const float *__restrict__ prow, int h, int nblk = 0, int b0 = 0) {
-#if WANN_DT == 6
+#if WANN_QUAD_ROWS
 #pragma unroll
   for (int c = 0; c < (N + 3) / 4; c++)
     if (NBC > 0 ? 4 * c < NBC : b0 + 4 * c < nblk) rb[c] = ld_quad(prow, (b0 >> 2) + c, h);
@@ -276,11 +299,11 @@ __device__ __forceinline__ float l2_pair(const float *__restrict__ prow, const f
                                          int h, bool active) {
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   if (active) {
-#if WANN_DT == 6 || WANN_DT == 7
+#if WANN_QUAD_ROWS || WANN_DT == 7
     const int nfull = D8 & ~1;
     if (D8 & 1) {
       const int b = D8 - 1;
-#if WANN_DT == 6
+#if WANN_QUAD_ROWS
       const u32x4 last = ld_quad(prow, b >> 2, h);
       const float4 q = q_blk(qv, b, h);
       l2_step(a0, a1, a2, a3, cvt_blk(quad_blk(last, b & 3)), q);

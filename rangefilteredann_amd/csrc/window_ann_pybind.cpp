@@ -17,6 +17,7 @@
 
 #include "../../include/wann.h"
 #include "wann_bf16.h"
+#include "wann_f8.h"
 
 namespace py = pybind11;
 using namespace pybind11::literals;
@@ -70,9 +71,23 @@ static py::array bf16_bits_of(const py::handle &a) {
   return std::move(out);
 }
 
+// numpy has no float8 either: any array numpy casts to float32 -> the uint8 bit patterns of its values rounded to OCP E4M3
+// (nearest, ties to even; what rounds above 448, infinities and NaN become the NaN pattern: float_to_f8 -- an index refuses those).
+// VALUES are rounded, whatever the array's dtype: a uint8 array is never read as bit patterns.
+static py::array f8_bits_of(const py::handle &a) {
+  FArray f = FArray::ensure(a);
+  if (!f) return py::array();
+  py::array_t<uint8_t> out(std::vector<py::ssize_t>(f.shape(), f.shape() + f.ndim()));
+  const float *src = f.data();
+  uint8_t *dst = out.mutable_data();
+  for (py::ssize_t i = 0, n = f.size(); i < n; i++) dst[i] = wann::float_to_f8(src[i]);
+  return std::move(out);
+}
+
 // any array -> a C-contiguous array of the element type `dtype` (py::array_t<T>::ensure semantics; float16, which pybind11 has no
-// C++ type for, through numpy: astype rounds to nearest, ties to even; bfloat16: bf16_bits_of)
+// C++ type for, through numpy: astype rounds to nearest, ties to even; bfloat16: bf16_bits_of; float8: f8_bits_of)
 static py::array as_elem(int dtype, const py::handle &a) {
+  if (dtype == WANN_DTYPE_F8) return f8_bits_of(a);
   if (dtype == WANN_DTYPE_BF16) return bf16_bits_of(a);
   if (dtype == WANN_DTYPE_F16) return py::module_::import("numpy").attr("ascontiguousarray")(a, "dtype"_a = "float16");
   if (dtype == WANN_DTYPE_F32) return FArray::ensure(a);
@@ -600,6 +615,10 @@ PYBIND11_MODULE(_window_ann, m) {
   // and round its values to bfloat16 (a torch.bfloat16 tensor t passes through t.float().numpy() exactly)
   add_variant<WANN_METRIC_L2, WANN_DTYPE_BF16>(m, "BFloat16Euclidian");
   add_variant<WANN_METRIC_MIPS, WANN_DTYPE_BF16>(m, "BFloat16Mips");
+  // and float8 points (wann.h WANN_DTYPE_F8, OCP E4M3): the same, rounded to float8 -- values out of range become NaN patterns,
+  // which the constructor (and a host batch_search) refuses with the offending row: data is never silently saturated
+  add_variant<WANN_METRIC_L2, WANN_DTYPE_F8>(m, "Float8Euclidian");
+  add_variant<WANN_METRIC_MIPS, WANN_DTYPE_F8>(m, "Float8Mips");
 
   // python_bindings.cpp:67-86: builder and index names of the unfiltered Vamana variants
   add_vamana<WANN_METRIC_L2, WANN_DTYPE_F32>(m, "float_euclidian", "VamanaFloatEuclidianIndex");
@@ -629,6 +648,21 @@ PYBIND11_MODULE(_window_ann, m) {
     const float *src = f.data();
     float *dst = out.mutable_data();
     for (py::ssize_t i = 0, n = f.size(); i < n; i++) dst[i] = wann::bf16_to_float(wann::float_to_bf16(src[i]));
+    return out;
+  }, "a"_a);
+  // what a float8 index stores of `a`: its values rounded to OCP E4M3, as uint8 bit patterns / as the float32 values they widen to
+  m.def("float8_bits", [](py::object a) {
+    py::array b = f8_bits_of(a);
+    if (!b) throw std::runtime_error("float8_bits: not convertible to a float32 array");
+    return b;
+  }, "a"_a);
+  m.def("float8_round", [](py::object a) {
+    FArray f = FArray::ensure(a);
+    if (!f) throw std::runtime_error("float8_round: not convertible to a float32 array");
+    py::array_t<float> out(std::vector<py::ssize_t>(f.shape(), f.shape() + f.ndim()));
+    const float *src = f.data();
+    float *dst = out.mutable_data();
+    for (py::ssize_t i = 0, n = f.size(); i < n; i++) dst[i] = wann::f8_to_float(wann::float_to_f8(src[i]));
     return out;
   }, "a"_a);
   m.def("device_count", [] { return wann_device_count(); });
@@ -678,16 +712,19 @@ PYBIND11_MODULE(_window_ann, m) {
       "metric"_a, "points"_a, "graph_rows"_a, "subset_start"_a, "queries"_a, "query_ids"_a, "beam"_a,
       "limit"_a = 10000000, "degree_limit"_a = 10000, "device"_a = 0);
   // raw_beam_search over points of any element type (dtype: 0 float32, 1 uint8, 2 int8, 3 float16, 5 bfloat16 -- there `points` is a
-  // uint16 array of BIT PATTERNS, as float16 takes np.float16); queries stay float32
+  // uint16 array of BIT PATTERNS, as float16 takes np.float16 -- 8 float8: a uint8 array of bit patterns); queries stay float32
   m.def(
       "raw_beam_search_typed",
       [](int metric, int dtype, py::array points_in, py::array_t<int32_t, py::array::c_style | py::array::forcecast> graph_rows,
          int64_t subset_start, FArray queries, py::array_t<int64_t, py::array::c_style | py::array::forcecast> query_ids,
          int64_t beam, int64_t limit, int64_t degree_limit, int device) {
-        if ((dtype < WANN_DTYPE_F32 || dtype > WANN_DTYPE_F16) && dtype != WANN_DTYPE_BF16) throw std::runtime_error("unknown dtype");
+        if ((dtype < WANN_DTYPE_F32 || dtype > WANN_DTYPE_F16) && dtype != WANN_DTYPE_BF16 && dtype != WANN_DTYPE_F8) throw std::runtime_error("unknown dtype");
+        if (dtype == WANN_DTYPE_F8 && !py::isinstance<py::array_t<uint8_t>>(points_in))
+          throw std::runtime_error("dtype 8 takes the points as a uint8 array of float8 (E4M3) bit patterns");
         if (dtype == WANN_DTYPE_BF16 && !py::isinstance<py::array_t<uint16_t>>(points_in))
           throw std::runtime_error("dtype 5 takes the points as a uint16 array of bfloat16 bit patterns");
-        py::array points = dtype == WANN_DTYPE_BF16 ? py::array(py::array_t<uint16_t, py::array::c_style>::ensure(points_in)) : as_elem(dtype, points_in);
+        py::array points = dtype == WANN_DTYPE_BF16 ? py::array(py::array_t<uint16_t, py::array::c_style>::ensure(points_in))
+                         : dtype == WANN_DTYPE_F8 ? py::array(py::array_t<uint8_t, py::array::c_style>::ensure(points_in)) : as_elem(dtype, points_in);
         if (points.ndim() != 2 || graph_rows.ndim() != 2 || queries.ndim() != 2) throw std::runtime_error("bad shapes");
         int64_t n = points.shape(0), d = points.shape(1), sn = graph_rows.shape(0), md = graph_rows.shape(1) - 1;
         int64_t nq = queries.shape(0);

@@ -61,18 +61,22 @@ def _module():
 _DTYPES = {"float": "Float", "uint8": "Uint8", "int8": "Int8"}
 # "float16" is not a type of the reference (wrapper.py raises "Invalid data type" for it, and so do these constructors by
 # default): float16 points, rows of the float32 index on the upcast points (include/wann.h WANN_DTYPE_F16).  The --dtype float16
-# experiments ask for it with float16=True.  "bfloat16" (WANN_DTYPE_BF16) resolves under the same opt-in and no other.
-_FLOAT16 = {"float16": "Float16", "bfloat16": "BFloat16"}
+# experiments ask for it with float16=True.  "bfloat16" (WANN_DTYPE_BF16) resolves under the same opt-in and no other,
+# and so does "float8" (WANN_DTYPE_F8, OCP E4M3).
+_FLOAT16 = {"float16": "Float16", "bfloat16": "BFloat16", "float8": "Float8"}
 _HALF_DTYPES = tuple(_FLOAT16)
 
 
 def round_to_dtype(a, dtype):
-    """What an index of the half-width `dtype` stores of `a`: a float16 array (numpy astype: nearest, ties to even), or -- numpy
-    has no bfloat16 -- the float32 values rounded to bfloat16 (`bfloat16_round`), which the BFloat16 classes take as they are."""
+    """What an index of the narrow `dtype` stores of `a`: a float16 array (numpy astype: nearest, ties to even), or -- numpy
+    has no bfloat16 and no float8 -- the float32 values rounded to bfloat16 (`bfloat16_round`) / to float8 E4M3 (`float8_round`:
+    values beyond 448 become NaN, which the index refuses), which the BFloat16 / Float8 classes take as they are."""
     if dtype == "float16":
         return np.asarray(a).astype(np.float16)
     if dtype == "bfloat16":
         return _module().bfloat16_round(np.asarray(a))
+    if dtype == "float8":
+        return _module().float8_round(np.asarray(a))
     return a
 _METRICS = {"Euclidian": "Euclidian", "mips": "Mips"}
 
@@ -252,6 +256,7 @@ class Settings:
     methods: Tuple[str, ...] = ()  # subset of: prefiltering postfiltering vamana_tree optimized_postfiltering smart_combined three_split super_opt_postfiltering
     # "float16": points and queries rounded to float16 (numpy astype: nearest, ties to even) and searched by the Float16 classes;
     # "bfloat16": rounded to bfloat16 (bfloat16_round) and searched by the BFloat16 classes, cache subdirectory bfloat16/;
+    # "float8": rounded to float8 E4M3 (float8_round) and searched by the Float8 classes, cache subdirectory float8/;
     # recall is still taken against the dataset's stored ground truth of the original data.  Graph caches go to a subdirectory
     # of their own: a float16 index's graphs are those of the ROUNDED points, under the same file names as the float32 graphs.
     dtype: str = "float"
@@ -439,8 +444,8 @@ def build_for_memory(index_type, data, filter_values, metric, dataset_name, alph
     """Construct the index exactly as all_memories.py:25-83 does and return (index, bytes).  The reference reports the
     growth of the process RSS (its index lives in host memory); this engine's index lives in HBM, so the figure is the
     device footprint (`index.device_bytes()`: vectors + labels + decoding + adjacency pool + partition tables).
-    dtype "float16" / "bfloat16": the points are rounded to that type and the Float16 / BFloat16 class is built, its graphs in
-    <cache_root>/float16/ or <cache_root>/bfloat16/."""
+    dtype "float16" / "bfloat16" / "float8": the points are rounded to that type and the Float16 / BFloat16 / Float8 class is
+    built, its graphs in <cache_root>/float16/, <cache_root>/bfloat16/ or <cache_root>/float8/."""
     half = dtype in _HALF_DTYPES
     if half:
         data, cache_root = round_to_dtype(data, dtype), os.path.join(cache_root, dtype)
@@ -520,8 +525,8 @@ def main(argv=None):
                          "super-postfiltering} as experiments/all_memories.py, else with --vamana_tree_split_factor as "
                          "experiments/memory_footprint.py")
     ap.add_argument("--index_type", type=str, default=None)
-    ap.add_argument("--dtype", choices=("float", "float16", "bfloat16"), default="float",
-                    help="float16 / bfloat16: round points and queries to that type and search the Float16 / BFloat16 index classes "
+    ap.add_argument("--dtype", choices=("float", "float16", "bfloat16", "float8"), default="float",
+                    help="float16 / bfloat16 / float8: round points and queries to that type and search the Float16 / BFloat16 / Float8 index classes "
                          "(own graph cache subdirectory and results prefix; recall against the original data's ground truth)")
     args = ap.parse_args(argv)
     threads = args.threads or (os.cpu_count() or 1)

@@ -11,7 +11,9 @@ float32 index built on the unrounded points (its own cache) at the same setting 
 --dtype bfloat16: the same legs for the BFloat16 classes -- points and queries rounded with bfloat16_round (nearest, ties to
 even, 8 significant bits), a cache directory of its own, identical rows required between the bfloat16 index and the float32
 index on the upcast points; the report's keys say "bfloat16" where they say "float16" by default.
-Prints one JSON object.   python tools/bench_half.py [--dtype float16|bfloat16] [--configs sift,glove,deep] [--reps 10] [--no-unrounded]"""
+--dtype float8: likewise for the Float8 classes (OCP E4M3, one byte an element: float8_round).  --scale S multiplies points and
+queries by S before rounding -- a power of two changes no ordering, and moves unit-norm components out of E4M3's subnormal range.
+Prints one JSON object.   python tools/bench_half.py [--dtype float16|bfloat16|float8] [--scale 1] [--configs sift,glove,deep] [--reps 10] [--no-unrounded]"""
 import argparse
 import json
 import os
@@ -34,7 +36,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="sift,glove,deep")
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16", help="the half-width element type under test")
+    ap.add_argument("--dtype", choices=("float16", "bfloat16", "float8"), default="float16", help="the narrow element type under test")
+    ap.add_argument("--scale", type=float, default=1.0, help="multiply points and queries by this (a power of two) before rounding")
     ap.add_argument("--cache", default="/tmp/wann_half_cache")
     ap.add_argument("--no-unrounded", dest="unrounded", action="store_false", help="skip the float32 index on the unrounded points")
     ap.add_argument("--setting", default="", help="'beam,mult': skip the sweep (profiling runs)")
@@ -48,13 +51,15 @@ def main():
 
     dev = torch.device("cuda:0")
     HALF = args.dtype
-    half_cls = {"float16": "Float16", "bfloat16": "BFloat16"}[HALF]
+    half_cls = {"float16": "Float16", "bfloat16": "BFloat16", "float8": "Float8"}[HALF]
+    half_esz = 1 if HALF == "float8" else 2
 
-    def rounded(a):  # what an index of the type stores: a float16 array / the float32 values of the bfloat16 roundings
-        return a.astype(np.float16) if HALF == "float16" else wa.bfloat16_round(a)
+    def rounded(a):  # what an index of the type stores: a float16 array / the float32 values of the bfloat16 or float8 roundings
+        a = a * np.float32(args.scale) if args.scale != 1.0 else a
+        return a.astype(np.float16) if HALF == "float16" else wa.bfloat16_round(a) if HALF == "bfloat16" else wa.float8_round(a)
 
     K, R, L, ALPHA = fc.K, fc.R, fc.L, fc.ALPHA
-    report = dict(tool="tools/bench_half.py", hbm_tb_per_s=HBM_TBPS, legs=[])
+    report = dict(tool="tools/bench_half.py", dtype=HALF, scale=args.scale, hbm_tb_per_s=HBM_TBPS, legs=[])
 
     def log(msg):
         print(f"[half] {msg}", file=sys.stderr, flush=True)
@@ -150,7 +155,7 @@ def main():
                    **{HALF + "_build_s": round(build_s, 1)}, setting=dict(beam=best[0], mult=best[1]), sweep=sweep,
                    rows_identical=rows_identical, counters_equal=counters_equal,
                    counters=dict((k, hc[k]) for k in ("beam_searches", "hops", "dist_cmps", "brute_rows", "label_reads", "spec_searches")))
-        for tag, index, esz in (("float32", f, 4), (HALF, h, 2)):
+        for tag, index, esz in (("float32", f, 4), (HALF, h, half_esz)):
             ms = float(np.median(times[tag]))
             km = float(np.mean(kms[tag]))
             gb = (4 * (R + 1) * hc["hops"] + esz * d * hc["dist_cmps"] + 4 * hc["label_reads"]) / 1e9
