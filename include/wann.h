@@ -20,6 +20,8 @@
  *   wann_batch_search_device_async / wann_wait   that call without blocking: two batches in flight (src/range_filter_tree.h:62-96)
  *   wann_batch_search_device_ids   that call for queries that are not a contiguous range of their batch: per-query own ids
  *       (ParlayANN/algorithms/utils/beamSearch.h:128, src/range_filter_tree.h:71-72; src/postfilter_vamana.h:161-181 for what it is for)
+ *   wann_set_refine_rows / wann_batch_search_device_refined / wann_batch_search_refined   (not calls of the reference) a float16 /
+ *       bfloat16 / float8 index searched for refine_k >= k candidates that are re-ranked against the caller's float32 rows
  *   wann_query_params        QueryParams   ParlayANN/algorithms/utils/types.h:115-140, python_bindings.cpp:204-209
  *   wann_build_params        BuildParams   ParlayANN/algorithms/utils/types.h:77-112,  python_bindings.cpp:211-213
  *
@@ -410,6 +412,65 @@ int wann_set_dense_rows(wann_index *index, int on);
 int wann_dense_rows(const wann_index *index);
 int64_t wann_dense_rows_bytes(const wann_index *index);
 int wann_last_dense_rows(const wann_index *index);
+
+/* REFINED SEARCH: re-rank a compact index's candidates against full-precision rows.  A WANN_DTYPE_F16 / BF16 / F8 index answers
+ * for the ROUNDED points.  A caller who still has the float32 points gives them to the index as a ROW STORE; a refined call then
+ * searches the compact rows for refine_k >= k candidates (a half or a quarter of the float32 bytes per scored row), scores
+ * those candidates against the store's rows and returns the best k.  This saves bandwidth, NOT capacity: the float32 rows sit
+ * in HBM beside the compact index.
+ *
+ * wann_set_refine_rows: `points` is the host array of full-precision points, (n, d) row-major float32, IN THE CALLER'S POINT
+ * ORDER -- the order of the array the index was created from, which is the order of the ids every kind returns (decoded ids of
+ * the sorted kinds, raw ids of the post filter): the store is indexed by returned id and knows nothing of the label sort.  The
+ * device copy has its rows zero padded to a multiple of 16 floats, the float32 index's row pitch.  points == NULL drops the store
+ * (n and d are then ignored).  A second call replaces the store.  WANN_ERR_INVALID, with a message: a null index, n or d not
+ * the index's, or a non-finite element (the message names the first offending row; the store in place is kept).
+ * WANN_ERR_UNSUPPORTED: an index of any other element type -- float32 has nothing to refine, and a uint8 / int8 search turns
+ * the query into bytes, so one fp32 query cannot serve both spaces.  The rows are NOT compared with the index's rounded points:
+ * a caller who scaled points and queries by a power of two to fit float8 passes the scaled originals, and distances are
+ * reported in the space of the queries.  With WANN_DEVICES the store lives on the primary, which the refined calls serve.
+ * wann_refine_rows_bytes: device bytes of the store, n * 4 * 16 * ceil(d / 16); 0 without one, -1 for a null index.
+ * wann_device_bytes does not count the store (as it does not count the shadow copies).
+ *
+ * wann_batch_search_device_refined: wann_batch_search_device's semantics -- fp32 device queries (not rounded), device ranges,
+ * d_ids / d_dists of nq x qp->k, `hip_stream`, blocking -- with this result.  Let C(q) be the row the ordinary call returns for
+ * query q with k = refine_k and everything else of `qp` unchanged.
+ *   - The candidates are the entries of C(q) before its first pad; a pad is an entry with dist == FLT_MAX and id == the kind's
+ *     padding id (0 for the sorted kinds, 2^32-1 for the post filter and the PrefilterIndex), and pads are always a suffix.
+ *   - Each candidate id gets the distance of (store row id, q) in the FLOAT32 INDEX'S arithmetic and evaluation order: the bits a
+ *     WANN_DTYPE_F32 index of those rows returns for that pair (the kernel calls the float32 row-distance routines themselves).
+ *   - The result is the first qp->k candidates under the key (refined distance, id), the exact scan's order, followed by pads
+ *     (padding id, FLT_MAX).
+ *   - An id the search returned twice (fenwick and three_split can) is a candidate twice and may be returned twice: duplicates
+ *     are kept, as everywhere else.
+ *   - No address is ever made from a pad's id.
+ * It needs a store and qp->k <= refine_k <= 1024, and whatever the ordinary call demands of k holds for refine_k; otherwise
+ * WANN_ERR_INVALID.  If the re-rank kernel's LDS need for this (d, k) -- the staged query row and the k-entry list, per wave --
+ * exceeds a workgroup's 160 KiB the call returns WANN_ERR_UNSUPPORTED before anything is launched; it never truncates.  The
+ * search itself is the ordinary call's at k = refine_k, untouched: afterwards wann_get_counters reports that search (every
+ * operation counter equals the ordinary call's at k = refine_k).
+ * wann_batch_search_refined: the host-buffer form.  `queries` is (nq, d) FLOAT32 -- unlike wann_batch_search, which takes the
+ * index dtype's bit patterns and so searches with rounded queries; here the fp32 queries are uploaded as they are and go
+ * through the device path.  ids / dists: nq x qp->k, host.  Serves the primary.
+ * wann_get_refine_counters: the last refined call's re-rank -- queries, candidates scored (pads excluded) and the HIP-event
+ * time of the re-rank launch alone (wann_counters::device_ms stays the search's).
+ * There is no asynchronous form and no all-gather form, and no environment switch: refinement happens where it is called.
+ * Return values: 0, or a WANN_ERR_* code as above; a NULL index is answered with the NEGATIVE code -WANN_ERR_INVALID by the
+ * setter, both searches and the counters' getter (as by the setters of the shadow rows), and with -1 by wann_refine_rows_bytes. */
+typedef struct {
+  int64_t refined_queries; /* queries of the last refined call                              */
+  int64_t refined_rows;    /* candidates scored against the store (pads excluded)           */
+  double refine_ms;        /* HIP-event time of the re-rank launch alone                    */
+} wann_refine_counters;
+int wann_set_refine_rows(wann_index *index, const float *points, int64_t n, int64_t d);
+int64_t wann_refine_rows_bytes(const wann_index *index);
+int wann_batch_search_device_refined(wann_index *index, const void *d_queries, const float *d_ranges, int64_t nq,
+                                     int64_t query_id_base, const char *method, const wann_query_params *qp, int64_t refine_k,
+                                     uint32_t *d_ids, float *d_dists, void *hip_stream);
+int wann_batch_search_refined(wann_index *index, const float *queries, const float *ranges, int64_t nq, const char *method,
+                              const wann_query_params *qp, int64_t refine_k, uint32_t *ids, float *dists);
+int wann_get_refine_counters(const wann_index *index, wann_refine_counters *out);
+
 /* In-process multi-device mode: with WANN_DEVICES=a,b,... in the environment wann_index_create makes the index resident on
  * every listed device (a device may be listed twice) and wann_batch_search -- the host-buffer call, the reference's boundary
  * (src/range_filter_tree.h:62-96: one call parallelises over all queries) -- cuts its batch into contiguous shards, one host

@@ -41,6 +41,12 @@ int main(int argc, char **argv) {
   CHECK(wann_num_points(nullptr) == -1 && wann_dim(nullptr) == -1 && wann_num_levels(nullptr) == -1 && wann_max_degree(nullptr) == -1);
   int64_t s, e;
   CHECK(wann_partition_range(nullptr, 0, 0, &s, &e) == WANN_ERR_INVALID);
+  // the refined search (wann.h REFINED SEARCH): a null index is answered with the negative code, and -1 bytes
+  wann_refine_counters rc;
+  CHECK(wann_set_refine_rows(nullptr, pts.data(), n, d) == -WANN_ERR_INVALID && wann_set_refine_rows(nullptr, nullptr, 0, 0) == -WANN_ERR_INVALID);
+  CHECK(wann_refine_rows_bytes(nullptr) == -1 && wann_get_refine_counters(nullptr, &rc) == -WANN_ERR_INVALID);
+  CHECK(wann_batch_search_refined(nullptr, pts.data(), labels.data(), 1, "fenwick", &qp, 20, ids, dists) == -WANN_ERR_INVALID);
+  CHECK(wann_batch_search_device_refined(nullptr, nullptr, nullptr, 0, 0, "fenwick", &qp, 20, nullptr, nullptr, nullptr) == -WANN_ERR_INVALID);
   if (wann_device_count() == 0) {
     CHECK(wann_index_create(WANN_KIND_TREE_VAMANA, 0, WANN_DTYPE_F32, pts.data(), n, d, labels.data(), 100, 2, 0.5, &bp, 0, 2) == nullptr);
     CHECK(strstr(wann_last_error(), "no usable gfx950 device") != nullptr);

@@ -123,6 +123,8 @@ wann_index::~wann_index() {
   lanes.clear();  // (joins the workers before the streams and buffers they use go away)
   if (own_stream) (void)hipStreamDestroy(own_stream);
   if (side_stream) (void)hipStreamDestroy(side_stream);
+  for (hipEvent_t e : ev_refine)
+    if (e) (void)hipEventDestroy(e);
 }
 
 extern "C" {
@@ -668,6 +670,164 @@ int wann_batch_search(wann_index *I, const void *queries, const float *ranges, i
       I->last_exact.rows_scanned += e.rows_scanned;
     }
   }
+  return WANN_OK;
+}
+
+// ---- refined search (wann.h REFINED SEARCH): the full-precision row store and the re-rank of a compact index's candidates ----
+
+// (a null index is answered with the NEGATIVE code by all of these, as by the setters of the shadow rows)
+int wann_set_refine_rows(wann_index *I, const float *points, int64_t n, int64_t d) {
+  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(I->mu);
+  if (!points) {
+    I->d_refine.release();
+    return WANN_OK;
+  }
+  if (I->dtype != WANN_DTYPE_F16 && I->dtype != WANN_DTYPE_BF16 && I->dtype != WANN_DTYPE_F8)
+    return fail(WANN_ERR_UNSUPPORTED, "refine rows: float16 / bfloat16 / float8 indexes only (a float32 index has nothing to refine; a uint8 / "
+                                      "int8 search turns the query into bytes)");
+  const BuildSpec &s = I->host().spec;
+  if (n != s.n || d != s.d)
+    return fail(WANN_ERR_INVALID, "refine rows: " + std::to_string((long long)n) + " x " + std::to_string((long long)d) + " points, the index holds " +
+                                      std::to_string((long long)s.n) + " x " + std::to_string((long long)s.d));
+  for (int64_t r = 0; r < n; r++)
+    for (int64_t j = 0; j < d; j++)
+      if (!std::isfinite(points[r * d + j]))
+        return fail(WANN_ERR_INVALID, "refine rows: non-finite element in point row " + std::to_string((long long)r) + " (an infinity or a NaN)");
+  try {
+    upload_refine_rows(*I, points);
+  } catch (HipError &e) {
+    (void)hipGetLastError();
+    I->d_refine.release();
+    return fail(WANN_ERR_HIP, e.what());
+  } catch (std::exception &e) {
+    I->d_refine.release();
+    return fail(WANN_ERR_INVALID, e.what());
+  }
+  return WANN_OK;
+}
+
+int64_t wann_refine_rows_bytes(const wann_index *I) { return I ? (int64_t)I->d_refine.bytes() : -1; }
+
+namespace {
+// what a refined call needs beyond the ordinary call's arguments (under I.mu); nothing has been launched when this fails
+int refine_refused(const wann_index &I, const wann_query_params &qp, int64_t refine_k) {
+  static_assert(kMaxK == 1024, "the message below names the limit");
+  if (!I.d_refine.p) return fail(WANN_ERR_INVALID, "refined search: the index has no refine rows (wann_set_refine_rows)");
+  if (qp.k <= 0 || refine_k < qp.k || refine_k > kMaxK) return fail(WANN_ERR_INVALID, "refined search: k <= refine_k <= 1024 is required, and k >= 1");
+  const int64_t d = I.host().spec.d, need = refine_lds_bytes(refine_row_words(d), (int)qp.k);
+  if (need > kLdsPerWorkgroup)
+    return fail(WANN_ERR_UNSUPPORTED, "refined search: rows of " + std::to_string((long long)d) + " elements at k = " + std::to_string((long long)qp.k) +
+                                          " need " + std::to_string((long long)need) + " bytes of LDS per workgroup, the limit is " +
+                                          std::to_string(kLdsPerWorkgroup));
+  return WANN_OK;
+}
+
+// the refined call on device buffers (under I.mu, refine_refused passed): the ordinary blocking search at k = refine_k into the
+// workspace, then k_refine on the same stream into the caller's rows
+void search_refined_device(wann_index &I, const float *d_queries, const float *d_ranges, int64_t nq, int64_t qid_base, const char *method,
+                           const wann_query_params &qp, int64_t refine_k, uint32_t *d_ids, float *d_dists, hipStream_t st) {
+  HIP_CHECK(hipSetDevice(I.device));
+  Workspace &W = I.ws;
+  W.refine_ids.ensure((size_t)std::max<int64_t>(nq * refine_k, 1));
+  W.refine_dists.ensure((size_t)std::max<int64_t>(nq * refine_k, 1));
+  W.refine_ctr.ensure(1);
+  for (hipEvent_t &e : I.ev_refine)
+    if (!e) HIP_CHECK(hipEventCreate(&e));
+  wann_query_params wide = qp;
+  wide.k = refine_k;
+  const Tuning T = snapshot_tuning(I);
+  I.last_refine = wann_refine_counters{};
+  I.note_row_store(run_batch(I, W, I.side_stream, I.last, d_queries, d_ranges, nq, qid_base, method, wide, W.refine_ids.p, W.refine_dists.p, st, T));
+  if (nq == 0) return;
+  const BuildSpec &s = I.host().spec;
+  RefineArgs ra{};
+  ra.ix.points = I.d_refine.p;
+  ra.ix.n = s.n;
+  ra.ix.d = (int32_t)s.d;
+  ra.ix.stride = (int32_t)refine_row_words(s.d);
+  ra.ix.metric = s.metric;
+  ra.ix.dtype = WANN_DTYPE_F32;
+  ra.queries = d_queries;
+  ra.cand_ids = W.refine_ids.p;
+  ra.cand_dists = W.refine_dists.p;
+  ra.nq = nq;
+  ra.refine_k = (int32_t)refine_k;
+  ra.k = (int32_t)qp.k;
+  ra.pad_id = I.host().sorted ? 0u : 0xFFFFFFFFu;  // (k_finalize's padding ids)
+  ra.ids = d_ids;
+  ra.dists = d_dists;
+  ra.rows_scored = W.refine_ctr.p;
+  unsigned long long scored = 0;
+  HIP_CHECK(hipMemsetAsync(W.refine_ctr.p, 0, sizeof(unsigned long long), st));
+  HIP_CHECK(hipEventRecord(I.ev_refine[0], st));
+  if (launch_refine(ra, I.num_cus, st)) throw HipError(std::string("k_refine: ") + refine_launch_last_error());
+  HIP_CHECK(hipEventRecord(I.ev_refine[1], st));
+  HIP_CHECK(hipMemcpyAsync(&scored, W.refine_ctr.p, sizeof scored, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, I.ev_refine[0], I.ev_refine[1]));
+  I.last_refine = wann_refine_counters{nq, (int64_t)scored, ms};
+}
+}  // namespace
+
+int wann_batch_search_device_refined(wann_index *I, const void *d_queries, const float *d_ranges, int64_t nq, int64_t query_id_base,
+                                     const char *method, const wann_query_params *qp, int64_t refine_k, uint32_t *d_ids, float *d_dists,
+                                     void *hip_stream) {
+  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
+  if (!qp || nq < 0) return fail(WANN_ERR_INVALID, "invalid argument to wann_batch_search_device_refined");
+  std::lock_guard<std::mutex> lk(I->mu);
+  if (const int rc = refine_refused(*I, *qp, refine_k)) return rc;
+  try {
+    search_refined_device(*I, (const float *)d_queries, d_ranges, nq, query_id_base, method, *qp, refine_k, d_ids, d_dists, (hipStream_t)hip_stream);
+  } catch (HipError &e) {
+    return fail(WANN_ERR_HIP, e.what());
+  } catch (std::exception &e) {
+    return fail(WANN_ERR_INVALID, e.what());
+  }
+  return WANN_OK;
+}
+
+int wann_batch_search_refined(wann_index *I, const float *queries, const float *ranges, int64_t nq, const char *method,
+                              const wann_query_params *qp, int64_t refine_k, uint32_t *ids, float *dists) {
+  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
+  if (!qp || nq < 0 || (nq > 0 && (!queries || !ranges || !ids || !dists)))
+    return fail(WANN_ERR_INVALID, "invalid argument to wann_batch_search_refined");
+  std::lock_guard<std::mutex> lk(I->mu);
+  if (const int rc = refine_refused(*I, *qp, refine_k)) return rc;
+  try {
+    HIP_CHECK(hipSetDevice(I->device));
+    Workspace &W = I->ws;
+    const int64_t d = I->host().spec.d, k = qp->k;
+    W.q_stage.ensure((size_t)std::max<int64_t>(nq * d, 1));
+    W.r_stage.ensure((size_t)std::max<int64_t>(nq * 2, 1));
+    W.id_stage.ensure((size_t)std::max<int64_t>(nq * k, 1));
+    W.dist_stage.ensure((size_t)std::max<int64_t>(nq * k, 1));
+    hipStream_t st = I->own_stream;
+    if (nq) {  // (fp32 as they are: the device path's queries are not rounded)
+      HIP_CHECK(hipMemcpyAsync(W.q_stage.p, queries, (size_t)nq * d * 4, hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipMemcpyAsync(W.r_stage.p, ranges, (size_t)nq * 8, hipMemcpyHostToDevice, st));
+    }
+    search_refined_device(*I, W.q_stage.p, W.r_stage.p, nq, 0, method, *qp, refine_k, W.id_stage.p, W.dist_stage.p, st);
+    if (nq) {
+      HIP_CHECK(hipMemcpyAsync(ids, W.id_stage.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(dists, W.dist_stage.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    }
+  } catch (HipError &e) {
+    return fail(WANN_ERR_HIP, e.what());
+  } catch (std::exception &e) {
+    return fail(WANN_ERR_INVALID, e.what());
+  }
+  return WANN_OK;
+}
+
+int wann_get_refine_counters(const wann_index *I, wann_refine_counters *out) {
+  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
+  if (!out) return fail(WANN_ERR_INVALID, "null argument");
+  wann_index *M = const_cast<wann_index *>(I);
+  std::lock_guard<std::mutex> lk(M->mu);
+  *out = I->last_refine;
   return WANN_OK;
 }
 

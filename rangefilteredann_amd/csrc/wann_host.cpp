@@ -287,6 +287,21 @@ void upload_index(wann_index &I) {
                              I.d_parts.bytes() + I.d_fv.bytes() + I.d_fi.bytes() + I.d_wst_off.bytes());
 }
 
+// The full-precision row store of a compact index (wann_set_refine_rows): the caller's float32 points, row r = point r of the
+// array the index was made from (the order of returned ids: nothing here knows the label sort), zero padded to the float32
+// index's row pitch so that the float32 row-distance routines read it as they read a float32 index.
+void upload_refine_rows(wann_index &I, const float *points) {
+  const BuildSpec &s = I.host().spec;
+  const int64_t words = refine_row_words(s.d);
+  HIP_CHECK(hipSetDevice(I.device));
+  std::vector<float> rows((size_t)s.n * words, 0.f);
+  parallel_for(s.n, s.threads > 0 ? s.threads : default_threads(), [&](int64_t r) {
+    memcpy(rows.data() + r * words, points + r * s.d, (size_t)s.d * sizeof(float));
+  });
+  I.d_refine.release();  // (exactly n rows: wann_refine_rows_bytes is the store's size)
+  I.d_refine.upload(rows);
+}
+
 // Global scratch of a launch whose searches keep their seen-filter in global memory: the per-slot filter tables
 // (entries tagged with the slot's search epoch), the epochs, and the per-slot exact seen bitmaps.  A table whose
 // slot layout changes (or that was reallocated) is zeroed together with its epochs.

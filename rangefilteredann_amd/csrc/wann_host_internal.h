@@ -29,6 +29,7 @@
 #include "wann_device.h"
 #include "wann_gemm_device.h"
 #include "wann_gpu_build.h"
+#include "wann_refine_device.h"
 #include "wann_hip_util.h"
 #include "wann_tuning.h"
 
@@ -74,6 +75,11 @@ struct Workspace {
   DevBuf<unsigned long long> vlog;  // QueryParams::verbose: per-task records of the doubling loop (SearchArgs::vlog)
   DevBuf<int32_t> vlog_n;
   DevBuf<int64_t> vroute;            // QueryParams::verbose on a tree class: the descent's dump (RouteArgs::vroute)
+  // wann_batch_search_device_refined: the search's rows at k = refine_k (nq x refine_k ids and distances, 8 bytes an entry),
+  // what k_refine reads; the candidates it scored
+  DevBuf<uint32_t> refine_ids;
+  DevBuf<float> refine_dists;
+  DevBuf<unsigned long long> refine_ctr;
   DevBuf<int32_t> gat_send, gat_recv;  // wann_batch_search_allgather: this replica's [2][cap][k] planes / everybody's [world][2][cap][k]
   int32_t big_stride = 0;
   int32_t *h_ints = nullptr;  // pinned
@@ -184,6 +190,13 @@ struct wann_index {
     last_scan_rows = (stores >> 8) & 0xff;
     last_dense_rows = (stores >> 16) & 1;
   }
+  // wann_set_refine_rows (float16 / bfloat16 / float8 indexes; under mu): the caller's full-precision points as float32 rows in
+  // the CALLER'S point order -- the order of returned ids -- zero padded to refine_row_words(d) words, the float32 index's row
+  // pitch.  Only k_refine reads it (wann_batch_search_device_refined).  Empty: no store.  The primary's only: the refined calls
+  // serve the primary, like wann_batch_search_device.  Not in device_bytes (wann_refine_rows_bytes reports it).
+  DevBuf<float> d_refine;
+  wann_refine_counters last_refine{};  // of the last refined call (under mu)
+  hipEvent_t ev_refine[2] = {nullptr, nullptr};  // round the k_refine launch (created at the first refined call)
   DevBuf<uint32_t> d_decoding;
   DevBuf<int32_t> d_graph, d_fi;
   DevBuf<PartDesc> d_parts;
@@ -247,6 +260,8 @@ namespace wann_host {
 
 Tuning snapshot_tuning(wann_index &I);  // the index's switches for one call (WANN_TEST_HOOKS=1: re-read from the environment first)
 void upload_index(wann_index &I);
+// wann_set_refine_rows: (n, d) float32 points in the caller's order -> I.d_refine (checked by the caller; throws HipError)
+void upload_refine_rows(wann_index &I, const float *points);
 int ensure_filter_scratch(DevBuf<int32_t> &table, DevBuf<int32_t> &epoch, DevBuf<uint32_t> &seen, int64_t &layout, int slots,
                           int table_bits, int64_t seen_words, hipStream_t st, bool any_slots = false);
 struct RoundCfg {

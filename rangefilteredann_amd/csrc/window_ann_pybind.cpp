@@ -258,6 +258,71 @@ class Index {
   bool dense_rows() const { return wann_dense_rows(h_) != 0; }
   int64_t dense_rows_bytes() const { return wann_dense_rows_bytes(h_); }
 
+  // float16 / bfloat16 / float8 indexes: the full-precision points (any array numpy casts to float32, in the order of the array
+  // the index was created from) as the row store of the refined calls (wann_set_refine_rows); None drops the store
+  void set_refine_rows(py::object points) {
+    int rc;
+    if (points.is_none()) {
+      rc = wann_set_refine_rows(h_, nullptr, 0, 0);
+    } else {
+      FArray pts = FArray::ensure(points);
+      if (!pts) throw std::runtime_error("refine rows must be convertible to a float32 array");
+      if (pts.ndim() != 2) throw std::runtime_error("refine rows numpy array must be 2-dimensional");
+      const float *pp = pts.data();
+      const int64_t n = pts.shape(0), d = pts.shape(1);
+      py::gil_scoped_release nogil;
+      rc = wann_set_refine_rows(h_, pp, n, d);
+    }
+    if (rc) raise_last("set_refine_rows failed");
+  }
+  int64_t refine_rows_bytes() const { return wann_refine_rows_bytes(h_); }
+  // the refined host-buffer call: FLOAT32 queries (not rounded to the index's element type), refine_k >= k candidates from the
+  // compact rows re-ranked against the refine rows
+  NeighborsAndDistances search_refined(py::object queries_in, py::object filters, uint64_t nq, const std::string &method, const QueryParams &qp,
+                                       int64_t refine_k) {
+    FArray fr = FArray::ensure(filters);
+    if (!fr) throw std::runtime_error("filters must be a sequence of (lo, hi) pairs");
+    if (fr.ndim() != 2 || fr.shape(1) != 2 || (uint64_t)fr.shape(0) < nq) throw std::runtime_error("filters must have shape (num_queries, 2)");
+    FArray queries = FArray::ensure(queries_in);
+    if (!queries) throw std::runtime_error("queries must be convertible to a float32 array");
+    if (queries.ndim() != 2 || (uint64_t)queries.shape(0) < nq || queries.shape(1) != wann_dim(h_))
+      throw std::runtime_error("queries must have shape (num_queries, dimension)");
+    if (qp.c.k < 1) throw std::runtime_error("k must be in [1, 1024]");
+    size_t k = (size_t)qp.c.k;
+    py::array_t<unsigned int> ids({(size_t)nq, k});
+    py::array_t<float> dists({(size_t)nq, k});
+    const float *qptr = queries.data(), *rptr = fr.data();
+    unsigned int *ip = ids.mutable_data();
+    float *dp = dists.mutable_data();
+    int rc;
+    {
+      py::gil_scoped_release nogil;
+      rc = wann_batch_search_refined(h_, qptr, rptr, (int64_t)nq, method.c_str(), &qp.c, refine_k, ip, dp);
+    }
+    if (rc) raise_last("batch_search_refined failed");
+    return std::make_pair(ids, dists);
+  }
+  // ... and the device-resident one (every *_ptr a device address on this index's GPU; ids / dists are num_queries x k)
+  void search_device_refined(uint64_t q_ptr, uint64_t r_ptr, int64_t nq, int64_t query_id_base, const std::string &method, const QueryParams &qp,
+                             int64_t refine_k, uint64_t ids_ptr, uint64_t dists_ptr, uint64_t stream) {
+    int rc;
+    {
+      py::gil_scoped_release nogil;
+      rc = wann_batch_search_device_refined(h_, (const void *)q_ptr, (const float *)r_ptr, nq, query_id_base, method.c_str(), &qp.c, refine_k,
+                                            (uint32_t *)ids_ptr, (float *)dists_ptr, (void *)stream);
+    }
+    if (rc) raise_last("batch_search_device_refined failed");
+  }
+  py::dict refine_counters() const {
+    wann_refine_counters c;
+    if (wann_get_refine_counters(h_, &c)) raise_last("refine_counters failed");
+    py::dict d;
+    d["refined_queries"] = c.refined_queries;
+    d["refined_rows"] = c.refined_rows;
+    d["refine_ms"] = c.refine_ms;
+    return d;
+  }
+
   // PrefilterIndex only: distinct wide windows on the matrix cores (wann_set_dense_windows); returns the previous setting
   bool set_dense_windows(bool on) {
     const int rc = wann_set_dense_windows(h_, on ? 1 : 0);
@@ -392,6 +457,13 @@ static void common_defs(py::class_<C> &c) {
       .def("set_dense_rows", &C::set_dense_rows, "on"_a)
       .def("dense_rows", &C::dense_rows)
       .def("dense_rows_bytes", &C::dense_rows_bytes)
+      .def("set_refine_rows", &C::set_refine_rows, "points"_a.none(true))
+      .def("refine_rows_bytes", &C::refine_rows_bytes)
+      .def("batch_search_refined", &C::search_refined, "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a,
+           "refine_k"_a)
+      .def("batch_search_device_refined", &C::search_device_refined, "queries_ptr"_a, "filters_ptr"_a, "num_queries"_a, "query_id_base"_a,
+           "query_method"_a, "query_params"_a, "refine_k"_a, "ids_ptr"_a, "dists_ptr"_a, "stream"_a = 0)
+      .def("refine_counters", &C::refine_counters)
       .def("max_degree", &C::max_degree)
       .def("num_replicas", &C::num_replicas)
       .def("num_points", &C::num_points)
