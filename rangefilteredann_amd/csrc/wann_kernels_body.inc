@@ -639,8 +639,14 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
           if (la >= 0) {
             la_withdraw(A, la);
             A.sub_cmps[parent] = -3;  // (withdrawn: neither the scan nor the resolver touches it again)
-          } else
-            atomicCAS((unsigned long long *)&A.sub_cmps[parent], ~0ull, ~2ull);  // -1 (none) -> -3
+          } else {
+            // (the operands are formed HERE: as plain constants the compiler set the pair up at kernel entry and held four vector
+            // registers for it through every core -- in the float32 unit's k_search<0, 0>, which sits at the 256-register limit,
+            // the first thing to go to scratch)
+            unsigned long long none = ~0ull;
+            asm volatile("" : "+v"(none));
+            atomicCAS((unsigned long long *)&A.sub_cmps[parent], none, none - 2);  // -1 (none) -> -3
+          }
         }
         __threadfence();
         int old_done = 0;

@@ -2525,8 +2525,10 @@ __device__ __forceinline__ void wave_beam_search_mid(const IndexView &ix, const 
 // computed by ONE loop over the passing candidates in which every lane compares its beam entries
 // and its own candidate with the broadcast candidate key (ballots give the insertion point and
 // the duplicate test as scalars), so there is no binary search and a single LDS round trip per
-// hop (write the merged beam, read it back).  Same results as wave_beam_search (the parity tests
-// run both).
+// hop (write the merged beam, read it back).  The loop has two forms: a lean one, two candidates
+// per trip, for rows of distinct ids, and the general multiset rule for a row that lists a node
+// twice (row_dup, found by the seen-filter's class loop).  Same results as wave_beam_search (the
+// parity tests run both).
 // --------------------------------------------------------------------------------------------
 template <int METRIC, int NE>
 __device__ __forceinline__ void wave_beam_search_small(const IndexView &ix, const PartDesc &part, const WaveLds &L,
@@ -2553,6 +2555,7 @@ __device__ __forceinline__ void wave_beam_search_small(const IndexView &ix, cons
   for (int j = 0; j < NE; j++) e[j] = ~0ull;
   if (lane == 0) e[0] = (u64)fkey(d0) << 32;
   unsigned long long tp = 0, acc[6] = {0, 0, 0, 0, 0, 0}, nc_total = 0;
+  unsigned long long n_clash = 0, n_dup = 0;  // hops whose row had two lanes in one filter slot / listed a node twice
 #define WANN_PHASE(i)                                       \
   do {                                                      \
     if (prof) {                                             \
@@ -2595,18 +2598,32 @@ __device__ __forceinline__ void wave_beam_search_small(const IndexView &ix, cons
     if (valid) rb = L.ltable[loc];
     const bool clash = valid && (rb != (int)(TAG | (uint32_t)lane));
     bool seen;
-    const bool had_clash = ballot64(clash) != 0;
-    if (!had_clash) {
+    bool row_dup = false;  // wave-uniform: the row lists some node twice (only then can two candidates of a hop carry one key)
+    u64 losers = ballot64(clash);
+    if (!losers) {
       seen = valid && (old == a);
       WAVE_SYNC();
       if (valid) L.ltable[loc] = a;
     } else {  // shared slots (or a node listed twice): exact sequential emulation
-      u64 eq = ballot64(valid);
-      for (int b = 0; b < bits; b++) {
-        const bool bit = (loc >> b) & 1u;
-        const u64 bm = ballot64(valid && bit);
-        eq &= bit ? bm : ~bm;
-      }
+      if (prof) n_clash++;
+      // eq = the valid lanes that share my slot with another, me included; 0 for a lane alone in its slot.  Every class of two
+      // or more lanes has a loser (one tag survives per slot), so one ballot per loser's class names them all -- usually one
+      // class of two lanes.
+      u64 eq = 0;
+      do {
+        const uint32_t cl = (uint32_t)rdlane((int)loc, ctz64(losers));
+        const bool mine = valid && (loc == cl);
+        const u64 cls = ballot64(mine);
+        if (mine) eq = cls;
+        losers &= ~cls;
+        // equal ids share a slot, so a node listed twice sits inside one class: every member but the last against the later
+        // ones (the copies need not be neighbours in the class: (x, y, x) in one slot)
+        for (u64 r = cls; r & (r - 1); r &= r - 1) {
+          const u64 same = ballot64(valid && a == rdlane(a, ctz64(r)));
+          row_dup |= (same & (same - 1)) != 0;
+        }
+      } while (losers);
+      if (prof && row_dup) n_dup++;
       const u64 lower = eq & lanemask_lt();
       const u64 higher = (lane == 63) ? 0ull : (eq >> (lane + 1));
       const int prev_lane = lower ? (63 - __builtin_clzll(lower)) : lane;
@@ -2648,41 +2665,66 @@ __device__ __forceinline__ void wave_beam_search_small(const IndexView &ix, cons
       const u64 kk = key | 1ull;
       int rank = 0, mypos = 0, cp = 0;
       bool mydup = false;
-      for (u64 mm = smask; mm; mm &= mm - 1) {
-        const int i = ctz64(mm);
-        const u64 ki = rdlane64(kk, i);
-        bool below[NE];
-        int pos_i = 0;
-        u64 eqb = 0;
-        int neq = 0;
+      if (WANN_LIKELY(!row_dup)) {
+        // The row's ids are distinct, so the candidates' keys are distinct (the id is part of the key): no passing candidate
+        // before i carries i's key (the general rule's ji is always 0, so dup_i = 0 < neq = "the beam holds the key") and its
+        // tie branch of before_me never fires.  What a candidate contributes depends on it and the beam alone, so the order
+        // is free: two per trip, the second masked off when the count is odd, and no branch in the body but the back edge.
+        for (u64 mm = smask; mm;) {
+          const int i0 = ctz64(mm);
+          mm &= mm - 1;
+          const bool two = mm != 0;
+          const int i1 = two ? ctz64(mm) : i0;
+          mm &= mm - 1;
+          const u64 k0 = rdlane64(kk, i0), k1 = rdlane64(kk, i1);
+          bool below0[NE], below1[NE];
+          int pos0 = 0, pos1 = 0;
+          u64 eqb0 = 0, eqb1 = 0;
 #pragma unroll
-        for (int j = 0; j < NE; j++) {
-          below[j] = ek[j] < ki;  // my beam entry sorts before candidate i
-          pos_i += popc64(ballot64(below[j]));
-          const u64 eqj = ballot64(ek[j] == ki);
-          eqb |= eqj;
-          neq += popc64(eqj);
+          for (int j = 0; j < NE; j++) {
+            below0[j] = ek[j] < k0;  // my beam entry sorts before the candidate
+            below1[j] = ek[j] < k1;
+            pos0 += popc64(ballot64(below0[j]));
+            pos1 += popc64(ballot64(below1[j]));
+            eqb0 |= ballot64(ek[j] == k0);
+            eqb1 |= ballot64(ek[j] == k1);
+          }
+          const bool new0 = eqb0 == 0, new1 = two & (eqb1 == 0);  // (one candidate left: i1 = i0, and it counts once)
+          mypos = (lane == i0) ? pos0 : mypos;
+          mypos = (lane == i1) ? pos1 : mypos;
+          mydup = (lane == i0) ? (eqb0 != 0) : mydup;
+          mydup = (lane == i1) ? (eqb1 != 0) : mydup;
+          cp += (int)new0 + (int)new1;
+          rank += ((new0 & pass & (k0 < kk)) ? 1 : 0) + ((new1 & pass & (k1 < kk)) ? 1 : 0);
+#pragma unroll
+          for (int j = 0; j < NE; j++)  // (empty slots are never written back)
+            sx[j] += ((new0 & !below0[j]) ? 1 : 0) + ((new1 & !below1[j]) ? 1 : 0);
         }
-        bool dup_i, before_me;
-        if (!had_clash) {
-          // the row held distinct ids in distinct filter slots, so candidate keys are distinct and
-          // candidate i is a copy only if the beam already holds its key
-          dup_i = eqb != 0;
-          before_me = pass && (ki < kk);
-        } else {  // general multiset rule of std::set_union
+      } else {  // general multiset rule of std::set_union: a node listed twice may pass twice and be kept twice
+        for (u64 mm = smask; mm; mm &= mm - 1) {
+          const int i = ctz64(mm);
+          const u64 ki = rdlane64(kk, i);
+          bool below[NE];
+          int pos_i = 0, neq = 0;
+#pragma unroll
+          for (int j = 0; j < NE; j++) {
+            below[j] = ek[j] < ki;  // my beam entry sorts before candidate i
+            pos_i += popc64(ballot64(below[j]));
+            neq += popc64(ballot64(ek[j] == ki));
+          }
           const int ji = popc64(ballot64(pass && kk == ki) & (((u64)1 << i) - 1));
-          dup_i = ji < neq;
-          before_me = pass && (ki < kk || (ki == kk && i < lane));
-        }
-        if (lane == i) {
-          mypos = pos_i;
-          mydup = dup_i;
-        }
-        if (!dup_i) {
-          cp++;
-          rank += before_me ? 1 : 0;
+          const bool dup_i = ji < neq;
+          const bool before_me = pass && (ki < kk || (ki == kk && i < lane));
+          if (lane == i) {
+            mypos = pos_i;
+            mydup = dup_i;
+          }
+          if (!dup_i) {
+            cp++;
+            rank += before_me ? 1 : 0;
 #pragma unroll
-          for (int j = 0; j < NE; j++) sx[j] += (!below[j]) ? 1 : 0;  // (empty slots are never written back)
+            for (int j = 0; j < NE; j++) sx[j] += (!below[j]) ? 1 : 0;  // (empty slots are never written back)
+          }
         }
       }
       if (prof) {
@@ -2727,6 +2769,8 @@ __device__ __forceinline__ void wave_beam_search_small(const IndexView &ix, cons
   if (prof && lane == 0) {
     for (int i = 0; i < 6; i++) atomicAdd(&prof[i], acc[i]);
     atomicAdd(&prof[6], nc_total);
+    atomicAdd(&prof[7], n_clash);
+    atomicAdd(&prof[8], n_dup);
   }
   m_out = m;
   nvis_out = nvis;

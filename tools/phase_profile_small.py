@@ -1,6 +1,8 @@
 """Dev tool: per-phase cycles of the register-resident small-beam core (wave_beam_search_small: beams <= 128) under load, on a
 stand-alone graph -- squared L2 (d = 128, SIFT-like) beside inner product (d = 96 / 100, unit-norm mixture rows), to see where
-the hop of the MIPS legs goes.  Needs a `make PROFILE=1` build on LD_LIBRARY_PATH for the phase lines.
+the hop of the MIPS legs goes.  Needs a `make PROFILE=1` build on LD_LIBRARY_PATH for the phase lines (`[wann phases 5..8]`
+of this core: cycles of the union loop, its candidates, hops whose row had two lanes in one filter slot, hops whose row
+listed a node twice).
 Usage: python tools/phase_profile_small.py [n] [beams] [nqs] [metric:d]"""
 import os, sys, time, numpy as np
 os.environ.setdefault("WANN_TEST_HOOKS", "1")
