@@ -127,6 +127,7 @@ void gpu_build_graphs(const IndexView &view, int32_t *d_graph, const std::vector
 
   std::vector<BuildItem> items;
   size_t rounds = 0, total_items = 0;
+  size_t big_groups = 0, big_rounds = 0;  // what went to the second reverse pass (reported under WANN_VERBOSE only)
   try {
     for (;;) {
       items.clear();
@@ -175,6 +176,8 @@ void gpu_build_graphs(const IndexView &view, int32_t *d_graph, const std::vector
       if (h_ints[5] & 1) throw std::runtime_error("gpu build overflow: a visited list exceeded the LDS candidate buffer");
       if (h_ints[4] > 0) {  // hub nodes whose reverse-edge group did not fit the LDS buffer
         A.big = 1;
+        big_groups += (size_t)h_ints[4];
+        big_rounds++;
         if (launch_build_reverse(A, std::min(big_blocks, (h_ints[4] + wpb - 1) / wpb), st))
           throw HipError(std::string("k_build_reverse(big): ") + build_launch_last_error());
         HIP_CHECK(hipMemcpyAsync(h_ints, d_ints.p, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -225,8 +228,10 @@ void gpu_build_graphs(const IndexView &view, int32_t *d_graph, const std::vector
       });
     }
     if (verbose)
-      fprintf(stderr, "[wann gpu build] %zu partitions, %zu inserts, %zu rounds: device %.1fs, copy-back %.1fs\n", nj,
-              total_items, rounds, t_dev - t_begin, now_s() - t_dev);
+      fprintf(stderr,
+              "[wann gpu build] %zu partitions, %zu inserts, %zu rounds: device %.1fs, copy-back %.1fs; second reverse pass: %zu groups in "
+              "%zu rounds\n",
+              nj, total_items, rounds, t_dev - t_begin, now_s() - t_dev, big_groups, big_rounds);
   } catch (...) {
     (void)hipHostFree(h_ints);
     throw;

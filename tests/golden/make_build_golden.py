@@ -6,6 +6,15 @@ files the reference's PostfilterVamanaIndex writes for two inputs with continuou
 candidates of a prune or neighbour sort are exactly equidistant there, so the result does not depend on
 libstdc++'s std::sort tie order) and for one integer-valued input full of ties (reproduced by the builders'
 reference-tie-order mode: ORC_REF_TIES / WANN_REF_TIES).  Only data is written.  Usage:  python tests/golden/make_build_golden.py
+
+A warning to the next fixture author: the reference's first builds in a process can differ from later ones.  Of three
+consecutive builds of the stored gauss_l2 input (d = 12) the first two differed from the file stored here and the third equalled
+it, while the oracle's builder wrote the stored file every time; with other thread counts or other builds before it, a dozen
+builds in a row each wrote another file.  The cause is the padding of float rows: PointRange (point_range.h:99-107) copies d
+floats into aligned_alloc'ed rows and never clears the rest, and the AVX distances (NSGDist.h:49-66) read (d + 7) & ~7 floats.
+Only where the padding happens to be zero is the graph the one of zero-padded rows that is stored here.  Use a d that is a
+multiple of 8, or build in a process started with MALLOC_PERTURB_=255 (glibc then zero-fills every block it hands out), build
+several times and compare -- make_build_alpha_golden.py does all of that.
 """
 import hashlib
 import os

@@ -33,6 +33,37 @@ def load_build():
     return np.load(os.path.join(GOLDEN, "build_golden.npz"))
 
 
+BUILD_ALPHA_FLOAT = ["gauss_l2_a120", "gauss_l2_a1175", "unit_mips_a120"]
+BUILD_ALPHA_BYTE = ["u8_l2", "u8_mips", "i8_l2", "i8_mips", "i8_mips_a120"]  # (exact ties: reference tie order)
+BUILD_ALPHA_CASES = BUILD_ALPHA_FLOAT + BUILD_ALPHA_BYTE + ["star_mips"]
+STAR = dict(n=12000, d=32, R=16, L=16)  # the hub input of star_mips (golden/make_build_alpha_golden.py)
+_build_alpha = {}
+
+
+def build_alpha_case(name):
+    """One case of build_alpha_golden.npz (graph files the reference wrote at alpha != 1, for byte types and for a hub input):
+    dict(X, labels, R, L, metric, alpha, sfx, file_name, file).  star_mips stores no input: it is util.star_hub's, regenerated
+    here and checked against the stored digest."""
+    if "data" not in _build_alpha:
+        _build_alpha["data"] = np.load(os.path.join(GOLDEN, "build_alpha_golden.npz"))
+    data = _build_alpha["data"]
+    R, L, metric, alpha = data[f"{name}|meta"]
+    c = dict(R=int(R), L=int(L), metric=int(metric), alpha=float(alpha), sfx=data[f"{name}|sfx"].tobytes().decode(),
+             file_name=data[f"{name}|file_name"].tobytes().decode(), file=data[f"{name}|file"].tobytes())
+    if f"{name}|X" in data.files:
+        c["X"], c["labels"] = data[f"{name}|X"], data[f"{name}|labels"]
+    else:
+        import hashlib
+
+        from oracle import oracle as orc
+        from util import star_hub
+        n = STAR["n"]
+        c["X"] = star_hub(n, STAR["d"], "mips", [int(orc.random_permutation(n)[0])])
+        c["labels"] = np.arange(n, dtype=np.float32)
+        assert hashlib.sha256(c["X"].tobytes()).digest() == data[f"{name}|X_sha256"].tobytes(), "star_hub no longer generates the fixture's input"
+    return c
+
+
 def unpack_cache(graphs, kind, dst):
     """Write the reference-built graph cache files of `kind` under dst/ and return the prefix."""
     os.makedirs(dst, exist_ok=True)

@@ -153,6 +153,47 @@ def tie_queries(X, nq, seed, lo=0, hi=12):
     return Q
 
 
+def star_hub(n, d, metric, hub_ids, norms=(8.0,), seed=0, elem=None):
+    """Points of which nearly every one chooses the same out-neighbour (a HUB), so that a whole insertion batch of the graph
+    builder becomes one reverse-edge group for that node.  hub_ids: the rows that become hubs -- a hub collects (nearly) every
+    row of a partition only when it is the partition's start point, start + oracle.random_permutation(size)[0].
+    metric "mips": rows with positive coordinates on the unit sphere; hub j is norms[j] times a unit vector with equal
+    coordinates, over all d dimensions when there is one hub, over the j-th of len(hub_ids) equal slices of the dimensions
+    otherwise (hubs orthogonal to each other: one hub does not prune another out of a row, every hub prunes ordinary points).
+    metric "l2": standard-normal rows scaled to unit length (mixed signs), the (single) hub is the zero vector.
+    elem = np.uint8 (mips): integers 0 .. 15, the hub row is all 255.  Returns float32 rows, or rows of `elem`."""
+    rng = np.random.default_rng(seed)
+    hub_ids = [int(h) for h in hub_ids]
+    norms = list(norms) + [norms[-1]] * (len(hub_ids) - len(norms))
+    if elem is not None:
+        assert metric == "mips" and len(hub_ids) == 1
+        X = rng.integers(0, 16, size=(n, d)).astype(elem)
+        X[hub_ids[0]] = 255
+        return X
+    X = rng.standard_normal((n, d))
+    if metric == "mips":
+        X = np.abs(X)
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    if metric == "mips":
+        w = d // len(hub_ids)
+        for j, h in enumerate(hub_ids):
+            X[h] = 0
+            lo, hi = (0, d) if len(hub_ids) == 1 else (j * w, (j + 1) * w)
+            X[h, lo:hi] = norms[j] / np.sqrt(hi - lo)
+    else:
+        assert len(hub_ids) == 1
+        X[hub_ids[0]] = 0
+    return X.astype(np.float32)
+
+
+def tree_hub_ids(oracle, n):
+    """star_hub's hub_ids for a tree with split_factor 2 over ascending labels (ids are positions): the start points of the
+    root partition and of its two halves"""
+    half = n // 2
+    c = int(oracle.random_permutation(half)[0])
+    return [int(oracle.random_permutation(n)[0]), c, half + c]
+
+
 def repeated_labels(n, seed, n_values):
     """Labels drawn from n_values distinct float32 values: runs of about n / n_values points share a label."""
     rng = np.random.default_rng(seed)
