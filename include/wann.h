@@ -22,6 +22,8 @@
  *       (ParlayANN/algorithms/utils/beamSearch.h:128, src/range_filter_tree.h:71-72; src/postfilter_vamana.h:161-181 for what it is for)
  *   wann_set_refine_rows / wann_batch_search_device_refined / wann_batch_search_refined   (not calls of the reference) a float16 /
  *       bfloat16 / float8 index searched for refine_k >= k candidates that are re-ranked against the caller's float32 rows
+ *   wann_batch_search_device_wide / wann_batch_search_wide   (not calls of the reference) rows of `width` columns from the search
+ *       that stops as at k: the tail of the frontier that src/postfilter_vamana.h:141-188 returns and batch_search drops
  *   wann_query_params        QueryParams   ParlayANN/algorithms/utils/types.h:115-140, python_bindings.cpp:204-209
  *   wann_build_params        BuildParams   ParlayANN/algorithms/utils/types.h:77-112,  python_bindings.cpp:211-213
  *
@@ -413,6 +415,40 @@ int wann_dense_rows(const wann_index *index);
 int64_t wann_dense_rows_bytes(const wann_index *index);
 int wann_last_dense_rows(const wann_index *index);
 
+/* WIDE ROWS: stop as at k, keep up to `width` entries (not calls of the reference; it computes this and drops the tail).
+ * The reference's query() (src/postfilter_vamana.h:141-188) returns the whole filtered frontier of the last beam it searched;
+ * knn appears in its stop test `frontier.size() < knn` and in batch_search's copy of the first knn entries, nowhere else.  An
+ * ordinary call uses one number, qp->k, for three things; a wide call separates them:
+ *   k       what the caller gets back,
+ *   stop_k  the doubling loop ends at the first level with >= stop_k in-window entries,
+ *   width   the columns of the search's row.
+ * wann_batch_search_device_wide has k = width and stop_k = qp->k; every other entry point has k == stop_k == width.  Semantics:
+ *   - Every graph search of the call runs the reference's loop with knn = stop_k: the doubling, the speculated levels, the final
+ *     re-search by final_beam_multiply and the postfiltering_max_beam end.
+ *   - The call keeps the first `width` in-window entries of the frontier that loop returns.  Pads follow, as today.
+ *   - Exact scans keep the best `width`: tiny windows, PrefilterIndex, prefilter leaves, the ends of fenwick / three_split and
+ *     wann_set_exact_windows scans.
+ *   - Merges (k_finalize_multi) keep `width`.
+ *   - Consequently the first stop_k columns are the ordinary call's row at k = stop_k.
+ *   - beam_searches, hops and dist_cmps equal that call's counters.  (They count the graph searches.  What goes by the row's
+ *     columns follows `width`: label_reads -- a level's beam is filtered until `width` entries are kept -- and the dense path,
+ *     which takes rows of at most 16 columns: exact windows (wann_set_exact_windows) and PrefilterIndex windows that the call at
+ *     k = stop_k scores on the matrix cores may be scanned by a wide call, as by the ordinary call at k = width -- the same
+ *     rows either way, gemm_* counters as that call's.  Which windows are exact does not depend on any k.)
+ * wann_batch_search_device_wide: wann_batch_search_device's arguments and `width`; d_ids / d_dists are nq x width.  It requires
+ * 1 <= qp->k <= width <= 1024 (WANN_ERR_INVALID otherwise) and refuses qp->verbose with WANN_ERR_UNSUPPORTED when width != qp->k:
+ * the printed words name one k.  Nothing is launched by a refused call.  Any element type and any index kind; on kinds with no
+ * graph search it equals the ordinary call at k = width.  width == qp->k is the ordinary call.
+ * wann_batch_search_wide: the host-buffer form, queries as wann_batch_search takes them (the index dtype's bit patterns); ids /
+ * dists: nq x width, host.
+ * Primary device only and blocking only: no asynchronous, all-gather or WANN_DEVICES-replica form.  A NULL index is answered
+ * with the NEGATIVE code -WANN_ERR_INVALID. */
+int wann_batch_search_device_wide(wann_index *index, const void *d_queries, const float *d_ranges, int64_t nq, int64_t query_id_base,
+                                  const char *method, const wann_query_params *qp, int64_t width, uint32_t *d_ids, float *d_dists,
+                                  void *hip_stream);
+int wann_batch_search_wide(wann_index *index, const void *queries, const float *ranges, int64_t nq, const char *method,
+                           const wann_query_params *qp, int64_t width, uint32_t *ids, float *dists);
+
 /* REFINED SEARCH: re-rank a compact index's candidates against full-precision rows.  A WANN_DTYPE_F16 / BF16 / F8 index answers
  * for the ROUNDED points.  A caller who still has the float32 points gives them to the index as a ROW STORE; a refined call then
  * searches the compact rows for refine_k >= k candidates (a half or a quarter of the float32 bytes per scored row), scores
@@ -452,6 +488,12 @@ int wann_last_dense_rows(const wann_index *index);
  * wann_batch_search_refined: the host-buffer form.  `queries` is (nq, d) FLOAT32 -- unlike wann_batch_search, which takes the
  * index dtype's bit patterns and so searches with rounded queries; here the fp32 queries are uploaded as they are and go
  * through the device path.  ids / dists: nq x qp->k, host.  Serves the primary.
+ * wann_batch_search_device_refined_stop / wann_batch_search_refined_stop: the refined calls with one more argument, stop_k,
+ * qp->k <= stop_k <= refine_k (WANN_ERR_INVALID otherwise).  C(q) is then the WIDE row (above) at (stop_k, width = refine_k): the
+ * search stops as the ordinary call at k = stop_k does and the re-rank sees up to refine_k entries of that same frontier, so the
+ * candidates cost the search at stop_k, not the one at refine_k.  Afterwards wann_get_counters reports that search:
+ * beam_searches, hops and dist_cmps equal the ordinary call's at k = stop_k.  The functions without the argument are the case
+ * stop_k = refine_k.  qp->verbose with stop_k != refine_k: WANN_ERR_UNSUPPORTED, nothing launched.
  * wann_get_refine_counters: the last refined call's re-rank -- queries, candidates scored (pads excluded) and the HIP-event
  * time of the re-rank launch alone (wann_counters::device_ms stays the search's).
  * There is no asynchronous form and no all-gather form, and no environment switch: refinement happens where it is called.
@@ -469,6 +511,11 @@ int wann_batch_search_device_refined(wann_index *index, const void *d_queries, c
                                      uint32_t *d_ids, float *d_dists, void *hip_stream);
 int wann_batch_search_refined(wann_index *index, const float *queries, const float *ranges, int64_t nq, const char *method,
                               const wann_query_params *qp, int64_t refine_k, uint32_t *ids, float *dists);
+int wann_batch_search_device_refined_stop(wann_index *index, const void *d_queries, const float *d_ranges, int64_t nq,
+                                          int64_t query_id_base, const char *method, const wann_query_params *qp, int64_t refine_k,
+                                          int64_t stop_k, uint32_t *d_ids, float *d_dists, void *hip_stream);
+int wann_batch_search_refined_stop(wann_index *index, const float *queries, const float *ranges, int64_t nq, const char *method,
+                                   const wann_query_params *qp, int64_t refine_k, int64_t stop_k, uint32_t *ids, float *dists);
 int wann_get_refine_counters(const wann_index *index, wann_refine_counters *out);
 
 /* In-process multi-device mode: with WANN_DEVICES=a,b,... in the environment wann_index_create makes the index resident on

@@ -493,7 +493,7 @@ int wann_predict_costs(wann_index *I, const float *ranges, int64_t nq, const cha
     ra.method = mcode;
     ra.maxt = maxt;
     ra.qtask_cnt = W.qtask_cnt.p;
-    ra.k = k;
+    ra.stop_k = k;
     ra.beam = (int32_t)std::min<int64_t>(std::max<int64_t>(qp->beam_width, 1), INT32_MAX);
     ra.max_beam = (int32_t)std::min<int64_t>(qp->postfiltering_max_beam, INT32_MAX);
     ra.has_ratio = qp->has_min_query_to_bucket_ratio;
@@ -545,8 +545,9 @@ int wann_predict_costs(wann_index *I, const float *ranges, int64_t nq, const cha
 
 namespace {
 // one replica's share of a host-buffer call: stage, search (queries keep their global numbers), copy back
+// (stop_k: run_batch's -- 0 but for the wide call, whose qp.k is the rows' width)
 void search_host_one(wann_index &T, const void *queries, const float *ranges, int64_t nq, int64_t qid_base, const char *method,
-                     const wann_query_params &qp, uint32_t *ids, float *dists) {
+                     const wann_query_params &qp, uint32_t *ids, float *dists, int64_t stop_k = 0) {
   std::lock_guard<std::mutex> lk(T.mu);
   HIP_CHECK(hipSetDevice(T.device));
   const Tuning tune = snapshot_tuning(T);  // (WANN_TEST_HOOKS=1 only: re-read)
@@ -567,7 +568,8 @@ void search_host_one(wann_index &T, const void *queries, const float *ranges, in
     HIP_CHECK(hipMemcpyAsync(W.q_stage.p, queries, (size_t)nq * d * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(W.r_stage.p, ranges, (size_t)nq * 8, hipMemcpyHostToDevice, st));
   }
-  T.note_row_store(run_batch(T, W, T.side_stream, T.last, W.q_stage.p, W.r_stage.p, nq, qid_base, method, qp, W.id_stage.p, W.dist_stage.p, st, tune));
+  T.note_row_store(run_batch(T, W, T.side_stream, T.last, W.q_stage.p, W.r_stage.p, nq, qid_base, method, qp, W.id_stage.p, W.dist_stage.p, st, tune,
+                             nullptr, stop_k));
   if (nq) {
     HIP_CHECK(hipMemcpyAsync(ids, W.id_stage.p, (size_t)nq * qp.k * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(dists, W.dist_stage.p, (size_t)nq * qp.k * 4, hipMemcpyDeviceToHost, st));
@@ -673,6 +675,57 @@ int wann_batch_search(wann_index *I, const void *queries, const float *ranges, i
   return WANN_OK;
 }
 
+// ---- wide rows (wann.h WIDE ROWS): the search that stops as at qp->k, rows of `width` columns ----
+
+// what a wide call needs beyond the ordinary call's arguments; nothing has been launched when this fails
+static int wide_refused(const wann_query_params &qp, int64_t width) {
+  static_assert(kMaxK == 1024, "the message below names the limit");
+  if (qp.k <= 0 || width < qp.k || width > kMaxK) return fail(WANN_ERR_INVALID, "wide search: k <= width <= 1024 is required, and k >= 1");
+  if (qp.verbose && width != qp.k)
+    return fail(WANN_ERR_UNSUPPORTED, "wide search: a verbose call prints the reference's words, which name one k: width must equal k");
+  return WANN_OK;
+}
+
+int wann_batch_search_device_wide(wann_index *I, const void *d_queries, const float *d_ranges, int64_t nq, int64_t query_id_base,
+                                  const char *method, const wann_query_params *qp, int64_t width, uint32_t *d_ids, float *d_dists,
+                                  void *hip_stream) {
+  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
+  if (!qp || nq < 0) return fail(WANN_ERR_INVALID, "invalid argument to wann_batch_search_device_wide");
+  if (const int rc = wide_refused(*qp, width)) return rc;
+  std::lock_guard<std::mutex> lk(I->mu);
+  try {
+    wann_query_params wide = *qp;  // (run_batch: qp.k is the rows' width)
+    wide.k = width;
+    const Tuning T = snapshot_tuning(*I);
+    I->note_row_store(run_batch(*I, I->ws, I->side_stream, I->last, (const float *)d_queries, d_ranges, nq, query_id_base, method, wide, d_ids,
+                                d_dists, (hipStream_t)hip_stream, T, nullptr, qp->k));
+  } catch (HipError &e) {
+    return fail(WANN_ERR_HIP, e.what());
+  } catch (std::exception &e) {
+    return fail(WANN_ERR_INVALID, e.what());
+  }
+  return WANN_OK;
+}
+
+int wann_batch_search_wide(wann_index *I, const void *queries, const float *ranges, int64_t nq, const char *method,
+                           const wann_query_params *qp, int64_t width, uint32_t *ids, float *dists) {
+  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
+  if (!qp || nq < 0) return fail(WANN_ERR_INVALID, "invalid argument to wann_batch_search_wide");
+  if (const int rc = wide_refused(*qp, width)) return rc;
+  if (nq > 0 && (!queries || !ranges || !ids || !dists)) return fail(WANN_ERR_INVALID, "invalid argument to wann_batch_search_wide");
+  if (f8_nan_refused(I->dtype, queries, nq, I->H.spec.d, "query")) return WANN_ERR_INVALID;
+  try {
+    wann_query_params wide = *qp;
+    wide.k = width;
+    search_host_one(*I, queries, ranges, nq, 0, method, wide, ids, dists, qp->k);  // (the primary, whatever WANN_DEVICES lists)
+  } catch (HipError &e) {
+    return fail(WANN_ERR_HIP, e.what());
+  } catch (std::exception &e) {
+    return fail(WANN_ERR_INVALID, e.what());
+  }
+  return WANN_OK;
+}
+
 // ---- refined search (wann.h REFINED SEARCH): the full-precision row store and the re-rank of a compact index's candidates ----
 
 // (a null index is answered with the NEGATIVE code by all of these, as by the setters of the shadow rows)
@@ -711,10 +764,14 @@ int64_t wann_refine_rows_bytes(const wann_index *I) { return I ? (int64_t)I->d_r
 
 namespace {
 // what a refined call needs beyond the ordinary call's arguments (under I.mu); nothing has been launched when this fails
-int refine_refused(const wann_index &I, const wann_query_params &qp, int64_t refine_k) {
+// (stop_k: the search's stop threshold -- refine_k for the calls without the argument)
+int refine_refused(const wann_index &I, const wann_query_params &qp, int64_t refine_k, int64_t stop_k) {
   static_assert(kMaxK == 1024, "the message below names the limit");
   if (!I.d_refine.p) return fail(WANN_ERR_INVALID, "refined search: the index has no refine rows (wann_set_refine_rows)");
   if (qp.k <= 0 || refine_k < qp.k || refine_k > kMaxK) return fail(WANN_ERR_INVALID, "refined search: k <= refine_k <= 1024 is required, and k >= 1");
+  if (stop_k < qp.k || stop_k > refine_k) return fail(WANN_ERR_INVALID, "refined search: k <= stop_k <= refine_k is required");
+  if (qp.verbose && stop_k != refine_k)
+    return fail(WANN_ERR_UNSUPPORTED, "refined search: a verbose call prints the reference's words, which name one k: stop_k must equal refine_k");
   const int64_t d = I.host().spec.d, need = refine_lds_bytes(refine_row_words(d), (int)qp.k);
   if (need > kLdsPerWorkgroup)
     return fail(WANN_ERR_UNSUPPORTED, "refined search: rows of " + std::to_string((long long)d) + " elements at k = " + std::to_string((long long)qp.k) +
@@ -723,10 +780,11 @@ int refine_refused(const wann_index &I, const wann_query_params &qp, int64_t ref
   return WANN_OK;
 }
 
-// the refined call on device buffers (under I.mu, refine_refused passed): the ordinary blocking search at k = refine_k into the
-// workspace, then k_refine on the same stream into the caller's rows
+// the refined call on device buffers (under I.mu, refine_refused passed): the blocking search that stops as at k = stop_k, rows
+// of refine_k columns (the ordinary search at k = refine_k where the two are equal), into the workspace, then k_refine on the same
+// stream into the caller's rows
 void search_refined_device(wann_index &I, const float *d_queries, const float *d_ranges, int64_t nq, int64_t qid_base, const char *method,
-                           const wann_query_params &qp, int64_t refine_k, uint32_t *d_ids, float *d_dists, hipStream_t st) {
+                           const wann_query_params &qp, int64_t refine_k, int64_t stop_k, uint32_t *d_ids, float *d_dists, hipStream_t st) {
   HIP_CHECK(hipSetDevice(I.device));
   Workspace &W = I.ws;
   W.refine_ids.ensure((size_t)std::max<int64_t>(nq * refine_k, 1));
@@ -738,7 +796,8 @@ void search_refined_device(wann_index &I, const float *d_queries, const float *d
   wide.k = refine_k;
   const Tuning T = snapshot_tuning(I);
   I.last_refine = wann_refine_counters{};
-  I.note_row_store(run_batch(I, W, I.side_stream, I.last, d_queries, d_ranges, nq, qid_base, method, wide, W.refine_ids.p, W.refine_dists.p, st, T));
+  I.note_row_store(run_batch(I, W, I.side_stream, I.last, d_queries, d_ranges, nq, qid_base, method, wide, W.refine_ids.p, W.refine_dists.p, st, T, nullptr,
+                             stop_k));
   if (nq == 0) return;
   const BuildSpec &s = I.host().spec;
   RefineArgs ra{};
@@ -771,15 +830,17 @@ void search_refined_device(wann_index &I, const float *d_queries, const float *d
 }
 }  // namespace
 
-int wann_batch_search_device_refined(wann_index *I, const void *d_queries, const float *d_ranges, int64_t nq, int64_t query_id_base,
-                                     const char *method, const wann_query_params *qp, int64_t refine_k, uint32_t *d_ids, float *d_dists,
-                                     void *hip_stream) {
+// (`who`: the entry point's name, for the message.  The calls without a stop_k pass refine_k: the ordinary search at k = refine_k.)
+static int refined_device_call(const char *who, wann_index *I, const void *d_queries, const float *d_ranges, int64_t nq, int64_t query_id_base,
+                               const char *method, const wann_query_params *qp, int64_t refine_k, int64_t stop_k, uint32_t *d_ids, float *d_dists,
+                               void *hip_stream) {
   if (!I) return -fail(WANN_ERR_INVALID, "null argument");
-  if (!qp || nq < 0) return fail(WANN_ERR_INVALID, "invalid argument to wann_batch_search_device_refined");
+  if (!qp || nq < 0) return fail(WANN_ERR_INVALID, std::string("invalid argument to ") + who);
   std::lock_guard<std::mutex> lk(I->mu);
-  if (const int rc = refine_refused(*I, *qp, refine_k)) return rc;
+  if (const int rc = refine_refused(*I, *qp, refine_k, stop_k)) return rc;
   try {
-    search_refined_device(*I, (const float *)d_queries, d_ranges, nq, query_id_base, method, *qp, refine_k, d_ids, d_dists, (hipStream_t)hip_stream);
+    search_refined_device(*I, (const float *)d_queries, d_ranges, nq, query_id_base, method, *qp, refine_k, stop_k, d_ids, d_dists,
+                          (hipStream_t)hip_stream);
   } catch (HipError &e) {
     return fail(WANN_ERR_HIP, e.what());
   } catch (std::exception &e) {
@@ -788,13 +849,27 @@ int wann_batch_search_device_refined(wann_index *I, const void *d_queries, const
   return WANN_OK;
 }
 
-int wann_batch_search_refined(wann_index *I, const float *queries, const float *ranges, int64_t nq, const char *method,
-                              const wann_query_params *qp, int64_t refine_k, uint32_t *ids, float *dists) {
+int wann_batch_search_device_refined(wann_index *I, const void *d_queries, const float *d_ranges, int64_t nq, int64_t query_id_base,
+                                     const char *method, const wann_query_params *qp, int64_t refine_k, uint32_t *d_ids, float *d_dists,
+                                     void *hip_stream) {
+  return refined_device_call("wann_batch_search_device_refined", I, d_queries, d_ranges, nq, query_id_base, method, qp, refine_k, refine_k, d_ids,
+                             d_dists, hip_stream);
+}
+
+int wann_batch_search_device_refined_stop(wann_index *I, const void *d_queries, const float *d_ranges, int64_t nq, int64_t query_id_base,
+                                          const char *method, const wann_query_params *qp, int64_t refine_k, int64_t stop_k, uint32_t *d_ids,
+                                          float *d_dists, void *hip_stream) {
+  return refined_device_call("wann_batch_search_device_refined_stop", I, d_queries, d_ranges, nq, query_id_base, method, qp, refine_k, stop_k, d_ids,
+                             d_dists, hip_stream);
+}
+
+static int refined_host_call(const char *who, wann_index *I, const float *queries, const float *ranges, int64_t nq, const char *method,
+                             const wann_query_params *qp, int64_t refine_k, int64_t stop_k, uint32_t *ids, float *dists) {
   if (!I) return -fail(WANN_ERR_INVALID, "null argument");
   if (!qp || nq < 0 || (nq > 0 && (!queries || !ranges || !ids || !dists)))
-    return fail(WANN_ERR_INVALID, "invalid argument to wann_batch_search_refined");
+    return fail(WANN_ERR_INVALID, std::string("invalid argument to ") + who);
   std::lock_guard<std::mutex> lk(I->mu);
-  if (const int rc = refine_refused(*I, *qp, refine_k)) return rc;
+  if (const int rc = refine_refused(*I, *qp, refine_k, stop_k)) return rc;
   try {
     HIP_CHECK(hipSetDevice(I->device));
     Workspace &W = I->ws;
@@ -808,7 +883,7 @@ int wann_batch_search_refined(wann_index *I, const float *queries, const float *
       HIP_CHECK(hipMemcpyAsync(W.q_stage.p, queries, (size_t)nq * d * 4, hipMemcpyHostToDevice, st));
       HIP_CHECK(hipMemcpyAsync(W.r_stage.p, ranges, (size_t)nq * 8, hipMemcpyHostToDevice, st));
     }
-    search_refined_device(*I, W.q_stage.p, W.r_stage.p, nq, 0, method, *qp, refine_k, W.id_stage.p, W.dist_stage.p, st);
+    search_refined_device(*I, W.q_stage.p, W.r_stage.p, nq, 0, method, *qp, refine_k, stop_k, W.id_stage.p, W.dist_stage.p, st);
     if (nq) {
       HIP_CHECK(hipMemcpyAsync(ids, W.id_stage.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipMemcpyAsync(dists, W.dist_stage.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
@@ -820,6 +895,16 @@ int wann_batch_search_refined(wann_index *I, const float *queries, const float *
     return fail(WANN_ERR_INVALID, e.what());
   }
   return WANN_OK;
+}
+
+int wann_batch_search_refined(wann_index *I, const float *queries, const float *ranges, int64_t nq, const char *method,
+                              const wann_query_params *qp, int64_t refine_k, uint32_t *ids, float *dists) {
+  return refined_host_call("wann_batch_search_refined", I, queries, ranges, nq, method, qp, refine_k, refine_k, ids, dists);
+}
+
+int wann_batch_search_refined_stop(wann_index *I, const float *queries, const float *ranges, int64_t nq, const char *method,
+                                   const wann_query_params *qp, int64_t refine_k, int64_t stop_k, uint32_t *ids, float *dists) {
+  return refined_host_call("wann_batch_search_refined_stop", I, queries, ranges, nq, method, qp, refine_k, stop_k, ids, dists);
 }
 
 int wann_get_refine_counters(const wann_index *I, wann_refine_counters *out) {

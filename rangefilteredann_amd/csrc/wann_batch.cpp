@@ -216,7 +216,8 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
 // What one call is: decided once from (index, switches, QueryParams, method, batch size) by plan_batch, const from then on.
 struct BatchPlan {
   int kind;             // the index class (WANN_KIND_*)
-  int k, mcode;         // QueryParams::k, the method (M_*)
+  int k, mcode;         // QueryParams::k -- the columns of every row of the call --, the method (M_*)
+  int stop_k;           // the doubling loops' knn: a level with >= stop_k in-window entries ends its chain (k but for a wide call)
   int maxt;             // task slots per query
   int64_t exact_set;    // wann_set_exact_windows' limit as this call read it: what the dense_mu decision goes by
   int64_t exact_limit;  // the limit the call runs with
@@ -233,7 +234,7 @@ struct BatchPlan {
   int64_t inkernel_cap;
 };
 
-static BatchPlan plan_batch(const wann_index &I, const Tuning &T, const wann_query_params &qp, const char *method, int64_t nq) {
+static BatchPlan plan_batch(const wann_index &I, const Tuning &T, const wann_query_params &qp, const char *method, int64_t nq, int64_t stop_k) {
   BatchPlan P{};
   const HostIndex &H = I.host();
   P.kind = H.spec.kind;
@@ -244,6 +245,7 @@ static BatchPlan plan_batch(const wann_index &I, const Tuning &T, const wann_que
   // (a verbose call is the reference's trace: it ignores the option)
   P.exact_limit = qp.verbose ? 0 : P.exact_set;
   P.k = (int)qp.k;
+  P.stop_k = (int)stop_k;
   P.mcode = method_code(method);
   const bool tree = P.kind == WANN_KIND_TREE_PREFILTER || P.kind == WANN_KIND_TREE_VAMANA;
   // fenwick / three_split cover a window with several buckets (+ two brute-forced ends)
@@ -355,7 +357,7 @@ void Batch::route() const {
   ra.method = P.mcode;
   ra.maxt = P.maxt;
   ra.qtask_cnt = W.qtask_cnt.p;
-  ra.k = P.k;
+  ra.stop_k = P.stop_k;
   ra.beam = (int32_t)std::min<int64_t>(qp.beam_width, INT32_MAX);
   ra.max_beam = (int32_t)std::min<int64_t>(qp.postfiltering_max_beam, INT32_MAX);
   ra.has_ratio = qp.has_min_query_to_bucket_ratio;
@@ -544,7 +546,7 @@ void SearchRounds::companion(SearchArgs &a, SearchArgs &big, LaunchCfg &big_lc, 
       a.la_base0 = big.la_base0 = (int32_t)(nq * P.maxt);
       a.la_cap = big.la_cap = (int32_t)std::min<int64_t>(nq * P.maxt + P.sub_slots, INT32_MAX);
       a.la_min_beam = big.la_min_beam = (int32_t)std::max<int64_t>(4 * first_beam, 160);
-      a.la_found_max = big.la_found_max = (int32_t)((2 * qp.k + 4) / 5);
+      a.la_found_max = big.la_found_max = (int32_t)((2 * (int64_t)P.stop_k + 4) / 5);
       if (deep_pollers == 0 && scan_on) {  // (companion mode: there are speculating tasks)
         big.scan_list = W.list_big.p + 3 * (size_t)W.big_stride;
         big.scan_count = W.ints.p + I_SCAN_COUNT;
@@ -553,7 +555,7 @@ void SearchRounds::companion(SearchArgs &a, SearchArgs &big, LaunchCfg &big_lc, 
       }
       if (T.la_eager) {  // test hook: every chain that fails its second level asks for one
         a.la_min_beam = big.la_min_beam = (int32_t)(2 * first_beam);
-        a.la_found_max = big.la_found_max = (int32_t)qp.k;
+        a.la_found_max = big.la_found_max = (int32_t)P.stop_k;
       }
     }
     big.force_poll_timeout = T.force_poll_timeout ? 1 : 0;  // test hook
@@ -774,7 +776,8 @@ void SearchRounds::follow_up(const SearchArgs &sa, int next_n) {
       }
       if (!fits)
         throw std::runtime_error("beam search has to double beyond a beam of " + std::to_string((long long)kLargestBeam) + " (k = " +
-                                 std::to_string(P.k) + ", postfiltering_max_beam = " + std::to_string((long long)max_beam) +
+                                 std::to_string(P.stop_k) + (P.stop_k != P.k ? ", row width = " + std::to_string(P.k) : std::string()) +
+                                 ", postfiltering_max_beam = " + std::to_string((long long)max_beam) +
                                  "): its seen-filter would exceed 2^31 entries");
     }
     sb.next_list = (stage & 1) ? W.list_b.p : W.list_a.p;
@@ -835,6 +838,7 @@ SearchArgs Batch::search_args() const {
   sa.raw_qids = reinterpret_cast<const long long *>(d_qids);  // (null unless the caller names every query's own id)
   sa.tasks = W.tasks.p;
   sa.k = P.k;
+  sa.stop_k = P.stop_k;
   sa.limit = qp.limit;
   sa.degree_limit = (int32_t)std::min<int64_t>(qp.degree_limit, INT32_MAX);
   sa.mult = (int32_t)std::min<int64_t>(qp.final_beam_multiply, INT32_MAX);
@@ -1041,14 +1045,18 @@ void Batch::copy_counters(const SearchRounds &R, bool tried_dense, float batch_m
 // W / side / last: the lane of this batch (the index's own members for the blocking calls, an AsyncLane's for the asynchronous one)
 int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
-               const int64_t *d_qids) {
+               const int64_t *d_qids, int64_t stop_k) {
   static_assert(kMaxK == 1024, "the message below names the limit");
   if (qp.k <= 0 || qp.k > kMaxK) throw std::runtime_error("k must be in [1, 1024]");
+  if (stop_k == 0) stop_k = qp.k;
+  if (stop_k < 1 || stop_k > qp.k) throw std::runtime_error("stop_k must be in [1, row width]");
+  // (the words of the reference's trace name one k: the C ABI refuses such a call as unsupported before it gets here)
+  if (stop_k != qp.k && qp.verbose) throw std::runtime_error("a wide call cannot be verbose");
   // the brute-force classes ignore the beam (the reference driver passes beam_size = 0 there, run_our_method.py:256)
   if (qp.beam_width <= 0 && I.host().vamana_leaves) throw std::runtime_error("beam_width must be positive");
   if (qp.postfiltering_max_beam > (1 << 20)) throw std::runtime_error("postfiltering_max_beam too large");
   HIP_CHECK(hipSetDevice(I.device));
-  const BatchPlan P = plan_batch(I, T, qp, method, nq);
+  const BatchPlan P = plan_batch(I, T, qp, method, nq, stop_k);
   // The exact scan keeps a wave's query row and its k-entry list in the LDS (brute_lds_bytes_per_wave): rows too long for a
   // CU's 160 KiB are refused here, before anything of the batch is queued (config_for says the same of the beam search).
   if (nq > 0 && P.may_brute) {

@@ -148,7 +148,7 @@ struct RouteArgs {
   const float *ranges;  // nq x 2
   int64_t nq;
   int32_t method;
-  int32_t k;
+  int32_t stop_k;  // the doubling loop's knn (SearchArgs::stop_k): what the routing heuristics predict a chain's length from
   int32_t beam, max_beam;
   int32_t has_ratio;
   float ratio;
@@ -214,7 +214,9 @@ struct SearchArgs {
   const int32_t *mid_count;
   int32_t *cursor;
   int32_t B;             // first beam of every task of this launch
-  int32_t k;
+  int32_t k;             // columns of a task's row in out_key: the first k in-window entries of a beam are kept
+  int32_t stop_k;        // the doubling loop's knn (postfilter_vamana.h:161-172): a level with >= stop_k in-window entries ends
+                         // the chain; 1 <= stop_k <= k, equal to k in every call but the wide ones (wann.h WIDE ROWS)
   int64_t limit;
   int32_t degree_limit;
   int32_t mult;          // final_beam_multiply
@@ -287,7 +289,7 @@ struct SearchArgs {
   int32_t scan_num;  // the scan asks for a look-ahead when the highest level is expected to find at most k * scan_num / 8 entries
   const int32_t *scan_list, *scan_count;  // idle pollers scan these speculating tasks (k_route's list) for ones that will
   int32_t scan_min_top;                   // need the level after their highest one (highest beam >= scan_min_top); null = no scan
-  int32_t la_found_max;  // a chain asks for a look-ahead when its last level found fewer in-window entries than this (0.4 k)
+  int32_t la_found_max;  // a chain asks for a look-ahead when its last level found fewer in-window entries than this (0.4 stop_k)
   // QueryParams::verbose (postfilter_vamana.h:155-185,230): one record per search of a task's doubling loop -- beam << 42 |
   // unfiltered beam size << 21 | in-window entries of the WHOLE final beam -- in vlog[task * vlog_cap + i], i < vlog_n[task]
   // (one-wave legacy kernel only: the host routes a verbose call there, without speculative levels); null = off

@@ -282,9 +282,11 @@ int method_code(const char *m);
 // T.half_rows, else the index's own rows -- and, shifted left by 8, the store its k_brute launch read (the same one if
 // T.scan_rows, else kStoreRows; kStoreRows too for a batch that launched no scan) -- and, shifted left by 16, 1 if a score launch
 // of its dense path read the one-byte copy (T.dense_rows) for at least one query.
+// stop_k: the rows have qp.k columns, and every graph search's doubling loop ends at the first level with >= stop_k in-window
+// entries (wann.h WIDE ROWS); 0 = qp.k, the ordinary call.  1 <= stop_k <= qp.k otherwise, and not with qp.verbose.
 int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last, const float *d_queries, const float *d_ranges, int64_t nq,
                int64_t qid_base, const char *method, const wann_query_params &qp, uint32_t *d_ids, float *d_dists, hipStream_t st, const Tuning &T,
-               const int64_t *d_qids = nullptr);
+               const int64_t *d_qids = nullptr, int64_t stop_k = 0);
 void build_pending(wann_index &I, std::vector<HostPart *> &pending);
 // host queries of the index's element type (uint8 / int8 / float16 / bfloat16 / float8) -> the fp32 rows every kernel stages (exact)
 std::vector<float> bytes_to_float(int dtype, const void *src, int64_t count);

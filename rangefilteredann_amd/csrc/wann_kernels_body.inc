@@ -276,14 +276,14 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
             if (nsub < 3 || top < A.scan_min_top || 2 * top > A.big_cap || 2 * top >= A.max_beam) continue;
             if (__hip_atomic_load(&A.sub_cmps[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != -1) continue;
             const int ft = __hip_atomic_load(&A.out_cnt[sbase + nsub - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (ft >= A.k) continue;  // (out_cnt of a sub-task slot is -1 until its search has finished)
+            if (ft >= A.stop_k) continue;  // (out_cnt of a sub-task slot is -1 until its search has finished)
             // the highest level has failed -- or the largest lower level that has finished (down to an eighth of the highest
             // beam) found so little that the highest one is expected to find at most k: in-window entries scale with the beam
             bool deeper = ft >= 0;
             for (int r = nsub - 2; !deeper && r >= 0 && r >= nsub - 4; r--) {
               const int f = __hip_atomic_load(&A.out_cnt[sbase + r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               if (f >= 0) {
-                deeper = ((long long)f << (nsub - 1 - r)) * 8 <= (long long)A.k * A.scan_num;
+                deeper = ((long long)f << (nsub - 1 - r)) * 8 <= (long long)A.stop_k * A.scan_num;
                 break;
               }
             }
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
       b = __hip_atomic_load(A.next_beam + ti, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else if (sub) b = (long long)A.B << (int)A.tasks[ti].a;
     else if (A.start_beam) b = A.start_beam[ti];
-    // A speculated level is MOOT once a lower level of its task has found k entries (the sequential loop stops at the first
+    // A speculated level is MOOT once a lower level of its task has found stop_k entries (the sequential loop stops at the first
     // such level, postfilter_vamana.h:161-172): it is not searched (here) or stops at its next check (one-wave core).  The
     // lowest successful level of a task is kept in sub_hops[parent] (the host presets it to a huge value per batch).
     const bool spec_level = sub && !(A.tasks[ti].flags & 16);
@@ -560,7 +560,8 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
         }
         break;
       }
-      // ---- post filter: keep beam entries whose label lies in [lo,hi], first k of them
+      // ---- post filter: keep beam entries whose label lies in [lo,hi], first k of them (k: the row's columns; whether the
+      //      level has ENOUGH is decided on stop_k <= k below -- wann.h WIDE ROWS: equal but for the wide calls)
       //      (postfilter_vamana.h:234-251); ids become sorted-order indices (subset[local])
       int found = 0;
       long long labs = 0;
@@ -614,7 +615,7 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
         }
         break;
       }
-      if (A.la_count && !sub && (found >= A.k || final_pass)) {  // the chain ends here: a look-ahead of its next level is not needed
+      if (A.la_count && !sub && (found >= A.stop_k || final_pass)) {  // the chain ends here: a look-ahead of its next level is not needed
         if (lane == 0) {
           const int la = la_slot_of(A, ti);
           if (la >= 0) {
@@ -625,16 +626,16 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
       }
       if (sub) {
         // Publish this level, then the LAST sub-task to finish replays the sequential rule over the
-        // levels: the result is that of the first level with >= k in-window entries (or of the last
+        // levels: the result is that of the first level with >= stop_k in-window entries (or of the last
         // level), exactly what the doubling loop returns; it then continues as the parent.
         const int parent = (int)A.tasks[ti].b;
-        // a level that has found k entries makes every higher level of its task moot (see above)
-        if (found >= A.k && !moot && lane == 0) atomicMin((unsigned long long *)&A.sub_hops[parent], (unsigned long long)my_level);
+        // a level that has found stop_k entries makes every higher level of its task moot (see above)
+        if (found >= A.stop_k && !moot && lane == 0) atomicMin((unsigned long long *)&A.sub_hops[parent], (unsigned long long)my_level);
         // ... and settles that the chain will not go beyond its speculated levels: a look-ahead an
         // idle poller is running for it (the pollers' scan) is called off NOW, not when the slowest level has finished --
         // the poller is free for the next chain that needs one; the scan leaves the task alone from now on (a moot top level
         // reports nothing found: that must not look like a failed one)
-        if (A.la_count && found >= A.k && lane == 0) {
+        if (A.la_count && found >= A.stop_k && lane == 0) {
           const int la = la_slot_of(A, parent);
           if (la >= 0) {
             la_withdraw(A, la);
@@ -657,7 +658,7 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
         __threadfence();
         int succ = -1;
         for (int r = 0; r < nsub; r++)
-          if (__hip_atomic_load(&A.out_cnt[sbase + r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= A.k) {
+          if (__hip_atomic_load(&A.out_cnt[sbase + r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= A.stop_k) {
             succ = r;
             break;
           }
@@ -702,7 +703,7 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
         b = (long long)A.B << upto;
       }
       if (final_pass) break;
-      if (found >= A.k) {  // doubling loop ends here (postfilter_vamana.h:161-172); final re-search?
+      if (found >= A.stop_k) {  // doubling loop ends here (postfilter_vamana.h:161-172); final re-search?
         long long fb = b * ((A.tasks[ti].flags & 2) ? 1 : A.mult);
         if (fb > A.max_beam) fb = A.max_beam;
         if (fb <= b) break;
@@ -919,8 +920,8 @@ struct Emitter {
       // 161-172); the sequential rule "first level with >= k in-window results" is applied afterwards.
       // a first beam that expects fewer than 4k in-window entries fails now and then: such a task starts before the
       // bulk, so that its second, longer search is not what the launch ends with
-      if (t.mode == T_GRAPH && (uint64_t)A.beam * w < 4ull * (uint64_t)A.k * (uint64_t)pd.n) t.flags |= 8;
-      if (t.mode == T_GRAPH && w > 0 && 2ull * (uint64_t)A.k * (uint64_t)pd.n >= (uint64_t)A.cap_inkernel * w) atomicAdd(A.risk_count, 1);
+      if (t.mode == T_GRAPH && (uint64_t)A.beam * w < 4ull * (uint64_t)A.stop_k * (uint64_t)pd.n) t.flags |= 8;
+      if (t.mode == T_GRAPH && w > 0 && 2ull * (uint64_t)A.stop_k * (uint64_t)pd.n >= (uint64_t)A.cap_inkernel * w) atomicAdd(A.risk_count, 1);
       // (partition / window >= heavy_ratio, with an eighth of slack: a window one point wider than a power-of-two share of
       // its partition is as heavy as one that is not)
       if (t.mode == T_GRAPH && w > 0 && 8ull * (uint64_t)pd.n >= (8ull * (uint64_t)A.heavy_ratio - 1ull) * w) {
@@ -930,7 +931,7 @@ struct Emitter {
           // beam * w / n_p >= k, plus one
           int nsub = 0;
           long long bb = A.beam;
-          const unsigned long long need = (unsigned long long)A.k * (uint64_t)pd.n;
+          const unsigned long long need = (unsigned long long)A.stop_k * (uint64_t)pd.n;
           bool reached = false;  // the loop ended at the first level predicted to hold k entries (bb = its beam)
           while (bb < A.max_beam && (bb <= A.cap_inkernel || bb <= A.big_cap) && nsub < 12) {
             nsub++;
@@ -950,7 +951,7 @@ struct Emitter {
           // bound by throughput -- measured on SIFT-1M at (80, x1): 2^-4 4.6 -> 4.3 ms, 2^-5 6.7 -> 5.6 ms with it, 2^-6 ... 2^-11
           // 10 - 40 % SLOWER with blanket extra levels (profiles/r06_extra_level_speculation.txt).
           if (A.spec_extra > 0 && reached && nsub >= A.spec_extra && nsub < 12 && (unsigned long long)bb * w < 2ull * need && 2 * bb < A.max_beam &&
-              2 * bb <= A.cap_inkernel && 8ull * (unsigned long long)A.k * (unsigned long long)ix.n <= 36ull * (unsigned long long)A.beam * w)  // (an eighth of slack, like the heavy rule)
+              2 * bb <= A.cap_inkernel && 8ull * (unsigned long long)A.stop_k * (unsigned long long)ix.n <= 36ull * (unsigned long long)A.beam * w)  // (an eighth of slack, like the heavy rule)
             nsub++;
           if (nsub >= 2) {
             const int base = atomicAdd(A.sub_count, nsub);

@@ -110,7 +110,7 @@ struct RawGraph {
     sa.mult = 1;
     sa.pool_bytes = rc.pool_bytes;
     sa.force_general = force_general ? 1 : 0;
-    sa.k = 1;
+    sa.k = sa.stop_k = 1;
     sa.limit = limit;
     sa.degree_limit = (int32_t)std::min<int64_t>(degree_limit, INT32_MAX);
     sa.ctr = d_ctr.p;

@@ -156,6 +156,46 @@ class Index {
     return std::make_pair(ids, dists);
   }
 
+  // the wide host-buffer call (wann.h WIDE ROWS): batch_search's arguments, rows of `width` columns from the search that stops as
+  // at query_params.k
+  NeighborsAndDistances search_wide(py::array queries_in, py::object filters, uint64_t nq, const std::string &method, const QueryParams &qp,
+                                    int64_t width) {
+    FArray fr = FArray::ensure(filters);
+    if (!fr) throw std::runtime_error("filters must be a sequence of (lo, hi) pairs");
+    if (fr.ndim() != 2 || fr.shape(1) != 2 || (uint64_t)fr.shape(0) < nq)
+      throw std::runtime_error("filters must have shape (num_queries, 2)");
+    py::array queries = as_elem(dtype_, queries_in);
+    if (!queries) throw std::runtime_error("queries must be convertible to an array of the index's element type");
+    if (queries.ndim() != 2 || (uint64_t)queries.shape(0) < nq || queries.shape(1) != wann_dim(h_))
+      throw std::runtime_error("queries must have shape (num_queries, dimension)");
+    // (a width the library refuses gets empty rows: the call below fails before it touches them)
+    const size_t w = (width >= 1 && width <= 1024) ? (size_t)width : 0;
+    py::array_t<unsigned int> ids({(size_t)nq, w});
+    py::array_t<float> dists({(size_t)nq, w});
+    const void *qptr = queries.data();
+    const float *rptr = fr.data();
+    unsigned int *ip = ids.mutable_data();
+    float *dp = dists.mutable_data();
+    int rc;
+    {
+      py::gil_scoped_release nogil;
+      rc = wann_batch_search_wide(h_, qptr, rptr, (int64_t)nq, method.c_str(), &qp.c, width, ip, dp);
+    }
+    if (rc) raise_last("batch_search_wide failed");
+    return std::make_pair(ids, dists);
+  }
+  // ... and the device-resident one (ids / dists are num_queries x width)
+  void search_device_wide(uint64_t q_ptr, uint64_t r_ptr, int64_t nq, int64_t query_id_base, const std::string &method, const QueryParams &qp,
+                          int64_t width, uint64_t ids_ptr, uint64_t dists_ptr, uint64_t stream) {
+    int rc;
+    {
+      py::gil_scoped_release nogil;
+      rc = wann_batch_search_device_wide(h_, (const void *)q_ptr, (const float *)r_ptr, nq, query_id_base, method.c_str(), &qp.c, width,
+                                         (uint32_t *)ids_ptr, (float *)dists_ptr, (void *)stream);
+    }
+    if (rc) raise_last("batch_search_device_wide failed");
+  }
+
   // device-resident call: every *_ptr is a device address on this index's GPU (e.g. torch .data_ptr())
   void search_device(uint64_t q_ptr, uint64_t r_ptr, int64_t nq, int64_t query_id_base, const std::string &method,
                      const QueryParams &qp, uint64_t ids_ptr, uint64_t dists_ptr, uint64_t stream) {
@@ -278,8 +318,10 @@ class Index {
   int64_t refine_rows_bytes() const { return wann_refine_rows_bytes(h_); }
   // the refined host-buffer call: FLOAT32 queries (not rounded to the index's element type), refine_k >= k candidates from the
   // compact rows re-ranked against the refine rows
+  // stop_k (None: refine_k, the search at k = refine_k): the search stops as at k = stop_k and the re-rank sees up to refine_k
+  // entries of that frontier (wann_batch_search_refined_stop)
   NeighborsAndDistances search_refined(py::object queries_in, py::object filters, uint64_t nq, const std::string &method, const QueryParams &qp,
-                                       int64_t refine_k) {
+                                       int64_t refine_k, std::optional<int64_t> stop_k) {
     FArray fr = FArray::ensure(filters);
     if (!fr) throw std::runtime_error("filters must be a sequence of (lo, hi) pairs");
     if (fr.ndim() != 2 || fr.shape(1) != 2 || (uint64_t)fr.shape(0) < nq) throw std::runtime_error("filters must have shape (num_queries, 2)");
@@ -297,19 +339,22 @@ class Index {
     int rc;
     {
       py::gil_scoped_release nogil;
-      rc = wann_batch_search_refined(h_, qptr, rptr, (int64_t)nq, method.c_str(), &qp.c, refine_k, ip, dp);
+      rc = stop_k ? wann_batch_search_refined_stop(h_, qptr, rptr, (int64_t)nq, method.c_str(), &qp.c, refine_k, *stop_k, ip, dp)
+                  : wann_batch_search_refined(h_, qptr, rptr, (int64_t)nq, method.c_str(), &qp.c, refine_k, ip, dp);
     }
     if (rc) raise_last("batch_search_refined failed");
     return std::make_pair(ids, dists);
   }
   // ... and the device-resident one (every *_ptr a device address on this index's GPU; ids / dists are num_queries x k)
   void search_device_refined(uint64_t q_ptr, uint64_t r_ptr, int64_t nq, int64_t query_id_base, const std::string &method, const QueryParams &qp,
-                             int64_t refine_k, uint64_t ids_ptr, uint64_t dists_ptr, uint64_t stream) {
+                             int64_t refine_k, uint64_t ids_ptr, uint64_t dists_ptr, uint64_t stream, std::optional<int64_t> stop_k) {
     int rc;
     {
       py::gil_scoped_release nogil;
-      rc = wann_batch_search_device_refined(h_, (const void *)q_ptr, (const float *)r_ptr, nq, query_id_base, method.c_str(), &qp.c, refine_k,
-                                            (uint32_t *)ids_ptr, (float *)dists_ptr, (void *)stream);
+      rc = stop_k ? wann_batch_search_device_refined_stop(h_, (const void *)q_ptr, (const float *)r_ptr, nq, query_id_base, method.c_str(), &qp.c,
+                                                          refine_k, *stop_k, (uint32_t *)ids_ptr, (float *)dists_ptr, (void *)stream)
+                  : wann_batch_search_device_refined(h_, (const void *)q_ptr, (const float *)r_ptr, nq, query_id_base, method.c_str(), &qp.c,
+                                                     refine_k, (uint32_t *)ids_ptr, (float *)dists_ptr, (void *)stream);
     }
     if (rc) raise_last("batch_search_device_refined failed");
   }
@@ -460,9 +505,15 @@ static void common_defs(py::class_<C> &c) {
       .def("set_refine_rows", &C::set_refine_rows, "points"_a.none(true))
       .def("refine_rows_bytes", &C::refine_rows_bytes)
       .def("batch_search_refined", &C::search_refined, "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a,
-           "refine_k"_a)
+           "refine_k"_a, py::kw_only(), "stop_k"_a = py::none())
       .def("batch_search_device_refined", &C::search_device_refined, "queries_ptr"_a, "filters_ptr"_a, "num_queries"_a, "query_id_base"_a,
-           "query_method"_a, "query_params"_a, "refine_k"_a, "ids_ptr"_a, "dists_ptr"_a, "stream"_a = 0)
+           "query_method"_a, "query_params"_a, "refine_k"_a, "ids_ptr"_a, "dists_ptr"_a, "stream"_a = 0, py::kw_only(), "stop_k"_a = py::none())
+      .def("batch_search_wide", &C::search_wide, "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a, "width"_a)
+      .def("batch_search_wide",
+           [](C &self, py::array q, py::object f, uint64_t nq, const QueryParams &qp, int64_t width) { return self.search_wide(q, f, nq, "", qp, width); },
+           "queries"_a, "filters"_a, "num_queries"_a, "query_params"_a, "width"_a)
+      .def("batch_search_device_wide", &C::search_device_wide, "queries_ptr"_a, "filters_ptr"_a, "num_queries"_a, "query_id_base"_a,
+           "query_method"_a, "query_params"_a, "width"_a, "ids_ptr"_a, "dists_ptr"_a, "stream"_a = 0)
       .def("refine_counters", &C::refine_counters)
       .def("max_degree", &C::max_degree)
       .def("num_replicas", &C::num_replicas)

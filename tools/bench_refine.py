@@ -5,13 +5,19 @@ against the full-precision rows reach the float32 index's recall, and what does 
 Data: a GloVe-like synthetic set -- a Gaussian mixture with unit-scale elements, scaled by a power of two (2^5) into float8's
 range (bench.py's own points are integers: they round to themselves and would show nothing).  Index: VamanaRangeFilterTreeIndex,
 optimized_postfilter, window fraction 2^-3, k = 10.  Legs: the float32 index; then the Float16 / BFloat16 / Float8 index of the
-rounded points unrefined and refined at refine_k = k, 2k, 4k.  All four indexes are resident and the thirteen legs ALTERNATE within
+rounded points unrefined and refined at refine_k = k, 2k, 4k.  The equal-recall legs ("stop as at k"): the
+compact indexes refined at refine_k = 2k, 4k, 8k with stop_k = k -- the search of the unrefined leg, up to refine_k entries of its
+last frontier re-ranked (wann_batch_search_device_refined_stop) -- and the float32 index at wider beams (`--float32-beams`), so that
+a refined leg can be compared with a float32 leg of no higher recall.  All four indexes are resident and all legs ALTERNATE within
 one job, `--reps` repetitions each.  Per repetition: device ms from HIP events (the
 search's device_ms plus, for a refined leg, the re-rank launch's refine_ms), wall ms of the blocking device-buffer call; per leg
 QPS from the median wall ms and recall@10 against the exact ground truth of the UNROUNDED points (float64, on the GPU).
 A refined leg "wins" only if its recall is no lower than the float32 leg's at the same beam and every one of its repetitions
-beats every float32 repetition (device ms).  Prints one JSON object (profiles/refine_bench.json).
-   python tools/bench_refine.py [--n 1000000] [--d 100] [--nq 10000] [--reps 3] [--setting 80,1] [--metric Euclidian]"""
+beats every float32 repetition (device ms); recalls are compared UNROUNDED (`recall_exact`; `neighbours_found` of
+`neighbours_total` are the integers behind it -- four decimals cannot separate legs a few neighbours apart); `beats` lists every float32 leg (any beam) a refined leg wins against by that same
+rule.  Prints one JSON object (profiles/refine_bench.json; with the equal-recall legs profiles/refine_stop_bench.json).
+   python tools/bench_refine.py [--n 1000000] [--d 100] [--nq 10000] [--reps 3] [--setting 80,1] [--metric Euclidian]
+                                [--float32-beams 100,120,160] [--stop-refine 2,4,8]"""
 import argparse
 import json
 import os
@@ -61,6 +67,13 @@ def ground_truth(torch, Xt, labt, Qt, Wt, k, mips):
     return out, cnt
 
 
+def recall_hits(torch, gt, gcnt, ids):
+    """(true neighbours found, true neighbours there are) over the batch: integers, so that two legs compare exactly"""
+    ids64 = ids.to(torch.int64) & 0xFFFFFFFF
+    hit = ((gt[:, :, None] == ids64[:, None, :]) & (gt[:, :, None] >= 0)).any(2).sum(1)
+    return int(hit.sum().item()), int(gcnt.sum().item())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -71,6 +84,8 @@ def main():
     ap.add_argument("--setting", default="80,1", help="'beam,mult'")
     ap.add_argument("--metric", default="Euclidian", choices=("Euclidian", "Mips"))
     ap.add_argument("--types", default="Float16,BFloat16,Float8")
+    ap.add_argument("--float32-beams", default="100,120,160", help="further float32 legs at these beams ('' = none)")
+    ap.add_argument("--stop-refine", default="2,4,8", help="refined legs at stop_k = k and refine_k = these multiples of k ('' = none)")
     ap.add_argument("--out", default="", help="also write the JSON object to this file")
     args = ap.parse_args()
     reps = max(1, args.reps)
@@ -90,7 +105,15 @@ def main():
     gt, gcnt = ground_truth(torch, torch.from_numpy(X).to(dev), torch.from_numpy(labels).to(dev), Qt, Wt, K, args.metric == "Mips")
     ids_t = torch.empty((nq, K), dtype=torch.int32, device=dev)
     dist_t = torch.empty((nq, K), dtype=torch.float32, device=dev)
-    qp = wa.QueryParams(K, beam, 1.35, 10_000_000, 10_000, mult, 10_000, None, False)
+    qps = {}
+
+    def qp_at(b):
+        if b not in qps:
+            qps[b] = wa.QueryParams(K, b, 1.35, 10_000_000, 10_000, mult, 10_000, None, False)
+        return qps[b]
+
+    wide_beams = [int(x) for x in args.float32_beams.split(",") if x]
+    stop_mults = [int(x) for x in args.stop_refine.split(",") if x]
     rounders = {"Float": lambda x: x, "Float16": lambda x: x.astype(np.float16).astype(np.float32), "BFloat16": wa.bfloat16_round,
                 "Float8": wa.float8_round}
     legs, plans, build_s = {}, [], {}
@@ -101,33 +124,40 @@ def main():
                                                                            build_params=wa.BuildParams(64, 500, 1.0, ""))
         build_s[typ] = round(time.time() - t0, 1)
         indexes[typ] = idx
-        plans.append((typ if typ != "Float" else "Float32", typ, 0))
+        # a plan: (tag, index, refine_k or 0, stop_k or None = the search at k = refine_k, beam)
+        plans.append((typ if typ != "Float" else "Float32", typ, 0, None, beam))
         if typ != "Float":
             idx.set_refine_rows(X)
-            plans += [(f"{typ}+refine{r}", typ, r) for r in (K, 2 * K, 4 * K)]
+            plans += [(f"{typ}+refine{r}", typ, r, None, beam) for r in (K, 2 * K, 4 * K)]
+            plans += [(f"{typ}+refine{m * K}@stop{K}", typ, m * K, K, beam) for m in stop_mults]
+        else:
+            plans += [(f"Float32@beam{b}", typ, 0, None, b) for b in wide_beams]
 
-    def run(typ, refine_k):
+    def run(typ, refine_k, stop_k, b):
         idx = indexes[typ]
         if refine_k:
-            idx.batch_search_device_refined(Qt.data_ptr(), Wt.data_ptr(), nq, 0, "optimized_postfilter", qp, refine_k, ids_t.data_ptr(),
-                                            dist_t.data_ptr(), 0)
+            idx.batch_search_device_refined(Qt.data_ptr(), Wt.data_ptr(), nq, 0, "optimized_postfilter", qp_at(b), refine_k, ids_t.data_ptr(),
+                                            dist_t.data_ptr(), 0, stop_k=stop_k)
         else:
-            idx.batch_search_device(Qt.data_ptr(), Wt.data_ptr(), nq, 0, "optimized_postfilter", qp, ids_t.data_ptr(), dist_t.data_ptr(), 0)
+            idx.batch_search_device(Qt.data_ptr(), Wt.data_ptr(), nq, 0, "optimized_postfilter", qp_at(b), ids_t.data_ptr(), dist_t.data_ptr(), 0)
 
-    for tag, typ, r in plans:  # warm-up, recall, counters
-        run(typ, r)
-        run(typ, r)
+    for tag, typ, r, stop_k, b in plans:  # warm-up, recall, counters
+        run(typ, r, stop_k, b)
+        run(typ, r, stop_k, b)
         torch.cuda.synchronize()
         idx = indexes[typ]
         c = idx.counters()
-        legs[tag] = dict(refine_k=r, recall_at_10=round(bench.recall_of(torch, gt, gcnt, ids_t), 4), hops=c["hops"], dist_cmps=c["dist_cmps"],
+        recall = bench.recall_of(torch, gt, gcnt, ids_t)  # (the mean over queries; recall_exact is compared, recall_at_10 is for reading)
+        hits, slots = recall_hits(torch, gt, gcnt, ids_t)
+        legs[tag] = dict(refine_k=r, stop_k=(stop_k if stop_k else r) if r else 0, beam=b, recall_at_10=round(recall, 4), recall_exact=recall,
+                         neighbours_found=hits, neighbours_total=slots, hops=c["hops"], dist_cmps=c["dist_cmps"],
                          beam_searches=c["beam_searches"], device_bytes=int(idx.device_bytes()), refine_rows_bytes=int(idx.refine_rows_bytes()),
                          build_s=build_s[typ], device_ms=[], search_ms=[], refine_ms=[], wall_ms=[])
     for _ in range(reps):
-        for tag, typ, r in plans:
+        for tag, typ, r, stop_k, b in plans:
             torch.cuda.synchronize()
             t = time.perf_counter()
-            run(typ, r)
+            run(typ, r, stop_k, b)
             wall = (time.perf_counter() - t) * 1e3
             search = indexes[typ].counters()["device_ms"]
             refine = indexes[typ].refine_counters()["refine_ms"] if r else 0.0
@@ -140,10 +170,13 @@ def main():
     for tag, leg in legs.items():
         leg["qps"] = round(nq / float(np.median(leg["wall_ms"])) * 1e3)
         leg["device_ms_median"] = round(float(np.median(leg["device_ms"])), 3)
-        if tag != "Float32":
-            leg["recall_not_lower_than_float32"] = bool(leg["recall_at_10"] >= f32["recall_at_10"])
+        if not tag.startswith("Float32"):
+            leg["recall_not_lower_than_float32"] = bool(leg["recall_exact"] >= f32["recall_exact"])
             leg["every_rep_beats_every_float32_rep"] = bool(max(leg["device_ms"]) < min(f32["device_ms"]))
             leg["wins"] = bool(leg["refine_k"] > 0 and leg["recall_not_lower_than_float32"] and leg["every_rep_beats_every_float32_rep"])
+            # the same rule against every float32 leg: the one at the same beam and the ones at wider beams
+            leg["beats"] = [t for t, o in legs.items() if t.startswith("Float32") and leg["refine_k"] > 0 and
+                            leg["recall_exact"] >= o["recall_exact"] and max(leg["device_ms"]) < min(o["device_ms"])]
     res = dict(tool="tools/bench_refine.py",
                workload=f"VamanaRangeFilterTreeIndex*{args.metric} n={n} d={d} R=64 L=500 cutoff=1000 split=2 optimized_postfilter window 2^{args.fraction} "
                         f"nq={nq} k={K}; Gaussian mixture x {SCALE:g}",
