@@ -7,6 +7,8 @@
 #include <vector>
 
 #include "../../include/wann.h"
+#include "wann_build_device.h"
+#include "wann_gemm_device.h"
 
 static int fails = 0;
 #define CHECK(c)                                                                                           \
@@ -66,6 +68,23 @@ int main(int argc, char **argv) {
   CHECK(wann_build_cache_shard(WANN_KIND_TREE_VAMANA, 0, WANN_DTYPE_F32, pts.data(), n, d, labels.data(), 100, 2, 0.5, &bp, 3, 2, 2) == WANN_ERR_INVALID);
   wann_build_params nocache{8, 16, 1.0, ""};
   CHECK(wann_build_cache_shard(WANN_KIND_TREE_VAMANA, 0, WANN_DTYPE_F32, pts.data(), n, d, labels.data(), 100, 2, 0.5, &nocache, 0, 1, 2) == WANN_ERR_INVALID);
+  // the unit lookups against the kinds of unit written out here (wann_row_types.h): every listed unit is linked in and has all
+  // the launchers its callers ask for, a type without a unit of a kind yields none -- never another type's
+  for (int id = -1; id <= 9; id++) {
+    const bool search = (id >= 0 && id <= 3) || (id >= 5 && id <= 8), dense = search && id != 7, build = id >= 0 && id <= 2;
+    const wann::SearchUnit *su = wann::search_unit_of(id);
+    const wann::GemmUnit *gu = wann::gemm_unit_of(id);
+    const wann::BuildUnit *bu = wann::build_unit_of(id);
+    CHECK((su != nullptr) == search && (gu != nullptr) == dense && (bu != nullptr) == build);
+    if (su) CHECK(su->search_occupancy && su->launch_search && su->launch_brute);
+    if (gu) CHECK(gu->gemm_scores != nullptr);
+    if (bu) CHECK(bu->launch_build_insert && bu->launch_build_reverse && bu->launch_build_final && bu->build_launch_last_error);
+    for (int other = -1; other < id; other++) {
+      if (su && wann::search_unit_of(other)) CHECK(su != wann::search_unit_of(other));
+      if (gu && wann::gemm_unit_of(other)) CHECK(gu != wann::gemm_unit_of(other));
+      if (bu && wann::build_unit_of(other)) CHECK(bu != wann::build_unit_of(other));
+    }
+  }
   if (fails) {
     fprintf(stderr, "abi sanitize test: %d check(s) failed\n", fails);
     return 1;

@@ -1,6 +1,6 @@
 // bf16_sanitize_test.cpp -- the host side of the bfloat16 element type (WANN_DTYPE_BF16) under address + undefined-behaviour
 // sanitizers (make sanitize, third program): the conversions of wann_bf16.h over every bit pattern, the rounding rule's edges,
-// and the layout predicate of wann_device.h, which must treat bfloat16 rows exactly as float16 rows.  CPU only; no HIP.
+// and the layout predicate of wann_row_types.h, which must treat bfloat16 rows exactly as float16 rows.  CPU only; no HIP.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>

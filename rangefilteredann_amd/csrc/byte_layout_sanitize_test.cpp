@@ -1,4 +1,4 @@
-// byte_layout_sanitize_test.cpp -- the layout of the device copy of the one-byte shadow rows (u8_row_position in wann_device.h,
+// byte_layout_sanitize_test.cpp -- the layout of the device copy of the one-byte shadow rows (u8_row_position in wann_row_types.h,
 // interleave_u8_rows in wann_build.cpp) under address + undefined-behaviour sanitizers (make sanitize): the packed rows of a
 // point set, interleaved in buffers of exactly n rows, hold x[r][e] at byte u8_row_position(e) of row r and zero in every other
 // byte, and the permutation's inverse gives the packed rows back.  CPU only; no HIP.

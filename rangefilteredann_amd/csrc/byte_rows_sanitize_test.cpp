@@ -1,6 +1,6 @@
 // byte_rows_sanitize_test.cpp -- the host side of the one-byte shadow rows of a float32 index (wann_set_byte_rows) under address
 // + undefined-behaviour sanitizers (make sanitize, fourth program): the eligibility rule (rows_u8_exact), the packing of a
-// point set into zero-padded byte rows, and the layout predicates of wann_device.h.  CPU only; no HIP.
+// point set into zero-padded byte rows, and the layout predicates of wann_row_types.h.  CPU only; no HIP.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>

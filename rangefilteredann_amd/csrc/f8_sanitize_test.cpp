@@ -1,6 +1,6 @@
 // f8_sanitize_test.cpp -- the host side of the float8 element type (WANN_DTYPE_F8, OCP E4M3) under address + undefined-behaviour
 // sanitizers (a program of make sanitize): the conversions of wann_f8.h over every bit pattern both ways, the rounding rule's
-// edges, the layout predicates of wann_device.h / wann_gemm_device.h for d = 1 .. 10 000, the packing of a float8 index's rows
+// edges, the layout predicates of wann_row_types.h / wann_device.h / wann_gemm_device.h for d = 1 .. 10 000, the packing of a float8 index's rows
 // and the refusal of NaN patterns.  CPU only; no HIP.
 #include <math.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// half_layout_sanitize_test.cpp -- the layout of the device copy of the half shadow rows (h16_row_position in wann_device.h,
+// half_layout_sanitize_test.cpp -- the layout of the device copy of the half shadow rows (h16_row_position in wann_row_types.h,
 // interleave_h16_rows in wann_build.cpp) under address + undefined-behaviour sanitizers (make sanitize): the half rows of a
 // point set, paired in buffers of exactly n rows, hold x[r][e] at half h16_row_position(e) of row r and zero in every other
 // half, and the permutation's inverse gives the natural-order rows back.  CPU only; no HIP.

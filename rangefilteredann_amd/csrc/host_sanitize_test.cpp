@@ -235,6 +235,53 @@ static void check_scan_lds() {
   CHECK(brute_lds_bytes((int64_t)1 << 31, kMaxK) > kLdsPerWorkgroup);
 }
 
+// The row-type table (wann_row_types.h) against the values written out here: every class, the caller's bytes, the device
+// pitch, the staged query's length and the kinds of unit of every id from -1 to 9.  (That the two layout rules are
+// permutations: byte_layout_sanitize_test.cpp and half_layout_sanitize_test.cpp.)
+static void check_row_types() {
+  struct Want {
+    int id, known, caller_bytes, byte_dot, two_byte, quad, upcast, pitch /* 0 the spec's, 1 two-byte, 2 one-byte */, search, dense, build;
+  };
+  const Want want[] = {{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, {0, 1, 4, 0, 0, 0, 0, 0, 1, 1, 1}, {1, 1, 1, 1, 0, 0, 0, 0, 1, 1, 1},
+                       {2, 1, 1, 1, 0, 0, 0, 0, 1, 1, 1},  {3, 1, 2, 0, 1, 0, 1, 1, 1, 1, 0}, {4, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                       {5, 1, 2, 0, 1, 0, 1, 1, 1, 1, 0},  {6, 0, 0, 0, 0, 1, 0, 2, 1, 1, 0}, {7, 0, 0, 0, 1, 0, 0, 1, 1, 0, 0},
+                       {8, 1, 1, 0, 0, 1, 1, 2, 1, 1, 0},  {9, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
+  const int ds[10] = {1, 31, 32, 33, 63, 64, 65, 100, 128, 2048};
+  const int two_byte_words[10] = {16, 16, 16, 32, 32, 32, 48, 64, 64, 1024};  // ((2 d + 63) / 64) * 16
+  const int one_byte_words[10] = {16, 16, 16, 16, 16, 16, 32, 32, 32, 512};   // ((d + 63) / 64) * 16
+  const int f32_words[10] = {16, 32, 32, 48, 64, 64, 80, 112, 128, 2048};     // d rounded up to 16: the float32 row, the widened types' query
+  const int spec = 12345;  // (a stride no rule gives: the types that keep the spec's hand it through)
+  static_assert(kRowsU8Widened == 6 && kRowsF16Paired == 7 && kRowsF8 == 8, "the ids that code names");
+  int seen = 0;
+  for (const Want &w : want) {
+    CHECK(w.id == seen - 1);
+    seen++;
+    CHECK(known_dtype(w.id) == (w.known != 0));
+    CHECK(element_bytes(w.id) == w.caller_bytes);
+    CHECK(byte_rows(w.id) == (w.byte_dot != 0));
+    CHECK(two_byte_rows(w.id) == (w.two_byte != 0));
+    CHECK(one_byte_widened_rows(w.id) == (w.quad != 0));
+    CHECK(widened_rows(w.id) == (w.two_byte != 0 || w.quad != 0));
+    CHECK(upcast_built(w.id) == (w.upcast != 0));
+    CHECK(row_type(w.id).search == (w.search != 0) && row_type(w.id).dense == (w.dense != 0) && row_type(w.id).build == (w.build != 0));
+    CHECK(row_type(w.id).id == (w.search ? w.id : -1));  // (every listed type has a search unit; an unlisted id is no entry at all)
+    for (int i = 0; i < 10; i++) {
+      const int d = ds[i], words = w.pitch == 1 ? two_byte_words[i] : w.pitch == 2 ? one_byte_words[i] : spec;
+      CHECK(row_stride_words(w.id, d, spec) == words);
+      CHECK(query_words(w.id, d, words) == ((w.two_byte || w.quad) ? f32_words[i] : words));
+      IndexView v{};
+      v.dtype = w.id, v.d = d, v.stride = words;
+      CHECK(query_words(v) == query_words(w.id, d, words));
+    }
+  }
+  CHECK(seen == 11);
+  for (int i = 0; i < 10; i++) {  // the build spec's stride: the stored rows -- the float32 upcast where the type is built from it
+    CHECK(spec_stride_words(0, ds[i]) == f32_words[i] && spec_stride_words(3, ds[i]) == f32_words[i] && spec_stride_words(5, ds[i]) == f32_words[i] &&
+          spec_stride_words(8, ds[i]) == f32_words[i]);
+    CHECK(spec_stride_words(1, ds[i]) == one_byte_words[i] && spec_stride_words(2, ds[i]) == one_byte_words[i]);
+  }
+}
+
 int main(int argc, char **argv) {
   const std::string tmp = argc > 1 ? argv[1] : "/tmp/wann_sanitize";
   (void)system(("mkdir -p " + tmp).c_str());
@@ -388,6 +435,7 @@ int main(int argc, char **argv) {
         CHECK(dense_row_class(v) == kRowsNone);
       }
   check_scan_lds();
+  check_row_types();
   check_refdump();
   // the C ABI's argument validation (no device needed for these paths) lives in wann_abi.cpp and is covered by tests/test_abi.py
   if (fails) {

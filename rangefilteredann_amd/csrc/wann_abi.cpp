@@ -1004,32 +1004,35 @@ int wann_rows_fp16_exact(const float *rows, int64_t n, int64_t d) {
   return rows_fp16_exact(rows, n, d, d, 0) ? 1 : 0;
 }
 
-int wann_set_half_rows(wann_index *I, int on) {
+// The four row switches (wann_host_internal.h RowSwitch).  Setting one: under tune_mu -- what snapshot_tuning holds while it
+// copies the index's switches for a call; nothing is allocated or freed, a batch in flight keeps its snapshot -- on the primary
+// and every replica, each bounded by its own "a copy exists"; returns the primary's setting now in force.
+static int set_row_switch(wann_index *I, const RowSwitch &s, int on) {
   if (!I) return -fail(WANN_ERR_INVALID, "null argument");
-  // (tune_mu: what snapshot_tuning holds while it copies the index's switches for a call; nothing is allocated or freed)
   int now;
   {
     std::lock_guard<std::mutex> lk(I->tune_mu);
-    now = I->half_rows_on = on != 0 && I->d_half.p != nullptr;
+    now = I->*s.on = on != 0 && (I->*s.has_copy)();
   }
   for (auto &R : I->replicas) {
     std::lock_guard<std::mutex> lr(R->tune_mu);
-    R->half_rows_on = on != 0 && R->d_half.p != nullptr;
+    (*R).*s.on = on != 0 && ((*R).*s.has_copy)();
   }
   return now;
 }
-
-int wann_half_rows(const wann_index *I) {
+static int row_switch(const wann_index *I, const RowSwitch &s) {
   if (!I) return 0;
-  wann_index *M = const_cast<wann_index *>(I);
-  std::lock_guard<std::mutex> lk(M->tune_mu);
-  return I->half_rows_on ? 1 : 0;
+  std::lock_guard<std::mutex> lk(const_cast<wann_index *>(I)->tune_mu);
+  return I->*s.on ? 1 : 0;
 }
+static int last_row_switch(const wann_index *I, const RowSwitch &s) { return I ? (I->*s.last).load() : 0; }
 
+int wann_set_half_rows(wann_index *I, int on) { return set_row_switch(I, kHalfRowsSwitch, on); }
+int wann_half_rows(const wann_index *I) { return row_switch(I, kHalfRowsSwitch); }
 int64_t wann_half_rows_bytes(const wann_index *I) { return I ? (int64_t)I->d_half.bytes() : -1; }
 
 int64_t wann_half_row_position(int64_t element) { return element < 0 ? -1 : h16_row_position(element); }
-int wann_last_half_rows(const wann_index *I) { return I ? I->last_half_rows.load() : 0; }
+int wann_last_half_rows(const wann_index *I) { return last_row_switch(I, kHalfRowsSwitch); }
 
 int wann_rows_u8_exact(const float *rows, int64_t n, int64_t d) {
   if (n <= 0 || d <= 0) return 1;  // (no value fails the test)
@@ -1039,79 +1042,19 @@ int wann_rows_u8_exact(const float *rows, int64_t n, int64_t d) {
 
 int64_t wann_byte_row_position(int64_t element) { return element < 0 ? -1 : u8_row_position(element); }
 
-int wann_set_byte_rows(wann_index *I, int on) {
-  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
-  // (tune_mu, as wann_set_half_rows: nothing is allocated or freed, a batch in flight keeps its snapshot)
-  int now;
-  {
-    std::lock_guard<std::mutex> lk(I->tune_mu);
-    now = I->byte_rows_on = on != 0 && I->d_bytes.p != nullptr;
-  }
-  for (auto &R : I->replicas) {
-    std::lock_guard<std::mutex> lr(R->tune_mu);
-    R->byte_rows_on = on != 0 && R->d_bytes.p != nullptr;
-  }
-  return now;
-}
-
-int wann_byte_rows(const wann_index *I) {
-  if (!I) return 0;
-  wann_index *M = const_cast<wann_index *>(I);
-  std::lock_guard<std::mutex> lk(M->tune_mu);
-  return I->byte_rows_on ? 1 : 0;
-}
-
+int wann_set_byte_rows(wann_index *I, int on) { return set_row_switch(I, kByteRowsSwitch, on); }
+int wann_byte_rows(const wann_index *I) { return row_switch(I, kByteRowsSwitch); }
 int64_t wann_byte_rows_bytes(const wann_index *I) { return I ? (int64_t)I->d_bytes.bytes() : -1; }
-int wann_last_byte_rows(const wann_index *I) { return I ? I->last_byte_rows.load() : 0; }
+int wann_last_byte_rows(const wann_index *I) { return last_row_switch(I, kByteRowsSwitch); }
 
-int wann_set_scan_rows(wann_index *I, int on) {
-  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
-  // (tune_mu, as wann_set_half_rows: nothing is allocated or freed, a batch in flight keeps its snapshot)
-  int now;
-  {
-    std::lock_guard<std::mutex> lk(I->tune_mu);
-    now = I->scan_rows_on = on != 0 && (I->d_half.p != nullptr || I->d_bytes.p != nullptr);
-  }
-  for (auto &R : I->replicas) {
-    std::lock_guard<std::mutex> lr(R->tune_mu);
-    R->scan_rows_on = on != 0 && (R->d_half.p != nullptr || R->d_bytes.p != nullptr);
-  }
-  return now;
-}
+int wann_set_scan_rows(wann_index *I, int on) { return set_row_switch(I, kScanRowsSwitch, on); }
+int wann_scan_rows(const wann_index *I) { return row_switch(I, kScanRowsSwitch); }
+int wann_last_scan_rows(const wann_index *I) { return last_row_switch(I, kScanRowsSwitch); }
 
-int wann_scan_rows(const wann_index *I) {
-  if (!I) return 0;
-  wann_index *M = const_cast<wann_index *>(I);
-  std::lock_guard<std::mutex> lk(M->tune_mu);
-  return I->scan_rows_on ? 1 : 0;
-}
-
-int wann_last_scan_rows(const wann_index *I) { return I ? I->last_scan_rows.load() : 0; }
-
-int wann_set_dense_rows(wann_index *I, int on) {
-  if (!I) return -fail(WANN_ERR_INVALID, "null argument");
-  // (tune_mu, as wann_set_half_rows: nothing is allocated or freed, a batch in flight keeps its snapshot)
-  int now;
-  {
-    std::lock_guard<std::mutex> lk(I->tune_mu);
-    now = I->dense_rows_on = on != 0 && I->has_dense_copy();
-  }
-  for (auto &R : I->replicas) {
-    std::lock_guard<std::mutex> lr(R->tune_mu);
-    R->dense_rows_on = on != 0 && R->has_dense_copy();
-  }
-  return now;
-}
-
-int wann_dense_rows(const wann_index *I) {
-  if (!I) return 0;
-  wann_index *M = const_cast<wann_index *>(I);
-  std::lock_guard<std::mutex> lk(M->tune_mu);
-  return I->dense_rows_on ? 1 : 0;
-}
-
+int wann_set_dense_rows(wann_index *I, int on) { return set_row_switch(I, kDenseRowsSwitch, on); }
+int wann_dense_rows(const wann_index *I) { return row_switch(I, kDenseRowsSwitch); }
 int64_t wann_dense_rows_bytes(const wann_index *I) { return I ? I->dense_copy_bytes() : -1; }
-int wann_last_dense_rows(const wann_index *I) { return I ? I->last_dense_rows.load() : 0; }
+int wann_last_dense_rows(const wann_index *I) { return last_row_switch(I, kDenseRowsSwitch); }
 int wann_num_replicas(const wann_index *I) { return I ? 1 + (int)I->replicas.size() : -1; }
 
 int wann_build_cache_shard(int kind, int metric, int dtype, const void *points, int64_t n, int64_t d,

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "wann_half.h"
+#include "wann_row_types.h"
 
 namespace wann {
 
@@ -27,8 +28,8 @@ inline uint16_t float_to_bf16(float f) {
   return sign | (uint16_t)(r >> 16);
 }
 
-// two-byte float element types (wann.h WANN_DTYPE_F16 = 3, WANN_DTYPE_BF16 = 5) share the row layout; these pick the conversion
-inline float two_byte_to_float(int dtype, uint16_t v) { return dtype == 5 ? bf16_to_float(v) : half_to_float(v); }
-inline uint16_t float_to_two_byte(int dtype, float f) { return dtype == 5 ? float_to_bf16(f) : float_to_half(f); }
+// the two-byte float element types (float16, bfloat16) share the row layout; these pick the conversion
+inline float two_byte_to_float(int dtype, uint16_t v) { return dtype == kRowsBF16 ? bf16_to_float(v) : half_to_float(v); }
+inline uint16_t float_to_two_byte(int dtype, float f) { return dtype == kRowsBF16 ? float_to_bf16(f) : float_to_half(f); }
 
 }  // namespace wann

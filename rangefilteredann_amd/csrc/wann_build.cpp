@@ -210,7 +210,7 @@ void pack_f8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64
   });
 }
 
-// The packed rows in the layout the device copy has (u8_row_position, wann_device.h), in place: a permutation of the bytes of
+// The packed rows in the layout the device copy has (u8_row_position, wann_row_types.h), in place: a permutation of the bytes of
 // every aligned group of 32, padding included -- a row is `words` 32-bit words, a whole number of groups.
 void interleave_u8_rows(float *rows, int64_t n, int64_t words, int threads) {
   if (words <= 0 || words % 8 != 0) throw std::runtime_error("interleave_u8_rows: a row is a whole number of 32-byte groups");
@@ -224,7 +224,7 @@ void interleave_u8_rows(float *rows, int64_t n, int64_t words, int threads) {
   });
 }
 
-// Half rows in natural order into the layout the half shadow rows' device copy has (h16_row_position, wann_device.h), in
+// Half rows in natural order into the layout the half shadow rows' device copy has (h16_row_position, wann_row_types.h), in
 // place: a permutation of the halves of every aligned group of 16, padding included -- a row is `words` 32-bit words, a whole
 // number of groups.
 void interleave_h16_rows(float *rows, int64_t n, int64_t words, int threads) {
@@ -293,8 +293,8 @@ static float byte_distance(int metric, const T *p, const T *q, int d) {
 // metric: bit 0 = inner product; bits 4-5 = element type of the rows (0 float32, 1 uint8, 2 int8)
 float host_distance(int metric, const float *p, const float *q, int d) {
   const int dtype = (metric >> 4) & 3;
-  if (dtype == 1) return byte_distance<uint8_t>(metric & 1, (const uint8_t *)p, (const uint8_t *)q, d);
-  if (dtype == 2) return byte_distance<int8_t>(metric & 1, (const int8_t *)p, (const int8_t *)q, d);
+  if (dtype == kRowsU8) return byte_distance<uint8_t>(metric & 1, (const uint8_t *)p, (const uint8_t *)q, d);
+  if (dtype == kRowsI8) return byte_distance<int8_t>(metric & 1, (const int8_t *)p, (const int8_t *)q, d);
   return (metric & 1) ? mips_ref_order(p, q, d) : l2_ref_order(p, q, d);
 }
 
@@ -755,9 +755,9 @@ void build_host_index(HostIndex &H, const void *points, const float *labels, int
   if (s.threads <= 0) s.threads = default_threads();
   // bytes per element of the caller's rows and of the stored rows (float16 / bfloat16 / float8 points are stored as their exact
   // float32 upcast: the graphs of such an index are those of the float32 index on the upcast points, byte for byte)
-  const bool half = s.dtype == 3 || s.dtype == 5, f8 = s.dtype == kRowsF8;
-  const int64_t esz = s.dtype == 0 ? 4 : half ? 2 : 1, ssz = (half || f8) ? 4 : esz;
-  s.stride = ((s.d * ssz + 63) / 64) * 16;      // 64-byte rows (point_range.h:39-44), zero padded; in 32-bit words
+  const bool half = element_bytes(s.dtype) == 2, f8 = s.dtype == kRowsF8;
+  const int64_t esz = element_bytes(s.dtype);
+  s.stride = spec_stride_words(s.dtype, s.d);  // 64-byte rows (point_range.h:39-44), zero padded; in 32-bit words
   H.sorted = (s.kind == 2 || s.kind == 3 || s.kind == 4);
   H.vamana_leaves = (s.kind == 1 || s.kind == 3 || s.kind == 4);
   const int64_t n = s.n;

@@ -66,15 +66,15 @@ bool rows_fp16_exact(const float *rows, int64_t n, int64_t d, int64_t stride, in
 // index needs to be searched from one-byte rows (wann.h wann_rows_u8_exact).  threads <= 0: default_threads().
 bool rows_u8_exact(const float *rows, int64_t n, int64_t d, int64_t stride, int threads);
 // such a point set as one-byte rows: the d values of row r as bytes, natural order, at word r * out_words of the ZEROED buffer
-// `out` (n * out_words 32-bit words; out_words * 4 >= d -- u8_widened_stride_words(d) in wann_device.h)
+// `out` (n * out_words 32-bit words; out_words * 4 >= d -- u8_widened_stride_words(d) in wann_row_types.h)
 void pack_u8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64_t out_words, int threads, float *out);
 // the rows of a float8 index (`rows`: the exact float32 upcast of its E4M3 patterns) as those patterns again, the same way
 void pack_f8_rows(const float *rows, int64_t n, int64_t d, int64_t stride, int64_t out_words, int threads, float *out);
 // packed rows (natural order) into the device copy's layout, in place: the byte at position e of a row moves to position
-// u8_row_position(e) (wann_device.h: a permutation inside every aligned 32 bytes).  `words` 32-bit words per row, a multiple of 8.
+// u8_row_position(e) (wann_row_types.h: a permutation inside every aligned 32 bytes).  `words` 32-bit words per row, a multiple of 8.
 void interleave_u8_rows(float *rows, int64_t n, int64_t words, int threads);
 // half rows (natural order, zero padded) into the half shadow rows' device layout, in place: the half at position e of a row
-// moves to position h16_row_position(e) (wann_device.h: a permutation inside every aligned 16 halves).  `words` 32-bit words
+// moves to position h16_row_position(e) (wann_row_types.h: a permutation inside every aligned 16 halves).  `words` 32-bit words
 // per row, a multiple of 8.
 void interleave_h16_rows(float *rows, int64_t n, int64_t words, int threads);
 

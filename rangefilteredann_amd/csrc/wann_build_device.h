@@ -37,6 +37,16 @@ struct BuildArgs {
   int32_t ref_ties;                           // order exactly equidistant candidates as the reference's std::sort does (wann_stdsort.h)
 };
 
+// One unit's build launchers (the end of wann_build_kernels_body.inc, compiled once per row type that has a build unit): the
+// entry points of the same names below look the unit up by ix.dtype (build_unit_of: null for a type without one, an error there)
+struct BuildUnit {
+  int (*launch_build_insert)(const BuildArgs &a, int blocks, int table_lds, void *stream);
+  int (*launch_build_reverse)(const BuildArgs &a, int blocks, void *stream);
+  int (*launch_build_final)(const BuildArgs &a, int blocks, void *stream);
+  const char *(*build_launch_last_error)();
+};
+WANN_UNIT_LOOKUP(build, BuildUnit, build_unit, build_unit_of)
+
 int launch_build_insert(const BuildArgs &a, int blocks, int table_lds, void *stream);
 int launch_build_publish(const BuildArgs &a, void *stream);
 size_t build_sort_temp_bytes(int64_t npairs);

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "wann_build_device.h"
 #include "wann_stdsort.h"
@@ -26,14 +27,7 @@
 namespace wann {
 
 // One translation unit per element type of the point set (WANN_DT, see wann_kernels_body.inc): kernels and launchers in
-// a per-type namespace, the dispatchers on IndexView::dtype with the float32 unit.
-#if WANN_DT == 0
-#define WANN_DT_NS dt_f32
-#elif WANN_DT == 1
-#define WANN_DT_NS dt_u8
-#else
-#define WANN_DT_NS dt_i8
-#endif
+// a per-type namespace (WANN_DT_NS, wann_row_types.h), the entry points that pick a unit by IndexView::dtype with the float32 unit.
 namespace WANN_DT_NS {
 
 constexpr int kBuildWaves = 2;  // waves per workgroup of the build kernels
@@ -342,7 +336,7 @@ __global__ __launch_bounds__(64 * kBuildWaves) void k_build_final(BuildArgs A) {
 // launchers
 // ------------------------------------------------------------------------------------------------
 static thread_local const char *g_berr = "";
-const char *build_launch_last_error() { return g_berr; }
+static const char *build_launch_last_error() { return g_berr; }
 static int bcheck(hipError_t e) {
   if (e != hipSuccess) {
     g_berr = hipGetErrorString(e);
@@ -368,7 +362,7 @@ static int set_lds(K kern, size_t lds) {
   return 0;
 }
 
-int launch_build_insert(const BuildArgs &a, int blocks, int table_lds, void *stream) {
+static int launch_build_insert(const BuildArgs &a, int blocks, int table_lds, void *stream) {
   if (blocks <= 0 || a.nitems <= 0) return 0;
   size_t lds = (size_t)build_lds_bytes_per_wave(a.ix.stride, a.L, a.bits, table_lds, a.vis_cap, a.R) * kBuildWaves;
   dim3 grid(blocks), block(64 * kBuildWaves);
@@ -415,7 +409,7 @@ int launch_build_sort_groups(const BuildArgs &a, void *temp, size_t temp_bytes, 
   return bcheck(hipGetLastError());
 }
 
-int launch_build_reverse(const BuildArgs &a, int blocks, void *stream) {
+static int launch_build_reverse(const BuildArgs &a, int blocks, void *stream) {
   if (blocks <= 0) return 0;
   size_t lds = (size_t)build_lds_bytes_per_wave(a.ix.stride, 0, 0, 0, a.vis_cap, a.R) * kBuildWaves;
   dim3 grid(blocks), block(64 * kBuildWaves);
@@ -432,7 +426,7 @@ int launch_build_reverse(const BuildArgs &a, int blocks, void *stream) {
   return bcheck(hipGetLastError());
 }
 
-int launch_build_final(const BuildArgs &a, int blocks, void *stream) {
+static int launch_build_final(const BuildArgs &a, int blocks, void *stream) {
   if (blocks <= 0 || a.nitems <= 0) return 0;
   size_t lds = (size_t)build_lds_bytes_per_wave(a.ix.stride, 0, 0, 0, 0, 0) * kBuildWaves;
   dim3 grid(blocks), block(64 * kBuildWaves);
@@ -441,49 +435,39 @@ int launch_build_final(const BuildArgs &a, int blocks, void *stream) {
   return bcheck(hipGetLastError());
 }
 
+// (reached through a function: host code only, and no order of initialisation to depend on)
+const BuildUnit &build_unit() {
+  static constexpr BuildUnit unit = {launch_build_insert, launch_build_reverse, launch_build_final, build_launch_last_error};
+  return unit;
+}
+
 }  // namespace WANN_DT_NS
 
 #if WANN_DT == 0
-namespace dt_u8 {
-const char *build_launch_last_error();
-int launch_build_insert(const BuildArgs &a, int blocks, int table_lds, void *stream);
-int launch_build_reverse(const BuildArgs &a, int blocks, void *stream);
-int launch_build_final(const BuildArgs &a, int blocks, void *stream);
+// the entry points: the view's row type picks the unit (a type without a build unit is an error, never another type's
+// kernels); the type-independent launchers are the float32 unit's.  A failed launch leaves its unit's error text here.
+static thread_local const char *g_build_err = "";
+const char *build_launch_last_error() { return g_build_err; }
+static const BuildUnit *unit_or_error(const IndexView &ix) {
+  const BuildUnit *u = build_unit_of(ix.dtype);
+  if (!u) {
+    static thread_local char text[48];
+    snprintf(text, sizeof text, "row type %d has no build unit", ix.dtype);
+    g_build_err = text;
+  }
+  return u;
 }
-namespace dt_i8 {
-const char *build_launch_last_error();
-int launch_build_insert(const BuildArgs &a, int blocks, int table_lds, void *stream);
-int launch_build_reverse(const BuildArgs &a, int blocks, void *stream);
-int launch_build_final(const BuildArgs &a, int blocks, void *stream);
+static int record(int rc, const BuildUnit &u = dt_f32::build_unit()) {
+  if (rc) g_build_err = u.build_launch_last_error();
+  return rc;
 }
-// dispatch on the element type (the type-independent launchers are the float32 unit's)
-static thread_local int g_last_dt = 0;
-const char *build_launch_last_error() {
-  return g_last_dt == 1 ? dt_u8::build_launch_last_error() : g_last_dt == 2 ? dt_i8::build_launch_last_error() : dt_f32::build_launch_last_error();
-}
-int launch_build_insert(const BuildArgs &a, int blocks, int table_lds, void *stream) {
-  g_last_dt = a.ix.dtype;
-  return a.ix.dtype == 1 ? dt_u8::launch_build_insert(a, blocks, table_lds, stream) : a.ix.dtype == 2 ? dt_i8::launch_build_insert(a, blocks, table_lds, stream)
-                                                                                                : dt_f32::launch_build_insert(a, blocks, table_lds, stream);
-}
-int launch_build_reverse(const BuildArgs &a, int blocks, void *stream) {
-  g_last_dt = a.ix.dtype;
-  return a.ix.dtype == 1 ? dt_u8::launch_build_reverse(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_build_reverse(a, blocks, stream)
-                                                                                          : dt_f32::launch_build_reverse(a, blocks, stream);
-}
-int launch_build_final(const BuildArgs &a, int blocks, void *stream) {
-  g_last_dt = a.ix.dtype;
-  return a.ix.dtype == 1 ? dt_u8::launch_build_final(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_build_final(a, blocks, stream)
-                                                                                        : dt_f32::launch_build_final(a, blocks, stream);
-}
-int launch_build_publish(const BuildArgs &a, void *stream) {
-  g_last_dt = 0;
-  return dt_f32::launch_build_publish(a, stream);
-}
+int launch_build_insert(const BuildArgs &a, int blocks, int table_lds, void *stream) { const BuildUnit *u = unit_or_error(a.ix); return u ? record(u->launch_build_insert(a, blocks, table_lds, stream), *u) : 1; }
+int launch_build_reverse(const BuildArgs &a, int blocks, void *stream) { const BuildUnit *u = unit_or_error(a.ix); return u ? record(u->launch_build_reverse(a, blocks, stream), *u) : 1; }
+int launch_build_final(const BuildArgs &a, int blocks, void *stream) { const BuildUnit *u = unit_or_error(a.ix); return u ? record(u->launch_build_final(a, blocks, stream), *u) : 1; }
+int launch_build_publish(const BuildArgs &a, void *stream) { return record(dt_f32::launch_build_publish(a, stream)); }
 size_t build_sort_temp_bytes(int64_t npairs) { return dt_f32::build_sort_temp_bytes(npairs); }
 int launch_build_sort_groups(const BuildArgs &a, void *temp, size_t temp_bytes, void *stream) {
-  g_last_dt = 0;
-  return dt_f32::launch_build_sort_groups(a, temp, temp_bytes, stream);
+  return record(dt_f32::launch_build_sort_groups(a, temp, temp_bytes, stream));
 }
 int build_lds_bytes_per_wave(int stride, int L, int bits, int table_lds, int vis_cap, int R) {
   return dt_f32::build_lds_bytes_per_wave(stride, L, bits, table_lds, vis_cap, R);

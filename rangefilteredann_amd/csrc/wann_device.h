@@ -14,6 +14,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "wann_row_types.h"
+
 namespace wann {
 
 struct PartDesc {
@@ -42,61 +44,12 @@ struct IndexView {
   const int64_t *sup_shift;
   int64_t n;
   int32_t d, stride, rs, maxdeg, metric, kind, nlevels, cutoff, split, vamana_leaves;
-  int32_t dtype;  // element type of `points` (wann.h WANN_DTYPE_*): float32 rows, uint8 / int8 rows of d bytes padded to a
-                  // multiple of 64, or float16 / bfloat16 rows of d two-byte elements padded to a multiple of 32 -- `stride` counts 32-bit words in every
-                  // case and `points` is addressed in words.  6 (kRowsU8Widened, below) only in the view of a float32 index's one-byte shadow rows,
-                  // 7 (kRowsF16Paired) only in the view of its half shadow rows.  8 (kRowsF8): float8 rows of d bytes padded to a multiple
-                  // of 64, in the one-byte shadow rows' interleaved order
+  int32_t dtype;  // the row type of `points` (wann_row_types.h: an element type of wann.h, or one of the two internal view types of a
+                  // float32 index's shadow rows) -- `stride` counts 32-bit words in every case and `points` is addressed in words
 };
 
-// two-byte float rows: float16 (3) and bfloat16 (5) share the row pitch and layout rules -- d elements in natural order, zero
-// padded to a multiple of 32 (64 B) -- and the staged query's length (WANN_HALF_ROWS in wann_wave.h is the device side); the
-// half shadow rows of a float32 index (7, below) share all of it but the order of the elements inside a group of 16
-// Half shadow rows of a float32 index (dtype 7: an INTERNAL view type like 6 below, never a WANN_DTYPE_* the C ABI accepts): the
-// float16 rows' values, pitch and padding with the halves of every aligned group of 16 elements PAIRED (h16_row_position); the
-// kernels of wann_kernels_h16.hip read them, and every predicate treats such a view as a float16 one.
-constexpr int kRowsF16Paired = 7;
-constexpr bool two_byte_rows(int dtype) { return dtype == 3 || dtype == 5 || dtype == kRowsF16Paired; }
-constexpr int64_t two_byte_stride_words(int64_t d) { return ((d * 2 + 63) / 64) * 16; }
-// THE LAYOUT of the half shadow rows' device copy (wann_index::d_half, search_view), stated once: a row keeps its pitch, and
-// inside every aligned group of 16 elements the halves are permuted -- element e of a row sits at half h16_row_position(e) of
-// it.  Lane h of a lane pair owns the blocks 8 b + 4 h (wann_wave.h), and its two blocks b = 2 c and 2 c + 1 are the 16
-// contiguous bytes at byte 32 c + 16 h of the row: one 16-byte load per lane brings two blocks (a PAIR).  Rows stay padded with
-// zeros to 64 bytes, so every pair exists and is 16-byte aligned.  interleave_h16_rows (wann_build.h) turns natural-order rows
-// into this order before the upload; wann_half_row_position (wann.h) is this function.  Native float16 / bfloat16 indexes keep
-// the natural order: the dense path, the build kernels and finalisation read those rows.
-constexpr int64_t h16_row_position(int64_t e) { return 16 * (e >> 4) + 8 * ((e >> 2) & 1) + 4 * ((e >> 3) & 1) + (e & 3); }
-
-// One-byte shadow rows of a float32 index (dtype 6: an INTERNAL view type, never a WANN_DTYPE_* the C ABI accepts): every value
-// is an integer 0 .. 255 stored as a uint8 -- d bytes, zero padded to a multiple of 64 -- and the beam-search
-// kernels of wann_kernels_w8.hip widen each byte exactly to the float32 it stands for.  k_search is launched on such a view, and k_brute under wann_set_scan_rows;
-// under wann_set_dense_rows the dense path's k_gemm_scores too (wann_gemm_kernels_w8.hip: each byte widened to the bfloat16 it also is).
-constexpr int kRowsU8Widened = 6;
-constexpr int64_t u8_widened_stride_words(int64_t d) { return ((d + 63) / 64) * 16; }
-// THE LAYOUT of the device copy (wann_index::d_bytes, byte_view), stated once: a row keeps its pitch, and inside every aligned
-// group of 32 elements the bytes are permuted -- element e of a row sits at byte u8_row_position(e) of it.  A row BLOCK is four
-// consecutive elements (wann_wave.h); lane h of a lane pair owns the blocks 8 b + 4 h, and for b = 4 c .. 4 c + 3 those four
-// blocks are the 16 contiguous bytes at 32 c + 16 h: one 16-byte load per lane brings four blocks (a QUAD), a lane pair covers 32
-// contiguous bytes per load instruction.  The padded row is a whole number of quads and its padding is zero, so a whole quad
-// may always be loaded.  pack_u8_rows (wann_build.h) writes the natural order, interleave_u8_rows turns it into this one
-// before the upload; wann_byte_row_position (wann.h) is this function.
-constexpr int64_t u8_row_position(int64_t e) { return 32 * (e >> 5) + 16 * ((e >> 2) & 1) + 4 * ((e >> 3) & 3) + (e & 3); }
-// rows narrower than float32 that are scored as their exact float32 upcast against an fp32 query: the two-byte float rows and
-// the one-byte shadow rows (WANN_WIDENED_ROWS in wann_wave.h is the device side)
-// Float8 rows (wann.h WANN_DTYPE_F8 = 8, OCP E4M3 bit patterns): an element type of the C ABI whose device rows have the one-byte
-// shadow rows' pitch (u8_widened_stride_words) and LAYOUT (u8_row_position inside every aligned group of 32 elements); the
-// kernels of wann_kernels_f8.hip / wann_gemm_kernels_f8.hip widen each byte exactly to the float32 (bfloat16) it stands for.
-// Host arrays and cache inputs keep the natural order: interleave_u8_rows runs before the upload.
-constexpr int kRowsF8 = 8;
-// one-byte rows in the interleaved layout, fetched 16 bytes at a time (WANN_QUAD_ROWS in wann_wave.h is the device side)
-constexpr bool one_byte_widened_rows(int dtype) { return dtype == kRowsU8Widened || dtype == kRowsF8; }
-constexpr bool widened_rows(int dtype) { return two_byte_rows(dtype) || one_byte_widened_rows(dtype); }
-// element types whose host rows (HostIndex::pts) are the exact float32 upcast of the caller's: both builders build from those
-constexpr bool upcast_built(int dtype) { return dtype == 3 || dtype == 5 || dtype == kRowsF8; }
-
-// 32-bit words of a staged query (fp32, zero padded; the LDS the kernels reserve for it): `stride` for float32 / byte rows, the
-// float32 row length (d rounded up to 16) for widened rows -- the same LDS layout as the float32 index (host side of qv_words)
-inline int query_words(const IndexView &v) { return widened_rows(v.dtype) ? ((v.d + 15) & ~15) : v.stride; }
+// (what a row type is -- its classes, pitch, layout and units: wann_row_types.h, the one place)
+inline int query_words(const IndexView &v) { return query_words(v.dtype, v.d, v.stride); }
 
 enum { T_EMPTY = 0, T_GRAPH = 1, T_BRUTE = 2, T_BRUTE_GATHER = 3, T_PARENT = 4 };
 // Task::flags: 1 = heavy (schedule first), 2 = final_beam_multiply forced to 1, 4 = speculative sub-task, 8 = mid priority
@@ -353,6 +306,14 @@ struct LaunchCfg {
   int waves_per_block;  // 0 = kWavesPerBlock
   int big;              // the companion kernel for levels beyond cap_inkernel (k_search<METRIC, true>)
 };
+// One unit's search and scan launchers (the end of wann_kernels_body.inc, compiled once per row type): the entry points of the
+// same names below look the unit up by ix.dtype (search_unit_of: null for a type without a search unit, an error there)
+struct SearchUnit {
+  int (*search_occupancy)(const SearchArgs &a, const LaunchCfg &cfg);
+  int (*launch_search)(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
+  int (*launch_brute)(const BruteArgs &a, int blocks, void *stream);
+};
+WANN_UNIT_LOOKUP(search, SearchUnit, search_unit, search_unit_of)
 int launch_route(const RouteArgs &a, void *stream);
 int launch_order_heavy(const OrderArgs &a, void *stream);
 // a one-thread kernel that ends when *resident >= need (or after ~0.25 ms): orders the ordinary launch behind the companion's start

@@ -129,15 +129,15 @@ struct CoverArgs {
 // Anything longer, and a stride that is not a multiple of 16 words, is kRowsNone: the exact scan.
 enum DenseRows { kRowsNone, kRowsNarrow, kRowsWide, kRowsLong };
 inline DenseRows dense_row_class(const IndexView &ix) {
-  const bool bytes = ix.dtype == 1 || ix.dtype == 2;
+  const bool bytes = byte_rows(ix.dtype);
   const int words = query_words(ix);
   if ((ix.stride & 15) || words < 16 || words > (bytes ? kGemmMaxBytes / 4 : kGemmMaxFloats)) return kRowsNone;
   if (words <= 128) return kRowsNarrow;
-  if (ix.dtype == 5 || ix.dtype == kRowsF8) return kRowsNone;  // bfloat16 / float8 rows beyond 128 elements: the exact scan, with or without WANN_DENSE_LONG_ROWS
+  if (ix.dtype == kRowsBF16 || ix.dtype == kRowsF8) return kRowsNone;  // bfloat16 / float8 rows beyond 128 elements: the exact scan, with or without WANN_DENSE_LONG_ROWS
   // (the view of a float32 index's one-byte shadow rows, wann_set_dense_rows: its score kernel is the bfloat16 one with a byte
   // fetch and covers the narrow class alone -- longer rows are scored from the float32 rows)
   if (ix.dtype == kRowsU8Widened) return kRowsNone;
-  return ix.dtype == 0 && words <= 512 ? kRowsWide : kRowsLong;
+  return ix.dtype == kRowsF32 && words <= 512 ? kRowsWide : kRowsLong;
 }
 
 // One unit's launchers (wann_gemm_launch.inc, compiled once per element type): a null return = launched, otherwise the error
@@ -150,6 +150,8 @@ struct GemmUnit {
   const char *(*select_rerank)(const GemmArgs &a, Counters *ctr, void *stream);
   const char *(*rerank_cover)(const CoverArgs &c, void *stream);
 };
+
+WANN_UNIT_LOOKUP(dense, GemmUnit, gemm_unit, gemm_unit_of)  // (null: the row type has no dense unit)
 
 // entry points (the float32 unit): each looks up ix.dtype's unit, calls it and records the error; 0 = launched
 int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);  // float32 / float16 / bfloat16 rows

@@ -48,6 +48,7 @@
 //                    k_rerank_cover and the rescue read the float8 rows.  Rows of up to 128 elements; longer ones take the scan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include <algorithm>
 
@@ -62,20 +63,7 @@ namespace wann {
 #define WANN_GNS_BEGIN
 #define WANN_GNS_END
 #else
-#if WANN_DT == 1
-#define WANN_DT_NS_G dt_u8
-#elif WANN_DT == 2
-#define WANN_DT_NS_G dt_i8
-#elif WANN_DT == 3
-#define WANN_DT_NS_G dt_f16
-#elif WANN_DT == 5
-#define WANN_DT_NS_G dt_bf16
-#elif WANN_DT == 8
-#define WANN_DT_NS_G dt_f8
-#else
-#define WANN_DT_NS_G dt_w8  // (the one-byte shadow rows of a float32 index: the unit holds a score kernel and nothing else)
-#endif
-#define WANN_GNS_BEGIN namespace WANN_DT_NS_G {
+#define WANN_GNS_BEGIN namespace WANN_DT_NS {  // (wann_row_types.h: the unit's namespace)
 #define WANN_GNS_END }
 #endif
 
@@ -539,7 +527,7 @@ __device__ __forceinline__ void insert4_chain(float &m1, float &m2, float &m3, f
 // Bfloat16 rows (WANN_DT = 5) have a kernel body of their own: one staged row per point, two products.
 #if WANN_DT == 5
 #include "wann_gemm_kernels_bf16.inc"
-#elif WANN_DT == 6 || WANN_DT == 8  // (float8 rows: the same kernel, another widening)
+#elif WANN_QUAD_ROWS  // (float8 rows: the same kernel, another widening)
 #include "wann_gemm_kernels_w8.inc"
 #else
 WANN_GNS_BEGIN

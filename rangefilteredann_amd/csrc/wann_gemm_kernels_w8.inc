@@ -8,7 +8,7 @@
 //     values, because the product it runs first, bl x a_hi, adds only zeros on such a row;
 //   * a point arrives as BYTES, a quarter of the float32 row, from the copy the beam searches read (wann_index::d_bytes) or a
 //     PrefilterIndex's own (wann_index::d_dense).  The copy is interleaved inside aligned groups of 32 elements (u8_row_position,
-//     wann_device.h): the 16-byte chunk h of group g holds the four 4-element blocks 2 s + h, s = 0 .. 3, of that group.  Two
+//     wann_row_types.h): the 16-byte chunk h of group g holds the four 4-element blocks 2 s + h, s = 0 .. 3, of that group.  Two
 //     threads serve a point row, thread h loading chunk h of every group: one 16-byte load a thread and group, four at
 //     STRIDE = 128, one at STRIDE <= 32; a lane pair covers 32 contiguous bytes per load instruction.  The row pitch is a
 //     multiple of 64 bytes and the padding is zero, so whole groups can always be loaded;

@@ -1,7 +1,7 @@
 // wann_gemm_launch.inc -- the launchers of the dense prefilter path, included at the end of wann_gemm_kernels_body.inc: one text,
 // compiled in every unit (float32, uint8, int8, float16, bfloat16, one-byte shadow rows, float8) against that unit's kernels.  A unit picks its kernels by the row class
 // (dense_row_class, wann_gemm_device.h: the only place that knows a row length) and exposes its launchers as one constant table,
-// gemm_unit(); the float32 unit also holds the entry points of wann_gemm_device.h, which look the table up by ix.dtype (unit_of).
+// gemm_unit(); the float32 unit also holds the entry points of wann_gemm_device.h, which look the table up by ix.dtype (gemm_unit_of).
 // Every launcher returns null when it has launched, otherwise the error text.
 
 static const char *gerr_of(hipError_t e) { return e == hipSuccess ? nullptr : hipGetErrorString(e); }
@@ -59,7 +59,7 @@ static ScoreKernel pick_score_kernel(const IndexView &ix) {
   // long: run-time slab count, both operands staged per slab (queries pre-split, `words` words a row), one workgroup per CU
 #if WANN_DT == 3
   if (rows == kRowsLong) return {k_gemm_scores_hslab, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
-#elif WANN_DT == 5 || WANN_DT == 6 || WANN_DT == 8
+#elif WANN_DT == 5 || WANN_QUAD_ROWS
   // (bfloat16 and float8 rows, and the one-byte shadow rows of a float32 index: narrow only; dense_row_class names no other class for them)
 #else
   if (rows == kRowsLong) return {k_gemm_scores_long, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
@@ -157,15 +157,9 @@ WANN_GNS_END
 #if WANN_DT == 0
 // ------------------------------------------------------------------------------------------------
 // entry points (wann_gemm_device.h) and the launchers of the grouping / cover kernels, which only this unit has
-namespace dt_u8 { const GemmUnit &gemm_unit(); }
-namespace dt_i8 { const GemmUnit &gemm_unit(); }
-namespace dt_f16 { const GemmUnit &gemm_unit(); }
-namespace dt_bf16 { const GemmUnit &gemm_unit(); }
-namespace dt_w8 { const GemmUnit &gemm_unit(); }
-namespace dt_f8 { const GemmUnit &gemm_unit(); }
-static const GemmUnit &unit_of(const IndexView &ix) {
-  return ix.dtype == 1 ? dt_u8::gemm_unit() : ix.dtype == 2 ? dt_i8::gemm_unit() : ix.dtype == 3 ? dt_f16::gemm_unit()
-       : ix.dtype == 5 ? dt_bf16::gemm_unit() : ix.dtype == kRowsU8Widened ? dt_w8::gemm_unit() : ix.dtype == kRowsF8 ? dt_f8::gemm_unit() : gemm_unit();
+// (the float32 unit's kernels and launchers keep their names outside any dt_* namespace; this is its unit for the lookup)
+namespace dt_f32 {
+const GemmUnit &gemm_unit() { return wann::gemm_unit(); }
 }
 
 static thread_local const char *g_gerr = "";
@@ -174,13 +168,23 @@ static int record(const char *err) {
   if (err) g_gerr = err;
   return err ? 1 : 0;
 }
+// calls the launcher `fn` of the row type's unit and records its error; a type without a dense unit, or whose unit lacks that
+// launcher, is an error that names the type -- no other type's kernels stand in
+template <typename... P, typename... A>
+static int unit_launch(int dtype, const char *(*GemmUnit::*fn)(P...), const char *what, const A &...args) {
+  const GemmUnit *u = gemm_unit_of(dtype);
+  if (u && u->*fn) return record((u->*fn)(args...));
+  static thread_local char text[80];
+  snprintf(text, sizeof text, "row type %d has no dense %s launcher", dtype, what);
+  return record(text);
+}
 
-int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream) { return record(unit_of(ix).point_sums(ix, norm2, max_bits, nullptr, stream)); }
-int launch_point_terms(const IndexView &ix, int32_t *term, void *stream) { return record(unit_of(ix).point_sums(ix, nullptr, nullptr, term, stream)); }
+int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream) { return unit_launch(ix.dtype, &GemmUnit::point_sums, "point_sums", ix, norm2, max_bits, nullptr, stream); }
+int launch_point_terms(const IndexView &ix, int32_t *term, void *stream) { return unit_launch(ix.dtype, &GemmUnit::point_sums, "point_sums", ix, nullptr, nullptr, term, stream); }
 int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream) { return record(gemm_unit().prep_queries(queries, nq, d, stride, out, stream)); }
-int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream) { return record(unit_of(ix).prep_queries(queries, nq, ix.d, ix.stride, out, stream)); }
-int launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream) { return record(unit_of(a.ix).gemm_scores(a, num_cus, stream)); }
-int launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream) { return record(unit_of(a.ix).select_rerank(a, ctr, stream)); }
+int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream) { return unit_launch(ix.dtype, &GemmUnit::prep_queries, "prep_queries", queries, nq, ix.d, ix.stride, out, stream); }
+int launch_gemm_scores(const GemmArgs &a, int num_cus, void *stream) { return unit_launch(a.ix.dtype, &GemmUnit::gemm_scores, "gemm_scores", a, num_cus, stream); }
+int launch_select_rerank(const GemmArgs &a, Counters *ctr, void *stream) { return unit_launch(a.ix.dtype, &GemmUnit::select_rerank, "select_rerank", a, ctr, stream); }
 
 int launch_group_windows(const GemmArgs &a, Counters *ctr, void *stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -211,9 +215,9 @@ int launch_cover_pass(const CoverArgs &c, int pass, int num_cus, void *stream, c
   a.groups = c.groups + (int64_t)pass * c.nblocks;
   a.tile_group = c.tile_group + (int64_t)pass * c.tile_stride;
   a.gq = c.gq + (int64_t)pass * c.pair_stride;
-  if (record(unit_of(a.ix).gemm_scores(a, num_cus, stream))) return 1;
+  if (launch_gemm_scores(a, num_cus, stream)) return 1;
   CoverArgs cp = c;
   cp.pass = pass;
-  return record(unit_of(c.g.ix).rerank_cover(cp, stream));
+  return unit_launch(c.g.ix.dtype, &GemmUnit::rerank_cover, "rerank_cover", cp, stream);
 }
 #endif  // WANN_DT == 0

@@ -50,11 +50,30 @@ Tuning snapshot_tuning(wann_index &I) {
   std::lock_guard<std::mutex> lk(I.tune_mu);
   if (I.tune.hooks_live) I.tune = Tuning::from_env();
   Tuning t = I.tune;
-  t.half_rows = I.half_rows_on && I.d_half.p != nullptr;
-  t.byte_rows = I.byte_rows_on && I.d_bytes.p != nullptr;
-  t.scan_rows = I.scan_rows_on && (I.d_half.p != nullptr || I.d_bytes.p != nullptr);
-  t.dense_rows = I.dense_rows_on && I.has_dense_copy();
+  t.half_rows = row_switch_in_force(I, kHalfRowsSwitch);
+  t.byte_rows = row_switch_in_force(I, kByteRowsSwitch);
+  t.scan_rows = row_switch_in_force(I, kScanRowsSwitch);
+  t.dense_rows = row_switch_in_force(I, kDenseRowsSwitch);
   return t;
+}
+
+// A shadow copy of a float32 index's rows in `buf`: n rows of `words` 32-bit words, zeroed, filled by fill(rows) -- packed and
+// laid out -- and uploaded.  An index that cannot have the copy (no host or device memory) simply has none: `buf` stays empty.
+template <typename Fill>
+static void upload_shadow_rows(DevBuf<float> &buf, int64_t n, int64_t words, Fill fill) {
+  std::vector<float> rows;
+  try {
+    rows.assign((size_t)n * words, 0.f);
+    buf.ensure(rows.size());
+  } catch (std::bad_alloc &) {
+    buf.release();
+  } catch (HipError &) {
+    (void)hipGetLastError();  // (the allocation that failed is not left behind as the next call's error)
+    buf.release();
+  }
+  if (!buf.p) return;
+  fill(rows.data());
+  buf.upload(rows);
 }
 
 void upload_index(wann_index &I) {
@@ -79,7 +98,7 @@ void upload_index(wann_index &I) {
   v.d = (int32_t)s.d;
   // float16 / bfloat16 points: the host rows are their float32 upcast; the device rows are two-byte elements again (exact), 64-byte padded
   // float8 points: likewise one-byte patterns again, d bytes zero padded to a multiple of 64, in the one-byte shadow rows' layout
-  v.stride = (int32_t)(two_byte_rows(s.dtype) ? two_byte_stride_words(s.d) : s.dtype == WANN_DTYPE_F8 ? u8_widened_stride_words(s.d) : s.stride);
+  v.stride = (int32_t)row_stride_words(s.dtype, s.d, s.stride);
   v.metric = s.metric;
   v.dtype = s.dtype;
   v.kind = s.kind;
@@ -101,7 +120,7 @@ void upload_index(wann_index &I) {
   } else if (s.dtype == WANN_DTYPE_F8) {
     std::vector<float> rows((size_t)s.n * v.stride, 0.f);
     pack_f8_rows(H.pts.data(), s.n, s.d, s.stride, v.stride, s.threads, rows.data());
-    interleave_u8_rows(rows.data(), s.n, v.stride, s.threads);  // (the device layout: u8_row_position, wann_device.h)
+    interleave_u8_rows(rows.data(), s.n, v.stride, s.threads);  // (the device layout: u8_row_position, wann_row_types.h)
     I.d_points.upload(rows);
   } else {
     I.d_points.upload(H.pts);
@@ -109,72 +128,33 @@ void upload_index(wann_index &I) {
   // float32 points that are all binary16 values, on an index with graphs: a second copy as half rows (the float16 branch's
   // conversion and padding) for the beam searches, which are bound by the bytes of the rows they score.  Every shape the
   // float16 k_search serves qualifies -- that is every shape: a float16 index of any kind / metric / R / d runs these kernels.
-  // An index that cannot have the copy (no memory) simply has none.
   if (s.dtype == WANN_DTYPE_F32 && H.vamana_leaves && rows_fp16_exact(H.pts.data(), s.n, s.d, s.stride, s.threads)) {
-    const int64_t hstride = ((s.d * 2 + 63) / 64) * 16;
-    std::vector<float> rows;
-    try {
-      rows.assign((size_t)s.n * hstride, 0.f);
-      I.d_half.ensure(rows.size());
-    } catch (std::bad_alloc &) {
-      I.d_half.release();
-    } catch (HipError &) {
-      (void)hipGetLastError();  // (the allocation that failed is not left behind as the next call's error)
-      I.d_half.release();
-    }
-    if (I.d_half.p) {
+    const int64_t hstride = row_stride_words(kRowsF16Paired, s.d, s.stride);
+    upload_shadow_rows(I.d_half, s.n, hstride, [&](float *rows) {
       parallel_for(s.n, s.threads > 0 ? s.threads : default_threads(), [&](int64_t r) {
         const float *src = H.pts.data() + r * s.stride;
-        uint16_t *dst = reinterpret_cast<uint16_t *>(rows.data() + r * hstride);
+        uint16_t *dst = reinterpret_cast<uint16_t *>(rows + r * hstride);
         for (int64_t j = 0; j < s.d; j++) dst[j] = float_to_half(src[j]);
       });
-      interleave_h16_rows(rows.data(), s.n, hstride, s.threads);  // (the copy's layout: h16_row_position, wann_device.h)
-      I.d_half.upload(rows);
-    }
+      interleave_h16_rows(rows, s.n, hstride, s.threads);  // (the copy's layout: h16_row_position, wann_row_types.h)
+    });
   }
   // ... and where they are all integers 0 .. 255 (SIFT / BIGANN are), a third copy as one-byte rows: a quarter of the float32
   // bytes, scored by the kernels of wann_kernels_w8.hip.  Beside the half copy, not instead of it: wann_set_byte_rows chooses
   // between batches without allocating anything, and the copy is off until it is asked for.
-  if (s.dtype == WANN_DTYPE_F32 && H.vamana_leaves && rows_u8_exact(H.pts.data(), s.n, s.d, s.stride, s.threads)) {
-    const int64_t bstride = u8_widened_stride_words(s.d);
-    std::vector<float> rows;
-    try {
-      rows.assign((size_t)s.n * bstride, 0.f);
-      I.d_bytes.ensure(rows.size());
-    } catch (std::bad_alloc &) {
-      I.d_bytes.release();
-    } catch (HipError &) {
-      (void)hipGetLastError();  // (the allocation that failed is not left behind as the next call's error)
-      I.d_bytes.release();
-    }
-    if (I.d_bytes.p) {
-      pack_u8_rows(H.pts.data(), s.n, s.d, s.stride, bstride, s.threads, rows.data());
-      interleave_u8_rows(rows.data(), s.n, bstride, s.threads);  // (the copy's layout: u8_row_position, wann_device.h)
-      I.d_bytes.upload(rows);
-    }
-  }
+  const int64_t bstride = row_stride_words(kRowsU8Widened, s.d, s.stride);
+  const auto fill_u8_rows = [&](float *rows) {
+    pack_u8_rows(H.pts.data(), s.n, s.d, s.stride, bstride, s.threads, rows);
+    interleave_u8_rows(rows, s.n, bstride, s.threads);  // (the copy's layout: u8_row_position, wann_row_types.h)
+  };
+  if (s.dtype == WANN_DTYPE_F32 && H.vamana_leaves && rows_u8_exact(H.pts.data(), s.n, s.d, s.stride, s.threads))
+    upload_shadow_rows(I.d_bytes, s.n, bstride, fill_u8_rows);
   // A float32 PrefilterIndex of such points keeps the same one-byte rows for the score kernel of its dense path
   // (wann_set_dense_rows, off by default), where that kernel takes them: rows of the narrow class.  The layout of d_bytes, the
   // row order of d_points, a buffer of its own: the index has no beam searches and no byte rows to switch on.
   if (s.dtype == WANN_DTYPE_F32 && s.kind == WANN_KIND_PREFILTER && dense_row_class(v) == kRowsNarrow &&
-      rows_u8_exact(H.pts.data(), s.n, s.d, s.stride, s.threads)) {
-    const int64_t bstride = u8_widened_stride_words(s.d);
-    std::vector<float> rows;
-    try {
-      rows.assign((size_t)s.n * bstride, 0.f);
-      I.d_dense.ensure(rows.size());
-    } catch (std::bad_alloc &) {
-      I.d_dense.release();
-    } catch (HipError &) {
-      (void)hipGetLastError();  // (the allocation that failed is not left behind as the next call's error)
-      I.d_dense.release();
-    }
-    if (I.d_dense.p) {
-      pack_u8_rows(H.pts.data(), s.n, s.d, s.stride, bstride, s.threads, rows.data());
-      interleave_u8_rows(rows.data(), s.n, bstride, s.threads);
-      I.d_dense.upload(rows);
-    }
-  }
+      rows_u8_exact(H.pts.data(), s.n, s.d, s.stride, s.threads))
+    upload_shadow_rows(I.d_dense, s.n, bstride, fill_u8_rows);
   I.d_labels.upload(H.labels);
   I.d_decoding.upload(H.decoding);
   v.points = I.d_points.p;
@@ -260,14 +240,14 @@ void upload_index(wann_index &I) {
   I.search_view = v;
   if (I.d_half.p) {
     I.search_view.points = I.d_half.p;
-    I.search_view.stride = (int32_t)(((s.d * 2 + 63) / 64) * 16);
+    I.search_view.stride = (int32_t)row_stride_words(kRowsF16Paired, s.d, s.stride);
     I.search_view.dtype = kRowsF16Paired;
     I.half_rows_on = true;
   }
   I.byte_view = v;
   if (I.d_bytes.p) {  // (byte_rows_on stays false: the one-byte rows are opt-in, wann_set_byte_rows)
     I.byte_view.points = I.d_bytes.p;
-    I.byte_view.stride = (int32_t)u8_widened_stride_words(s.d);
+    I.byte_view.stride = (int32_t)bstride;
     I.byte_view.dtype = kRowsU8Widened;
   }
   // the copy the dense path's score launches read under wann_set_dense_rows: the PrefilterIndex's own, or the one-byte shadow
@@ -278,7 +258,7 @@ void upload_index(wann_index &I) {
     const float *copy = I.d_dense.p ? I.d_dense.p : (exact_kind && dense_row_class(v) == kRowsNarrow) ? I.d_bytes.p : nullptr;
     if (copy) {
       I.dense_view.points = copy;
-      I.dense_view.stride = (int32_t)u8_widened_stride_words(s.d);
+      I.dense_view.stride = (int32_t)bstride;
       I.dense_view.dtype = kRowsU8Widened;
     }
   }
@@ -460,7 +440,7 @@ void build_pending(wann_index &I, std::vector<HostPart *> &pending) {
 
 std::vector<float> bytes_to_float(int dtype, const void *src, int64_t count) {
   std::vector<float> out((size_t)count);
-  if (two_byte_rows(dtype)) {
+  if (element_bytes(dtype) == 2) {
     const uint16_t *p = (const uint16_t *)src;
     for (int64_t i = 0; i < count; i++) out[(size_t)i] = two_byte_to_float(dtype, p[i]);
   } else if (dtype == WANN_DTYPE_F8) {

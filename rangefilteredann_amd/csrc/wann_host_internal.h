@@ -180,6 +180,9 @@ struct wann_index {
   bool dense_rows_on = false;
   std::atomic<int> last_dense_rows{0};  // a score launch of the last finished batch read the copy
   bool has_dense_copy() const { return dense_view.dtype == kRowsU8Widened && dense_view.points != nullptr; }
+  bool has_half_copy() const { return d_half.p != nullptr; }
+  bool has_byte_copy() const { return d_bytes.p != nullptr; }
+  bool has_scan_copy() const { return has_half_copy() || has_byte_copy(); }
   int64_t dense_copy_bytes() const { return !has_dense_copy() ? 0 : (int64_t)(d_dense.p ? d_dense.bytes() : d_bytes.bytes()); }
   // which row stores a finished batch read (run_batch's result: the beam searches' store, the scan's in the next byte, whether
   // a dense score launch read the one-byte copy in the byte after that)
@@ -258,6 +261,21 @@ struct wann_index {
 
 namespace wann_host {
 
+// A row switch of an index (wann_set_half_rows / _byte_rows / _scan_rows / _dense_rows): the flag the setter writes under
+// tune_mu, the "a copy exists" predicate that bounds it, and what the last finished batch did.  The setters and getters of the
+// C ABI and snapshot_tuning go through these four records.
+struct RowSwitch {
+  bool wann_index::*on;
+  bool (wann_index::*has_copy)() const;
+  std::atomic<int> wann_index::*last;
+};
+constexpr RowSwitch kHalfRowsSwitch = {&wann_index::half_rows_on, &wann_index::has_half_copy, &wann_index::last_half_rows};
+constexpr RowSwitch kByteRowsSwitch = {&wann_index::byte_rows_on, &wann_index::has_byte_copy, &wann_index::last_byte_rows};
+constexpr RowSwitch kScanRowsSwitch = {&wann_index::scan_rows_on, &wann_index::has_scan_copy, &wann_index::last_scan_rows};
+constexpr RowSwitch kDenseRowsSwitch = {&wann_index::dense_rows_on, &wann_index::has_dense_copy, &wann_index::last_dense_rows};
+// (under I.tune_mu)
+inline bool row_switch_in_force(const wann_index &I, const RowSwitch &s) { return I.*s.on && (I.*s.has_copy)(); }
+
 Tuning snapshot_tuning(wann_index &I);  // the index's switches for one call (WANN_TEST_HOOKS=1: re-read from the environment first)
 void upload_index(wann_index &I);
 // wann_set_refine_rows: (n, d) float32 points in the caller's order -> I.d_refine (checked by the caller; throws HipError)
@@ -290,16 +308,13 @@ int run_batch(wann_index &I, Workspace &W, hipStream_t side, wann_counters &last
 void build_pending(wann_index &I, std::vector<HostPart *> &pending);
 // host queries of the index's element type (uint8 / int8 / float16 / bfloat16 / float8) -> the fp32 rows every kernel stages (exact)
 std::vector<float> bytes_to_float(int dtype, const void *src, int64_t count);
-// bytes per element of the caller's points / host queries
-inline int64_t element_bytes(int dtype) { return dtype == WANN_DTYPE_F32 ? 4 : two_byte_rows(dtype) ? 2 : 1; }
-// the element types the C ABI accepts (wann.h: 4 is unassigned)
-inline bool known_dtype(int dtype) {
-  return dtype == WANN_DTYPE_F32 || dtype == WANN_DTYPE_U8 || dtype == WANN_DTYPE_I8 || dtype == WANN_DTYPE_F16 || dtype == WANN_DTYPE_BF16 ||
-         dtype == WANN_DTYPE_F8;
-}
+// (element_bytes, known_dtype and the row-type predicates: wann_row_types.h)
+static_assert(WANN_DTYPE_F32 == kRowsF32 && WANN_DTYPE_U8 == kRowsU8 && WANN_DTYPE_I8 == kRowsI8 && WANN_DTYPE_F16 == kRowsF16 &&
+                  WANN_DTYPE_BF16 == kRowsBF16,
+              "the C ABI's element types are row types of the table");
 static_assert(WANN_DTYPE_F8 == kRowsF8, "the float8 element type is its own view type");
 // uint8 / int8 rows: scored with v_dot4 by kernels built for more waves per SIMD
-inline bool byte_rows(const IndexView &v) { return v.dtype == WANN_DTYPE_U8 || v.dtype == WANN_DTYPE_I8; }
+inline bool byte_rows(const IndexView &v) { return wann::byte_rows(v.dtype); }
 // this view's four-wave k_search is built for THREE waves per SIMD (at most 168 registers): the inner-product and byte-row
 // kernels.  The squared-L2 kernels keep two whole rows per lane pair in flight and are built for two: float32 needs 256
 // registers, float16 (k_search<0, 0, 3>) 215, the paired half shadow rows (k_search<0, 0, 7>) 189 -- see DESIGN.md 3.10.

@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <stdio.h>
+
 #include <algorithm>
 
 #include "wann_device.h"
@@ -27,40 +29,8 @@ namespace wann {
 // One translation unit per element type (WANN_DT, set by wann_kernels.hip / _u8.hip / _i8.hip / _f16.hip / _bf16.hip / _w8.hip / _h16.hip / _f8.hip before this body is
 // included): the search and scan kernels and their launchers live in a per-type namespace; the type-independent
 // kernels (routing, finalisation) and the dispatchers are compiled with the float32 unit only.
-#if WANN_DT == 0
-#define WANN_DT_NS dt_f32
-#elif WANN_DT == 1
-#define WANN_DT_NS dt_u8
-#elif WANN_DT == 2
-#define WANN_DT_NS dt_i8
-#elif WANN_DT == 3
-#define WANN_DT_NS dt_f16
-#elif WANN_DT == 5
-#define WANN_DT_NS dt_bf16
-#elif WANN_DT == 7
-#define WANN_DT_NS dt_h16  // (the half shadow rows of a float32 index, paired: its k_search and, under wann_set_scan_rows, its plain k_brute)
-#elif WANN_DT == 8
-#define WANN_DT_NS dt_f8  // (float8 rows: k_search, the staged scan for sorted rows and the plain k_brute for the PrefilterIndex's gathered ones)
-#else
-#define WANN_DT_NS dt_w8  // (the one-byte shadow rows of a float32 index: its k_search and, under wann_set_scan_rows, its scan)
-#endif
-// The float16 unit's search kernels carry the element type as a third template argument (k_search<METRIC, KIND, 3>): their
-// symbols differ from the float32 / byte-row kernels' in more than the namespace, and per-type tools and tests that select
-// the reference's three types by the kernel name's template arguments keep selecting exactly those (tests/test_float16.py
-// checks the float16 kernels' own register budget).
-#if WANN_DT == 3
-#define WANN_DT_TPARAM , int ROWS_DT = 3
-#elif WANN_DT == 5  // (the bfloat16 unit likewise)
-#define WANN_DT_TPARAM , int ROWS_DT = 5
-#elif WANN_DT == 6  // (and the one-byte shadow rows' unit)
-#define WANN_DT_TPARAM , int ROWS_DT = 6
-#elif WANN_DT == 7  // (and the paired half shadow rows')
-#define WANN_DT_TPARAM , int ROWS_DT = 7
-#elif WANN_DT == 8  // (and the float8 unit)
-#define WANN_DT_TPARAM , int ROWS_DT = 8
-#else
-#define WANN_DT_TPARAM
-#endif
+// (the unit's namespace WANN_DT_NS, the template parameter WANN_DT_TPARAM of the widened types' kernels and the class flags come
+// from the row type's entry in wann_row_types.h)
 #ifndef WANN_MIPS_WAVES
 #define WANN_MIPS_WAVES 3  // waves per SIMD the four-wave kernel of inner-product / byte rows is built for (dev: 4 = 128 registers)
 #endif
@@ -775,7 +745,7 @@ __global__ __launch_bounds__(KIND == 1 ? 64 * (1 + kHelpers) : (KIND == 2 ? 64 :
 // The float8 unit holds both: the staged kernel for the sorted kinds, whose T_BRUTE rows are contiguous, and the plain one for
 // the PrefilterIndex, whose T_BRUTE_GATHER rows are not (scan_staged, wann_device.h, chooses) -- the same routines on the
 // same blocks either way.
-#define WANN_SCAN_STAGED (WANN_DT == 6 || WANN_DT == 8)
+#define WANN_SCAN_STAGED WANN_QUAD_ROWS
 #define WANN_SCAN_PLAIN (WANN_DT != 6)
 #if WANN_SCAN_PLAIN
 template <int METRIC>
@@ -1540,7 +1510,7 @@ static int search_occupancy_t(int threads, size_t lds) {
   return n;
 }
 
-int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
+static int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
   const int wpb = cfg.waves_per_block > 0 ? cfg.waves_per_block : kWavesPerBlock;
   const size_t lds = (size_t)search_lds_bytes_per_wave(query_words(a.ix), a.pool_bytes) * wpb;
   const int threads = 64 * wpb + ((cfg.big == 1 && a.helper) ? 64 * a.helper : 0);
@@ -1549,7 +1519,7 @@ int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
   return a.ix.metric == 1 ? search_occupancy_t<1, 0>(threads, lds) : search_occupancy_t<0, 0>(threads, lds);
 }
 
-int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
+static int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
   if (cfg.blocks <= 0) return 0;
   const int wpb = cfg.waves_per_block > 0 ? cfg.waves_per_block : kWavesPerBlock;
   size_t lds = (size_t)search_lds_bytes_per_wave(query_words(a.ix), a.pool_bytes) * wpb;
@@ -1576,7 +1546,7 @@ static int launch_brute_t(const BruteArgs &a, dim3 grid, dim3 block, size_t lds,
   return check(hipGetLastError());
 }
 
-int launch_brute(const BruteArgs &a, int blocks, void *stream) {
+static int launch_brute(const BruteArgs &a, int blocks, void *stream) {
   if (blocks <= 0) return 0;
   // (long rows or a wide k: more than a launch gets unasked -- run_batch has refused what exceeds kLdsPerWorkgroup)
   const bool staged = scan_staged(a.ix, a.k);  // (wann_device.h: by the view's type and kind -- this unit's kernel for it)
@@ -1586,63 +1556,28 @@ int launch_brute(const BruteArgs &a, int blocks, void *stream) {
                           : launch_brute_t<0>(a, grid, block, lds, (hipStream_t)stream, staged);
 }
 
+// (reached through a function: host code only, and no order of initialisation to depend on)
+const SearchUnit &search_unit() {
+  static constexpr SearchUnit unit = {search_occupancy, launch_search, launch_brute};
+  return unit;
+}
+
 }  // namespace WANN_DT_NS
 
 #if WANN_DT == 0
-// dispatch on the index's element type
-namespace dt_u8 {
-int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
-int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
-int launch_brute(const BruteArgs &a, int blocks, void *stream);
+// the entry points: the view's row type picks the unit (a type without a search unit is an error, never another type's kernels)
+static const SearchUnit *unit_or_error(const IndexView &ix) {
+  const SearchUnit *u = search_unit_of(ix.dtype);
+  if (!u) {
+    static thread_local char text[48];
+    snprintf(text, sizeof text, "row type %d has no search unit", ix.dtype);
+    g_launch_err = text;
+  }
+  return u;
 }
-namespace dt_i8 {
-int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
-int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
-int launch_brute(const BruteArgs &a, int blocks, void *stream);
-}
-namespace dt_f16 {
-int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
-int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
-int launch_brute(const BruteArgs &a, int blocks, void *stream);
-}
-namespace dt_bf16 {
-int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
-int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
-int launch_brute(const BruteArgs &a, int blocks, void *stream);
-}
-namespace dt_w8 {  // (a view of one-byte shadow rows: the beam search, and the exact scan under wann_set_scan_rows)
-int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
-int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
-int launch_brute(const BruteArgs &a, int blocks, void *stream);
-}
-namespace dt_h16 {  // (a view of paired half shadow rows, likewise)
-int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
-int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
-int launch_brute(const BruteArgs &a, int blocks, void *stream);
-}
-namespace dt_f8 {
-int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream);
-int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg);
-int launch_brute(const BruteArgs &a, int blocks, void *stream);
-}
-int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) {
-  return a.ix.dtype == 1 ? dt_u8::search_occupancy(a, cfg) : a.ix.dtype == 2 ? dt_i8::search_occupancy(a, cfg)
-       : a.ix.dtype == 3 ? dt_f16::search_occupancy(a, cfg) : a.ix.dtype == 5 ? dt_bf16::search_occupancy(a, cfg)
-       : a.ix.dtype == kRowsU8Widened ? dt_w8::search_occupancy(a, cfg) : a.ix.dtype == kRowsF16Paired ? dt_h16::search_occupancy(a, cfg)
-       : a.ix.dtype == kRowsF8 ? dt_f8::search_occupancy(a, cfg) : dt_f32::search_occupancy(a, cfg);
-}
-int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) {
-  return a.ix.dtype == 1 ? dt_u8::launch_search(a, cfg, stream) : a.ix.dtype == 2 ? dt_i8::launch_search(a, cfg, stream)
-       : a.ix.dtype == 3 ? dt_f16::launch_search(a, cfg, stream) : a.ix.dtype == 5 ? dt_bf16::launch_search(a, cfg, stream)
-       : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_search(a, cfg, stream) : a.ix.dtype == kRowsF16Paired ? dt_h16::launch_search(a, cfg, stream)
-       : a.ix.dtype == kRowsF8 ? dt_f8::launch_search(a, cfg, stream) : dt_f32::launch_search(a, cfg, stream);
-}
-int launch_brute(const BruteArgs &a, int blocks, void *stream) {
-  return a.ix.dtype == 1 ? dt_u8::launch_brute(a, blocks, stream) : a.ix.dtype == 2 ? dt_i8::launch_brute(a, blocks, stream)
-       : a.ix.dtype == 3 ? dt_f16::launch_brute(a, blocks, stream) : a.ix.dtype == 5 ? dt_bf16::launch_brute(a, blocks, stream)
-       : a.ix.dtype == kRowsU8Widened ? dt_w8::launch_brute(a, blocks, stream) : a.ix.dtype == kRowsF16Paired ? dt_h16::launch_brute(a, blocks, stream)
-       : a.ix.dtype == kRowsF8 ? dt_f8::launch_brute(a, blocks, stream) : dt_f32::launch_brute(a, blocks, stream);
-}
+int search_occupancy(const SearchArgs &a, const LaunchCfg &cfg) { const SearchUnit *u = unit_or_error(a.ix); return u ? u->search_occupancy(a, cfg) : -1; }
+int launch_search(const SearchArgs &a, const LaunchCfg &cfg, void *stream) { const SearchUnit *u = unit_or_error(a.ix); return u ? u->launch_search(a, cfg, stream) : 1; }
+int launch_brute(const BruteArgs &a, int blocks, void *stream) { const SearchUnit *u = unit_or_error(a.ix); return u ? u->launch_brute(a, blocks, stream) : 1; }
 
 int launch_finalize(const FinalizeArgs &a, void *stream) {
   if (a.nq == 0) return 0;

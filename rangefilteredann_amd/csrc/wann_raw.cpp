@@ -36,7 +36,9 @@ struct RawGraph {
     subset_n = subset_n_;
     maxdeg = (int32_t)maxdeg_;
     const int64_t esz = element_bytes(dtype);
-    const int64_t stride = ((d * esz + 63) / 64) * 16;  // 32-bit words per row
+    // 32-bit words per device row: the caller's elements, zero padded to 64 bytes (the type's own pitch rule; the stride of the
+    // host rows, which float32 and byte rows keep, is the second argument)
+    const int64_t stride = row_stride_words(dtype, d, spec_stride_words(dtype, d));
     std::vector<float> pts((size_t)n * stride, 0.f);
     for (int64_t i = 0; i < n; i++) memcpy(pts.data() + i * stride, (const char *)points + i * d * esz, (size_t)(d * esz));
     if (dtype == WANN_DTYPE_F8) interleave_u8_rows(pts.data(), n, stride, 0);  // (float8 rows: the device layout, u8_row_position)

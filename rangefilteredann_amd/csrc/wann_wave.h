@@ -6,7 +6,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// the row type of this translation unit (wann_kernels.hip, _u8, _i8, _f16, ... set it before anything is included); a unit
+// without one is a float32 unit.  Its namespace and class flags -- WANN_DT_NS, WANN_BYTE_ROWS, WANN_HALF_ROWS, WANN_QUAD_ROWS,
+// WANN_WIDENED_ROWS -- come from the type's entry in wann_row_types.h.
+#ifndef WANN_DT
+#define WANN_DT 0
+#endif
 #include "wann_device.h"
+#include "wann_row_types.h"
 
 namespace wann {
 
@@ -81,20 +88,8 @@ __device__ __forceinline__ u64 hash64_2(u64 x) {
 }
 
 // --------------------------------------------------------------------------------------------
-// element type of the point rows: one translation unit per type (wann_kernels.hip, _u8, _i8, _f16)
+// the rows of this unit's type: blocks, loads and the widening to float32
 // --------------------------------------------------------------------------------------------
-#ifndef WANN_DT
-#define WANN_DT 0  // 0 = float32 rows, 1 = uint8, 2 = int8, 3 = float16, 5 = bfloat16 (4 is unassigned, see wann.h),
-                   // 6 = the one-byte shadow rows of a float32 index (internal: kRowsU8Widened in wann_device.h),
-                   // 7 = its half shadow rows, paired (internal: kRowsF16Paired),
-                   // 8 = float8 (OCP E4M3) rows, in the one-byte shadow rows' layout
-#endif
-#define WANN_BYTE_ROWS (WANN_DT == 1 || WANN_DT == 2)
-#define WANN_HALF_ROWS (WANN_DT == 3 || WANN_DT == 5 || WANN_DT == 7)  // two-byte float rows (two_byte_rows in wann_device.h is the host side)
-// rows narrower than float32, scored as their exact float32 upcast against the fp32 query (widened_rows is the host side)
-#define WANN_QUAD_ROWS (WANN_DT == 6 || WANN_DT == 8)  // one-byte rows, interleaved and fetched 16 bytes (a quad of blocks) at a time
-#define WANN_WIDENED_ROWS (WANN_HALF_ROWS || WANN_QUAD_ROWS)
-
 // A row BLOCK is four consecutive elements e..e+3 of a row (e a multiple of 4): a float4 of a float32 row, 8 bytes of a
 // float16 row.  Float16 rows (WANN_DT = 3) keep the natural element order, padded with zeros to a multiple of 32 halves
 // (64 B); `stride` still counts 32-bit words, so element e of a row sits at half e of its first word.  cvt_blk turns a block
@@ -105,31 +100,28 @@ __device__ __forceinline__ u64 hash64_2(u64 x) {
 // know how a unit fetches: ld_blk, one load per block, here and for float32 / bfloat16 / byte rows (the two shadow-row units
 // of a float32 index, 6 and 7, permute the elements inside a row and fetch 16 bytes at a time: below).
 // (macros: the float32 and byte-row units compile exactly the expressions they compiled before the float16 unit existed)
-#if WANN_DT == 3
+#if WANN_DT == 3 || WANN_DT == 7
+// (the float16 rows and the half shadow rows of a float32 index share the block and its conversion, and so the arithmetic,
+// block order, lane pairing and accumulators; only the fetch differs)
 typedef uint2 rowblk_t;
 __device__ __forceinline__ float h2f(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
 __device__ __forceinline__ float4 h4_to_f4(uint2 w) {
   return make_float4(h2f(w.x & 0xffffu), h2f(w.x >> 16), h2f(w.y & 0xffffu), h2f(w.y >> 16));
 }
-#define ld_blk(prow, e) (*reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(prow) + (e)))
 #define cvt_blk(w) h4_to_f4(w)
-#elif WANN_DT == 7
-// the half shadow rows of a float32 index: the float16 unit's blocks and conversion, and so its arithmetic, block order, lane
-// pairing and accumulators.  Only the fetch differs.  The rows are PAIRED (h16_row_position, wann_device.h): the blocks
+#if WANN_DT == 3
+#define ld_blk(prow, e) (*reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(prow) + (e)))
+#else
+// The half shadow rows are PAIRED (h16_row_position, wann_row_types.h): the blocks
 // 8 b + 4 h of lane h, b = 2 c and 2 c + 1, are the 16 contiguous bytes at 32 c + 16 h of the row -- one 16-byte load
 // (ld_pair), split at once into the two blocks' slots: RowBlks stays one uint2 per block, as in the float16 unit (held as
 // 16-byte pairs the four-wave kernel spilled).  The loaders issue the pairs that hold a block below the count, in pair order; a
 // block at or beyond the row's count is never consumed (the padding is zero, but the staged query ends with the row).  Rows
 // start on multiples of 64 bytes, so every pair is 16-byte aligned.  (Like the one-byte unit this one has no ld_blk: a single
 // block's address would follow the natural order.)
-typedef uint2 rowblk_t;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float h2f(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
-__device__ __forceinline__ float4 h4_to_f4(uint2 w) {
-  return make_float4(h2f(w.x & 0xffffu), h2f(w.x >> 16), h2f(w.y & 0xffffu), h2f(w.y >> 16));
-}
 #define ld_pair(prow, c, h) (*reinterpret_cast<const u32x4 *>(reinterpret_cast<const unsigned char *>(prow) + 32 * (c) + 16 * (h)))
-#define cvt_blk(w) h4_to_f4(w)
+#endif
 #elif WANN_DT == 5
 // bfloat16 rows: the float16 rows' layout and blocks.  A bfloat16 is the top 16 bits of a float32, so the conversion is
 // integer-only -- a shift or a mask, then a bit cast: subnormals, signed zeros, inf and NaN come through whatever the FP mode.
@@ -140,50 +132,44 @@ __device__ __forceinline__ float4 b4_to_f4(uint2 w) {
 }
 #define ld_blk(prow, e) (*reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(prow) + (e)))
 #define cvt_blk(w) b4_to_f4(w)
-#elif WANN_DT == 6
-// one-byte shadow rows of a float32 index whose values are all integers 0 .. 255: a block is ONE aligned 32-bit word, the
-// elements e .. e+3 of the row (rows zero padded to a multiple of 64 bytes).  Each byte widens UNSIGNED
-// to the float32 it was made from (v_cvt_f32_ubyte0..3: exact), and the float32 arithmetic follows in its own order against the
-// fp32 query in the float32 LDS layout.  A held block stays its packed word: a quarter of a float32 block.
-// The rows are INTERLEAVED (u8_row_position, wann_device.h): the blocks 8 b + 4 h of lane h, b = 4 c .. 4 c + 3, are the 16
+#elif WANN_QUAD_ROWS
+// one-byte shadow rows of a float32 index whose values are all integers 0 .. 255 (6), and float8 rows (8): a block is ONE
+// aligned 32-bit word, the elements e .. e+3 of the row (rows zero padded to a multiple of 64 bytes); the float32 arithmetic
+// follows the widening in its own order against the fp32 query in the float32 LDS layout.  A held block stays its packed word:
+// a quarter of a float32 block.
+// The rows are INTERLEAVED (u8_row_position, wann_row_types.h): the blocks 8 b + 4 h of lane h, b = 4 c .. 4 c + 3, are the 16
 // contiguous bytes at 32 c + 16 h of the row -- a QUAD, one 16-byte load (ld_quad); quad_blk(q, i) is block b = 4 c + i of it.
-// RowBlks' loaders of this unit fetch quads, in quad order, and RowBlks keeps them quads; the routines consume blocks in the
+// RowBlks' loaders of these units fetch quads, in quad order, and RowBlks keeps them quads; the routines consume blocks in the
 // float32 order through the same accessor as every unit.  A block at or beyond the row's block count is never consumed (the
 // quad's padding is zero, but the staged query ends with the row).  A block's number is a compile-time constant of an unrolled
 // loop wherever it is consumed; the one last block of an odd run-time count is a select between the four words (never a
 // register index).  A quad is typed with 8-byte alignment: rows in HBM start on multiples of 64 (one global_load_dwordx4),
-// rows staged in the LDS (k_brute_staged) on multiples of 8 (two 8-byte reads).  (The unit has no ld_blk: a single block's
+// rows staged in the LDS (k_brute_staged) on multiples of 8 (two 8-byte reads).  (The units have no ld_blk: a single block's
 // address would follow the natural order.)
 typedef uint32_t rowblk_t;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 rowquad_t __attribute__((aligned(8)));
+// Only the widening differs between the two:
+#if WANN_DT == 6
+// each byte widens UNSIGNED to the float32 it was made from (v_cvt_f32_ubyte0..3: exact)
 __device__ __forceinline__ float4 u4_to_f4(uint32_t w) {
   return make_float4((float)(w & 0xffu), (float)((w >> 8) & 0xffu), (float)((w >> 16) & 0xffu), (float)(w >> 24));
 }
-#define ld_quad(prow, c, h) (*reinterpret_cast<const rowquad_t *>(reinterpret_cast<const unsigned char *>(prow) + 32 * (c) + 16 * (h)))
-__device__ __forceinline__ uint32_t quad_blk(const u32x4 &q, int i) { return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w; }
 #define cvt_blk(w) u4_to_f4(w)
-typedef u32x4 rowheld_t;  // what a lane holds of a row: quads
-constexpr int kHeldBlks = 4;
-#define held_blk(w, i) quad_blk(w, i)
-#elif WANN_DT == 8
-// float8 rows (OCP E4M3, wann.h WANN_DTYPE_F8): the one-byte shadow rows' layout, blocks, quads, loaders and lane pairing --
-// a block is one aligned 32-bit word, rows are interleaved (u8_row_position), a lane fetches a QUAD with one 16-byte load.
-// Only the widening differs: v_cvt_pk_f32_fp8 turns two E4M3 bytes of the word into two float32, two instructions a block.
-// It is exact for every finite pattern whatever the FP mode: an E4M3 value has four significant bits and an exponent of
-// 2^-9 .. 2^8, so even its subnormals are NORMAL float32 values -- no multiply, nothing the float32 denormal mode can flush.
-// (The NaN patterns 0x7f / 0xff never reach a row: the host refuses them.)  The float32 arithmetic follows in its own order.
-typedef uint32_t rowblk_t;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 rowquad_t __attribute__((aligned(8)));
+#else
+// float8 (OCP E4M3, wann.h WANN_DTYPE_F8): v_cvt_pk_f32_fp8 turns two E4M3 bytes of the word into two float32, two
+// instructions a block.  It is exact for every finite pattern whatever the FP mode: an E4M3 value has four significant bits and
+// an exponent of 2^-9 .. 2^8, so even its subnormals are NORMAL float32 values -- no multiply, nothing the float32 denormal mode
+// can flush.  (The NaN patterns 0x7f / 0xff never reach a row: the host refuses them.)
 typedef float f8pair_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float4 f8x4_to_f4(uint32_t w) {
   const f8pair_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
   return make_float4(lo.x, lo.y, hi.x, hi.y);
 }
+#define cvt_blk(w) f8x4_to_f4(w)
+#endif
 #define ld_quad(prow, c, h) (*reinterpret_cast<const rowquad_t *>(reinterpret_cast<const unsigned char *>(prow) + 32 * (c) + 16 * (h)))
 __device__ __forceinline__ uint32_t quad_blk(const u32x4 &q, int i) { return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w; }
-#define cvt_blk(w) f8x4_to_f4(w)
 typedef u32x4 rowheld_t;  // what a lane holds of a row: quads
 constexpr int kHeldBlks = 4;
 #define held_blk(w, i) quad_blk(w, i)
@@ -200,7 +186,7 @@ constexpr int kHeldBlks = 1;
 #endif
 // 32-bit words of the staged (fp32, zero padded) query and of the LDS reserved for it: `stride` for float32 / byte rows; for
 // widened rows (float16 / bfloat16 / one-byte shadow rows) the float32 row length, d rounded up to 16 -- every routine reads the
-// query up to d rounded up to 8, and the LDS layout of such a view equals the float32 index's (query_words in wann_device.h is the host side)
+// query up to d rounded up to 8, and the LDS layout of such a view equals the float32 index's (query_words of wann_row_types.h, on the host)
 __device__ __forceinline__ int qv_words(const IndexView &ix) { return WANN_WIDENED_ROWS ? ((ix.d + 15) & ~15) : ix.stride; }
 
 // --------------------------------------------------------------------------------------------

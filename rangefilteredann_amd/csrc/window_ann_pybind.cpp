@@ -262,39 +262,29 @@ class Index {
     d["dense_rows"] = wann_last_dense_rows(h_);
     return d;
   }
-  // float32 indexes with graphs whose points are all binary16 values: the beam searches read a half-precision copy of the rows
-  // (wann_set_half_rows); returns the setting now in force -- False on an index without such a copy
-  bool set_half_rows(bool on) {
-    const int rc = wann_set_half_rows(h_, on ? 1 : 0);
-    if (rc < 0) raise_last("set_half_rows failed");
+  // a row switch's setter (wann_set_*_rows): the setting now in force
+  bool set_row_switch(int (*set)(wann_index *, int), bool on, const char *what) {
+    const int rc = set(h_, on ? 1 : 0);
+    if (rc < 0) raise_last(what);
     return rc != 0;
   }
+  // float32 indexes with graphs whose points are all binary16 values: the beam searches read a half-precision copy of the rows
+  // (wann_set_half_rows); returns the setting now in force -- False on an index without such a copy
+  bool set_half_rows(bool on) { return set_row_switch(wann_set_half_rows, on, "set_half_rows failed"); }
   bool half_rows() const { return wann_half_rows(h_) != 0; }
   int64_t half_rows_bytes() const { return wann_half_rows_bytes(h_); }
   // ... and whose points are all integers 0 .. 255: the beam searches read a one-byte copy of the rows instead, once asked to
   // (wann_set_byte_rows, off by default); returns the setting now in force -- False on an index without such a copy
-  bool set_byte_rows(bool on) {
-    const int rc = wann_set_byte_rows(h_, on ? 1 : 0);
-    if (rc < 0) raise_last("set_byte_rows failed");
-    return rc != 0;
-  }
+  bool set_byte_rows(bool on) { return set_row_switch(wann_set_byte_rows, on, "set_byte_rows failed"); }
   bool byte_rows() const { return wann_byte_rows(h_) != 0; }
   int64_t byte_rows_bytes() const { return wann_byte_rows_bytes(h_); }
   // the exact scans read the shadow copy the beam searches read (wann_set_scan_rows, off by default); returns the setting now
   // in force -- False on an index without a shadow copy
-  bool set_scan_rows(bool on) {
-    const int rc = wann_set_scan_rows(h_, on ? 1 : 0);
-    if (rc < 0) raise_last("set_scan_rows failed");
-    return rc != 0;
-  }
+  bool set_scan_rows(bool on) { return set_row_switch(wann_set_scan_rows, on, "set_scan_rows failed"); }
   bool scan_rows() const { return wann_scan_rows(h_) != 0; }
   // the score launches of the dense path read the one-byte copy of a float32 index of byte-exact points (wann_set_dense_rows, off
   // by default); returns the setting now in force -- False on an index without a copy that path can read
-  bool set_dense_rows(bool on) {
-    const int rc = wann_set_dense_rows(h_, on ? 1 : 0);
-    if (rc < 0) raise_last("set_dense_rows failed");
-    return rc != 0;
-  }
+  bool set_dense_rows(bool on) { return set_row_switch(wann_set_dense_rows, on, "set_dense_rows failed"); }
   bool dense_rows() const { return wann_dense_rows(h_) != 0; }
   int64_t dense_rows_bytes() const { return wann_dense_rows_bytes(h_); }
 
@@ -642,7 +632,7 @@ struct VamanaIndexT {
     FILE *f = fopen(path.c_str(), "rb");
     if (!f) throw std::runtime_error("cannot open query file " + path);
     uint32_t head[2] = {0, 0};
-    const size_t esz = DTYPE == WANN_DTYPE_F32 ? 4 : 1;
+    const size_t esz = (size_t)wann::element_bytes(DTYPE);
     std::vector<unsigned char> raw;
     bool ok = fread(head, 4, 2, f) == 2 && (int64_t)head[1] == wann_vamana_dim(h) && head[0] >= nq;
     if (ok) {
