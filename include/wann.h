@@ -119,8 +119,11 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * file names on the upcast points; bfloat16 bit patterns as host-buffer queries, fp32 device queries (not rounded), float32
  * labels; no wann_vamana_* variant.  Its MFMA prefilter path covers rows of up to 128 elements with a kernel of its own (a
  * bfloat16 row is its own high bf16 term: one staged row per point, two products per step instead of three, the float32
- * kernel's scores on the upcast row); longer rows take the exact scan, with or without WANN_DENSE_LONG_ROWS.  A bfloat16 index
- * has no shadow rows (wann_half_rows: 0).
+ * kernel's scores on the upcast row); longer rows take the exact scan, with or without WANN_DENSE_LONG_ROWS -- unless the INDEX
+ * opts in: after wann_set_dense_long_rows(index, 1) rows of 129 .. 2048 elements take that path too (shared windows, cover
+ * groups, exact windows), on k_gemm_scores_bfslab -- a slab-walking kernel whose point operand is the row's own bytes and whose
+ * accumulators are the float32 long-row kernel's on the upcast rows: the same ids, distance bits and dense counters.  Rows
+ * beyond 2048 elements and k > 16 stay on the scan.  A bfloat16 index has no shadow rows (wann_half_rows: 0).
  * The value is 5: 4 is UNASSIGNED and refused as an unknown dtype, like every other value not listed here.
  * WANN_DTYPE_F8 (not a type of the reference): float8 points, rows of uint8_t bit patterns of OCP E4M3 ("e4m3fn": 1 sign bit, 4
  * exponent bits with bias 7, 3 mantissa bits; no infinities, 0x7f / 0xff are NaN, the largest finite value is 448, subnormals
@@ -414,6 +417,15 @@ int wann_set_dense_rows(wann_index *index, int on);
 int wann_dense_rows(const wann_index *index);
 int64_t wann_dense_rows_bytes(const wann_index *index);
 int wann_last_dense_rows(const wann_index *index);
+/* Long bfloat16 rows on the dense path (see WANN_DTYPE_BF16).
+ * wann_set_dense_long_rows: whether rows of 129 .. 2048 elements take the MFMA prefilter path in the NEXT batches (a batch
+ * submitted earlier keeps what it was submitted with), in every call form.  Returns the setting now in force, 0 / 1: asking for 1
+ * on an index whose element type has no such kernel -- every type but WANN_DTYPE_BF16; the other types' long rows hang on
+ * WANN_DENSE_LONG_ROWS -- leaves it at 0 and returns 0.  Allocates and frees nothing; applies to every replica of WANN_DEVICES; a
+ * NEGATIVE error for a null index.  Changes no result row: what the dense path cannot prove goes to the exact scan as before.
+ * wann_dense_long_rows: that setting (0 after wann_index_create; 0 for a null index). */
+int wann_set_dense_long_rows(wann_index *index, int on);
+int wann_dense_long_rows(const wann_index *index);
 
 /* WIDE ROWS: stop as at k, keep up to `width` entries (not calls of the reference; it computes this and drops the tail).
  * The reference's query() (src/postfilter_vamana.h:141-188) returns the whole filtered frontier of the last beam it searched;

@@ -116,8 +116,8 @@ struct CoverArgs {
 //                                      / k_gemm_scores_wide4
 //   float16        16 .. 128           -                         129 .. 2048 (kGemmMaxFloats)
 //                  k_gemm_scores<W>                              k_gemm_scores_hslab
-//   bfloat16       16 .. 128           -                         -
-//                  k_gemm_scores<W>, two products (the row is its own high bf16 term)
+//   bfloat16       16 .. 128           -                         129 .. 2048 (kGemmMaxFloats), opt-in PER INDEX: wann_set_dense_long_rows
+//                  k_gemm_scores<W>, two products (the row is its own high bf16 term)           k_gemm_scores_bfslab (dense_row_class(ix, true))
 //   one-byte shadow rows of a float32 index (internal view type 6, wann_set_dense_rows)
 //                  16 .. 128           -                         -
 //                  k_gemm_scores<W> of wann_gemm_kernels_w8.inc: the bfloat16 kernel, a quarter of the float32 bytes fetched
@@ -128,11 +128,17 @@ struct CoverArgs {
 //
 // Anything longer, and a stride that is not a multiple of 16 words, is kRowsNone: the exact scan.
 enum DenseRows { kRowsNone, kRowsNarrow, kRowsWide, kRowsLong };
-inline DenseRows dense_row_class(const IndexView &ix) {
+// the row types whose long class hangs on the index's own switch (wann_set_dense_long_rows) instead of the process-wide one: on
+// every other type the switch stays off
+constexpr bool dense_long_switch_type(int dtype) { return dtype == kRowsBF16; }
+// long_switch: the index's wann_set_dense_long_rows setting (the host), or "the batch was admitted" (a unit's launchers, which
+// only pick among the unit's kernels); without it every answer is what it was before the switch existed
+inline DenseRows dense_row_class(const IndexView &ix, bool long_switch = false) {
   const bool bytes = byte_rows(ix.dtype);
   const int words = query_words(ix);
   if ((ix.stride & 15) || words < 16 || words > (bytes ? kGemmMaxBytes / 4 : kGemmMaxFloats)) return kRowsNone;
   if (words <= 128) return kRowsNarrow;
+  if (ix.dtype == kRowsBF16 && long_switch) return kRowsLong;          // (the index has opted in)
   if (ix.dtype == kRowsBF16 || ix.dtype == kRowsF8) return kRowsNone;  // bfloat16 / float8 rows beyond 128 elements: the exact scan, with or without WANN_DENSE_LONG_ROWS
   // (the view of a float32 index's one-byte shadow rows, wann_set_dense_rows: its score kernel is the bfloat16 one with a byte
   // fetch and covers the narrow class alone -- longer rows are scored from the float32 rows)

@@ -165,3 +165,161 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
 #undef WANN_FETCH
 }
 WANN_GNS_END
+
+// Bfloat16 rows of 129 .. 2048 elements (opt-in per index: wann_set_dense_long_rows): k_gemm_scores_bfslab, a K-loop over 2 .. 16
+// slabs of 128 elements with the work shape, tiles, selection and hand-over of k_gemm_scores_long, and these parts of its own:
+//   * the point operand is the row's bytes: a slab of a point is 256 B of bf16, copied HBM -> registers -> LDS as it arrives
+//     (no split, no conversion, no VALU work), PB = 272 B a staged row -- the narrow kernel's RB rule, an odd multiple of 16;
+//     128 points take 34 KiB where the float32 K-loop stages 66 KiB;
+//   * the freed LDS holds a SECOND point buffer: a unit (step, slab) multiplies out of Ps[u & 1] while the next unit is written
+//     to Ps[(u + 1) & 1] -- the writes wait for no barrier, and a unit ends with ONE barrier where k_gemm_scores_long has two.
+//     (HBM -> LDS directly was not built: global_load_lds writes a wave's 64 x 16 B contiguously, four rows without their pads,
+//     so the padded layout the ds_read_b128 of the B operand needs would cost an LDS -> LDS pass; see DESIGN.md 3.5)
+//   * the query operand (pre-split by the float32 unit's k_split_queries, qw words a row, [hi | lo] as k_gemm_scores_long stages
+//     it) is single-buffered but WAVE-PRIVATE: wave wv multiplies queries 32 wv .. 32 wv + 31 only, so it stages exactly those
+//     rows itself, behind its own reads of the previous slab -- LDS operations of one wave complete in order;
+//   * a k-step runs two products per tile, bh x a_lo then bh x a_hi: k_gemm_scores_long's order without its bl x a_hi, which
+//     on such a row adds only zeros.  The accumulators hold that kernel's values on the upcast rows, bit for bit.
+//   * base[] and rid[] are kept per step parity: the next step's values are written while the current step still reads its own.
+// Two row lengths, as for float16 rows: a point row is `stride` words = 2 stride elements (padded to 32), the split query and the
+// k-steps go by qw = d rounded up to 16 <= 2 stride.  Fetch offsets are clamped into the row / into qw; the last slab runs only
+// the k-steps the row has and never reads what the clamped fetches staged beyond them.
+// (a namespace of its own: tests/test_bfloat16.py counts the score kernels of dt_bf16 by name)
+namespace bf16_long {
+__global__ __launch_bounds__(256, 2) void k_gemm_scores_bfslab(GemmArgs A) {  // (2: a register cap of 256, the unit's; the LDS admits one workgroup)
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const IndexView &ix = A.ix;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  constexpr int W = 128, S = W / 16;
+  constexpr int PB = 2 * W + 16;  // bytes per staged point: one bf16 slab row + 16
+  constexpr int QB = 4 * W + 16;  // bytes per staged query: hi | lo bf16 + 16
+  unsigned char *Ps = smem;                                       // [2][128][PB] points of the current and the next unit
+  unsigned char *Qs = smem + 2 * 128 * PB;                        // [128][QB] queries of the slab; rows 32 wv .. + 31 belong to wave wv
+  float *base = reinterpret_cast<float *>(Qs + 128 * QB);         // [2][128] per step parity and staged point: |p|^2 / 0
+  int *rid = reinterpret_cast<int *>(base + 256);                 // [2][128] per step parity: the step's point rows
+  const int half = lane >> 5, col = lane & 31;
+  const bool mips = ix.metric == 1;
+  const float scale = mips ? -1.f : -2.f;
+  const int ntiles = A.plan[P_NTILES];
+  const int stride = ix.stride, qw = qv_words(ix), nslab = (qw + W - 1) / W;
+
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const GemmGroup grp = A.groups[A.tile_group[t]];
+    const int tl = t - grp.tile0, ch = tl / grp.nqt, q0 = (tl - ch * grp.nqt) << 7;
+    const int64_t w = grp.b - grp.a, wlast = w - 1;
+    const int64_t p_begin = (int64_t)ch * kGemmPointChunk;
+    const int64_t p_end = (p_begin + kGemmPointChunk < w) ? (p_begin + kGemmPointChunk) : w;
+    const int nstep = (int)((p_end - p_begin + 127) >> 7);
+    __syncthreads();  // the previous tile is done with the staging areas and the rows
+    if (tid < 128) rid[tid] = window_row(ix, grp.a + min(p_begin + tid, wlast));
+    // this lane's two query rows, 32 wv + 16 p + lane / 4 (its own wave's), split: qw words, hi pairs then lo pairs (rows beyond
+    // the group's last query repeat it; their lanes store nothing)
+    const unsigned char *qsrc[2];
+#pragma unroll
+    for (int p = 0; p < 2; p++)
+      qsrc[p] = reinterpret_cast<const unsigned char *>(A.qsplit + (int64_t)A.gq[grp.qoff + min(q0 + 32 * wv + 16 * p + (lane >> 2), grp.qcount - 1)] * qw);
+    __syncthreads();  // step 0's rows are in rid[0]
+    const int myrow = q0 + 32 * wv + col;
+    const bool live = myrow < grp.qcount;
+    const int64_t nsteps = (w + 127) >> 7;
+    f32x4 *erow = reinterpret_cast<f32x4 *>(A.scores + grp.soff) + ((int64_t)(live ? myrow : q0) * nsteps + (p_begin >> 7)) * 2 + half;
+    // A unit's fetch: sixteen threads per point row (256 B contiguous), eight rows per thread; four lanes per query row (64 B
+    // contiguous per term).  With a step's first slab come its norms and the NEXT step's rows.
+    u32x4 pre[8], qre[16];  // qre: pieces 0 .. 3 of a row: hi pairs, 4 .. 7: lo pairs
+    float pre_n = 0.f;
+    int pre_rid = 0;
+#define WANN_BF_FETCH(T, SL, NEWSTEP)                                                                      \
+  {                                                                                                        \
+    const int *rr = rid + 128 * ((T) & 1);                                                                 \
+    _Pragma("unroll") for (int i = 0; i < 8; i++) {                                                        \
+      const unsigned char *src = reinterpret_cast<const unsigned char *>(ix.points + (int64_t)rr[16 * i + (tid >> 4)] * stride); \
+      pre[i] = *reinterpret_cast<const u32x4 *>(src + min(2 * W * (SL) + 16 * (tid & 15), 4 * stride - 16)); \
+    }                                                                                                      \
+    _Pragma("unroll") for (int p = 0; p < 2; p++)                                                          \
+      _Pragma("unroll") for (int x = 0; x < 8; x++) {                                                      \
+        const int cb = 2 * W * (SL) + 16 * (lane & 3) + 64 * (x & 3);                                      \
+        qre[p * 8 + x] = *reinterpret_cast<const u32x4 *>(qsrc[p] + (x >> 2) * 2 * qw + min(cb, 2 * qw - 16)); \
+      }                                                                                                    \
+    if ((NEWSTEP) && tid < 128) {                                                                          \
+      if (!mips) pre_n = A.pnorm2[rr[tid]];                                                                \
+      pre_rid = window_row(ix, grp.a + min(p_begin + 128 * (int64_t)((T) + 1) + tid, wlast));              \
+    }                                                                                                      \
+  }
+    // ... and its way into the LDS: the points into buffer U & 1, this wave's queries over the slab it has just multiplied
+#define WANN_BF_STAGE(U, T, NEWSTEP)                                                                       \
+  {                                                                                                        \
+    unsigned char *pd = Ps + ((U) & 1) * 128 * PB + (tid >> 4) * PB + 16 * (tid & 15);                     \
+    _Pragma("unroll") for (int i = 0; i < 8; i++) *reinterpret_cast<u32x4 *>(pd + 16 * i * PB) = pre[i];   \
+    unsigned char *qd = Qs + (32 * wv + (lane >> 2)) * QB + 16 * (lane & 3);                               \
+    _Pragma("unroll") for (int p = 0; p < 2; p++)                                                          \
+      _Pragma("unroll") for (int x = 0; x < 8; x++)                                                        \
+        *reinterpret_cast<u32x4 *>(qd + 16 * p * QB + (x >> 2) * 2 * W + 64 * (x & 3)) = qre[p * 8 + x];   \
+    if ((NEWSTEP) && tid < 128) {                                                                          \
+      base[128 * ((T) & 1) + tid] = (p_begin + 128 * (int64_t)(T) + tid < p_end) ? (mips ? 0.f : pre_n) : kHuge; /* positions beyond the window never win */ \
+      rid[128 * (((T) + 1) & 1) + tid] = pre_rid;                                                          \
+    }                                                                                                      \
+  }
+    WANN_BF_FETCH(0, 0, true)
+    WANN_BF_STAGE(0, 0, true)
+    __syncthreads();
+    f32x16 acc[4];
+    int u = 0;  // units of this tile so far: the current one multiplies out of Ps[u & 1]
+    for (int st = 0; st < nstep; st++) {
+      for (int sl = 0; sl < nslab; sl++, u++) {
+        // the next unit: the next slab of this step, or slab 0 of the next step (none after the tile's last unit); its loads
+        // are in flight during this unit's MFMAs
+        const bool newstep = sl + 1 == nslab;
+        const bool more = !newstep || st + 1 < nstep;
+        const int nst = newstep ? st + 1 : st, nsl = newstep ? 0 : sl + 1;
+        if (more) WANN_BF_FETCH(nst, nsl, newstep)
+        if (sl == 0) {
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[j][r] = 0.f;
+        }
+        const unsigned char *pb = Ps + (u & 1) * 128 * PB + col * PB + 16 * half;
+        const unsigned char *qa = Qs + (32 * wv + col) * QB + 16 * half;
+        // two ds_read_b128 of the A operand and four of the B operand per k-step, for eight MFMAs
+#define WANN_BF_KSTEP(s)                                                                                   \
+  {                                                                                                        \
+    const bf16x8 a_hi = *reinterpret_cast<const bf16x8 *>(qa + 32 * (s));                                  \
+    const bf16x8 a_lo = *reinterpret_cast<const bf16x8 *>(qa + 2 * W + 32 * (s));                          \
+    bf16x8 bh[4];                                                                                          \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) bh[j] = *reinterpret_cast<const bf16x8 *>(pb + j * 32 * PB + 32 * (s)); \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[j], a_lo, acc[j], 0, 0, 0); \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[j], a_hi, acc[j], 0, 0, 0); \
+  }
+        const int ks = min(S, (qw - W * sl) >> 4);  // k-steps of this slab (workgroup-uniform)
+        // (one loop for full and partial slabs, as in k_gemm_scores_hslab: where an unrolled copy and the loop join, the
+        // accumulators live twice -- 51 registers spilled under the cap of 256)
+#pragma unroll 1
+        for (int s = 0; s < ks; s++) WANN_BF_KSTEP(s)
+#undef WANN_BF_KSTEP
+        if (newstep) {
+          // the four smallest of this lane's 64 scores, sorted; low six mantissa bits = 16 j + reg (which position)
+          const float *bs = base + 128 * (st & 1);
+          float m1 = kHuge, m2 = kHuge, m3 = kHuge, m4 = kHuge;
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+              const f32x4 b4 = *reinterpret_cast<const f32x4 *>(bs + 32 * j + 8 * g + 4 * half);
+#pragma unroll
+              for (int r = 0; r < 4; r++) {
+                const float sc = fmaf(scale, acc[j][4 * g + r], b4[r]);
+                const float x = __uint_as_float((__float_as_uint(sc) & ~63u) | (uint32_t)(16 * j + 4 * g + r));
+                insert4(m1, m2, m3, m4, x);
+              }
+            }
+          if (live) erow[2 * st] = f32x4{m1, m2, m3, m4};
+        }
+        if (more) WANN_BF_STAGE(u + 1, nst, newstep)
+        __syncthreads();  // the next unit is staged, and every wave is done with this one's point buffer
+      }
+    }
+#undef WANN_BF_FETCH
+#undef WANN_BF_STAGE
+  }
+}
+}  // namespace bf16_long

@@ -34,8 +34,9 @@
 //                    loads; opt-in), longer ones take the exact scan.
 //   bfloat16 rows (WANN_DT = 5) a k_gemm_scores of their own (wann_gemm_kernels_bf16.inc): a bfloat16 row is its own high bf16
 //                    term and has no low term, so a point is staged as one row, copied as it arrives, and a k-step runs two
-//                    products; the scores are the float32 kernel's on the upcast row.  Rows of up to 128 elements; longer
-//                    ones take the exact scan.
+//                    products; the scores are the float32 kernel's on the upcast row.  Rows of up to 128 elements; rows of
+//                    129 .. 2048 on an index that opts in (wann_set_dense_long_rows): k_gemm_scores_bfslab, a slab walk of its
+//                    own in the same file; longer ones take the exact scan.
 //   byte rows (WANN_DT = 1 / 2) k_gemm_scores_b on v_mfma_i32_32x32x32_i8: exact int32 sums, one product, no error bound --
 //                    see wann_gemm_kernels_bytes.inc.  Rows of 513 .. 2048 bytes: k_gemm_scores_bslab (both operands staged per
 //                    256-byte slab, quantised keys; opt-in), longer ones take the exact scan.

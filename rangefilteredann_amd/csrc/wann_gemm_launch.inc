@@ -35,7 +35,8 @@ static const char *unit_rerank_cover(const CoverArgs &c, void *stream) {
 #endif
 
 static ScoreKernel pick_score_kernel(const IndexView &ix) {
-  const DenseRows rows = dense_row_class(ix);
+  // (a type whose long class is the index's own switch: the host admitted the batch with it, this unit only picks the kernel)
+  const DenseRows rows = dense_row_class(ix, dense_long_switch_type(ix.dtype));
   const int words = query_words(ix);
   void (*kern)(GemmArgs) = nullptr;
 #if WANN_BYTE_ROWS
@@ -59,8 +60,11 @@ static ScoreKernel pick_score_kernel(const IndexView &ix) {
   // long: run-time slab count, both operands staged per slab (queries pre-split, `words` words a row), one workgroup per CU
 #if WANN_DT == 3
   if (rows == kRowsLong) return {k_gemm_scores_hslab, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
-#elif WANN_DT == 5 || WANN_QUAD_ROWS
-  // (bfloat16 and float8 rows, and the one-byte shadow rows of a float32 index: narrow only; dense_row_class names no other class for them)
+#elif WANN_DT == 5
+  // two point buffers of 128 x 272 B, the query slab, base[] and rid[] per step parity: 136 KiB, one workgroup per CU
+  if (rows == kRowsLong) return {bf16_long::k_gemm_scores_bfslab, (size_t)2 * 128 * (2 * 128 + 16) + 128 * (4 * 128 + 16) + 4 * 128 * 4, 1, true};
+#elif WANN_QUAD_ROWS
+  // (float8 rows and the one-byte shadow rows of a float32 index: narrow only; dense_row_class names no other class for them)
 #else
   if (rows == kRowsLong) return {k_gemm_scores_long, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
   if (rows == kRowsWide) {  // slabs of 128, A operand in registers, one workgroup per CU
@@ -112,7 +116,7 @@ static const char *unit_point_sums(const IndexView &ix, float *norm2, unsigned i
   return gerr_of(hipGetLastError());
 }
 
-#if !WANN_HALF_ROWS && WANN_DT != 8  // (float16 rows: the float32 unit's k_split_queries; bfloat16 / float8 rows have no long class)
+#if !WANN_HALF_ROWS && WANN_DT != 8  // (float16 and bfloat16 rows: the float32 unit's k_split_queries; float8 rows have no long class)
 static const char *unit_prep_queries(const float *queries, int64_t nq, int d, int words, uint32_t *out, void *stream) {
 #if WANN_BYTE_ROWS
   const int64_t items = nq * words;  // a thread per packed word

@@ -54,6 +54,7 @@ Tuning snapshot_tuning(wann_index &I) {
   t.byte_rows = row_switch_in_force(I, kByteRowsSwitch);
   t.scan_rows = row_switch_in_force(I, kScanRowsSwitch);
   t.dense_rows = row_switch_in_force(I, kDenseRowsSwitch);
+  t.dense_long_rows = row_switch_in_force(I, kDenseLongRowsSwitch);
   return t;
 }
 

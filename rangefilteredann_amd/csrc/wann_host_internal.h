@@ -180,6 +180,10 @@ struct wann_index {
   bool dense_rows_on = false;
   std::atomic<int> last_dense_rows{0};  // a score launch of the last finished batch read the copy
   bool has_dense_copy() const { return dense_view.dtype == kRowsU8Widened && dense_view.points != nullptr; }
+  // wann_set_dense_long_rows (under tune_mu; off by default, only ever on for a row type whose long class is per index --
+  // dense_long_switch_type, wann_gemm_device.h: bfloat16): rows of 129 .. 2048 elements take the dense path of the next batches
+  bool dense_long_rows_on = false;
+  bool has_dense_long_switch() const { return wann::dense_long_switch_type(dtype); }
   bool has_half_copy() const { return d_half.p != nullptr; }
   bool has_byte_copy() const { return d_bytes.p != nullptr; }
   bool has_scan_copy() const { return has_half_copy() || has_byte_copy(); }
@@ -273,6 +277,8 @@ constexpr RowSwitch kHalfRowsSwitch = {&wann_index::half_rows_on, &wann_index::h
 constexpr RowSwitch kByteRowsSwitch = {&wann_index::byte_rows_on, &wann_index::has_byte_copy, &wann_index::last_byte_rows};
 constexpr RowSwitch kScanRowsSwitch = {&wann_index::scan_rows_on, &wann_index::has_scan_copy, &wann_index::last_scan_rows};
 constexpr RowSwitch kDenseRowsSwitch = {&wann_index::dense_rows_on, &wann_index::has_dense_copy, &wann_index::last_dense_rows};
+// (wann_set_dense_long_rows: bounded by the row type, not by a copy; no "last" -- the dense counters say what a batch did)
+constexpr RowSwitch kDenseLongRowsSwitch = {&wann_index::dense_long_rows_on, &wann_index::has_dense_long_switch, nullptr};
 // (under I.tune_mu)
 inline bool row_switch_in_force(const wann_index &I, const RowSwitch &s) { return I.*s.on && (I.*s.has_copy)(); }
 

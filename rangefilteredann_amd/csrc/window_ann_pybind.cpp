@@ -287,6 +287,10 @@ class Index {
   bool set_dense_rows(bool on) { return set_row_switch(wann_set_dense_rows, on, "set_dense_rows failed"); }
   bool dense_rows() const { return wann_dense_rows(h_) != 0; }
   int64_t dense_rows_bytes() const { return wann_dense_rows_bytes(h_); }
+  // bfloat16 indexes: rows of 129 .. 2048 elements take the dense path too, on k_gemm_scores_bfslab (wann_set_dense_long_rows, off
+  // by default); returns the setting now in force -- False on an index of any other element type
+  bool set_dense_long_rows(bool on) { return set_row_switch(wann_set_dense_long_rows, on, "set_dense_long_rows failed"); }
+  bool dense_long_rows() const { return wann_dense_long_rows(h_) != 0; }
 
   // float16 / bfloat16 / float8 indexes: the full-precision points (any array numpy casts to float32, in the order of the array
   // the index was created from) as the row store of the refined calls (wann_set_refine_rows); None drops the store
@@ -404,6 +408,7 @@ class Index {
     d["byte_rows"] = wann_last_byte_rows(h_);  // 1: they read the one-byte shadow rows (then half_rows is 0)
     d["scan_rows"] = wann_last_scan_rows(h_);  // the rows its k_brute launch read: 0 the index's own, 1 the half rows, 2 the one-byte rows
     d["dense_rows"] = wann_last_dense_rows(h_);  // 1: a score launch of its dense path read the one-byte copy of the rows
+    d["dense_long_rows"] = wann_dense_long_rows(h_);  // the index's wann_set_dense_long_rows setting (a setting, not a count)
     return d;
   }
   static py::dict counters_dict(const wann_counters &c) {
@@ -492,6 +497,8 @@ static void common_defs(py::class_<C> &c) {
       .def("set_dense_rows", &C::set_dense_rows, "on"_a)
       .def("dense_rows", &C::dense_rows)
       .def("dense_rows_bytes", &C::dense_rows_bytes)
+      .def("set_dense_long_rows", &C::set_dense_long_rows, "on"_a)
+      .def("dense_long_rows", &C::dense_long_rows)
       .def("set_refine_rows", &C::set_refine_rows, "points"_a.none(true))
       .def("refine_rows_bytes", &C::refine_rows_bytes)
       .def("batch_search_refined", &C::search_refined, "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a,
