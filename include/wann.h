@@ -142,7 +142,9 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * device-buffer calls fp32 queries (not rounded); labels stay float32; no wann_vamana_* variant; wann_raw_beam_search_typed
  * accepts the type.  The MFMA prefilter path covers rows of up to 128 elements (each byte is also exactly one bfloat16 value: the
  * bfloat16 kernel behind a byte fetch, norms and re-rank on the float8 rows); longer rows take the exact scan, with or without
- * WANN_DENSE_LONG_ROWS.  A float8 index has no shadow copies: wann_half_rows, wann_byte_rows and wann_dense_rows are 0 and the
+ * WANN_DENSE_LONG_ROWS -- unless the INDEX opts in: after wann_set_dense_long_float8(index, 1) rows of 129 .. 2048 elements take
+ * that path too (shared windows, cover groups, exact windows), on k_gemm_scores_f8slab.  wann_set_dense_long_rows stays refused
+ * on a float8 index.  A float8 index has no shadow copies: wann_half_rows, wann_byte_rows and wann_dense_rows are 0 and the
  * four setters return 0 as on any index without a copy.
  * The value is 8: 6 and 7 are INTERNAL view types (the shadow rows above) and stay refused, like 4. */
 enum { WANN_DTYPE_F32 = 0, WANN_DTYPE_U8 = 1, WANN_DTYPE_I8 = 2, WANN_DTYPE_F16 = 3, WANN_DTYPE_BF16 = 5, WANN_DTYPE_F8 = 8 };
@@ -426,6 +428,17 @@ int wann_last_dense_rows(const wann_index *index);
  * wann_dense_long_rows: that setting (0 after wann_index_create; 0 for a null index). */
 int wann_set_dense_long_rows(wann_index *index, int on);
 int wann_dense_long_rows(const wann_index *index);
+/* Long float8 rows on the dense path (see WANN_DTYPE_F8): the same switch for the one type wann_set_dense_long_rows refuses.
+ * wann_set_dense_long_float8: whether rows of 129 .. 2048 elements of a WANN_DTYPE_F8 index take the MFMA prefilter path in the
+ * NEXT batches, in every call form, on k_gemm_scores_f8slab -- the bfloat16 slab kernel behind a fetch that widens each E4M3 byte
+ * to the bfloat16 it also is; the accumulators are the float32 long-row kernel's on the upcast rows: the same ids, distance bits
+ * and dense counters.  Returns the setting now in force, 0 / 1: asking for 1 on an index of any other element type leaves it at 0
+ * and returns 0.  Allocates and frees nothing; applies to every replica of WANN_DEVICES; a NEGATIVE error for a null index.
+ * Changes no result row.  Rows beyond 2048 elements and k > 16 stay on the scan; WANN_DENSE_LONG_ROWS does not move a float8
+ * index, on or off.
+ * wann_dense_long_float8: that setting (0 after wann_index_create; 0 for a null index). */
+int wann_set_dense_long_float8(wann_index *index, int on);
+int wann_dense_long_float8(const wann_index *index);
 
 /* WIDE ROWS: stop as at k, keep up to `width` entries (not calls of the reference; it computes this and drops the tail).
  * The reference's query() (src/postfilter_vamana.h:141-188) returns the whole filtered frontier of the last beam it searched;

@@ -1058,16 +1058,18 @@ int wann_last_dense_rows(const wann_index *I) { return last_row_switch(I, kDense
 
 int wann_set_dense_long_rows(wann_index *I, int on) { return set_row_switch(I, kDenseLongRowsSwitch, on); }
 int wann_dense_long_rows(const wann_index *I) { return row_switch(I, kDenseLongRowsSwitch); }
+int wann_set_dense_long_float8(wann_index *I, int on) { return set_row_switch(I, kDenseLongFloat8Switch, on); }
+int wann_dense_long_float8(const wann_index *I) { return row_switch(I, kDenseLongFloat8Switch); }
 // TEST HOOK, not part of include/wann.h and no commitment: dense_row_class (wann_gemm_device.h) for rows of d elements of an
-// element type, long_rows = the wann_set_dense_long_rows setting assumed -- 0 none, 1 narrow, 2 wide, 3 long; -1: unknown type or
-// d.  The CPU tests read the table through it without a device.
+// element type, long_rows = the switches assumed on (bit 0: wann_set_dense_long_rows, bit 1: wann_set_dense_long_float8) -- 0
+// none, 1 narrow, 2 wide, 3 long; -1: unknown type or d.  The CPU tests read the table through it without a device.
 int wann_test_dense_row_class(int dtype, int64_t d, int long_rows) {
   if (!known_dtype(dtype) || d <= 0 || d > (1 << 24)) return -1;
   IndexView v{};  // (the lengths an index of d such elements has: upload_index)
   v.dtype = dtype;
   v.d = (int32_t)d;
   v.stride = (int32_t)row_stride_words(dtype, d, spec_stride_words(dtype, d));
-  return (int)dense_row_class(v, long_rows != 0);
+  return (int)dense_row_class(v, (long_rows & 1) != 0, (long_rows & 2) != 0);
 }
 int wann_num_replicas(const wann_index *I) { return I ? 1 + (int)I->replicas.size() : -1; }
 

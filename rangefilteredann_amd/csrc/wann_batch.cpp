@@ -13,11 +13,11 @@ namespace wann_host {
 // tile planning and the hand-over to the exact scan all happen on the device: the host enqueues six launches and
 // never waits.
 // Which rows the score kernels take: the table above dense_row_class (wann_gemm_device.h).  The long class is opt-in
-// (WANN_DENSE_LONG_ROWS=1: until it is timed against the scan no batch moves to it by default; bfloat16 rows: the index's own
-// switch, wann_set_dense_long_rows, which alone makes their class long); k > 16 stays on the exact scan.
+// (WANN_DENSE_LONG_ROWS=1: until it is timed against the scan no batch moves to it by default; bfloat16 / float8 rows: the index's
+// own switch, wann_set_dense_long_rows / wann_set_dense_long_float8, which alone makes their class long); k > 16 stays on the exact scan.
 static bool dense_rows_ok(const wann_index &I, const Tuning &T, int k) {
-  const DenseRows rows = dense_row_class(I.view, T.dense_long_rows);
-  return k <= kSelect / 2 && rows != kRowsNone && (rows != kRowsLong || T.dense_long || T.dense_long_rows);
+  const DenseRows rows = dense_row_class(I.view, T.dense_long_rows, T.dense_long_float8);
+  return k <= kSelect / 2 && rows != kRowsNone && (rows != kRowsLong || T.dense_long || T.dense_long_rows || T.dense_long_float8);
 }
 
 // wann_set_dense_rows: the view the score launches of this call's dense path read instead of I.view -- the one-byte copy of a
@@ -41,7 +41,7 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   // need them packed to bytes (nq x stride words as well): the same buffer, the same cap.  qwords: the query's row length in
   // words -- the stride, but for float16 rows, whose stride counts half rows.
   const int qwords = query_words(I.view);
-  const bool long_rows = dense_row_class(I.view, T.dense_long_rows) == kRowsLong;
+  const bool long_rows = dense_row_class(I.view, T.dense_long_rows, T.dense_long_float8) == kRowsLong;
   if (long_rows && (unsigned long long)nq * (unsigned long long)qwords > (64ull << 20)) return;
   if (!I.have_norms) {
     if (bytes) {  // exact integer sums of the rows (wann_gemm_kernels_bytes.inc)
@@ -104,7 +104,7 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   ga.pnorm2_max_bits = I.d_pnorm2_max.p;
   ga.pterm = I.d_pterm.p;
   if (long_rows) {
-    // k_gemm_scores_long / _hslab / _bfslab take the queries already split into their bf16 terms: once per batch instead of once per
+    // k_gemm_scores_long / _hslab / _bfslab / _f8slab take the queries already split into their bf16 terms: once per batch instead of once per
     // (tile, step), nq x qwords x 4 bytes; k_gemm_scores_bslab takes them packed to biased bytes, the same size.  Counted like
     // the norms: a PrefilterIndex has never reported its dense buffers.
     I.g_qsplit.ensure((size_t)nq * (size_t)qwords);

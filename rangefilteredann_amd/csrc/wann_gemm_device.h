@@ -121,8 +121,9 @@ struct CoverArgs {
 //   one-byte shadow rows of a float32 index (internal view type 6, wann_set_dense_rows)
 //                  16 .. 128           -                         -
 //                  k_gemm_scores<W> of wann_gemm_kernels_w8.inc: the bfloat16 kernel, a quarter of the float32 bytes fetched
-//   float8         16 .. 128           -                         -
-//                  k_gemm_scores<W> of the one-byte rows (each E4M3 byte is one bf16: the bfloat16 kernel behind a byte fetch)
+//   float8         16 .. 128           -                         129 .. 2048 (kGemmMaxFloats), opt-in PER INDEX: wann_set_dense_long_float8
+//                  k_gemm_scores<W> of the one-byte rows (each E4M3 byte is one bf16:            k_gemm_scores_f8slab (dense_row_class(ix, false, true)):
+//                  the bfloat16 kernel behind a byte fetch)                                     k_gemm_scores_bfslab behind a byte-widening fetch
 //   uint8 / int8   16 .. 128 (512 B)   -                         129 .. 512 (kGemmMaxBytes / 4)
 //                  k_gemm_scores_b<N>                            k_gemm_scores_bslab, quantised keys: k_rerank_bslab
 //
@@ -131,14 +132,19 @@ enum DenseRows { kRowsNone, kRowsNarrow, kRowsWide, kRowsLong };
 // the row types whose long class hangs on the index's own switch (wann_set_dense_long_rows) instead of the process-wide one: on
 // every other type the switch stays off
 constexpr bool dense_long_switch_type(int dtype) { return dtype == kRowsBF16; }
-// long_switch: the index's wann_set_dense_long_rows setting (the host), or "the batch was admitted" (a unit's launchers, which
-// only pick among the unit's kernels); without it every answer is what it was before the switch existed
-inline DenseRows dense_row_class(const IndexView &ix, bool long_switch = false) {
+// ... and the type whose long class hangs on wann_set_dense_long_float8: a switch of its own, because wann_set_dense_long_rows is
+// pinned to refuse a float8 index
+constexpr bool dense_long_float8_type(int dtype) { return dtype == kRowsF8; }
+// long_switch / long_f8_switch: the index's wann_set_dense_long_rows / wann_set_dense_long_float8 setting (the host), or "the
+// batch was admitted" (a unit's launchers, which only pick among the unit's kernels); without them every answer is what it was
+// before the switches existed, and each moves its own type alone
+inline DenseRows dense_row_class(const IndexView &ix, bool long_switch = false, bool long_f8_switch = false) {
   const bool bytes = byte_rows(ix.dtype);
   const int words = query_words(ix);
   if ((ix.stride & 15) || words < 16 || words > (bytes ? kGemmMaxBytes / 4 : kGemmMaxFloats)) return kRowsNone;
   if (words <= 128) return kRowsNarrow;
   if (ix.dtype == kRowsBF16 && long_switch) return kRowsLong;          // (the index has opted in)
+  if (ix.dtype == kRowsF8 && long_f8_switch) return kRowsLong;         // (likewise)
   if (ix.dtype == kRowsBF16 || ix.dtype == kRowsF8) return kRowsNone;  // bfloat16 / float8 rows beyond 128 elements: the exact scan, with or without WANN_DENSE_LONG_ROWS
   // (the view of a float32 index's one-byte shadow rows, wann_set_dense_rows: its score kernel is the bfloat16 one with a byte
   // fetch and covers the narrow class alone -- longer rows are scored from the float32 rows)

@@ -9,6 +9,9 @@
 // The query side is the float32 kernel's: the tile of 128 float32 queries passes through the staging area (128 x (STRIDE + 4)
 // floats) on its way into registers, so the workgroup's LDS stays the float32 kernel's size although the staged points fill
 // only half of it -- the launcher, the occupancy (two workgroups per CU) and every tuning figure are unchanged.
+// (The float8 unit, WANN_DT = 8, includes this file too, for the slab kernel at its end alone: its narrow kernel is
+// wann_gemm_kernels_w8.inc's.)
+#if WANN_DT == 5
 WANN_GNS_BEGIN
 template <int STRIDE>  // row length of the float32 upcast (d rounded up to 16): a multiple of 16, <= 128
 __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
@@ -165,6 +168,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
 #undef WANN_FETCH
 }
 WANN_GNS_END
+#endif  // WANN_DT == 5 (the narrow kernel)
 
 // Bfloat16 rows of 129 .. 2048 elements (opt-in per index: wann_set_dense_long_rows): k_gemm_scores_bfslab, a K-loop over 2 .. 16
 // slabs of 128 elements with the work shape, tiles, selection and hand-over of k_gemm_scores_long, and these parts of its own:
@@ -185,8 +189,35 @@ WANN_GNS_END
 // k-steps go by qw = d rounded up to 16 <= 2 stride.  Fetch offsets are clamped into the row / into qw; the last slab runs only
 // the k-steps the row has and never reads what the clamped fetches staged beyond them.
 // (a namespace of its own: tests/test_bfloat16.py counts the score kernels of dt_bf16 by name)
-namespace bf16_long {
-__global__ __launch_bounds__(256, 2) void k_gemm_scores_bfslab(GemmArgs A) {  // (2: a register cap of 256, the unit's; the LDS admits one workgroup)
+//
+// Float8 rows of 129 .. 2048 elements (WANN_DT = 8; opt-in per index: wann_set_dense_long_float8): k_gemm_scores_f8slab, THIS text
+// with another point side -- an E4M3 value is one bfloat16 as well, so everything above holds, and the MFMA loop reads the same
+// staged rows.  What differs is how a slab of a point gets there:
+//   * it is 128 B of the row, in the interleaved layout of the one-byte rows (u8_row_position): four groups of 32 elements, a
+//     group = two 16-byte chunks, chunk h = the blocks of four 2 s + h, s = 0 .. 3.  Two threads serve a point row, as in
+//     wann_gemm_kernels_w8.inc: thread h loads chunk h of each of the slab's groups -- four 16-byte loads a thread and unit where
+//     the bfloat16 rows take eight, and sixteen prefetch registers instead of thirty-two;
+//   * the bytes wait as raw quads while the current unit multiplies and are widened ONCE, where they are staged (widen4_bf16:
+//     v_cvt_pk_f32_fp8, top halves -- sixteen calls a thread and unit): all four waves read every staged point, so widening on
+//     the read side would do it four times.  Block 2 s + h of group x goes to its NATURAL place, bytes 64 x + 16 s + 8 h of the
+//     272-byte row;
+//   * a row is `stride` words = 4 stride BYTES = 4 stride elements (padded to 64); qw = d rounded up to 16 <= 4 stride.  A group
+//     a k-step reads begins below qw, so all of it lies inside the row: only groups that are never multiplied are fetched from a
+//     clamped offset.  Where the last slab ends in half a group (qw an odd multiple of 16: d = 129 .. 144 is qw = 144 in a
+//     192-byte row) all four slots of the group are staged all the same -- unlike the narrow kernel's rows (its ns = 2 case) a
+//     staged slab row always has room for a whole group, its second half is the row's zero padding, and no k-step reads it.
+// (a namespace of its own here too: tests/test_float8.py counts the score kernels of dt_f8 by name)
+#if WANN_DT == 8
+#define WANN_BF_NS f8_long
+#define WANN_BF_KERNEL k_gemm_scores_f8slab
+#define WANN_BF_PRE 4  // 16-byte registers of a unit's point fetch: a chunk of each of the slab's four groups
+#else
+#define WANN_BF_NS bf16_long
+#define WANN_BF_KERNEL k_gemm_scores_bfslab
+#define WANN_BF_PRE 8  // eight rows, 16 B of each
+#endif
+namespace WANN_BF_NS {
+__global__ __launch_bounds__(256, 2) void WANN_BF_KERNEL(GemmArgs A) {  // (2: a register cap of 256, the unit's; the LDS admits one workgroup)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const IndexView &ix = A.ix;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -225,16 +256,27 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores_bfslab(GemmArgs A) {  //
     f32x4 *erow = reinterpret_cast<f32x4 *>(A.scores + grp.soff) + ((int64_t)(live ? myrow : q0) * nsteps + (p_begin >> 7)) * 2 + half;
     // A unit's fetch: sixteen threads per point row (256 B contiguous), eight rows per thread; four lanes per query row (64 B
     // contiguous per term).  With a step's first slab come its norms and the NEXT step's rows.
-    u32x4 pre[8], qre[16];  // qre: pieces 0 .. 3 of a row: hi pairs, 4 .. 7: lo pairs
+    // (float8 rows: two threads per point row, one row per thread -- chunk tid & 1 of each of the slab's four groups)
+    u32x4 pre[WANN_BF_PRE], qre[16];  // qre: pieces 0 .. 3 of a row: hi pairs, 4 .. 7: lo pairs
     float pre_n = 0.f;
     int pre_rid = 0;
-#define WANN_BF_FETCH(T, SL, NEWSTEP)                                                                      \
-  {                                                                                                        \
-    const int *rr = rid + 128 * ((T) & 1);                                                                 \
+#if WANN_DT == 8
+#define WANN_BF_FETCH_POINTS(SL)                                                                           \
+    {                                                                                                      \
+      const unsigned char *src = reinterpret_cast<const unsigned char *>(ix.points + (int64_t)rr[tid >> 1] * stride) + 16 * (tid & 1); \
+      _Pragma("unroll") for (int x = 0; x < 4; x++) pre[x] = *reinterpret_cast<const u32x4 *>(src + min(W * (SL) + 32 * x, 4 * stride - 32)); \
+    }
+#else
+#define WANN_BF_FETCH_POINTS(SL)                                                                           \
     _Pragma("unroll") for (int i = 0; i < 8; i++) {                                                        \
       const unsigned char *src = reinterpret_cast<const unsigned char *>(ix.points + (int64_t)rr[16 * i + (tid >> 4)] * stride); \
       pre[i] = *reinterpret_cast<const u32x4 *>(src + min(2 * W * (SL) + 16 * (tid & 15), 4 * stride - 16)); \
-    }                                                                                                      \
+    }
+#endif
+#define WANN_BF_FETCH(T, SL, NEWSTEP)                                                                      \
+  {                                                                                                        \
+    const int *rr = rid + 128 * ((T) & 1);                                                                 \
+    WANN_BF_FETCH_POINTS(SL)                                                                               \
     _Pragma("unroll") for (int p = 0; p < 2; p++)                                                          \
       _Pragma("unroll") for (int x = 0; x < 8; x++) {                                                      \
         const int cb = 2 * W * (SL) + 16 * (lane & 3) + 64 * (x & 3);                                      \
@@ -246,10 +288,21 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores_bfslab(GemmArgs A) {  //
     }                                                                                                      \
   }
     // ... and its way into the LDS: the points into buffer U & 1, this wave's queries over the slab it has just multiplied
+    // (float8 rows: widened here, block 2 s + (tid & 1) of group x to its natural place in the bf16 row)
+#if WANN_DT == 8
+#define WANN_BF_STAGE_POINTS(U)                                                                            \
+    unsigned char *pd = Ps + ((U) & 1) * 128 * PB + (tid >> 1) * PB + 8 * (tid & 1);                       \
+    _Pragma("unroll") for (int x = 0; x < 4; x++)                                                          \
+      _Pragma("unroll") for (int s = 0; s < 4; s++)                                                        \
+        *reinterpret_cast<uint2 *>(pd + 64 * x + 16 * s) = WANN_DT_NS::widen4_bf16(pre[x][s]);
+#else
+#define WANN_BF_STAGE_POINTS(U)                                                                            \
+    unsigned char *pd = Ps + ((U) & 1) * 128 * PB + (tid >> 4) * PB + 16 * (tid & 15);                     \
+    _Pragma("unroll") for (int i = 0; i < 8; i++) *reinterpret_cast<u32x4 *>(pd + 16 * i * PB) = pre[i];
+#endif
 #define WANN_BF_STAGE(U, T, NEWSTEP)                                                                       \
   {                                                                                                        \
-    unsigned char *pd = Ps + ((U) & 1) * 128 * PB + (tid >> 4) * PB + 16 * (tid & 15);                     \
-    _Pragma("unroll") for (int i = 0; i < 8; i++) *reinterpret_cast<u32x4 *>(pd + 16 * i * PB) = pre[i];   \
+    WANN_BF_STAGE_POINTS(U)                                                                                \
     unsigned char *qd = Qs + (32 * wv + (lane >> 2)) * QB + 16 * (lane & 3);                               \
     _Pragma("unroll") for (int p = 0; p < 2; p++)                                                          \
       _Pragma("unroll") for (int x = 0; x < 8; x++)                                                        \
@@ -320,6 +373,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores_bfslab(GemmArgs A) {  //
     }
 #undef WANN_BF_FETCH
 #undef WANN_BF_STAGE
+#undef WANN_BF_FETCH_POINTS
+#undef WANN_BF_STAGE_POINTS
   }
 }
-}  // namespace bf16_long
+}  // namespace bf16_long / f8_long
+#undef WANN_BF_NS
+#undef WANN_BF_KERNEL
+#undef WANN_BF_PRE

@@ -46,7 +46,9 @@
 //                    norms, selection and re-rank stay the float32 unit's, on the float32 rows.
 //   float8 rows (WANN_DT = 8, wann_gemm_kernels_f8.hip) that same kernel and fetch, each E4M3 byte widened to the bfloat16 it
 //                    also is (four significant bits, exponents 2^-9 .. 2^8).  A FULL unit: k_point_norms, k_rerank,
-//                    k_rerank_cover and the rescue read the float8 rows.  Rows of up to 128 elements; longer ones take the scan.
+//                    k_rerank_cover and the rescue read the float8 rows.  Rows of up to 128 elements; rows of 129 .. 2048 on an
+//                    index that opts in (wann_set_dense_long_float8): k_gemm_scores_f8slab, the text of k_gemm_scores_bfslab
+//                    with a point fetch of its own (wann_gemm_kernels_bf16.inc); longer ones take the scan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -530,6 +532,9 @@ __device__ __forceinline__ void insert4_chain(float &m1, float &m2, float &m3, f
 #include "wann_gemm_kernels_bf16.inc"
 #elif WANN_QUAD_ROWS  // (float8 rows: the same kernel, another widening)
 #include "wann_gemm_kernels_w8.inc"
+#if WANN_DT == 8  // (and the bfloat16 unit's slab kernel behind a byte-widening point fetch: k_gemm_scores_f8slab)
+#include "wann_gemm_kernels_bf16.inc"
+#endif
 #else
 WANN_GNS_BEGIN
 template <int STRIDE>  // padded row length in floats: a multiple of 16, <= 128

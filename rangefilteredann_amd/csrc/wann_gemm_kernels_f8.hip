@@ -2,5 +2,7 @@
 // per element type of the point set, see wann_gemm_kernels_body.inc.  The score kernel is wann_gemm_kernels_w8.inc's -- the
 // bfloat16 kernel behind a byte fetch -- with each byte widened to the bfloat16 it also is; unlike the unit of the one-byte
 // shadow rows this one is a full unit: norms, re-rank, cover re-rank and rescue read the float8 rows, there are no others.
+// Rows of 129 .. 2048 elements (wann_set_dense_long_float8): k_gemm_scores_f8slab, the bfloat16 unit's slab kernel behind a
+// byte-widening point fetch (wann_gemm_kernels_bf16.inc under WANN_DT == 8).
 #define WANN_DT 8
 #include "wann_gemm_kernels_body.inc"

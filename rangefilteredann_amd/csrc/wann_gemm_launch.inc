@@ -36,7 +36,7 @@ static const char *unit_rerank_cover(const CoverArgs &c, void *stream) {
 
 static ScoreKernel pick_score_kernel(const IndexView &ix) {
   // (a type whose long class is the index's own switch: the host admitted the batch with it, this unit only picks the kernel)
-  const DenseRows rows = dense_row_class(ix, dense_long_switch_type(ix.dtype));
+  const DenseRows rows = dense_row_class(ix, dense_long_switch_type(ix.dtype), dense_long_float8_type(ix.dtype));
   const int words = query_words(ix);
   void (*kern)(GemmArgs) = nullptr;
 #if WANN_BYTE_ROWS
@@ -63,8 +63,11 @@ static ScoreKernel pick_score_kernel(const IndexView &ix) {
 #elif WANN_DT == 5
   // two point buffers of 128 x 272 B, the query slab, base[] and rid[] per step parity: 136 KiB, one workgroup per CU
   if (rows == kRowsLong) return {bf16_long::k_gemm_scores_bfslab, (size_t)2 * 128 * (2 * 128 + 16) + 128 * (4 * 128 + 16) + 4 * 128 * 4, 1, true};
+#elif WANN_DT == 8
+  // (k_gemm_scores_bfslab's LDS: the staged rows are the same, only their way there differs)
+  if (rows == kRowsLong) return {f8_long::k_gemm_scores_f8slab, (size_t)2 * 128 * (2 * 128 + 16) + 128 * (4 * 128 + 16) + 4 * 128 * 4, 1, true};
 #elif WANN_QUAD_ROWS
-  // (float8 rows and the one-byte shadow rows of a float32 index: narrow only; dense_row_class names no other class for them)
+  // (the one-byte shadow rows of a float32 index: narrow only; dense_row_class names no other class for them)
 #else
   if (rows == kRowsLong) return {k_gemm_scores_long, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
   if (rows == kRowsWide) {  // slabs of 128, A operand in registers, one workgroup per CU
@@ -116,7 +119,7 @@ static const char *unit_point_sums(const IndexView &ix, float *norm2, unsigned i
   return gerr_of(hipGetLastError());
 }
 
-#if !WANN_HALF_ROWS && WANN_DT != 8  // (float16 and bfloat16 rows: the float32 unit's k_split_queries; float8 rows have no long class)
+#if !WANN_HALF_ROWS && WANN_DT != 8  // (float16, bfloat16 and float8 rows: the float32 unit's k_split_queries)
 static const char *unit_prep_queries(const float *queries, int64_t nq, int d, int words, uint32_t *out, void *stream) {
 #if WANN_BYTE_ROWS
   const int64_t items = nq * words;  // a thread per packed word

@@ -55,6 +55,7 @@ Tuning snapshot_tuning(wann_index &I) {
   t.scan_rows = row_switch_in_force(I, kScanRowsSwitch);
   t.dense_rows = row_switch_in_force(I, kDenseRowsSwitch);
   t.dense_long_rows = row_switch_in_force(I, kDenseLongRowsSwitch);
+  t.dense_long_float8 = row_switch_in_force(I, kDenseLongFloat8Switch);
   return t;
 }
 

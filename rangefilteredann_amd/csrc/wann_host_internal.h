@@ -184,6 +184,9 @@ struct wann_index {
   // dense_long_switch_type, wann_gemm_device.h: bfloat16): rows of 129 .. 2048 elements take the dense path of the next batches
   bool dense_long_rows_on = false;
   bool has_dense_long_switch() const { return wann::dense_long_switch_type(dtype); }
+  // wann_set_dense_long_float8 likewise, for the one type that switch moves (dense_long_float8_type: float8)
+  bool dense_long_float8_on = false;
+  bool has_dense_long_float8() const { return wann::dense_long_float8_type(dtype); }
   bool has_half_copy() const { return d_half.p != nullptr; }
   bool has_byte_copy() const { return d_bytes.p != nullptr; }
   bool has_scan_copy() const { return has_half_copy() || has_byte_copy(); }
@@ -279,6 +282,7 @@ constexpr RowSwitch kScanRowsSwitch = {&wann_index::scan_rows_on, &wann_index::h
 constexpr RowSwitch kDenseRowsSwitch = {&wann_index::dense_rows_on, &wann_index::has_dense_copy, &wann_index::last_dense_rows};
 // (wann_set_dense_long_rows: bounded by the row type, not by a copy; no "last" -- the dense counters say what a batch did)
 constexpr RowSwitch kDenseLongRowsSwitch = {&wann_index::dense_long_rows_on, &wann_index::has_dense_long_switch, nullptr};
+constexpr RowSwitch kDenseLongFloat8Switch = {&wann_index::dense_long_float8_on, &wann_index::has_dense_long_float8, nullptr};
 // (under I.tune_mu)
 inline bool row_switch_in_force(const wann_index &I, const RowSwitch &s) { return I.*s.on && (I.*s.has_copy)(); }
 

@@ -291,6 +291,9 @@ class Index {
   // by default); returns the setting now in force -- False on an index of any other element type
   bool set_dense_long_rows(bool on) { return set_row_switch(wann_set_dense_long_rows, on, "set_dense_long_rows failed"); }
   bool dense_long_rows() const { return wann_dense_long_rows(h_) != 0; }
+  // float8 indexes likewise, on k_gemm_scores_f8slab (wann_set_dense_long_float8, off by default; False on any other element type)
+  bool set_dense_long_float8(bool on) { return set_row_switch(wann_set_dense_long_float8, on, "set_dense_long_float8 failed"); }
+  bool dense_long_float8() const { return wann_dense_long_float8(h_) != 0; }
 
   // float16 / bfloat16 / float8 indexes: the full-precision points (any array numpy casts to float32, in the order of the array
   // the index was created from) as the row store of the refined calls (wann_set_refine_rows); None drops the store
@@ -409,6 +412,7 @@ class Index {
     d["scan_rows"] = wann_last_scan_rows(h_);  // the rows its k_brute launch read: 0 the index's own, 1 the half rows, 2 the one-byte rows
     d["dense_rows"] = wann_last_dense_rows(h_);  // 1: a score launch of its dense path read the one-byte copy of the rows
     d["dense_long_rows"] = wann_dense_long_rows(h_);  // the index's wann_set_dense_long_rows setting (a setting, not a count)
+    d["dense_long_float8"] = wann_dense_long_float8(h_);  // the index's wann_set_dense_long_float8 setting (likewise)
     return d;
   }
   static py::dict counters_dict(const wann_counters &c) {
@@ -499,6 +503,8 @@ static void common_defs(py::class_<C> &c) {
       .def("dense_rows_bytes", &C::dense_rows_bytes)
       .def("set_dense_long_rows", &C::set_dense_long_rows, "on"_a)
       .def("dense_long_rows", &C::dense_long_rows)
+      .def("set_dense_long_float8", &C::set_dense_long_float8, "on"_a)
+      .def("dense_long_float8", &C::dense_long_float8)
       .def("set_refine_rows", &C::set_refine_rows, "points"_a.none(true))
       .def("refine_rows_bytes", &C::refine_rows_bytes)
       .def("batch_search_refined", &C::search_refined, "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a,

@@ -3,9 +3,10 @@ queries; experiments/generate_advserial_dataset.py:8-69), PrefilterIndex brute f
   (i)  native windows [c - 0.5, c + 0.5] = one cluster = 1 % of the points: dense MFMA path vs the exact per-query scan
   (ii) synthetic 2^-12 windows (244 points): the exact scan kernel k_brute against its HBM roofline
 each against the REAL reference at its best thread count (child processes: the reference fixes its thread count at first use).
---dtype float32 | float16 | bfloat16 | uint8 | int8 (default float32) selects the element type of the point set: float16 and
+--dtype float32 | float16 | bfloat16 | float8 | uint8 | int8 (default float32) selects the element type of the point set: float16 and
 bfloat16 round the same set (a bfloat16 index opts in to its long-row kernel, k_gemm_scores_bfslab, per index: the dense legs run
-after set_dense_long_rows(True) where the build has that method), the byte types quantise it -- round(127 x) for int8 (MIPS), + 128 for uint8 (Euclidian), queries likewise -- and run
+after set_dense_long_rows(True) where the build has that method), float8 rounds the same set times 8 to E4M3 (and opts in to
+k_gemm_scores_f8slab likewise, with set_dense_long_float8(True)), the byte types quantise it -- round(127 x) for int8 (MIPS), + 128 for uint8 (Euclidian), queries likewise -- and run
 on the int8 MFMA with exact scores.  Every leg is timed as the median of repeated calls (min / max beside it: the spread).
 --dim D sets the row length (default 100; 512 = RedCaps, 768 / 1024 / 1536 = the long rows of k_gemm_scores_long (float32), k_gemm_scores_hslab (float16) and k_gemm_scores_bslab (uint8 / int8)), --clusters C
 the number of clusters (default 100), --metric l2 | mips the metric of the float types (default mips).  WANN_PF_CACHE=<dir> keeps
@@ -37,12 +38,12 @@ DTYPE = "float32" if BYTE_EXACT else _opt("--dtype", "float32")
 DIM = int(_opt("--dim", os.environ.get("WANN_PF_DIM", "128" if BYTE_EXACT else "100")))  # (WANN_PF_DIM: the option's older spelling)
 NCLU = int(_opt("--clusters", "100"))
 METRIC = _opt("--metric", "l2" if BYTE_EXACT else "mips")
-CLASS = {"float32": "FloatMips", "float16": "Float16Mips", "bfloat16": "BFloat16Mips", "int8": "Int8Mips", "uint8": "UInt8Euclidian"}[DTYPE]
-if METRIC == "l2" and DTYPE in ("float32", "float16", "bfloat16"):
+CLASS = {"float32": "FloatMips", "float16": "Float16Mips", "bfloat16": "BFloat16Mips", "float8": "Float8Mips", "int8": "Int8Mips", "uint8": "UInt8Euclidian"}[DTYPE]
+if METRIC == "l2" and DTYPE in ("float32", "float16", "bfloat16", "float8"):
     CLASS = CLASS.replace("Mips", "Euclidian")
 SHAPE_ARGS = ["--dtype", DTYPE, "--dim", str(DIM), "--clusters", str(NCLU), "--metric", METRIC]
-ELEM_BYTES = {"float32": 4, "float16": 2, "bfloat16": 2, "int8": 1, "uint8": 1}[DTYPE]
-UPCAST = DTYPE in ("float16", "bfloat16")  # (the reference has no such classes: the index answers like the float32 one on the upcast)
+ELEM_BYTES = {"float32": 4, "float16": 2, "bfloat16": 2, "float8": 1, "int8": 1, "uint8": 1}[DTYPE]
+UPCAST = DTYPE in ("float16", "bfloat16", "float8")  # (the reference has no such classes: the index answers like the float32 one on the upcast)
 
 
 def as_elem(a):
@@ -54,6 +55,10 @@ def as_elem(a):
     if DTYPE == "bfloat16":  # float32 values rounded to the nearest bfloat16, ties to even: what window_ann.bfloat16_round returns
         u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
         return ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32)
+    if DTYPE == "float8":  # 8 a rounded to the nearest E4M3 value, ties to even (four significant bits, subnormals in steps of 2^-9;
+        a = np.float32(8.0) * np.asarray(a, dtype=np.float32)  # |8 a| <= 8: far from the largest finite value): window_ann.float8_round
+        step = np.ldexp(np.float32(1.0), np.maximum(np.frexp(a)[1], -5) - 4)
+        return (np.rint(a / step) * step).astype(np.float32)
     q = np.rint(127.0 * a)
     return q.astype(np.int8) if DTYPE == "int8" else (q + 128).astype(np.uint8)
 
@@ -105,7 +110,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "--ref-worker":  # child: the real refer
     ref = orc.load_reference(prefer=("x86-64-v4", "native"))
     assert ref is not None
     with quiet_stdout():
-        ridx = getattr(ref, "PrefilterIndex" + CLASS.replace("BFloat16", "Float").replace("Float16", "Float"))(X.astype(np.float32) if UPCAST else X, labels)
+        ridx = getattr(ref, "PrefilterIndex" + CLASS.replace("BFloat16", "Float").replace("Float16", "Float").replace("Float8", "Float"))(X.astype(np.float32) if UPCAST else X, labels)
     if UPCAST:
         Q = Q.astype(np.float32)
     out = {}
@@ -139,6 +144,10 @@ nq = Q.shape[0]
 idx = getattr(wa, "PrefilterIndex" + CLASS)(X, labels)
 if DTYPE == "bfloat16" and hasattr(idx, "set_dense_long_rows"):  # (a parent build has no such kernel: its WANN_PF_ONLY=scan leg needs none)
     assert np.array_equal(X, wa.bfloat16_round(X)) and (idx.set_dense_long_rows(True) or DIM <= 128)
+if DTYPE == "float8":
+    assert np.array_equal(X, wa.float8_round(X)) and np.array_equal(Q, wa.float8_round(Q))
+    if hasattr(idx, "set_dense_long_float8"):  # (as above)
+        assert idx.set_dense_long_float8(True)
 qp = wa.QueryParams(10, 10, 1.35, 10**7, 10**4, 1, 10000, None, False)
 dev = torch.device("cuda:0")
 Qt = torch.from_numpy(Q.astype(np.float32)).to(dev)  # (device-buffer calls take fp32 queries; every element type converts exactly)
