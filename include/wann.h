@@ -123,7 +123,7 @@ enum { WANN_METRIC_L2 = 0, WANN_METRIC_MIPS = 1 };
  * opts in: after wann_set_dense_long_rows(index, 1) rows of 129 .. 2048 elements take that path too (shared windows, cover
  * groups, exact windows), on k_gemm_scores_bfslab -- a slab-walking kernel whose point operand is the row's own bytes and whose
  * accumulators are the float32 long-row kernel's on the upcast rows: the same ids, distance bits and dense counters.  Rows
- * beyond 2048 elements and k > 16 stay on the scan.  A bfloat16 index has no shadow rows (wann_half_rows: 0).
+ * beyond 2048 elements and k > 128 -- k > 16 without wann_set_dense_large_k -- stay on the scan.  A bfloat16 index has no shadow rows (wann_half_rows: 0).
  * The value is 5: 4 is UNASSIGNED and refused as an unknown dtype, like every other value not listed here.
  * WANN_DTYPE_F8 (not a type of the reference): float8 points, rows of uint8_t bit patterns of OCP E4M3 ("e4m3fn": 1 sign bit, 4
  * exponent bits with bias 7, 3 mantissa bits; no infinities, 0x7f / 0xff are NaN, the largest finite value is 448, subnormals
@@ -290,7 +290,7 @@ int wann_get_counters(const wann_index *index, wann_counters *out);
  * by the same kernels; candidates outside a query's own window are dropped before the exact re-rank.  Rows are those of the
  * exact scan (same ids, same distance bits: both order by (distance, id)); only the work counters differ: brute_rows no longer
  * counts the rows of the queries taken.  Row lengths the dense path does not take (float16 above 128 elements, bytes above 512 --
- * above 2048 elements or bytes where WANN_DENSE_LONG_ROWS=1 opts in to the long-row kernels) and k > 16 stay on the exact scan.  Applies to every replica of WANN_DEVICES and to every call form.
+ * above 2048 elements or bytes where WANN_DENSE_LONG_ROWS=1 opts in to the long-row kernels) and k > 128 -- k > 16 without wann_set_dense_large_k, which also asks 96 k positions of a window -- stay on the exact scan.  Applies to every replica of WANN_DEVICES and to every call form.
  * Returns the previous setting (0 / 1) or a NEGATIVE error: -WANN_ERR_UNSUPPORTED for on = 1 on any kind but
  * WANN_KIND_PREFILTER, -WANN_ERR_INVALID for a null index. */
 int wann_set_dense_windows(wann_index *index, int on);
@@ -316,7 +316,7 @@ int wann_get_dense_window_counters(const wann_index *index, wann_dense_window_co
  * and before the super tree scans its levels.  Queries with w > L, empty windows and windows outside the label span take the
  * ordinary path and return the ordinary rows bit for bit.  In a batch of at least 32 queries the flagged queries take the dense
  * prefilter path (shared-window groups and cover groups on the matrix cores, under its usual gates: windows of >= 1 024
- * points, >= 32 queries per block, 2 GiB of eligible rows per batch, k <= 16, the row-length limits per element type); what it
+ * points, >= 32 queries per block, 2 GiB of eligible rows per batch, k <= 16 -- k <= 128 after wann_set_dense_large_k --, the row-length limits per element type); what it
  * does not take or cannot prove goes to the exact scan, and both return the same rows bit for bit.  The scans and the dense
  * launches run beside the graph searches of the same batch.  While the limit is non-zero a batch holds the index's dense
  * buffers: the asynchronous lanes then run one batch at a time.  A call with wann_query_params::verbose set ignores the option
@@ -434,11 +434,23 @@ int wann_dense_long_rows(const wann_index *index);
  * to the bfloat16 it also is; the accumulators are the float32 long-row kernel's on the upcast rows: the same ids, distance bits
  * and dense counters.  Returns the setting now in force, 0 / 1: asking for 1 on an index of any other element type leaves it at 0
  * and returns 0.  Allocates and frees nothing; applies to every replica of WANN_DEVICES; a NEGATIVE error for a null index.
- * Changes no result row.  Rows beyond 2048 elements and k > 16 stay on the scan; WANN_DENSE_LONG_ROWS does not move a float8
+ * Changes no result row.  Rows beyond 2048 elements and k > 128 (k > 16 without wann_set_dense_large_k) stay on the scan; WANN_DENSE_LONG_ROWS does not move a float8
  * index, on or off.
  * wann_dense_long_float8: that setting (0 after wann_index_create; 0 for a null index). */
 int wann_set_dense_long_float8(wann_index *index, int on);
 int wann_dense_long_float8(const wann_index *index);
+/* Result widths of 17 .. 128 on the dense path.
+ * wann_set_dense_large_k: whether calls with k = 17 .. 128 take the MFMA prefilter path in the NEXT batches, in every call form and
+ * on all three routes (shared windows, wann_set_dense_windows, wann_set_exact_windows), on k_large_rerank / k_large_rerank_cover:
+ * 256 candidates per query kept as a sorted list (where k <= 16 keeps 32, one per lane), re-ranked exactly in passes of 64 rows,
+ * the same proof, rescue and hand-over to the exact scan.  For such a call a window is dense-eligible from max(1024, 96 k)
+ * positions (10 000-point windows: up to k = 104); narrower ones take the scan.  Returns the setting now in force, 0 / 1: asking
+ * for 1 on a WANN_DTYPE_U8 / WANN_DTYPE_I8 index leaves it at 0 and returns 0 (their k stays <= 16).  Allocates and frees nothing;
+ * applies to every replica of WANN_DEVICES; a NEGATIVE error for a null index.  Changes no result row -- ids and distance bits
+ * are the scan's -- and nothing at all for k <= 16 or k > 128.
+ * wann_dense_large_k: that setting (0 after wann_index_create; 0 for a null index). */
+int wann_set_dense_large_k(wann_index *index, int on);
+int wann_dense_large_k(const wann_index *index);
 
 /* WIDE ROWS: stop as at k, keep up to `width` entries (not calls of the reference; it computes this and drops the tail).
  * The reference's query() (src/postfilter_vamana.h:141-188) returns the whole filtered frontier of the last beam it searched;

@@ -235,6 +235,25 @@ static void check_scan_lds() {
   CHECK(brute_lds_bytes((int64_t)1 << 31, kMaxK) > kLdsPerWorkgroup);
 }
 
+// The dense path's window gate as a function of k (dense_min_window) and the LDS of its re-rank kernels (rerank_lds_bytes): k <= 16
+// keeps the two constants and k_rerank's bytes, beyond it 96 k positions and the list of kSelectLarge candidates.
+static void check_dense_large_k() {
+  static_assert(kSelectLarge == 256 && kDenseMaxK == 128 && kGroupMinWindow == 1024 && kCoverMinWindow == 1024, "the figures below assume these");
+  for (int floor : {kGroupMinWindow, kCoverMinWindow}) {
+    CHECK(dense_min_window(1, floor) == floor && dense_min_window(16, floor) == floor);
+    CHECK(dense_min_window(17, floor) == 1632 && dense_min_window(128, floor) == 12288);
+    for (int k = 1; k < kDenseMaxK; k++) CHECK(dense_min_window(k, floor) >= floor && dense_min_window(k, floor) <= dense_min_window(k + 1, floor));
+  }
+  CHECK(dense_min_window(104, kGroupMinWindow) <= 10000 && dense_min_window(105, kGroupMinWindow) > 10000);  // (the adversarial shape's windows)
+  // query row + 64 keys + 64 ids + 64 distances + the list: k <= 16 as it was, beyond it 2 KiB a wave whatever k is
+  CHECK(rerank_lds_bytes(view_of(WANN_DTYPE_F32, 128), 10) == 4 * (512 + 1024 + 80));
+  CHECK(rerank_lds_bytes(view_of(WANN_DTYPE_F32, 128), 16) == 4 * (512 + 1024 + 128));
+  CHECK(rerank_lds_bytes(view_of(WANN_DTYPE_F32, 128), 17) == 4 * (512 + 1024 + 2048));
+  CHECK(rerank_lds_bytes(view_of(WANN_DTYPE_F32, 128), 128) == 4 * (512 + 1024 + 2048));
+  CHECK(rerank_lds_bytes(view_of(WANN_DTYPE_F32, 2048), 128) == 45056 && 45056 < 48 * 1024);  // 4 x (8192 + 1024 + 2048)
+  CHECK(rerank_lds_bytes(view_of(WANN_DTYPE_F16, 2048), 128) == 45056);                       // (the staged query is the float32 upcast)
+}
+
 // The row-type table (wann_row_types.h) against the values written out here: every class, the caller's bytes, the device
 // pitch, the staged query's length and the kinds of unit of every id from -1 to 9.  (That the two layout rules are
 // permutations: byte_layout_sanitize_test.cpp and half_layout_sanitize_test.cpp.)
@@ -435,6 +454,7 @@ int main(int argc, char **argv) {
         CHECK(dense_row_class(v) == kRowsNone);
       }
   check_scan_lds();
+  check_dense_large_k();
   check_row_types();
   check_refdump();
   // the C ABI's argument validation (no device needed for these paths) lives in wann_abi.cpp and is covered by tests/test_abi.py

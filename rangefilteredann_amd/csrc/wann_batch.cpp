@@ -14,10 +14,12 @@ namespace wann_host {
 // never waits.
 // Which rows the score kernels take: the table above dense_row_class (wann_gemm_device.h).  The long class is opt-in
 // (WANN_DENSE_LONG_ROWS=1: until it is timed against the scan no batch moves to it by default; bfloat16 / float8 rows: the index's
-// own switch, wann_set_dense_long_rows / wann_set_dense_long_float8, which alone makes their class long); k > 16 stays on the exact scan.
+// own switch, wann_set_dense_long_rows / wann_set_dense_long_float8, which alone makes their class long); k > 128, and k > 16
+// without wann_set_dense_large_k (or on uint8 / int8 rows, with or without it), stays on the exact scan.
 static bool dense_rows_ok(const wann_index &I, const Tuning &T, int k) {
   const DenseRows rows = dense_row_class(I.view, T.dense_long_rows, T.dense_long_float8);
-  return k <= kSelect / 2 && rows != kRowsNone && (rows != kRowsLong || T.dense_long || T.dense_long_rows || T.dense_long_float8);
+  const bool k_ok = k <= kSelect / 2 || (T.dense_large_k && k <= kDenseMaxK && !byte_rows(I.view));
+  return k_ok && rows != kRowsNone && (rows != kRowsLong || T.dense_long || T.dense_long_rows || T.dense_long_float8);
 }
 
 // wann_set_dense_rows: the view the score launches of this call's dense path read instead of I.view -- the one-byte copy of a
@@ -273,9 +275,9 @@ static BatchPlan plan_batch(const wann_index &I, const Tuning &T, const wann_que
   P.spec = H.vamana_leaves && T.spec && I.view.rs <= 64 && !P.verbose_call;
   P.sub_slots = P.spec ? std::min<int64_t>(nq * (int64_t)P.maxt * 4 + 1024, (int64_t)1 << 26) : 0;
   // exact windows: the dense path takes the flagged queries of a batch of >= 32 (and lists what it leaves to the scan).  Neither
-  // dense stage takes a window narrower than kGroupMinWindow / kCoverMinWindow: a limit below both flags no such window, and the
-  // dense launches -- all of them empty -- are left out.
-  P.exact_dense = P.exact_limit >= std::min(kGroupMinWindow, kCoverMinWindow) && nq >= 32 && T.gemm && dense_rows_ok(I, T, P.k);
+  // dense stage takes a window narrower than kGroupMinWindow / kCoverMinWindow (k > 16: 96 k positions, dense_min_window): a limit
+  // below both flags no such window, and the dense launches -- all of them empty -- are left out.
+  P.exact_dense = P.exact_limit >= std::min(dense_min_window(P.k, kGroupMinWindow), dense_min_window(P.k, kCoverMinWindow)) && nq >= 32 && T.gemm && dense_rows_ok(I, T, P.k);
   P.inkernel_cap = kInKernelBeamCap;
   // speculative levels beyond the in-kernel cap: searched by "big" workgroups of the first launch (wave 0 owns
   // the LDS of all four waves), beams up to big_cap (the LDS beam must fit; 5792^2 < 2^25 bounds the filter

@@ -7,6 +7,9 @@
 namespace wann {
 
 constexpr int kSelect = 32;      // candidates kept per query by MFMA score before the exact re-rank
+// k = 17 .. kDenseMaxK (opt-in per index, wann_set_dense_large_k): k_large_rerank keeps kSelectLarge candidates per query as a
+// sorted list in LDS -- the same 2 : 1 ratio of candidates to results
+constexpr int kSelectLarge = 256, kDenseMaxK = kSelectLarge / 2;
 constexpr int kGemmPointChunk = 2048;  // window positions per tile (multiple of 128)
 constexpr int kGemmMaxFloats = 2048;   // longest float32 / float16 row, in 32-bit words of the float32 row (dense_row_class only)
 constexpr int kGemmMaxBytes = 2048;    // longest padded uint8 / int8 row, in bytes (dense_row_class only)
@@ -18,6 +21,14 @@ constexpr int kGroupMinQueries = 16, kGroupMinWindow = 1024;
 // queries left ineligible lose against the scan at every batch size below 10 000; the window width itself does not decide --
 // the batch's total scan work does, CoverArgs::min_rows)
 constexpr int kCoverMinQueries = 32, kCoverMinWindow = 1024;
+// The window gate as a function of k (k_group_insert / k_group_plan, the cover count, the sorted kinds' eligibility; `floor` is
+// kGroupMinWindow or kCoverMinWindow, and k <= 16 gets exactly that).  Beyond 16 a window must hold 96 k positions.  A block of
+// 64 positions hands over three candidates, so a block that holds FOUR or more of the k winners hides one, and every such block
+// costs the query a rescue scan.  With the winners uniform over the w / 64 blocks a block's count is Poisson with mean 64 k / w:
+// at w >= 96 k the mean is at most 2/3, P(>= 4) <= 0.005, under one block per query at k = 128 -- where w = 1024 would put four
+// winners into every other block.  96 is this derivation, not a measurement.
+constexpr int kLargeKWindowFactor = 96;
+constexpr int dense_min_window(int k, int floor) { return k <= kSelect / 2 || kLargeKWindowFactor * k < floor ? floor : kLargeKWindowFactor * k; }
 constexpr long long kCoverMinScanBytes = 1ll << 31;  // eligible windows' rows x bytes per row below which the scan is faster than the cover path's ~0.2 ms of launches
 constexpr int kCoverPairFloats = (kGemmPointChunk / 128) * 8;  // hand-over of one (query, block) pair: 16 steps x 2 half waves x 4 floats
 
@@ -150,6 +161,15 @@ inline DenseRows dense_row_class(const IndexView &ix, bool long_switch = false, 
   // fetch and covers the narrow class alone -- longer rows are scored from the float32 rows)
   if (ix.dtype == kRowsU8Widened) return kRowsNone;
   return ix.dtype == kRowsF32 && words <= 512 ? kRowsWide : kRowsLong;
+}
+
+// Dynamic LDS of the selection / re-rank kernels: four waves x (staged query row, candidate arrays, the merge list).  k <= 16
+// (k_rerank): a merge list of k entries.  Beyond (k_large_rerank): the list of kSelectLarge candidates, whose bytes the k-entry
+// merge list takes over once the selected rows' numbers sit in registers -- 44 KiB at d = 2048, under the 48 KiB a launch gets
+// without asking.
+inline size_t rerank_lds_bytes(const IndexView &ix, int k) {
+  const int list = k > kSelect / 2 ? kSelectLarge * 8 : ((k + 1) & ~1) * 8;
+  return (size_t)4 * (((query_words(ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + list);
 }
 
 // One unit's launchers (wann_gemm_launch.inc, compiled once per element type): a null return = launched, otherwise the error

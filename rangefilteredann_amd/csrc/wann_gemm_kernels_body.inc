@@ -181,7 +181,7 @@ __global__ void k_group_insert(GemmArgs A) {
   const int rank = atomicAdd(&A.slot_count[pos], 1);
   A.q_rank[q] = rank;
   // (the query that makes a slot a group says so: k_group_plan has nothing to do for a batch of distinct windows)
-  if (rank == kGroupMinQueries - 1 && t.b - t.a >= kGroupMinWindow) A.plan[P_ANY] = 1;
+  if (rank == kGroupMinQueries - 1 && t.b - t.a >= dense_min_window(A.k, kGroupMinWindow)) A.plan[P_ANY] = 1;
 }
 
 // exclusive prefix of v over the 1024 threads of the workgroup (+ the total): shuffles inside a wave, one pass over the 16
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(1024) void k_group_plan(GemmArgs A, Counters *ctr) 
       a = (int64_t)(key >> 32);
       b = (int64_t)(key & 0xffffffffull);
       w = b - a;
-      eligible = qc >= kGroupMinQueries && w >= kGroupMinWindow;
+      eligible = qc >= kGroupMinQueries && w >= dense_min_window(A.k, kGroupMinWindow);
     }
     // entries: per query and 128-position step two blocks (one per half wave) of four floats
     const unsigned long long need = eligible ? (unsigned long long)qc * (unsigned long long)((w + 127) >> 7) * 8ull : 0ull;
@@ -316,7 +316,7 @@ __device__ __forceinline__ int cover_state(const CoverArgs &C, int64_t q, int64_
   const Task t = C.g.tasks[q * C.g.tstride];
   a = t.a;
   b = t.b;
-  return b - a >= kCoverMinWindow ? 2 : 1;
+  return b - a >= dense_min_window(C.g.k, kCoverMinWindow) ? 2 : 1;
 }
 
 __global__ void k_cover_count(CoverArgs C) {
@@ -1658,6 +1658,243 @@ __global__ __launch_bounds__(256) void k_rerank_cover_bslab(CoverArgs C) {
   }
 }
 #endif
+
+#if !WANN_BYTE_ROWS
+// ------------------------------------------------------------------------------------------------
+// k = 17 .. kDenseMaxK (opt-in per index: wann_set_dense_large_k).  The score kernels' hand-over is the same for any k; what
+// ends at 16 above is the list of kSelect candidates held one per lane, the single wave_distances pass and the rank loop across
+// the wave.  Here the kSelectLarge best candidates are a sorted list of (score key << 32 | window position) in the wave's LDS,
+// 2 KiB, and admission is BATCHED: inserting one candidate at a time would shift a 256-entry list 400 times a query.
+//   * a trip reads 64 blocks' entries (a block per lane) and tests each block's three candidates against the threshold -- the
+//     list's last key once the list is full, nothing before;
+//   * survivors are compacted (ballot + prefix count) into a pending buffer of 64 entries;
+//   * a full buffer, or the end of the blocks, is sorted across the wave (the bitonic network of select_scores, on 64-bit
+//     entries) and merged into the list in one parallel step: wave_merge's presorted form -- a binary search per pending entry,
+//     the list shifted in destination space, truncated at kSelectLarge -- and the threshold is read again.  Candidates that
+//     waited through a flush are tested against the new threshold before they cost a slot.
+// The pending buffer is the wave's cand_key (idle until the re-rank; wave_merge stages the sorted run in it as well) and the list
+// is the wave's lbeam area: the selected positions move into registers (four row numbers a lane) before the re-rank's merge list
+// starts over the same bytes.  So a wave needs 2 KiB where k_rerank needs 8 k bytes, and four waves at d = 2048 stay at 44 KiB.
+// ------------------------------------------------------------------------------------------------
+constexpr int kLargeListBytes = kSelectLarge * 8;
+static_assert(kDenseMaxK * 8 <= kLargeListBytes, "the re-rank's merge list lives in the selection list's bytes");
+
+__device__ __forceinline__ u64 wave_sort_u64(u64 key) {  // ascending over the 64 lanes
+  const int lane = lane_id();
+#pragma unroll
+  for (int k = 2; k <= 64; k <<= 1)
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const u64 ok = ((u64)(uint32_t)__shfl_xor((int)(uint32_t)(key >> 32), j) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)key, j);
+      const bool take_min = ((lane & j) == 0) == ((lane & k) == 0);
+      key = (take_min ? (ok < key) : (ok > key)) ? ok : key;
+    }
+  return key;
+}
+
+// (one wave, one query; list[0 .. sel_cnt) = the selected candidates, best first; `cut` / `blk_bound` as select_scores returns them)
+template <class LOAD>
+__device__ __forceinline__ void select_scores_large(const LOAD &load, int64_t nblk, u64 *list, u64 *pend, int &sel_cnt, float &cut, float &blk_bound) {
+  const int lane = lane_id();
+  uint32_t thr = 0xffffffffu;  // (no float maps to it: every candidate passes until the list is full)
+  int m = 0, np = 0;
+  float bound = kHuge;
+  auto flush = [&]() {
+    WAVE_SYNC();
+    const u64 pk = wave_sort_u64(lane < np ? pend[lane] : ~0ull);
+    WAVE_SYNC();  // (wave_merge writes the sorted run back into pend)
+    int p0;
+    // (comparisons ignore an entry's bit 0, the beam's visited flag: two candidates that differ in nothing else tie, in either order)
+    m = wave_merge<u64 *, false, true>(list, m, kSelectLarge, lane < np, pk, pend, &p0);
+    np = 0;
+    if (m == kSelectLarge) thr = (uint32_t)(list[kSelectLarge - 1] >> 32);  // (the same address in every lane)
+  };
+  for (int64_t b0 = 0; b0 < nblk; b0 += 64) {
+    const int64_t bb = b0 + lane;
+    const f32x4 e = (bb < nblk) ? load(bb) : f32x4{kHuge, kHuge, kHuge, kHuge};
+    bound = fminf(bound, e[3]);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const uint32_t key = fkey(e[c]);
+      // block bb: step (bb >> 1), half (bb & 1); low bits 16 j + 4 g + r -> position 32 j + 8 g + 4 half + r
+      const uint32_t ix6 = __float_as_uint(e[c]) & 63u;
+      const int cp = (int)((bb >> 1) * 128 + 32 * (ix6 >> 4) + 8 * ((ix6 >> 2) & 3) + 4 * (bb & 1) + (ix6 & 3));
+      const u64 ent = ((u64)key << 32) | (uint32_t)cp;
+      bool want = e[c] < kHugeTest && key < thr;
+      for (;;) {
+        const u64 mask = ballot64(want);
+        if (!mask) break;
+        const int r = popc64(mask & lanemask_lt()), room = 64 - np, all = popc64(mask);
+        if (want && r < room) {
+          pend[np + r] = ent;
+          want = false;
+        }
+        np += all < room ? all : room;
+        if (np < 64) break;  // (everybody found a place)
+        flush();
+        want = want && key < thr;
+      }
+    }
+  }
+  if (np) flush();
+  WAVE_SYNC();
+  for (int o = 32; o > 0; o >>= 1) bound = fminf(bound, __shfl_xor(bound, o));
+  // every position that is not selected scores >= cut: candidates that were refused, or dropped off the end of the list, >= its
+  // last key (once the list is full), everything else >= its block's fourth smallest
+  sel_cnt = m;
+  cut = (m == kSelectLarge) ? funkey(thr) : 3.402823466e+38f;
+  blk_bound = (bound >= kHugeTest) ? 3.402823466e+38f : bound;
+}
+
+// rerank_query for K = 17 .. kDenseMaxK: the same arguments, proof, rescue and hand-over to the scan; the selection above,
+// ceil(cnt / 64) wave_distances passes whose (distance, id) keys are merged into L.lbeam truncated at K, and no rank loop: the
+// K-th exact distance is the merge list's last entry and the result row is the list.
+template <int METRIC, class LOAD>
+__device__ __forceinline__ void rerank_query_large(const GemmArgs &A, const WaveLds &L, const int qrow, const LOAD &load, const int64_t nblk_sel,
+                                                   const int64_t abase, const int64_t wa, const int64_t wb, unsigned long long *n_rescued,
+                                                   unsigned long long *n_unproven) {
+  const IndexView &ix = A.ix;
+  const int lane = lane_id();
+  const int K = A.k;
+  const int qw = qv_words(ix);
+  float q2 = 0.f;  // (the query row is on its way while the selection runs)
+  for (int i = lane; i < qw; i += 64) {
+    const float v = (i < ix.d) ? A.queries[(int64_t)qrow * ix.d + i] : 0.f;
+    L.qv[i] = v;
+    q2 = fmaf(v, v, q2);
+  }
+  int cnt;
+  float cut_sel, cut_blk;
+  select_scores_large(load, nblk_sel, L.lbeam, L.cand_key, cnt, cut_sel, cut_blk);
+  for (int o = 32; o > 0; o >>= 1) q2 += __shfl_xor(q2, o);
+  // the selected rows' numbers, four a lane (kSelectLarge / 64), all lookups in flight at once -- then the list's bytes are free
+  int rid0 = 0, rid1 = 0, rid2 = 0, rid3 = 0;
+  static_assert(kSelectLarge == 4 * 64, "four row numbers a lane");
+  if (lane < cnt) rid0 = window_row(ix, abase + (int64_t)(uint32_t)L.lbeam[lane]);
+  if (64 + lane < cnt) rid1 = window_row(ix, abase + (int64_t)(uint32_t)L.lbeam[64 + lane]);
+  if (128 + lane < cnt) rid2 = window_row(ix, abase + (int64_t)(uint32_t)L.lbeam[128 + lane]);
+  if (192 + lane < cnt) rid3 = window_row(ix, abase + (int64_t)(uint32_t)L.lbeam[192 + lane]);
+  WAVE_SYNC();
+  int m = 0, p0;
+#pragma unroll 1
+  for (int c0 = 0; c0 < cnt; c0 += 64) {
+    const int n = cnt - c0 < 64 ? cnt - c0 : 64;
+    const int rid = c0 == 0 ? rid0 : c0 == 64 ? rid1 : c0 == 128 ? rid2 : rid3;
+    L.cand_id[lane] = rid;
+    WAVE_SYNC();
+    const float dist = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, n, 0);
+    const u64 key = ((u64)fkey(dist) << 32) | ((u64)(uint32_t)rid << 1);
+    bool pass = lane < n;
+    if (m >= K) pass = pass && ((key | 1ull) < (L.lbeam[K - 1] | 1ull));
+    m = wave_merge(L.lbeam, m, K, pass, key, L.cand_key, &p0);
+  }
+  const int ti = qrow * A.tstride;  // the query's slot 0 (stand-alone PrefilterIndex: one task slot per query)
+  // proof: every unselected point has score >= cut, and |score - exact distance| <= E.
+  // E: the products the bf16 split drops (q1 p3 + q3 p1 + q2 p2 + ...) <= 3.02 * 2^-16 |q||p| (Cauchy-Schwarz over
+  // the columns), fp32 accumulation of 3 d products (A.acc_factor x the rounding adder's worst case), fp32 norms and the
+  // reference's own rounding.
+  const float pmax = __uint_as_float(*A.pnorm2_max_bits);
+  const float cerr = 3.02f * 1.52587890625e-5f + A.acc_factor * (float)(3 * ix.d + 8) * 5.9604645e-8f;
+  // + 2^-17 relative for the six mantissa bits that carry the position (|score| <= |q||p| resp. 2 (|q|^2 + |p|^2))
+  const float cerr2 = cerr + 7.62939453125e-6f;
+  // (never zero: an all-zero query under the inner product scores 0 everywhere, the position bits make every entry a
+  // different denormal, and d_k = -0 < cut would "prove" a top k among points that all tie -- only the scan's id order
+  // settles those).  The inner product's |q||p| is formed from the two roots: q2 * pmax underflows to 0 in fp32 once |q||p| is
+  // below about 2^-75 (rows and queries both scaled by 2^-40: E fell to FLT_MIN under scores of 2^-80 and wrong rows were
+  // certified) and overflows above 2^64.
+  const float E = fmaxf((METRIC == 1) ? cerr2 * (sqrtf(q2) * sqrtf(pmax)) : 2.f * cerr2 * (q2 + pmax), 1.17549435e-38f);
+  // k-th exact distance (the worst one that is returned; m = min(cnt, K): the candidates are distinct rows)
+  const float dk = m > 0 ? funkey((uint32_t)(L.lbeam[m - 1] >> 32)) : -3.402823466e+38f;
+  // two bounds on what was not selected: candidates that lost against the selected ones (>= the worst selected), and
+  // whatever the blocks kept to themselves (>= the smallest fourth entry); FLT_MAX = no such position exists
+  const float qoff = (METRIC == 1) ? 0.f : q2;  // the L2 scores leave |q|^2 out
+  const bool sel_ok = cut_sel == 3.402823466e+38f || (cnt >= K && dk + E < cut_sel + qoff - E);
+  const bool blk_ok = cut_blk == 3.402823466e+38f || (cnt >= K && dk + E < cut_blk + qoff - E);
+  bool proven = sel_ok && blk_ok;
+  if (!proven && sel_ok && cnt >= K) {
+    // Second chance: only some blocks' kept positions could still matter (fourth entry - E <= d_k + E; a fixed set, d_k
+    // can only improve).  Score those blocks exactly, 64 positions each, and merge; all other blocks stay proven.
+    // (the merge list already holds the selected candidates; a block's three candidates come by again and are dropped as copies)
+    int scanned = 0;
+    bool gave_up = false;
+    for (int64_t b0 = 0; b0 < nblk_sel && !gave_up; b0 += 64) {
+      const float m4 = (b0 + lane < nblk_sel) ? load(b0 + lane)[3] : kHuge;
+      u64 hide = ballot64(m4 < kHugeTest && m4 + qoff - E <= dk + E);
+      while (hide) {
+        const int64_t b = b0 + ctz64(hide);
+        hide &= hide - 1;
+        if (++scanned > 16) {
+          gave_up = true;
+          break;
+        }
+        const int64_t pos = abase + (b >> 1) * 128 + 32 * (lane >> 4) + 8 * ((lane >> 2) & 3) + 4 * (b & 1) + (lane & 3);
+        const bool valid = pos >= wa && pos < wb;  // (the query's own window: a cover group's block reaches beyond it)
+        const int r2 = valid ? window_row(ix, pos) : 0;
+        L.cand_id[lane] = r2;
+        WAVE_SYNC();
+        const float d2 = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, 64, 0);
+        const u64 k2 = ((u64)fkey(d2) << 32) | ((u64)(uint32_t)r2 << 1);
+        bool pass = valid;
+        if (m >= K) pass = pass && ((k2 | 1ull) < (L.lbeam[K - 1] | 1ull));
+        m = wave_merge(L.lbeam, m, K, pass, k2, L.cand_key, &p0);
+      }
+    }
+    if (!gave_up) {
+      proven = true;
+      if (lane == 0) atomicAdd(n_rescued, 1ull);
+    }
+  }
+  // (an unproven query's row is rewritten by the scan; until then it holds exact distances of rows of its window, like rerank_query's)
+  for (int x = lane; x < m; x += 64) {
+    const u64 e = L.lbeam[x];
+    A.out_key[(size_t)ti * K + x] = (e & 0xffffffff00000000ull) | (uint32_t)((uint32_t)e >> 1);
+  }
+  if (lane == 0) {
+    A.out_cnt[ti] = m;
+    if (!proven) {
+      A.brute_list[atomicAdd(A.brute_count, 1)] = ti;
+      atomicAdd(n_unproven, 1ull);
+    }
+  }
+  WAVE_SYNC();
+}
+
+// k_rerank / k_rerank_cover for K = 17 .. kDenseMaxK: the same grids, a wave per query; LDS per wave: the common part + the list
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_large_rerank(GemmArgs A, Counters *ctr) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int wv = threadIdx.x >> 6;
+  const int qw = qv_words(A.ix);
+  const int per_wave = wave_lds_common_bytes(qw) + kLargeListBytes;
+  const WaveLds L = carve_wave_lds(smem + (size_t)wv * per_wave, qw, kSelectLarge, true);
+  const int64_t ntq = A.plan[P_NTQ];
+  for (int64_t tq = (int64_t)blockIdx.x * 4 + wv; tq < ntq; tq += (int64_t)gridDim.x * 4) {
+    const GemmGroup grp = A.groups[A.tq_group[tq]];
+    const int64_t nblk = ((grp.b - grp.a + 127) >> 7) * 2;
+    const EntryRow load{reinterpret_cast<const f32x4 *>(A.scores + grp.soff) + (int64_t)A.tq_local[tq] * nblk};
+    rerank_query_large<METRIC>(A, L, A.gq[tq], load, nblk, grp.a, grp.a, grp.b, &ctr->gemm_rescued, &ctr->gemm_unproven);
+  }
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_large_rerank_cover(CoverArgs C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const GemmArgs &A = C.g;
+  const int wv = threadIdx.x >> 6;
+  const int qw = qv_words(A.ix);
+  const int per_wave = wave_lds_common_bytes(qw) + kLargeListBytes;
+  const WaveLds L = carve_wave_lds(smem + (size_t)wv * per_wave, qw, kSelectLarge, true);
+  if (C.pass >= C.cplan[CP_NPASS]) return;
+  for (int64_t q = (int64_t)blockIdx.x * 4 + wv; q < A.nq; q += (int64_t)gridDim.x * 4) {
+    if (C.q_pass[q] != C.pass) continue;  // (wave-uniform)
+    const Task t = A.tasks[q * A.tstride];
+    const int64_t s0 = t.a >> 7, nblk = (((t.b - 1) >> 7) - s0 + 1) * 2;
+    const CoverRow load{reinterpret_cast<const f32x4 *>(A.scores), C.qb_base + (int64_t)C.pass * C.pair_stride + C.q_off[q], s0, t.a, t.b,
+                        (int32_t)(t.a / kGemmPointChunk)};
+    rerank_query_large<METRIC>(A, L, (int)q, load, nblk, s0 << 7, t.a, t.b, &C.cctr->rescued, &C.cctr->unproven);
+  }
+}
+#endif  // !WANN_BYTE_ROWS (large k)
 WANN_GNS_END
 #endif  // WANN_DT != 6
 

@@ -18,15 +18,16 @@ WANN_GNS_BEGIN
 // compiler lays the template instances out in, so a unit's code object stays byte for byte what it was)
 // the selection / re-rank kernels: a wave per query, four waves x (staged query row, candidate arrays, the k-entry merge list) of LDS
 static dim3 rerank_grid(const GemmArgs &a) { return dim3((unsigned)std::min<int64_t>(4096, (a.nq + 3) / 4)); }
-static size_t rerank_lds_bytes(const IndexView &ix, int k) {
-  return (size_t)4 * (((query_words(ix) * 4 + 15) & ~15) + 64 * 8 + 64 * 4 + 64 * 4 + ((k + 1) & ~1) * 8);
-}
+// (their dynamic LDS: rerank_lds_bytes, wann_gemm_device.h)
 
 #if WANN_DT != 6  // (the unit of the one-byte shadow rows holds score kernels only)
 static const char *unit_rerank_cover(const CoverArgs &c, void *stream) {
   void (*kern)(CoverArgs) = nullptr;
 #if WANN_BYTE_ROWS
   if (dense_row_class(c.g.ix) == kRowsLong) kern = c.g.ix.metric == 1 ? k_rerank_cover_bslab<1> : k_rerank_cover_bslab<0>;  // (quantised keys)
+#endif
+#if !WANN_BYTE_ROWS
+  if (c.g.k > kSelect / 2) kern = c.g.ix.metric == 1 ? k_large_rerank_cover<1> : k_large_rerank_cover<0>;  // (wann_set_dense_large_k)
 #endif
   if (!kern) kern = c.g.ix.metric == 1 ? k_rerank_cover<1> : k_rerank_cover<0>;
   hipLaunchKernelGGL(kern, rerank_grid(c.g), dim3(256), rerank_lds_bytes(c.g.ix, c.g.k), (hipStream_t)stream, c);
@@ -141,6 +142,9 @@ static const char *unit_select_rerank(const GemmArgs &a, Counters *ctr, void *st
   void (*kern)(GemmArgs, Counters *) = nullptr;
 #if WANN_BYTE_ROWS
   if (dense_row_class(a.ix) == kRowsLong) kern = a.ix.metric == 1 ? k_rerank_bslab<1> : k_rerank_bslab<0>;  // (quantised keys)
+#endif
+#if !WANN_BYTE_ROWS
+  if (a.k > kSelect / 2) kern = a.ix.metric == 1 ? k_large_rerank<1> : k_large_rerank<0>;  // (wann_set_dense_large_k)
 #endif
   if (!kern) kern = a.ix.metric == 1 ? k_rerank<1> : k_rerank<0>;
   hipLaunchKernelGGL(kern, rerank_grid(a), dim3(256), rerank_lds_bytes(a.ix, a.k), (hipStream_t)stream, a, ctr);

@@ -187,6 +187,11 @@ struct wann_index {
   // wann_set_dense_long_float8 likewise, for the one type that switch moves (dense_long_float8_type: float8)
   bool dense_long_float8_on = false;
   bool has_dense_long_float8() const { return wann::dense_long_float8_type(dtype); }
+  // wann_set_dense_large_k (under tune_mu; off by default): calls with k = 17 .. kDenseMaxK take the dense path of the next
+  // batches, on k_large_rerank / k_large_rerank_cover.  Never on for uint8 / int8 rows: their selection works on quantised keys
+  // (select_keys) and has no large form.
+  bool dense_large_k_on = false;
+  bool has_dense_large_k() const { return !wann::byte_rows(dtype); }
   bool has_half_copy() const { return d_half.p != nullptr; }
   bool has_byte_copy() const { return d_bytes.p != nullptr; }
   bool has_scan_copy() const { return has_half_copy() || has_byte_copy(); }
@@ -283,6 +288,7 @@ constexpr RowSwitch kDenseRowsSwitch = {&wann_index::dense_rows_on, &wann_index:
 // (wann_set_dense_long_rows: bounded by the row type, not by a copy; no "last" -- the dense counters say what a batch did)
 constexpr RowSwitch kDenseLongRowsSwitch = {&wann_index::dense_long_rows_on, &wann_index::has_dense_long_switch, nullptr};
 constexpr RowSwitch kDenseLongFloat8Switch = {&wann_index::dense_long_float8_on, &wann_index::has_dense_long_float8, nullptr};
+constexpr RowSwitch kDenseLargeKSwitch = {&wann_index::dense_large_k_on, &wann_index::has_dense_large_k, nullptr};
 // (under I.tune_mu)
 inline bool row_switch_in_force(const wann_index &I, const RowSwitch &s) { return I.*s.on && (I.*s.has_copy)(); }
 

@@ -9,7 +9,9 @@ after set_dense_long_rows(True) where the build has that method), float8 rounds 
 k_gemm_scores_f8slab likewise, with set_dense_long_float8(True)), the byte types quantise it -- round(127 x) for int8 (MIPS), + 128 for uint8 (Euclidian), queries likewise -- and run
 on the int8 MFMA with exact scores.  Every leg is timed as the median of repeated calls (min / max beside it: the spread).
 --dim D sets the row length (default 100; 512 = RedCaps, 768 / 1024 / 1536 = the long rows of k_gemm_scores_long (float32), k_gemm_scores_hslab (float16) and k_gemm_scores_bslab (uint8 / int8)), --clusters C
-the number of clusters (default 100), --metric l2 | mips the metric of the float types (default mips).  WANN_PF_CACHE=<dir> keeps
+the number of clusters (default 100), --metric l2 | mips the metric of the float types (default mips), --k K the result width (default
+10; beyond 16 the dense legs run after set_dense_large_k(True) where the build has that method, on k_large_rerank: a window of
+10 000 points is dense-eligible up to k = 104).  WANN_PF_CACHE=<dir> keeps
 the generated set there for the next run of the same shape; WANN_PF_ONLY=mfma times the dense leg alone (runs under a profiler),
 WANN_PF_ONLY=scan the exact-scan leg alone, twice (the baseline run of a parent build); WANN_PF_NO_REF=1 leaves the CPU reference out.
 --byte-exact: the float32 index is fed the integer values of the uint8 leg, round(127 x) + 128, as float32 (d = 128 and the
@@ -38,10 +40,11 @@ DTYPE = "float32" if BYTE_EXACT else _opt("--dtype", "float32")
 DIM = int(_opt("--dim", os.environ.get("WANN_PF_DIM", "128" if BYTE_EXACT else "100")))  # (WANN_PF_DIM: the option's older spelling)
 NCLU = int(_opt("--clusters", "100"))
 METRIC = _opt("--metric", "l2" if BYTE_EXACT else "mips")
+K = int(_opt("--k", "10"))
 CLASS = {"float32": "FloatMips", "float16": "Float16Mips", "bfloat16": "BFloat16Mips", "float8": "Float8Mips", "int8": "Int8Mips", "uint8": "UInt8Euclidian"}[DTYPE]
 if METRIC == "l2" and DTYPE in ("float32", "float16", "bfloat16", "float8"):
     CLASS = CLASS.replace("Mips", "Euclidian")
-SHAPE_ARGS = ["--dtype", DTYPE, "--dim", str(DIM), "--clusters", str(NCLU), "--metric", METRIC]
+SHAPE_ARGS = ["--dtype", DTYPE, "--dim", str(DIM), "--clusters", str(NCLU), "--metric", METRIC, "--k", str(K)]
 ELEM_BYTES = {"float32": 4, "float16": 2, "bfloat16": 2, "float8": 1, "int8": 1, "uint8": 1}[DTYPE]
 UPCAST = DTYPE in ("float16", "bfloat16", "float8")  # (the reference has no such classes: the index answers like the float32 one on the upcast)
 
@@ -119,7 +122,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "--ref-worker":  # child: the real refer
         for _ in range(3):
             t = time.perf_counter()
             with quiet_stdout():
-                rids, rd = ridx.batch_search(Q, W.astype(np.float64), Q.shape[0], ref.QueryParams(10, 10, 1.35, 10**7, 10**4, 1, 10000, None, False))
+                rids, rd = ridx.batch_search(Q, W.astype(np.float64), Q.shape[0], ref.QueryParams(K, K, 1.35, 10**7, 10**4, 1, 10000, None, False))
             best = min(best, time.perf_counter() - t)
         out[name] = dict(qps=round(Q.shape[0] / best), dists_identical=bool(np.array_equal(rd, res["d_" + name])))
     print(json.dumps(out))
@@ -148,10 +151,12 @@ if DTYPE == "float8":
     assert np.array_equal(X, wa.float8_round(X)) and np.array_equal(Q, wa.float8_round(Q))
     if hasattr(idx, "set_dense_long_float8"):  # (as above)
         assert idx.set_dense_long_float8(True)
-qp = wa.QueryParams(10, 10, 1.35, 10**7, 10**4, 1, 10000, None, False)
+if K > 16 and hasattr(idx, "set_dense_large_k"):  # (a parent build has no such kernel: its WANN_PF_ONLY=scan leg needs none; byte types refuse)
+    assert idx.set_dense_large_k(True) or DTYPE in ("uint8", "int8")
+qp = wa.QueryParams(K, K, 1.35, 10**7, 10**4, 1, 10000, None, False)
 dev = torch.device("cuda:0")
 Qt = torch.from_numpy(Q.astype(np.float32)).to(dev)  # (device-buffer calls take fp32 queries; every element type converts exactly)
-it, dt = torch.empty((nq, 10), dtype=torch.int32, device=dev), torch.empty((nq, 10), dtype=torch.float32, device=dev)
+it, dt = torch.empty((nq, K), dtype=torch.int32, device=dev), torch.empty((nq, K), dtype=torch.float32, device=dev)
 
 
 REPS = int(os.environ.get("WANN_PF_REPS", "21"))
@@ -246,7 +251,7 @@ win_bytes = NCLU * per * padded_row_bytes(d)  # a window group reads each of its
 p12_dev_ms = out["p12"]["counters"]["device_ms"]
 spread = lambda leg: dict(ms=[out[leg]["ms"], again[leg]["ms"]], ms_min=[out[leg]["ms_min"], again[leg]["ms_min"]], ms_max=[out[leg]["ms_max"], again[leg]["ms_max"]],
                           device_ms=[round(out[leg]["counters"]["device_ms"], 3), round(again[leg]["counters"]["device_ms"], 3)])
-print(json.dumps(dict(workload=f"adversarial {NCLU}x10000 d={d} {DTYPE} {'Euclidian' if CLASS.endswith('Euclidian') else 'MIPS'}, {nq} queries, window = 1 cluster", mfma_ms=out["mfma"]["ms"], mfma_qps=out["mfma"]["qps"],
+print(json.dumps(dict(workload=f"adversarial {NCLU}x10000 d={d} {DTYPE} {'Euclidian' if CLASS.endswith('Euclidian') else 'MIPS'}, {nq} queries, window = 1 cluster" + ("" if K == 10 else f", k = {K}"), mfma_ms=out["mfma"]["ms"], mfma_qps=out["mfma"]["qps"],
                       scan_ms=out["scan"]["ms"], scan_qps=out["scan"]["qps"], mfma_equals_scan=bool(same),
                       scan_device_ms=round(out["scan"]["counters"]["device_ms"], 3), timed_calls_per_leg=REPS,
                       repeated_legs=dict(mfma=spread("mfma"), scan=spread("scan")),
