@@ -290,7 +290,7 @@ int wann_get_counters(const wann_index *index, wann_counters *out);
  * by the same kernels; candidates outside a query's own window are dropped before the exact re-rank.  Rows are those of the
  * exact scan (same ids, same distance bits: both order by (distance, id)); only the work counters differ: brute_rows no longer
  * counts the rows of the queries taken.  Row lengths the dense path does not take (float16 above 128 elements, bytes above 512 --
- * above 2048 elements or bytes where WANN_DENSE_LONG_ROWS=1 opts in to the long-row kernels) and k > 128 -- k > 16 without wann_set_dense_large_k, which also asks 96 k positions of a window -- stay on the exact scan.  Applies to every replica of WANN_DEVICES and to every call form.
+ * above 2048 elements or bytes where WANN_DENSE_LONG_ROWS=1 opts in to the long-row kernels) and k > 128 -- k > 16 without wann_set_dense_large_k (uint8 / int8: wann_set_dense_large_k_bytes), which also asks 96 k positions of a window -- stay on the exact scan.  Applies to every replica of WANN_DEVICES and to every call form.
  * Returns the previous setting (0 / 1) or a NEGATIVE error: -WANN_ERR_UNSUPPORTED for on = 1 on any kind but
  * WANN_KIND_PREFILTER, -WANN_ERR_INVALID for a null index. */
 int wann_set_dense_windows(wann_index *index, int on);
@@ -316,7 +316,7 @@ int wann_get_dense_window_counters(const wann_index *index, wann_dense_window_co
  * and before the super tree scans its levels.  Queries with w > L, empty windows and windows outside the label span take the
  * ordinary path and return the ordinary rows bit for bit.  In a batch of at least 32 queries the flagged queries take the dense
  * prefilter path (shared-window groups and cover groups on the matrix cores, under its usual gates: windows of >= 1 024
- * points, >= 32 queries per block, 2 GiB of eligible rows per batch, k <= 16 -- k <= 128 after wann_set_dense_large_k --, the row-length limits per element type); what it
+ * points, >= 32 queries per block, 2 GiB of eligible rows per batch, k <= 16 -- k <= 128 after wann_set_dense_large_k (uint8 / int8: wann_set_dense_large_k_bytes) --, the row-length limits per element type); what it
  * does not take or cannot prove goes to the exact scan, and both return the same rows bit for bit.  The scans and the dense
  * launches run beside the graph searches of the same batch.  While the limit is non-zero a batch holds the index's dense
  * buffers: the asynchronous lanes then run one batch at a time.  A call with wann_query_params::verbose set ignores the option
@@ -445,12 +445,26 @@ int wann_dense_long_float8(const wann_index *index);
  * 256 candidates per query kept as a sorted list (where k <= 16 keeps 32, one per lane), re-ranked exactly in passes of 64 rows,
  * the same proof, rescue and hand-over to the exact scan.  For such a call a window is dense-eligible from max(1024, 96 k)
  * positions (10 000-point windows: up to k = 104); narrower ones take the scan.  Returns the setting now in force, 0 / 1: asking
- * for 1 on a WANN_DTYPE_U8 / WANN_DTYPE_I8 index leaves it at 0 and returns 0 (their k stays <= 16).  Allocates and frees nothing;
+ * for 1 on a WANN_DTYPE_U8 / WANN_DTYPE_I8 index leaves it at 0 and returns 0 (their switch is wann_set_dense_large_k_bytes, below).  Allocates and frees nothing;
  * applies to every replica of WANN_DEVICES; a NEGATIVE error for a null index.  Changes no result row -- ids and distance bits
  * are the scan's -- and nothing at all for k <= 16 or k > 128.
  * wann_dense_large_k: that setting (0 after wann_index_create; 0 for a null index). */
 int wann_set_dense_large_k(wann_index *index, int on);
 int wann_dense_large_k(const wann_index *index);
+/* wann_set_dense_large_k_bytes: the same for WANN_DTYPE_U8 / WANN_DTYPE_I8 indexes, and for them alone: k = 17 .. 128 on the
+ * dense path in the NEXT batches, every call form, all three routes, the same window gate of max(1024, 96 k) positions, on
+ * k_large_rerank_b / k_large_rerank_cover_b.  Their hand-over keys are integers: 256 candidates per query are selected on them,
+ * and for rows of up to 512 bytes a key holds the very distance the scan returns, so the selected candidates are not scored
+ * again and no row of theirs is fetched -- they are only re-ordered from (distance, position) to (distance, id), ties at the
+ * k-th distance included.  Rows of 513 .. 2048 bytes (WANN_DENSE_LONG_ROWS=1) carry quantised keys and are re-scored in passes
+ * of 64.  The top k counts as proven only where the k-th distance lies strictly below everything left out; the rest is
+ * rescued block by block or handed to the exact scan.  Returns the setting now in force, 0 / 1: asking for 1 on an index of
+ * any other element type leaves it at 0 and returns 0.  Allocates and frees nothing; applies to every replica of WANN_DEVICES;
+ * a NEGATIVE error for a null index.  Changes no result row -- ids and distance bits are the scan's -- and nothing at all for
+ * k <= 16 or k > 128.  wann_set_dense_large_k does not move a byte index, with or without this switch.
+ * wann_dense_large_k_bytes: that setting (0 after wann_index_create; 0 for a null index). */
+int wann_set_dense_large_k_bytes(wann_index *index, int on);
+int wann_dense_large_k_bytes(const wann_index *index);
 
 /* WIDE ROWS: stop as at k, keep up to `width` entries (not calls of the reference; it computes this and drops the tail).
  * The reference's query() (src/postfilter_vamana.h:141-188) returns the whole filtered frontier of the last beam it searched;

@@ -15,10 +15,10 @@ namespace wann_host {
 // Which rows the score kernels take: the table above dense_row_class (wann_gemm_device.h).  The long class is opt-in
 // (WANN_DENSE_LONG_ROWS=1: until it is timed against the scan no batch moves to it by default; bfloat16 / float8 rows: the index's
 // own switch, wann_set_dense_long_rows / wann_set_dense_long_float8, which alone makes their class long); k > 128, and k > 16
-// without wann_set_dense_large_k (or on uint8 / int8 rows, with or without it), stays on the exact scan.
+// without the index's large-k switch (wann_set_dense_large_k; uint8 / int8 rows: wann_set_dense_large_k_bytes), stays on the exact scan.
 static bool dense_rows_ok(const wann_index &I, const Tuning &T, int k) {
   const DenseRows rows = dense_row_class(I.view, T.dense_long_rows, T.dense_long_float8);
-  const bool k_ok = k <= kSelect / 2 || (T.dense_large_k && k <= kDenseMaxK && !byte_rows(I.view));
+  const bool k_ok = k <= kSelect / 2 || (k <= kDenseMaxK && (byte_rows(I.view) ? T.dense_large_k_bytes : T.dense_large_k));
   return k_ok && rows != kRowsNone && (rows != kRowsLong || T.dense_long || T.dense_long_rows || T.dense_long_float8);
 }
 

@@ -7,7 +7,7 @@
 namespace wann {
 
 constexpr int kSelect = 32;      // candidates kept per query by MFMA score before the exact re-rank
-// k = 17 .. kDenseMaxK (opt-in per index, wann_set_dense_large_k): k_large_rerank keeps kSelectLarge candidates per query as a
+// k = 17 .. kDenseMaxK (opt-in per index, wann_set_dense_large_k; uint8 / int8: wann_set_dense_large_k_bytes): k_large_rerank keeps kSelectLarge candidates per query as a
 // sorted list in LDS -- the same 2 : 1 ratio of candidates to results
 constexpr int kSelectLarge = 256, kDenseMaxK = kSelectLarge / 2;
 constexpr int kGemmPointChunk = 2048;  // window positions per tile (multiple of 128)

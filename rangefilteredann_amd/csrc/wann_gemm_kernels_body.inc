@@ -1659,9 +1659,8 @@ __global__ __launch_bounds__(256) void k_rerank_cover_bslab(CoverArgs C) {
 }
 #endif
 
-#if !WANN_BYTE_ROWS
 // ------------------------------------------------------------------------------------------------
-// k = 17 .. kDenseMaxK (opt-in per index: wann_set_dense_large_k).  The score kernels' hand-over is the same for any k; what
+// k = 17 .. kDenseMaxK (opt-in per index: wann_set_dense_large_k; uint8 / int8 rows: wann_set_dense_large_k_bytes, further down).  The score kernels' hand-over is the same for any k; what
 // ends at 16 above is the list of kSelect candidates held one per lane, the single wave_distances pass and the rank loop across
 // the wave.  Here the kSelectLarge best candidates are a sorted list of (score key << 32 | window position) in the wave's LDS,
 // 2 KiB, and admission is BATCHED: inserting one candidate at a time would shift a 256-entry list 400 times a query.
@@ -1692,6 +1691,7 @@ __device__ __forceinline__ u64 wave_sort_u64(u64 key) {  // ascending over the 6
   return key;
 }
 
+#if !WANN_BYTE_ROWS
 // (one wave, one query; list[0 .. sel_cnt) = the selected candidates, best first; `cut` / `blk_bound` as select_scores returns them)
 template <class LOAD>
 __device__ __forceinline__ void select_scores_large(const LOAD &load, int64_t nblk, u64 *list, u64 *pend, int &sel_cnt, float &cut, float &blk_bound) {
@@ -1894,7 +1894,237 @@ __global__ __launch_bounds__(256) void k_large_rerank_cover(CoverArgs C) {
     rerank_query_large<METRIC>(A, L, (int)q, load, nblk, s0 << 7, t.a, t.b, &C.cctr->rescued, &C.cctr->unproven);
   }
 }
-#endif  // !WANN_BYTE_ROWS (large k)
+#else  // byte rows (large k)
+// ------------------------------------------------------------------------------------------------
+// The same for uint8 / int8 rows (opt-in per index: wann_set_dense_large_k_bytes).  The hand-over entries are integer keys
+// already, (dist + off) >> S << 6 | position in the block (wann_gemm_kernels_bytes.inc), so the list holds key << 32 | window
+// position with no fkey, and "no score" is key >= kNoKeyTest.  The list therefore orders by (distance, position bits, window
+// position).  Admission is select_scores_large's: trips of 64 blocks, ballot + prefix count into the pending buffer, a sorted
+// flush through wave_merge's presorted form, the threshold read again.  A candidate whose key EQUALS the threshold is refused:
+// `cut` only ever says "what was left out is no nearer than this, possibly as near".
+// ------------------------------------------------------------------------------------------------
+template <int METRIC, int KSH, class LOAD>
+__device__ __forceinline__ void select_keys_large(const LOAD &load, int64_t nblk, u64 *list, u64 *pend, int &sel_cnt, float &cut, float &blk_bound) {
+  const int lane = lane_id();
+  uint32_t thr = kNoKey;  // (every real key is below kNoKeyTest: all of them pass until the list is full)
+  int m = 0, np = 0;
+  uint32_t bound = kNoKey;
+  auto flush = [&]() {
+    WAVE_SYNC();
+    const u64 pk = wave_sort_u64(lane < np ? pend[lane] : ~0ull);
+    WAVE_SYNC();  // (wave_merge writes the sorted run back into pend)
+    int p0;
+    // (comparisons ignore an entry's bit 0; equal keys carry the same position bits, so bit 0 of their window positions is equal too)
+    m = wave_merge<u64 *, false, true>(list, m, kSelectLarge, lane < np, pk, pend, &p0);
+    np = 0;
+    if (m == kSelectLarge) thr = (uint32_t)(list[kSelectLarge - 1] >> 32);  // (the same address in every lane)
+  };
+  for (int64_t b0 = 0; b0 < nblk; b0 += 64) {
+    const int64_t bb = b0 + lane;
+    const u32x4 e = (bb < nblk) ? __builtin_bit_cast(u32x4, load(bb)) : u32x4{kNoKey, kNoKey, kNoKey, kNoKey};
+    bound = min(bound, e[3]);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const uint32_t key = e[c];
+      // block bb: step (bb >> 1), half (bb & 1); low bits 16 j + 4 g + r -> position 32 j + 8 g + 4 half + r
+      const uint32_t ix6 = key & 63u;
+      const int cp = (int)((bb >> 1) * 128 + 32 * (ix6 >> 4) + 8 * ((ix6 >> 2) & 3) + 4 * (bb & 1) + (ix6 & 3));
+      const u64 ent = ((u64)key << 32) | (uint32_t)cp;
+      bool want = key < kNoKeyTest && key < thr;
+      for (;;) {
+        const u64 mask = ballot64(want);
+        if (!mask) break;
+        const int r = popc64(mask & lanemask_lt()), room = 64 - np, all = popc64(mask);
+        if (want && r < room) {
+          pend[np + r] = ent;
+          want = false;
+        }
+        np += all < room ? all : room;
+        if (np < 64) break;  // (everybody found a place)
+        flush();
+        want = want && key < thr;
+      }
+    }
+  }
+  if (np) flush();
+  WAVE_SYNC();
+  for (int o = 32; o > 0; o >>= 1) bound = min(bound, (uint32_t)__shfl_xor((int)bound, o));
+  // every position that is not selected has a distance >= cut (its lower bound where KSH > 0): candidates that were refused, or
+  // dropped off the end of the list, >= its last key (once the list is full), everything else >= its block's fourth smallest
+  sel_cnt = m;
+  cut = (m == kSelectLarge) ? key_dist<METRIC, KSH>(thr) : 3.402823466e+38f;
+  blk_bound = (bound >= kNoKeyTest) ? 3.402823466e+38f : key_dist<METRIC, KSH>(bound);
+}
+
+// rerank_query for K = 17 .. kDenseMaxK on byte rows: the same arguments, the byte rules of its proof, rescue and hand-over.
+//   rows of up to 512 bytes (KSH = 0): a key holds the distance the scan returns -- the int32 sum, cast to float here as
+//     byte_pair casts it (key_scan_dist) -- so the selected candidates are NOT scored again: no row of theirs is fetched.  What is left to do is
+//     the order.  The list runs by (distance, position bits), the result by (distance, id), and the two differ wherever
+//     distances tie: with d_k the distance of list entry K - 1, the K results are the (distance, id)-smallest of ALL T entries
+//     whose distance is <= d_k -- T >= K, ties at d_k may reach past entry K - 1, and two integer sums beyond 2^24 may tie only
+//     as floats, so T is counted on the cast distances (the cast is monotonic: still a prefix of the list).  Their row numbers
+//     are looked up four a lane, all in flight, the keys become fkey(distance) << 32 | id << 1, and ceil(T / 64) wave_merge passes
+//     (ranked, cut at K) leave the result row in L.lbeam, over the list's bytes.  Ties at d_k that did NOT make the list are the
+//     proof's business: d_k must lie strictly below both cuts.
+//   rows of 513 .. 2048 bytes (KSH = kLongKeyShift): the keys are lower bounds, all cnt candidates are scored by wave_distances
+//     in passes of 64, as rerank_query_large does.
+// (the distance the scan returns for an unquantised key, BIT for bit: byte_reduce casts the integer sum and negates an inner
+// product AFTER the cast, so a zero inner product is -0 there -- as a bound key_dist's +0 serves, as a result it would sort
+// behind the rescue's copy of the same row and keep both)
+template <int METRIC>
+__device__ __forceinline__ float key_scan_dist(uint32_t key) { return METRIC == 1 ? -(float)(kMipsOff - (int)(key >> 6)) : (float)(int)(key >> 6); }
+
+template <int METRIC, int KSH, class LOAD>
+__device__ __forceinline__ void rerank_query_large_b(const GemmArgs &A, const WaveLds &L, const int qrow, const LOAD &load, const int64_t nblk_sel,
+                                                     const int64_t abase, const int64_t wa, const int64_t wb, unsigned long long *n_rescued,
+                                                     unsigned long long *n_unproven) {
+  const IndexView &ix = A.ix;
+  const int lane = lane_id();
+  const int K = A.k;
+  const int qw = qv_words(ix);
+  // (packed bytes, k_brute's rule; only the rescue and the long rows read them)
+  for (int i = lane; i < qw; i += 64) L.qv[i] = stage_query_word(A.queries, qrow, i, ix.d);
+  int cnt;
+  float cut_sel, cut_blk;
+  select_keys_large<METRIC, KSH>(load, nblk_sel, L.lbeam, L.cand_key, cnt, cut_sel, cut_blk);
+  static_assert(kSelectLarge == 4 * 64, "four list entries a lane");
+  int T = cnt;  // the entries that go into the merge: all of them, or those no farther than entry K - 1
+  if constexpr (KSH == 0) {
+    if (cnt >= K) {
+      const float dsel = key_dist<METRIC, 0>((uint32_t)(L.lbeam[K - 1] >> 32));  // (the same address in every lane)
+      T = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int x = 64 * j + lane;
+        T += popc64(ballot64(x < cnt && key_dist<METRIC, 0>((uint32_t)(L.lbeam[x] >> 32)) <= dsel));
+      }
+    }
+  }
+  // the entries' row numbers, four a lane, all lookups in flight at once (and their keys) -- then the list's bytes are free
+  int rid[4] = {0, 0, 0, 0};
+  uint32_t skey[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    if (64 * j + lane < T) {
+      const u64 e = L.lbeam[64 * j + lane];
+      skey[j] = (uint32_t)(e >> 32);
+      rid[j] = window_row(ix, abase + (int64_t)(uint32_t)e);
+    }
+  WAVE_SYNC();
+  int m = 0, p0;
+#pragma unroll 1
+  for (int c0 = 0; c0 < T; c0 += 64) {
+    const int n = T - c0 < 64 ? T - c0 : 64;
+    const int r = c0 == 0 ? rid[0] : c0 == 64 ? rid[1] : c0 == 128 ? rid[2] : rid[3];
+    float dist;
+    if constexpr (KSH == 0) {
+      dist = key_scan_dist<METRIC>(c0 == 0 ? skey[0] : c0 == 64 ? skey[1] : c0 == 128 ? skey[2] : skey[3]);
+    } else {
+      L.cand_id[lane] = r;
+      WAVE_SYNC();
+      dist = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, n, 0);
+    }
+    const u64 key = ((u64)fkey(dist) << 32) | ((u64)(uint32_t)r << 1);
+    bool pass = lane < n;
+    if (m >= K) pass = pass && ((key | 1ull) < (L.lbeam[K - 1] | 1ull));
+    m = wave_merge(L.lbeam, m, K, pass, key, L.cand_key, &p0);
+  }
+  const int ti = qrow * A.tstride;  // the query's slot 0 (stand-alone PrefilterIndex: one task slot per query)
+  // Byte rows: the scores ARE the distances k_brute returns (rows of more than 512 bytes: lower bounds of them, at most 3 below --
+  // the bounds below then only err towards the scan), so E = 0 and |q|^2 is part of the score.  What was not selected is only
+  // known to be NO BETTER than the cut in distance; at an equal distance a smaller id would win under k_brute's (dist, id)
+  // order, so the top k is certain only when d_k is STRICTLY below the cut, and a block is re-scanned when its fourth entry is
+  // <= d_k.
+  const float E = 0.f, qoff = 0.f;
+  // k-th exact distance (the worst one that is returned; m = min(cnt, K): the candidates are distinct rows)
+  const float dk = m > 0 ? funkey((uint32_t)(L.lbeam[m - 1] >> 32)) : -3.402823466e+38f;
+  const bool sel_ok = cut_sel == 3.402823466e+38f || (cnt >= K && dk + E < cut_sel + qoff - E);
+  const bool blk_ok = cut_blk == 3.402823466e+38f || (cnt >= K && dk + E < cut_blk + qoff - E);
+  bool proven = sel_ok && blk_ok;
+  if (!proven && sel_ok && cnt >= K) {
+    // Second chance, rerank_query's: the blocks whose fourth entry is <= d_k (a fixed set, d_k can only improve) are scored
+    // exactly, 64 positions each, and merged into the same list; a block's candidates that are in it already come by again with
+    // the same key bits -- the key's distance is wave_distances' -- and are dropped as copies.
+    int scanned = 0;
+    bool gave_up = false;
+    for (int64_t b0 = 0; b0 < nblk_sel && !gave_up; b0 += 64) {
+      const float m4 = (b0 + lane < nblk_sel) ? entry_score<METRIC, KSH>(load(b0 + lane)[3]) : kHuge;
+      u64 hide = ballot64(m4 < kHugeTest && m4 + qoff - E <= dk + E);
+      while (hide) {
+        const int64_t b = b0 + ctz64(hide);
+        hide &= hide - 1;
+        if (++scanned > 16) {
+          gave_up = true;
+          break;
+        }
+        const int64_t pos = abase + (b >> 1) * 128 + 32 * (lane >> 4) + 8 * ((lane >> 2) & 3) + 4 * (b & 1) + (lane & 3);
+        const bool valid = pos >= wa && pos < wb;  // (the query's own window: a cover group's block reaches beyond it)
+        const int r2 = valid ? window_row(ix, pos) : 0;
+        L.cand_id[lane] = r2;
+        WAVE_SYNC();
+        const float d2 = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, 64, 0);
+        const u64 k2 = ((u64)fkey(d2) << 32) | ((u64)(uint32_t)r2 << 1);
+        bool pass = valid;
+        if (m >= K) pass = pass && ((k2 | 1ull) < (L.lbeam[K - 1] | 1ull));
+        m = wave_merge(L.lbeam, m, K, pass, k2, L.cand_key, &p0);
+      }
+    }
+    if (!gave_up) {
+      proven = true;
+      if (lane == 0) atomicAdd(n_rescued, 1ull);
+    }
+  }
+  // (an unproven query's row is rewritten by the scan; until then it holds exact distances of rows of its window, like rerank_query's)
+  for (int x = lane; x < m; x += 64) {
+    const u64 e = L.lbeam[x];
+    A.out_key[(size_t)ti * K + x] = (e & 0xffffffff00000000ull) | (uint32_t)((uint32_t)e >> 1);
+  }
+  if (lane == 0) {
+    A.out_cnt[ti] = m;
+    if (!proven) {
+      A.brute_list[atomicAdd(A.brute_count, 1)] = ti;
+      atomicAdd(n_unproven, 1ull);
+    }
+  }
+  WAVE_SYNC();
+}
+
+// k_large_rerank / k_large_rerank_cover on byte rows: the same grids and LDS; KSH = 0 / kLongKeyShift as k_rerank / k_rerank_bslab
+template <int METRIC, int KSH>
+__global__ __launch_bounds__(256) void k_large_rerank_b(GemmArgs A, Counters *ctr) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int wv = threadIdx.x >> 6;
+  const int qw = qv_words(A.ix);
+  const int per_wave = wave_lds_common_bytes(qw) + kLargeListBytes;
+  const WaveLds L = carve_wave_lds(smem + (size_t)wv * per_wave, qw, kSelectLarge, true);
+  const int64_t ntq = A.plan[P_NTQ];
+  for (int64_t tq = (int64_t)blockIdx.x * 4 + wv; tq < ntq; tq += (int64_t)gridDim.x * 4) {
+    const GemmGroup grp = A.groups[A.tq_group[tq]];
+    const int64_t nblk = ((grp.b - grp.a + 127) >> 7) * 2;
+    const EntryRow load{reinterpret_cast<const f32x4 *>(A.scores + grp.soff) + (int64_t)A.tq_local[tq] * nblk};
+    rerank_query_large_b<METRIC, KSH>(A, L, A.gq[tq], load, nblk, grp.a, grp.a, grp.b, &ctr->gemm_rescued, &ctr->gemm_unproven);
+  }
+}
+
+template <int METRIC, int KSH>
+__global__ __launch_bounds__(256) void k_large_rerank_cover_b(CoverArgs C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const GemmArgs &A = C.g;
+  const int wv = threadIdx.x >> 6;
+  const int qw = qv_words(A.ix);
+  const int per_wave = wave_lds_common_bytes(qw) + kLargeListBytes;
+  const WaveLds L = carve_wave_lds(smem + (size_t)wv * per_wave, qw, kSelectLarge, true);
+  if (C.pass >= C.cplan[CP_NPASS]) return;
+  for (int64_t q = (int64_t)blockIdx.x * 4 + wv; q < A.nq; q += (int64_t)gridDim.x * 4) {
+    if (C.q_pass[q] != C.pass) continue;  // (wave-uniform)
+    const Task t = A.tasks[q * A.tstride];
+    const int64_t s0 = t.a >> 7, nblk = (((t.b - 1) >> 7) - s0 + 1) * 2;
+    const CoverRow load{reinterpret_cast<const f32x4 *>(A.scores), C.qb_base + (int64_t)C.pass * C.pair_stride + C.q_off[q], s0, t.a, t.b,
+                        (int32_t)(t.a / kGemmPointChunk)};
+    rerank_query_large_b<METRIC, KSH>(A, L, (int)q, load, nblk, s0 << 7, t.a, t.b, &C.cctr->rescued, &C.cctr->unproven);
+  }
+}
+#endif  // large k
 WANN_GNS_END
 #endif  // WANN_DT != 6
 

@@ -25,6 +25,10 @@ static const char *unit_rerank_cover(const CoverArgs &c, void *stream) {
   void (*kern)(CoverArgs) = nullptr;
 #if WANN_BYTE_ROWS
   if (dense_row_class(c.g.ix) == kRowsLong) kern = c.g.ix.metric == 1 ? k_rerank_cover_bslab<1> : k_rerank_cover_bslab<0>;  // (quantised keys)
+  if (c.g.k > kSelect / 2) {  // (wann_set_dense_large_k_bytes; the key shift follows the row class as above)
+    if (dense_row_class(c.g.ix) == kRowsLong) kern = c.g.ix.metric == 1 ? k_large_rerank_cover_b<1, kLongKeyShift> : k_large_rerank_cover_b<0, kLongKeyShift>;
+    else kern = c.g.ix.metric == 1 ? k_large_rerank_cover_b<1, 0> : k_large_rerank_cover_b<0, 0>;
+  }
 #endif
 #if !WANN_BYTE_ROWS
   if (c.g.k > kSelect / 2) kern = c.g.ix.metric == 1 ? k_large_rerank_cover<1> : k_large_rerank_cover<0>;  // (wann_set_dense_large_k)
@@ -142,6 +146,10 @@ static const char *unit_select_rerank(const GemmArgs &a, Counters *ctr, void *st
   void (*kern)(GemmArgs, Counters *) = nullptr;
 #if WANN_BYTE_ROWS
   if (dense_row_class(a.ix) == kRowsLong) kern = a.ix.metric == 1 ? k_rerank_bslab<1> : k_rerank_bslab<0>;  // (quantised keys)
+  if (a.k > kSelect / 2) {  // (wann_set_dense_large_k_bytes; the key shift follows the row class as above)
+    if (dense_row_class(a.ix) == kRowsLong) kern = a.ix.metric == 1 ? k_large_rerank_b<1, kLongKeyShift> : k_large_rerank_b<0, kLongKeyShift>;
+    else kern = a.ix.metric == 1 ? k_large_rerank_b<1, 0> : k_large_rerank_b<0, 0>;
+  }
 #endif
 #if !WANN_BYTE_ROWS
   if (a.k > kSelect / 2) kern = a.ix.metric == 1 ? k_large_rerank<1> : k_large_rerank<0>;  // (wann_set_dense_large_k)

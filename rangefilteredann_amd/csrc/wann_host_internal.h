@@ -188,10 +188,14 @@ struct wann_index {
   bool dense_long_float8_on = false;
   bool has_dense_long_float8() const { return wann::dense_long_float8_type(dtype); }
   // wann_set_dense_large_k (under tune_mu; off by default): calls with k = 17 .. kDenseMaxK take the dense path of the next
-  // batches, on k_large_rerank / k_large_rerank_cover.  Never on for uint8 / int8 rows: their selection works on quantised keys
-  // (select_keys) and has no large form.
+  // batches, on k_large_rerank / k_large_rerank_cover.  Never on for uint8 / int8 rows: their selection works on integer keys
+  // and has a switch of its own, below.
   bool dense_large_k_on = false;
   bool has_dense_large_k() const { return !wann::byte_rows(dtype); }
+  // wann_set_dense_large_k_bytes (likewise): the same for uint8 / int8 rows and for them alone, on k_large_rerank_b /
+  // k_large_rerank_cover_b (select_keys_large; rows of up to 512 bytes return the keys' distances and fetch no selected row).
+  bool dense_large_k_bytes_on = false;
+  bool has_dense_large_k_bytes() const { return wann::byte_rows(dtype); }
   bool has_half_copy() const { return d_half.p != nullptr; }
   bool has_byte_copy() const { return d_bytes.p != nullptr; }
   bool has_scan_copy() const { return has_half_copy() || has_byte_copy(); }
@@ -289,6 +293,7 @@ constexpr RowSwitch kDenseRowsSwitch = {&wann_index::dense_rows_on, &wann_index:
 constexpr RowSwitch kDenseLongRowsSwitch = {&wann_index::dense_long_rows_on, &wann_index::has_dense_long_switch, nullptr};
 constexpr RowSwitch kDenseLongFloat8Switch = {&wann_index::dense_long_float8_on, &wann_index::has_dense_long_float8, nullptr};
 constexpr RowSwitch kDenseLargeKSwitch = {&wann_index::dense_large_k_on, &wann_index::has_dense_large_k, nullptr};
+constexpr RowSwitch kDenseLargeKBytesSwitch = {&wann_index::dense_large_k_bytes_on, &wann_index::has_dense_large_k_bytes, nullptr};
 // (under I.tune_mu)
 inline bool row_switch_in_force(const wann_index &I, const RowSwitch &s) { return I.*s.on && (I.*s.has_copy)(); }
 

@@ -297,6 +297,9 @@ class Index {
   // k = 17 .. 128 on the dense path, on k_large_rerank (wann_set_dense_large_k, off by default; False on a uint8 / int8 index)
   bool set_dense_large_k(bool on) { return set_row_switch(wann_set_dense_large_k, on, "set_dense_large_k failed"); }
   bool dense_large_k() const { return wann_dense_large_k(h_) != 0; }
+  // the same on a uint8 / int8 index, on k_large_rerank_b (wann_set_dense_large_k_bytes, off by default; False on any other element type)
+  bool set_dense_large_k_bytes(bool on) { return set_row_switch(wann_set_dense_large_k_bytes, on, "set_dense_large_k_bytes failed"); }
+  bool dense_large_k_bytes() const { return wann_dense_large_k_bytes(h_) != 0; }
 
   // float16 / bfloat16 / float8 indexes: the full-precision points (any array numpy casts to float32, in the order of the array
   // the index was created from) as the row store of the refined calls (wann_set_refine_rows); None drops the store
@@ -417,6 +420,7 @@ class Index {
     d["dense_long_rows"] = wann_dense_long_rows(h_);  // the index's wann_set_dense_long_rows setting (a setting, not a count)
     d["dense_long_float8"] = wann_dense_long_float8(h_);  // the index's wann_set_dense_long_float8 setting (likewise)
     d["dense_large_k"] = wann_dense_large_k(h_);          // the index's wann_set_dense_large_k setting (likewise)
+    d["dense_large_k_bytes"] = wann_dense_large_k_bytes(h_);  // the index's wann_set_dense_large_k_bytes setting (likewise)
     return d;
   }
   static py::dict counters_dict(const wann_counters &c) {
@@ -511,6 +515,8 @@ static void common_defs(py::class_<C> &c) {
       .def("dense_long_float8", &C::dense_long_float8)
       .def("set_dense_large_k", &C::set_dense_large_k, "on"_a)
       .def("dense_large_k", &C::dense_large_k)
+      .def("set_dense_large_k_bytes", &C::set_dense_large_k_bytes, "on"_a)
+      .def("dense_large_k_bytes", &C::dense_large_k_bytes)
       .def("set_refine_rows", &C::set_refine_rows, "points"_a.none(true))
       .def("refine_rows_bytes", &C::refine_rows_bytes)
       .def("batch_search_refined", &C::search_refined, "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a,

@@ -10,8 +10,8 @@ k_gemm_scores_f8slab likewise, with set_dense_long_float8(True)), the byte types
 on the int8 MFMA with exact scores.  Every leg is timed as the median of repeated calls (min / max beside it: the spread).
 --dim D sets the row length (default 100; 512 = RedCaps, 768 / 1024 / 1536 = the long rows of k_gemm_scores_long (float32), k_gemm_scores_hslab (float16) and k_gemm_scores_bslab (uint8 / int8)), --clusters C
 the number of clusters (default 100), --metric l2 | mips the metric of the float types (default mips), --k K the result width (default
-10; beyond 16 the dense legs run after set_dense_large_k(True) where the build has that method, on k_large_rerank: a window of
-10 000 points is dense-eligible up to k = 104).  WANN_PF_CACHE=<dir> keeps
+10; beyond 16 the dense legs run after set_dense_large_k(True) where the build has that method, on k_large_rerank -- uint8 / int8: set_dense_large_k_bytes(True),
+on k_large_rerank_b --: a window of 10 000 points is dense-eligible up to k = 104).  WANN_PF_CACHE=<dir> keeps
 the generated set there for the next run of the same shape; WANN_PF_ONLY=mfma times the dense leg alone (runs under a profiler),
 WANN_PF_ONLY=scan the exact-scan leg alone, twice (the baseline run of a parent build); WANN_PF_NO_REF=1 leaves the CPU reference out.
 --byte-exact: the float32 index is fed the integer values of the uint8 leg, round(127 x) + 128, as float32 (d = 128 and the
@@ -153,6 +153,8 @@ if DTYPE == "float8":
         assert idx.set_dense_long_float8(True)
 if K > 16 and hasattr(idx, "set_dense_large_k"):  # (a parent build has no such kernel: its WANN_PF_ONLY=scan leg needs none; byte types refuse)
     assert idx.set_dense_large_k(True) or DTYPE in ("uint8", "int8")
+if K > 16 and DTYPE in ("uint8", "int8") and hasattr(idx, "set_dense_large_k_bytes"):  # (the byte types' own switch, likewise)
+    assert idx.set_dense_large_k_bytes(True)
 qp = wa.QueryParams(K, K, 1.35, 10**7, 10**4, 1, 10000, None, False)
 dev = torch.device("cuda:0")
 Qt = torch.from_numpy(Q.astype(np.float32)).to(dev)  # (device-buffer calls take fp32 queries; every element type converts exactly)
