@@ -465,6 +465,20 @@ int wann_dense_large_k(const wann_index *index);
  * wann_dense_large_k_bytes: that setting (0 after wann_index_create; 0 for a null index). */
 int wann_set_dense_large_k_bytes(wann_index *index, int on);
 int wann_dense_large_k_bytes(const wann_index *index);
+/* Centred operands on the dense path: data far from the origin.
+ * wann_set_dense_centred: whether squared-L2 batches of a WANN_DTYPE_F32 / WANN_DTYPE_F16 index with rows of at most 128 elements
+ * are scored, in the NEXT batches and on all three routes, on centred operands: the MFMA score kernel stages fl(q - c) and
+ * fl(p - c), c the mean row of the index (computed once, at the first such batch, with the norms |fl(p - c)|^2: n + padded row + 1
+ * floats of device memory), and the proof's bound runs on the centred norms.  |q - p|^2 is the same, the bound's terms
+ * |q|^2 + max |p|^2 are not: rows and queries with a large common component (non-negative histograms, embeddings with a large
+ * mean) otherwise send every query back to the exact scan.  Returns the setting now in force, 0 / 1: asking for 1 on an inner-product
+ * index or on one of any other element type leaves it at 0 and returns 0.  Applies to every replica of WANN_DEVICES; a NEGATIVE
+ * error for a null index.  Changes no result row -- every returned distance is still computed on the original rows and query, ids
+ * and distance bits are the scan's -- only which queries are proven, rescued or handed to the scan.  Batches it does not cover
+ * (longer rows, score launches that read the one-byte copy of wann_set_dense_rows, which keeps precedence) run as with the switch off.
+ * wann_dense_centred: that setting (0 after wann_index_create; 0 for a null index). */
+int wann_set_dense_centred(wann_index *index, int on);
+int wann_dense_centred(const wann_index *index);
 
 /* WIDE ROWS: stop as at k, keep up to `width` entries (not calls of the reference; it computes this and drops the tail).
  * The reference's query() (src/postfilter_vamana.h:141-188) returns the whole filtered frontier of the last beam it searched;

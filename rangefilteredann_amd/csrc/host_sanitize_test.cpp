@@ -254,6 +254,38 @@ static void check_dense_large_k() {
   CHECK(rerank_lds_bytes(view_of(WANN_DTYPE_F16, 2048), 128) == 45056);                       // (the staged query is the float32 upcast)
 }
 
+// wann_set_dense_centred without a device: which indexes the switch takes (dense_centred_type), which batches the centred route
+// (dense_centred_route), the layout of the centred buffer, the room k_row_centre's partial sums need inside it, and the error
+// term against its derivation evaluated in double precision.
+static void check_dense_centred() {
+  for (int dt = -1; dt <= 9; dt++)
+    for (int metric = 0; metric < 2; metric++)
+      CHECK(dense_centred_type(dt, metric) == ((dt == WANN_DTYPE_F32 || dt == WANN_DTYPE_F16) && metric == 0));
+  for (int dt : {WANN_DTYPE_F32, WANN_DTYPE_F16})
+    for (int d : {1, 16, 100, 128, 129, 200, 2048}) {
+      IndexView v = view_of(dt, d);
+      CHECK(dense_centred_route(v, true, false) == (d <= 128));  // (the narrow class alone)
+      CHECK(!dense_centred_route(v, false, false));              // (switch off)
+      CHECK(!dense_centred_route(v, true, true));                // (wann_set_dense_rows keeps precedence)
+      v.metric = 1;
+      CHECK(!dense_centred_route(v, true, false));
+    }
+  CHECK(!dense_centred_route(view_of(WANN_DTYPE_BF16, 64), true, false) && !dense_centred_route(view_of(WANN_DTYPE_F8, 64), true, false) &&
+        !dense_centred_route(view_of(WANN_DTYPE_U8, 64), true, false));
+  // norms | c | maximum: n + words + 1 floats; the partial sums are at most 256 rows of `words` floats and lie inside the norms'
+  // floats, or are the single row c
+  for (int64_t n : {(int64_t)1, (int64_t)15, (int64_t)16, (int64_t)127, (int64_t)128, (int64_t)1000, (int64_t)32767, (int64_t)32768, (int64_t)100000000})
+    for (int words : {16, 112, 128}) {
+      const int parts = centred_parts(n, words);
+      CHECK(centred_buf_floats(n, words) == (size_t)n + words + 1);
+      CHECK(parts >= 1 && parts <= 256 && (n >= words ? (int64_t)parts * words <= n : parts == 1));
+      const int64_t per = (n + parts - 1) / parts;  // (k_row_centre's slices cover every row)
+      CHECK(per * parts >= n);
+    }
+  const double u = std::ldexp(1.0, -24), u1 = u / (1.0 - u);
+  CHECK((double)kCentredErr > 2.0 * u1 + u1 * u1 && (double)kCentredErr <= 2.5 * u);
+}
+
 // The row-type table (wann_row_types.h) against the values written out here: every class, the caller's bytes, the device
 // pitch, the staged query's length and the kinds of unit of every id from -1 to 9.  (That the two layout rules are
 // permutations: byte_layout_sanitize_test.cpp and half_layout_sanitize_test.cpp.)
@@ -455,6 +487,7 @@ int main(int argc, char **argv) {
       }
   check_scan_lds();
   check_dense_large_k();
+  check_dense_centred();
   check_row_types();
   check_refdump();
   // the C ABI's argument validation (no device needed for these paths) lives in wann_abi.cpp and is covered by tests/test_abi.py

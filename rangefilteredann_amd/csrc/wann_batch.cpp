@@ -61,6 +61,15 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
     }
     I.have_norms = true;
   }
+  // wann_set_dense_centred: this batch is scored on fl(x - c) and proven on the centred norms.  The centre and those norms are
+  // computed once, at the first such batch, beside the uncentred ones (a later batch may run with the switch off again).
+  const bool centred = dense_centred_route(I.view, T.dense_centred, dense_score_view(I, T) != nullptr);
+  if (centred && !I.have_centred) {
+    I.d_centred.ensure(centred_buf_floats(I.view.n, qwords));
+    if (launch_centred_norms(I.view, I.d_centred.p, st)) throw HipError(std::string("k_row_centre / k_point_norms_centred: ") + gemm_launch_last_error());
+    if (sorted_exact) I.device_bytes += (int64_t)I.d_centred.bytes();  // (reported where the uncentred norms are)
+    I.have_centred = true;
+  }
   size_t cap = 64;
   while (cap < (size_t)nq * 2) cap <<= 1;
   I.g_slot_key.ensure(cap);
@@ -104,6 +113,11 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   ga.tq_local = I.g_tq_local.p;
   ga.pnorm2 = I.d_pnorm2.p;
   ga.pnorm2_max_bits = I.d_pnorm2_max.p;
+  if (centred) {  // (norms | c | the maximum's bits: what the score kernel's base[] and the proof's pmax read are the centred ones)
+    ga.pnorm2 = I.d_centred.p;
+    ga.centre = I.d_centred.p + I.view.n;
+    ga.pnorm2_max_bits = reinterpret_cast<const unsigned int *>(ga.centre + qwords);
+  }
   ga.pterm = I.d_pterm.p;
   if (long_rows) {
     // k_gemm_scores_long / _hslab / _bfslab / _f8slab take the queries already split into their bf16 terms: once per batch instead of once per

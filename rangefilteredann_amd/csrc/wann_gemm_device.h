@@ -86,7 +86,25 @@ struct GemmArgs {
   int32_t *out_cnt;
   int32_t *brute_list, *brute_count;  // exact scan: ungrouped queries + queries whose top-k could not be proven
   unsigned long long *prof;           // dev tool (make PROFILE=1): phase-cycle sums of k_gemm_scores
+  // A centred batch (wann_set_dense_centred; dense_centred_route): the index's centre c, `query_words` floats, zero beyond d.
+  // Non-null IS the flag: the score launch picks k_gemm_scores<STRIDE, true>, the proof sums |fl(q - c)|^2 and widens its bound
+  // by kCentredErr, and pnorm2 / pnorm2_max_bits above point at |fl(p - c)|^2 and its maximum.  Null: everything as it was.
+  const float *centre;
 };
+
+// What the proof's relative error gains on a centred batch, as a summand of cerr (E = 2 cerr2 (|q'|^2 + max |p'|^2)), for the two
+// elementwise roundings q' = fl(q - c), p' = fl(p - c).  Each is (x - c)(1 + delta), |delta| <= u = 2^-24 (a subtraction has no
+// underflow error), so q' - p' = (q - p) + e with |e| <= u' (|q'| + |p'|), u' = u / (1 - u), and
+//   | |q - p|^2 - |q' - p'|^2 | = | -2 (q' - p').e + |e|^2 | <= (2 u' + u'^2) (|q'| + |p'|)^2 <= 2 (2 u' + u'^2) (|q'|^2 + |p'|^2):
+// 2 u' + u'^2 < 2.0000003 x 2^-24 beside cerr.  2.5 x 2^-24 leaves room for the fp32 evaluation of the bound itself.
+constexpr float kCentredErr = 2.5f * 5.9604645e-8f;
+
+// Centred scoring is for float32 / float16 rows under squared L2 (the switch's predicate, wann_set_dense_centred) ...
+constexpr bool dense_centred_type(int dtype, int metric) { return (dtype == kRowsF32 || dtype == kRowsF16) && metric == 0; }
+// The buffer of a centred index, computed once: |fl(p - c)|^2 per point, c (`words` floats), the bits of the largest norm.
+// (k_row_centre's partial sums pass through the norms' floats before the norms are written: `centred_parts` rows of `words`.)
+constexpr size_t centred_buf_floats(int64_t n, int words) { return (size_t)n + (size_t)words + 1; }
+constexpr int centred_parts(int64_t n, int words) { return n >= (int64_t)256 * words ? 256 : n >= words ? (int)(n / words) : 1; }
 
 // Cover groups: the queries the window grouping left over, grouped by position block of the label argsort instead of by window.
 // A cover group is a GemmGroup (a, b = the block's bounds clipped to n, nch = 1), so the score kernels run on it as they are; a
@@ -163,6 +181,13 @@ inline DenseRows dense_row_class(const IndexView &ix, bool long_switch = false, 
   return ix.dtype == kRowsF32 && words <= 512 ? kRowsWide : kRowsLong;
 }
 
+// ... and a batch takes the centred route when the index's switch is in force, its rows are of the narrow class and the score
+// launches do not read the one-byte copy (wann_set_dense_rows keeps precedence: its bytes are no single bfloat16 values once
+// centred).  Every other batch is scored and proven as if the switch were off.
+inline bool dense_centred_route(const IndexView &ix, bool switch_on, bool byte_copy_scored) {
+  return switch_on && !byte_copy_scored && dense_centred_type(ix.dtype, ix.metric) && dense_row_class(ix) == kRowsNarrow;
+}
+
 // Dynamic LDS of the selection / re-rank kernels: four waves x (staged query row, candidate arrays, the merge list).  k <= 16
 // (k_rerank): a merge list of k entries.  Beyond (k_large_rerank): the list of kSelectLarge candidates, whose bytes the k-entry
 // merge list takes over once the selected rows' numbers sit in registers -- 44 KiB at d = 2048, under the 48 KiB a launch gets
@@ -181,12 +206,15 @@ struct GemmUnit {
   const char *(*gemm_scores)(const GemmArgs &a, int num_cus, void *stream);
   const char *(*select_rerank)(const GemmArgs &a, Counters *ctr, void *stream);
   const char *(*rerank_cover)(const CoverArgs &c, void *stream);
+  // float32 / float16: the centre and the centred norms into `buf` (centred_buf_floats: norms | c | maximum's bits); null elsewhere
+  const char *(*centred_sums)(const IndexView &ix, float *buf, void *stream);
 };
 
 WANN_UNIT_LOOKUP(dense, GemmUnit, gemm_unit, gemm_unit_of)  // (null: the row type has no dense unit)
 
 // entry points (the float32 unit): each looks up ix.dtype's unit, calls it and records the error; 0 = launched
 int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);  // float32 / float16 / bfloat16 rows
+int launch_centred_norms(const IndexView &ix, float *buf, void *stream);                          // float32 / float16 rows: k_row_centre, k_point_norms_centred
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream);                         // uint8 / int8 rows
 int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream);  // long float32 / float16 rows
 int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);  // long uint8 / int8 rows

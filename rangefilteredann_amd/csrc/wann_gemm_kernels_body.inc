@@ -135,6 +135,70 @@ __global__ void k_point_norms(IndexView ix, float *norm2, unsigned int *max_bits
 WANN_GNS_END
 #endif
 
+#if WANN_DT == 0 || WANN_DT == 3
+// ------------------------------------------------------------------------------------------------
+// Centred operands (opt-in per index: wann_set_dense_centred; squared L2, rows of at most 128 elements).  |q - p|^2 does not change
+// when one vector c is taken from both sides, but the terms of the proof's bound do: E = 2 cerr2 (|q|^2 + max |p|^2) grows with
+// the data's distance from the origin, the gaps it must resolve do not.  With c the mean row, the centred k_gemm_scores scores
+// fl(q - c) against fl(p - c) and the proof runs on their norms.  Any c is valid; only the bound's size depends on it.
+//
+//   k_row_centre           c[words] in fp32, once per index, in a fixed order (no floating-point atomics: c, and with it every
+//                          counter of the path, is the same from run to run).  stage 0: workgroup g sums its contiguous slice of
+//                          rows per column -- thread (column, sub) every other row of the slice, the two subs added through the
+//                          LDS -- and writes part[g][words].  stage 1, one workgroup: the partial sums in workgroup order, divided
+//                          by n; columns d .. words are zero; the maximum's bits are cleared for k_point_norms_centred.
+//   k_point_norms_centred  k_point_norms on fl(p_i - c_i): the fp32 subtraction the score kernel stages, element by element, so
+//                          that the norm is of the very values that are scored (|p|^2 - 2 c.p + |c|^2 would cancel instead).
+// A float16 row widens exactly first; c is float32 in both units.
+// ------------------------------------------------------------------------------------------------
+WANN_GNS_BEGIN
+__device__ __forceinline__ float centre_row_value(const IndexView &ix, int64_t row, int i) {
+  const float *p = ix.points + row * (int64_t)ix.stride;
+#if WANN_DT == 3
+  return h2f(reinterpret_cast<const unsigned short *>(p)[i]);
+#else
+  return p[i];
+#endif
+}
+
+__global__ __launch_bounds__(256) void k_row_centre(IndexView ix, int words, float *part, int nparts, float *c, unsigned int *max_bits, int stage) {
+  __shared__ float sh[128];
+  const int tid = threadIdx.x, col = tid & 127, sub = tid >> 7;
+  if (stage == 0) {
+    const int64_t per = (ix.n + nparts - 1) / nparts, r0 = (int64_t)blockIdx.x * per, r1 = r0 + per < ix.n ? r0 + per : ix.n;
+    float s = 0.f;
+    if (col < ix.d)
+      for (int64_t r = r0 + sub; r < r1; r += 2) s += centre_row_value(ix, r, col);
+    if (sub == 1) sh[col] = s;
+    __syncthreads();
+    if (sub == 0 && col < words) part[(int64_t)blockIdx.x * words + col] = s + sh[col];
+  } else if (tid < words) {  // (one workgroup; `part` may be `c` itself when there is one partial row: read, then written, by the same thread)
+    float s = 0.f;
+    for (int g = 0; g < nparts; g++) s += part[(int64_t)g * words + tid];
+    c[tid] = tid < ix.d ? s / (float)ix.n : 0.f;
+    if (tid == 0) *max_bits = 0u;
+  }
+}
+
+__global__ void k_point_norms_centred(IndexView ix, const float *c, float *norm2, unsigned int *max_bits) {
+  const int lane = lane_id();
+  const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= ix.n) return;
+  float s = 0.f;
+  for (int i = lane; i < ix.d; i += 64) {
+    const float v = centre_row_value(ix, row, i) - c[i];
+    s = fmaf(v, v, s);
+  }
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) {
+    norm2[row] = s;
+    // s >= 0: the bit pattern orders like the value; only a new maximum pays for the atomic
+    if (__float_as_uint(s) > __hip_atomic_load(max_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(max_bits, __float_as_uint(s));
+  }
+}
+WANN_GNS_END
+#endif
+
 #if WANN_DT == 0
 // ------------------------------------------------------------------------------------------------
 // grouping
@@ -537,7 +601,12 @@ __device__ __forceinline__ void insert4_chain(float &m1, float &m2, float &m3, f
 #endif
 #else
 WANN_GNS_BEGIN
-template <int STRIDE>  // padded row length in floats: a multiple of 16, <= 128
+// CENTRED (wann_set_dense_centred; squared L2 only): both operands are staged as fl(x - c), c = A.centre, which sits in the 512
+// bytes of LDS behind rid[] that the launch has always carried.  A thread's staging columns are the same for every row, 4 (tid & 3)
+// + 16 x, but its 4 nx values of c are read from the LDS where a block is staged, not kept: at STRIDE = 128 the kernel stands at
+// its 256 registers, and the reads are nx ds_read_b128 beside 2 nx stores.  base[] then takes the centred norms (A.pnorm2 points at
+// them); MFMA order, selection network, position bits and hand-over are the uncentred kernel's.
+template <int STRIDE, bool CENTRED = false>  // padded row length in floats: a multiple of 16, <= 128
 __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const IndexView &ix = A.ix;
@@ -547,6 +616,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
   unsigned char *Ps = smem;                                    // [128][RB]
   float *base = reinterpret_cast<float *>(smem + 128 * RB);    // [128] per staged point: |p|^2 / 0
   int *rid = reinterpret_cast<int *>(base + 128);              // [128] point rows of the block being fetched
+  [[maybe_unused]] float *cs = reinterpret_cast<float *>(rid + 128);  // [STRIDE] CENTRED: the centre (columns d .. STRIDE are zero)
+  if constexpr (CENTRED) {
+    if (tid < STRIDE) cs[tid] = A.centre[tid];  // (visible after the barrier that opens the first tile)
+  }
   constexpr int s4 = STRIDE >> 2;
   constexpr int nit = s4 >> 1;  // 128 rows x s4 float4 / 256 threads (s4 is even)
   constexpr int nx = s4 >> 2;   // staging: four threads per point row (64 B contiguous), 64 rows per pass, two passes
@@ -588,6 +661,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
         v[0] = src[min(c + 0, dlast)]; v[1] = src[min(c + 1, dlast)]; v[2] = src[min(c + 2, dlast)]; v[3] = src[min(c + 3, dlast)];
 #pragma unroll
         for (int e = 0; e < 4; e++) v[e] = (live && c + e < ix.d) ? v[e] : 0.f;
+        if constexpr (CENTRED) {  // (dead rows and the columns beyond d stay exactly zero)
+          const f32x4 cv = *reinterpret_cast<const f32x4 *>(cs + c);
+#pragma unroll
+          for (int e = 0; e < 4; e++) v[e] = (live && c + e < ix.d) ? v[e] - cv[e] : 0.f;
+        }
         *reinterpret_cast<f32x4 *>(Qs + r * DP + c) = v;
       }
       __syncthreads();
@@ -659,10 +737,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_scores(GemmArgs A) {
         for (int x = 0; x < nx; x++) {
 #if WANN_DT == 3
           const float4 vh = h4_to_f4(pre[p * nx + x]);
-          const f32x4 v = {vh.x, vh.y, vh.z, vh.w};
+          f32x4 v = {vh.x, vh.y, vh.z, vh.w};
 #else
-          const f32x4 v = pre[p * nx + x];
+          f32x4 v = pre[p * nx + x];
 #endif
+          if constexpr (CENTRED) v -= *reinterpret_cast<const f32x4 *>(cs + 4 * (tid & 3) + 16 * x);  // (c is zero beyond d, and so are the rows)
           uint32_t h0, l0, h1, l1;
           split2(v[0], v[1], h0, l0);
           split2(v[2], v[3], h1, l1);
@@ -1412,6 +1491,15 @@ __device__ __forceinline__ void select_scores(const LOAD &load, int64_t nblk, in
 template <int METRIC, int KSH>
 __device__ __forceinline__ float entry_score(float e) { return e; }
 __device__ __forceinline__ float no_entry() { return kHuge; }
+// the centre of a centred batch, or null: squared L2 in the float32 and float16 units alone (everywhere else a constant null --
+// those kernels stay the code they were)
+template <int METRIC>
+__device__ __forceinline__ const float *centre_of(const GemmArgs &A) {
+#if WANN_DT == 0 || WANN_DT == 3
+  if constexpr (METRIC == 0) return A.centre;
+#endif
+  return nullptr;
+}
 #else  // byte rows
 #include "wann_gemm_kernels_bytes.inc"
 __device__ __forceinline__ float no_entry() { return __uint_as_float(kNoKey); }
@@ -1466,10 +1554,14 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
 #if WANN_BYTE_ROWS
     for (int i = lane; i < qw; i += 64) L.qv[i] = stage_query_word(A.queries, qrow, i, ix.d);  // packed bytes, k_brute's rule
 #else
+    // (a centred batch, A.centre: the proof runs on the operands the score kernel staged -- q2 is the norm of fl(q - c), summed
+    // here, and A.pnorm2_max_bits the centred maximum; L.qv keeps the query itself for the exact distances)
+    const float *cen = centre_of<METRIC>(A);
     for (int i = lane; i < qw; i += 64) {
       const float v = (i < ix.d) ? A.queries[(int64_t)qrow * ix.d + i] : 0.f;
       L.qv[i] = v;
-      q2 = fmaf(v, v, q2);
+      const float vc = (cen && i < ix.d) ? v - cen[i] : v;
+      q2 = fmaf(vc, vc, q2);
     }
 #endif
     int sel_pos, cnt;
@@ -1507,7 +1599,7 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
     (void)q2;
 #else
     const float pmax = __uint_as_float(*A.pnorm2_max_bits);
-    const float cerr = 3.02f * 1.52587890625e-5f + A.acc_factor * (float)(3 * ix.d + 8) * 5.9604645e-8f;
+    const float cerr = 3.02f * 1.52587890625e-5f + A.acc_factor * (float)(3 * ix.d + 8) * 5.9604645e-8f + (cen ? kCentredErr : 0.f);
     // + 2^-17 relative for the six mantissa bits that carry the position (|score| <= |q||p| resp. 2 (|q|^2 + |p|^2))
     const float cerr2 = cerr + 7.62939453125e-6f;
     // (never zero: an all-zero query under the inner product scores 0 everywhere, the position bits make every entry a
@@ -1758,10 +1850,12 @@ __device__ __forceinline__ void rerank_query_large(const GemmArgs &A, const Wave
   const int K = A.k;
   const int qw = qv_words(ix);
   float q2 = 0.f;  // (the query row is on its way while the selection runs)
+  const float *cen = centre_of<METRIC>(A);  // (a centred batch: q2 and pmax are the centred operands', as in rerank_query)
   for (int i = lane; i < qw; i += 64) {
     const float v = (i < ix.d) ? A.queries[(int64_t)qrow * ix.d + i] : 0.f;
     L.qv[i] = v;
-    q2 = fmaf(v, v, q2);
+    const float vc = (cen && i < ix.d) ? v - cen[i] : v;
+    q2 = fmaf(vc, vc, q2);
   }
   int cnt;
   float cut_sel, cut_blk;
@@ -1794,7 +1888,7 @@ __device__ __forceinline__ void rerank_query_large(const GemmArgs &A, const Wave
   // the columns), fp32 accumulation of 3 d products (A.acc_factor x the rounding adder's worst case), fp32 norms and the
   // reference's own rounding.
   const float pmax = __uint_as_float(*A.pnorm2_max_bits);
-  const float cerr = 3.02f * 1.52587890625e-5f + A.acc_factor * (float)(3 * ix.d + 8) * 5.9604645e-8f;
+  const float cerr = 3.02f * 1.52587890625e-5f + A.acc_factor * (float)(3 * ix.d + 8) * 5.9604645e-8f + (cen ? kCentredErr : 0.f);
   // + 2^-17 relative for the six mantissa bits that carry the position (|score| <= |q||p| resp. 2 (|q|^2 + |p|^2))
   const float cerr2 = cerr + 7.62939453125e-6f;
   // (never zero: an all-zero query under the inner product scores 0 everywhere, the position bits make every entry a

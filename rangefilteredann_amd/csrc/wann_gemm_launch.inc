@@ -39,11 +39,18 @@ static const char *unit_rerank_cover(const CoverArgs &c, void *stream) {
 }
 #endif
 
-static ScoreKernel pick_score_kernel(const IndexView &ix) {
+// centred: the batch is scored on fl(x - c) (GemmArgs::centre) -- the float32 and float16 units' narrow kernel has that instance,
+// no other kernel and no other unit: asking for it there is an error, never the uncentred kernel in its place
+static ScoreKernel pick_score_kernel(const IndexView &ix, bool centred) {
   // (a type whose long class is the index's own switch: the host admitted the batch with it, this unit only picks the kernel)
   const DenseRows rows = dense_row_class(ix, dense_long_switch_type(ix.dtype), dense_long_float8_type(ix.dtype));
   const int words = query_words(ix);
   void (*kern)(GemmArgs) = nullptr;
+#if WANN_DT == 0 || WANN_DT == 3
+  if (centred && rows != kRowsNarrow) return {};
+#else
+  if (centred) return {};
+#endif
 #if WANN_BYTE_ROWS
   // long: run-time slab count, both operands staged per 256-byte slab (queries pre-packed)
   if (rows == kRowsLong) return {k_gemm_scores_bslab, (size_t)2 * 128 * (256 + 16) + 3 * 128 * 4, 2, true};
@@ -84,6 +91,22 @@ static ScoreKernel pick_score_kernel(const IndexView &ix) {
   }
 #endif
   if (rows != kRowsNarrow) return {};
+#if WANN_DT == 0 || WANN_DT == 3
+  if (centred) {
+    switch (words) {
+      case 16: kern = k_gemm_scores<16, true>; break;
+      case 32: kern = k_gemm_scores<32, true>; break;
+      case 48: kern = k_gemm_scores<48, true>; break;
+      case 64: kern = k_gemm_scores<64, true>; break;
+      case 80: kern = k_gemm_scores<80, true>; break;
+      case 96: kern = k_gemm_scores<96, true>; break;
+      case 112: kern = k_gemm_scores<112, true>; break;
+      default: kern = k_gemm_scores<128, true>; break;
+    }
+    // (c lies in the 512 bytes behind rid[]: the same LDS, the same two workgroups per CU)
+    return {kern, (size_t)128 * (4 * words + 16) + 3 * 128 * 4, 2, false};
+  }
+#endif
   switch (words) {
     case 16: kern = k_gemm_scores<16>; break;
     case 32: kern = k_gemm_scores<32>; break;
@@ -102,8 +125,8 @@ static ScoreKernel pick_score_kernel(const IndexView &ix) {
 }
 
 static const char *unit_gemm_scores(const GemmArgs &a, int num_cus, void *stream) {
-  const ScoreKernel s = pick_score_kernel(a.ix);
-  if (!s.kern) return "row too long for the dense prefilter tile";
+  const ScoreKernel s = pick_score_kernel(a.ix, a.centre != nullptr);
+  if (!s.kern) return a.centre ? "no centred score kernel for these rows" : "row too long for the dense prefilter tile";
   if (s.needs_qsplit && !a.qsplit) return "the long-row score kernel needs the split / packed queries";
   if (s.lds > 48 * 1024)
     if (const char *e = gerr_of(hipFuncSetAttribute((const void *)s.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds))) return e;
@@ -123,6 +146,22 @@ static const char *unit_point_sums(const IndexView &ix, float *norm2, unsigned i
 #endif
   return gerr_of(hipGetLastError());
 }
+
+#if WANN_DT == 0 || WANN_DT == 3
+// the centre, then the norms of the centred rows: three launches in stream order, once per index
+static const char *unit_centred_sums(const IndexView &ix, float *buf, void *stream) {
+  if (ix.n <= 0) return nullptr;
+  const int words = query_words(ix), nparts = centred_parts(ix.n, words);
+  float *norm2 = buf, *c = buf + ix.n;
+  unsigned int *max_bits = reinterpret_cast<unsigned int *>(c + words);
+  float *part = ix.n >= words ? norm2 : c;  // (nparts rows of `words` floats: they fit the norms' floats, or are the one row c itself)
+  hipLaunchKernelGGL(k_row_centre, dim3((unsigned)nparts), dim3(256), 0, (hipStream_t)stream, ix, words, part, nparts, c, max_bits, 0);
+  hipLaunchKernelGGL(k_row_centre, dim3(1), dim3(256), 0, (hipStream_t)stream, ix, words, part, nparts, c, max_bits, 1);
+  const int wpb = 4;  // a wave per row
+  hipLaunchKernelGGL(k_point_norms_centred, dim3((unsigned)((ix.n + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, ix, c, norm2, max_bits);
+  return gerr_of(hipGetLastError());
+}
+#endif
 
 #if !WANN_HALF_ROWS && WANN_DT != 8  // (float16, bfloat16 and float8 rows: the float32 unit's k_split_queries)
 static const char *unit_prep_queries(const float *queries, int64_t nq, int d, int words, uint32_t *out, void *stream) {
@@ -164,8 +203,12 @@ static const char *unit_select_rerank(const GemmArgs &a, Counters *ctr, void *st
 const GemmUnit &gemm_unit() {
 #if WANN_DT == 6
   static constexpr GemmUnit unit = {nullptr, nullptr, unit_gemm_scores, nullptr, nullptr};  // (only ever asked for gemm_scores: dense_prefilter)
+#elif WANN_DT == 3
+  static constexpr GemmUnit unit = {unit_point_sums, nullptr, unit_gemm_scores, unit_select_rerank, unit_rerank_cover, unit_centred_sums};
 #elif WANN_HALF_ROWS || WANN_DT == 8
   static constexpr GemmUnit unit = {unit_point_sums, nullptr, unit_gemm_scores, unit_select_rerank, unit_rerank_cover};
+#elif WANN_DT == 0
+  static constexpr GemmUnit unit = {unit_point_sums, unit_prep_queries, unit_gemm_scores, unit_select_rerank, unit_rerank_cover, unit_centred_sums};
 #else
   static constexpr GemmUnit unit = {unit_point_sums, unit_prep_queries, unit_gemm_scores, unit_select_rerank, unit_rerank_cover};
 #endif
@@ -199,6 +242,7 @@ static int unit_launch(int dtype, const char *(*GemmUnit::*fn)(P...), const char
 }
 
 int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream) { return unit_launch(ix.dtype, &GemmUnit::point_sums, "point_sums", ix, norm2, max_bits, nullptr, stream); }
+int launch_centred_norms(const IndexView &ix, float *buf, void *stream) { return unit_launch(ix.dtype, &GemmUnit::centred_sums, "centred_sums", ix, buf, stream); }
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream) { return unit_launch(ix.dtype, &GemmUnit::point_sums, "point_sums", ix, nullptr, nullptr, term, stream); }
 int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream) { return record(gemm_unit().prep_queries(queries, nq, d, stride, out, stream)); }
 int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream) { return unit_launch(ix.dtype, &GemmUnit::prep_queries, "prep_queries", queries, nq, ix.d, ix.stride, out, stream); }

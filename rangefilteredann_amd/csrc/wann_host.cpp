@@ -58,6 +58,7 @@ Tuning snapshot_tuning(wann_index &I) {
   t.dense_long_float8 = row_switch_in_force(I, kDenseLongFloat8Switch);
   t.dense_large_k = row_switch_in_force(I, kDenseLargeKSwitch);
   t.dense_large_k_bytes = row_switch_in_force(I, kDenseLargeKBytesSwitch);
+  t.dense_centred = row_switch_in_force(I, kDenseCentredSwitch);
   return t;
 }
 

@@ -196,6 +196,11 @@ struct wann_index {
   // k_large_rerank_cover_b (select_keys_large; rows of up to 512 bytes return the keys' distances and fetch no selected row).
   bool dense_large_k_bytes_on = false;
   bool has_dense_large_k_bytes() const { return wann::byte_rows(dtype); }
+  // wann_set_dense_centred (likewise): squared-L2 dense batches of a float32 / float16 index with rows of at most 128 elements are
+  // scored on fl(x - c), c the mean row, and proven on the centred norms (dense_centred_route, wann_gemm_device.h).  No result
+  // row changes; what changes is which queries the proof settles.
+  bool dense_centred_on = false;
+  bool has_dense_centred() const { return wann::dense_centred_type(dtype, host().spec.metric); }
   bool has_half_copy() const { return d_half.p != nullptr; }
   bool has_byte_copy() const { return d_bytes.p != nullptr; }
   bool has_scan_copy() const { return has_half_copy() || has_byte_copy(); }
@@ -231,6 +236,10 @@ struct wann_index {
   DevBuf<unsigned int> d_pnorm2_max;
   DevBuf<int32_t> d_pterm;
   bool have_norms = false;
+  // the centred route's own: |fl(p - c)|^2 per point, c, the bits of the largest norm (centred_buf_floats), computed at the first
+  // centred batch and reported where d_pnorm2 is
+  DevBuf<float> d_centred;
+  bool have_centred = false;
   // (touched by the blocking calls and by both asynchronous lanes, outside dense_mu for every class but PrefilterIndex)
   std::atomic<int> dense_idle{0};  // batches in a row on which the dense path found no window group (run_batch)
   std::atomic<uint32_t> dense_batches{0};
@@ -294,6 +303,7 @@ constexpr RowSwitch kDenseLongRowsSwitch = {&wann_index::dense_long_rows_on, &wa
 constexpr RowSwitch kDenseLongFloat8Switch = {&wann_index::dense_long_float8_on, &wann_index::has_dense_long_float8, nullptr};
 constexpr RowSwitch kDenseLargeKSwitch = {&wann_index::dense_large_k_on, &wann_index::has_dense_large_k, nullptr};
 constexpr RowSwitch kDenseLargeKBytesSwitch = {&wann_index::dense_large_k_bytes_on, &wann_index::has_dense_large_k_bytes, nullptr};
+constexpr RowSwitch kDenseCentredSwitch = {&wann_index::dense_centred_on, &wann_index::has_dense_centred, nullptr};
 // (under I.tune_mu)
 inline bool row_switch_in_force(const wann_index &I, const RowSwitch &s) { return I.*s.on && (I.*s.has_copy)(); }
 

@@ -300,6 +300,10 @@ class Index {
   // the same on a uint8 / int8 index, on k_large_rerank_b (wann_set_dense_large_k_bytes, off by default; False on any other element type)
   bool set_dense_large_k_bytes(bool on) { return set_row_switch(wann_set_dense_large_k_bytes, on, "set_dense_large_k_bytes failed"); }
   bool dense_large_k_bytes() const { return wann_dense_large_k_bytes(h_) != 0; }
+  // squared-L2 dense batches of a float32 / float16 index (rows of at most 128 elements) are scored and proven on operands centred on
+  // the mean row (wann_set_dense_centred, off by default; False on an inner-product index or any other element type)
+  bool set_dense_centred(bool on) { return set_row_switch(wann_set_dense_centred, on, "set_dense_centred failed"); }
+  bool dense_centred() const { return wann_dense_centred(h_) != 0; }
 
   // float16 / bfloat16 / float8 indexes: the full-precision points (any array numpy casts to float32, in the order of the array
   // the index was created from) as the row store of the refined calls (wann_set_refine_rows); None drops the store
@@ -421,6 +425,7 @@ class Index {
     d["dense_long_float8"] = wann_dense_long_float8(h_);  // the index's wann_set_dense_long_float8 setting (likewise)
     d["dense_large_k"] = wann_dense_large_k(h_);          // the index's wann_set_dense_large_k setting (likewise)
     d["dense_large_k_bytes"] = wann_dense_large_k_bytes(h_);  // the index's wann_set_dense_large_k_bytes setting (likewise)
+    d["dense_centred"] = wann_dense_centred(h_);          // the index's wann_set_dense_centred setting (likewise)
     return d;
   }
   static py::dict counters_dict(const wann_counters &c) {
@@ -517,6 +522,8 @@ static void common_defs(py::class_<C> &c) {
       .def("dense_large_k", &C::dense_large_k)
       .def("set_dense_large_k_bytes", &C::set_dense_large_k_bytes, "on"_a)
       .def("dense_large_k_bytes", &C::dense_large_k_bytes)
+      .def("set_dense_centred", &C::set_dense_centred, "on"_a)
+      .def("dense_centred", &C::dense_centred)
       .def("set_refine_rows", &C::set_refine_rows, "points"_a.none(true))
       .def("refine_rows_bytes", &C::refine_rows_bytes)
       .def("batch_search_refined", &C::search_refined, "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a,
