@@ -15,6 +15,10 @@
 // Every tie breaks by (distance, id) and every distance uses the reference-order routines of
 // wann_wave.h, so the graphs are byte-identical to the host builder's (wann_build.cpp) -- which
 // the tests check -- for any device occupancy.
+//
+// Row width is a compile-time property of k_build_insert / k_build_reverse / k_build_final (HALVES): 1 for rows of up to 64
+// slots (one per lane), 2 for rs = 80 .. 128 (max_degree 65 .. 128), where a lane owns slots l and l + 64.  The launchers choose
+// by ix.rs; the HALVES = 1 instances are the one-wave-wide kernels unchanged.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -114,8 +118,43 @@ __device__ __forceinline__ int build_lds_per_wave(int stride, int L, int bits, b
   return (bytes + 15) & ~15;
 }
 
+// A wide adjacency row (rs = 80 .. 128) in registers: a lane owns slots l and l + 64 -- the split wave_beam_search makes of such
+// a row (wann_wave.h, the nhalf loop).  Returns the degree.
+__device__ __forceinline__ int wide_row_load(const int32_t *row, int rs, int (&a)[2], u64 (&vm)[2]) {
+  const int lane = lane_id();
+  a[0] = row[lane];  // (rs > 64)
+  a[1] = -1;
+  if (64 + lane < rs) a[1] = row[64 + lane];
+  vm[0] = ballot64(a[0] >= 0);
+  vm[1] = ballot64(a[1] >= 0);
+  return popc64(vm[0]) + popc64(vm[1]);
+}
+
+// The row's neighbours to ids[0..deg) in ROW ORDER, all of half 0 before half 1: under the reference tie order the restated
+// std::sort runs on this very sequence (wann_stdsort.h), and another input order gives another file.
+__device__ __forceinline__ void wide_row_compact(const int (&a)[2], const u64 (&vm)[2], int32_t *ids) {
+  if (a[0] >= 0) ids[popc64(vm[0] & lanemask_lt())] = a[0];
+  if (a[1] >= 0) ids[popc64(vm[0]) + popc64(vm[1] & lanemask_lt())] = a[1];
+}
+
+// dst[i] = key of (distance from the point staged in L.qv, ids[i]) for i < deg <= 128.  wave_distances scores 64 candidates a
+// call and L.cand_dist holds 64 distances: two passes, each writing its keys before the next overwrites cand_dist.
+template <int METRIC>
+__device__ __forceinline__ void wide_row_keys(const IndexView &ix, const int32_t *ids, int deg, const WaveLds &L, int64_t row_off,
+                                              u64 *dst) {
+  const int lane = lane_id();
+#pragma unroll 1
+  for (int base = 0; base < deg; base += 64) {
+    const int cnt = (deg - base) < 64 ? (deg - base) : 64;
+    const float dn = wave_distances<METRIC>(ix, ids + base, L.cand_dist, L.qv, cnt, row_off);
+    if (lane < cnt) dst[base + lane] = mk_key(dn, ids[base + lane]);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
-template <int METRIC, bool TABLE_LDS>
+// HALVES = 2: rows of 65 .. 128 neighbours.  L.cand_id holds 64 ids, so the compacted row waits in out[] (R ints, idle until
+// wave_prune fills it), and the visited list leaves rs slots of sb[] for the row, not 64.
+template <int METRIC, bool TABLE_LDS, int HALVES>
 __global__ __launch_bounds__(64 * kBuildWaves) void k_build_insert(BuildArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const IndexView &ix = A.ix;
@@ -141,10 +180,11 @@ __global__ __launch_bounds__(64 * kBuildWaves) void k_build_insert(BuildArgs A) 
     WAVE_SYNC();
     int m;
     long long nvis, ncmp;
+    const int row_slots = HALVES == 1 ? 64 : ix.rs;  // what the visited list leaves of sb[] for the row's own keys
     // builder-side quirk: the searched point's own id is its PARENT index (App. B #17 of SURVEY.md)
     wave_beam_search<METRIC, TABLE_LDS, true, true>(ix, part, L, nullptr, gtable, A.L, A.bits, row_off + p,
-                                                    (int64_t)part.n, (int)A.R, sb, A.vis_cap - 64, m, nvis, ncmp);
-    if (nvis > A.vis_cap - 64) {  // visited list does not fit: the host rebuilds this partition
+                                                    (int64_t)part.n, (int)A.R, sb, A.vis_cap - row_slots, m, nvis, ncmp);
+    if (nvis > A.vis_cap - row_slots) {  // visited list does not fit: the host rebuilds this partition
       if (lane == 0) atomicOr(A.err, 1);
       if (lane == 0) A.fresh_cnt[t] = 0;
       continue;
@@ -157,14 +197,24 @@ __global__ __launch_bounds__(64 * kBuildWaves) void k_build_insert(BuildArgs A) 
       WAVE_SYNC();
     }
     // candidates += current out-neighbours of p with their distances (robustPrune add = true)
-    int a = -1;
-    if (lane < ix.rs) a = ix.graph[(part.row_base + p) * (int64_t)ix.rs + lane];
-    const u64 vm = ballot64(a >= 0);
-    const int deg = popc64(vm);
-    if (a >= 0) L.cand_id[popc64(vm & lanemask_lt())] = a;
-    WAVE_SYNC();
-    const float dn = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, deg, row_off);
-    if (lane < deg) sb[nc + lane] = mk_key(dn, L.cand_id[lane]);
+    int deg;
+    if constexpr (HALVES == 1) {
+      int a = -1;
+      if (lane < ix.rs) a = ix.graph[(part.row_base + p) * (int64_t)ix.rs + lane];
+      const u64 vm = ballot64(a >= 0);
+      deg = popc64(vm);
+      if (a >= 0) L.cand_id[popc64(vm & lanemask_lt())] = a;
+      WAVE_SYNC();
+      const float dn = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, deg, row_off);
+      if (lane < deg) sb[nc + lane] = mk_key(dn, L.cand_id[lane]);
+    } else {
+      int a[2];
+      u64 vm[2];
+      deg = wide_row_load(ix.graph + (part.row_base + p) * (int64_t)ix.rs, ix.rs, a, vm);
+      wide_row_compact(a, vm, out);
+      WAVE_SYNC();
+      wide_row_keys<METRIC>(ix, out, deg, L, row_off, sb + nc);
+    }
     nc += deg;
     WAVE_SYNC();
     if (A.ref_ties) {  // std::sort(candidates, by distance alone) (vamana/index.h:77-78)
@@ -173,6 +223,7 @@ __global__ __launch_bounds__(64 * kBuildWaves) void k_build_insert(BuildArgs A) 
     }
     const int outc = wave_prune<METRIC>(ix, row_off, p, sb, nc, A.R, A.alpha, L, out, A.ref_ties != 0);
     if (lane < outc) A.fresh[(size_t)t * A.R + lane] = out[lane];
+    if (HALVES == 2 && 64 + lane < outc) A.fresh[(size_t)t * A.R + 64 + lane] = out[64 + lane];
     if (lane == 0) A.fresh_cnt[t] = outc;
     WAVE_SYNC();
   }
@@ -204,7 +255,9 @@ __global__ void k_build_groups(const u64 *keys, int64_t npairs, int32_t *gstart,
   if (i == 0 || keys[i - 1] != k) gstart[atomicAdd(ngroups, 1)] = (int32_t)i;
 }
 
-template <int METRIC>
+// HALVES = 2: the row is read, scored and stored in two halves; its compacted ids wait in out[] as in k_build_insert.  A group
+// that outgrows the LDS buffer goes to the second pass (global scratch) exactly as a narrow row's does.
+template <int METRIC, int HALVES>
 __global__ __launch_bounds__(64 * kBuildWaves) void k_build_reverse(BuildArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const IndexView &ix = A.ix;
@@ -239,10 +292,17 @@ __global__ __launch_bounds__(64 * kBuildWaves) void k_build_reverse(BuildArgs A)
     const PartDesc part = ix.parts[pidx];
     const int64_t row_off = part.start;
     int32_t *row = A.graph_rw + (part.row_base + tgt) * (int64_t)rs;
-    int a = -1;
-    if (lane < rs) a = row[lane];
-    const u64 vm = ballot64(a >= 0);
-    const int deg = popc64(vm);
+    int a[HALVES];
+    u64 vm[HALVES];
+    int deg;
+    if constexpr (HALVES == 1) {
+      a[0] = -1;
+      if (lane < rs) a[0] = row[lane];
+      vm[0] = ballot64(a[0] >= 0);
+      deg = popc64(vm[0]);
+    } else {
+      deg = wide_row_load(row, rs, a, vm);
+    }
     if (deg + gsize <= A.R) {  // room: append in batch order (index.h:299-301)
       for (int j = lane; j < gsize; j += 64) row[deg + j] = A.sorted_val[b + j];
       continue;
@@ -256,10 +316,16 @@ __global__ __launch_bounds__(64 * kBuildWaves) void k_build_reverse(BuildArgs A)
     }
     // robustPrune(tgt, sources U current row) (index.h:302-305)
     for (int i = lane; i < ix.stride; i += 64) L.qv[i] = ix.points[(row_off + tgt) * (int64_t)ix.stride + i];
-    if (a >= 0) L.cand_id[popc64(vm & lanemask_lt())] = a;
-    WAVE_SYNC();
-    const float dr = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, deg, row_off);
-    if (lane < deg) sb[gsize + lane] = mk_key(dr, L.cand_id[lane]);
+    if constexpr (HALVES == 1) {
+      if (a[0] >= 0) L.cand_id[popc64(vm[0] & lanemask_lt())] = a[0];
+      WAVE_SYNC();
+      const float dr = wave_distances<METRIC>(ix, L.cand_id, L.cand_dist, L.qv, deg, row_off);
+      if (lane < deg) sb[gsize + lane] = mk_key(dr, L.cand_id[lane]);
+    } else {
+      wide_row_compact(a, vm, out);
+      WAVE_SYNC();
+      wide_row_keys<METRIC>(ix, out, deg, L, row_off, sb + gsize);
+    }
     WAVE_SYNC();
     for (int c0 = 0; c0 < gsize; c0 += 64) {
       const int cnt = (gsize - c0) < 64 ? (gsize - c0) : 64;
@@ -277,20 +343,26 @@ __global__ __launch_bounds__(64 * kBuildWaves) void k_build_reverse(BuildArgs A)
     }
     const int outc = wave_prune<METRIC>(ix, row_off, tgt, sb, gsize + deg, A.R, A.alpha, L, out, A.ref_ties != 0);
     if (lane < rs) row[lane] = (lane < outc) ? out[lane] : -1;
+    if (HALVES == 2 && 64 + lane < rs) row[64 + lane] = (64 + lane < outc) ? out[64 + lane] : -1;
     WAVE_SYNC();
   }
 }
 
 // final neighbour sort: one wave per pool row
-template <int METRIC>
+// HALVES = 2: a lane holds the keys of slots l and l + 64.  The wave's LDS carries rs keys (sb) and rs ids beyond the common
+// area (the launcher sizes it so): cand_id / cand_dist hold 64 entries each, and 128 keys in cand_key would run over them --
+// over the very ints the reference-order sort uses as its stack.  Here that stack is cand_key (128 ints; 45 needed at n = 128).
+template <int METRIC, int HALVES>
 __global__ __launch_bounds__(64 * kBuildWaves) void k_build_final(BuildArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const IndexView &ix = A.ix;
   const int lane = lane_id();
   const int wib = threadIdx.x >> 6;
-  const int per_wave = build_lds_per_wave(ix.stride, 0, 0, false, 0, 0);
-  const WaveLds L = carve_wave_lds(smem + (size_t)wib * per_wave, ix.stride, 0, true);
   const int rs = ix.rs;
+  const int per_wave = HALVES == 1 ? build_lds_per_wave(ix.stride, 0, 0, false, 0, 0) : build_lds_per_wave(ix.stride, 0, 0, false, rs, rs);
+  const WaveLds L = carve_wave_lds(smem + (size_t)wib * per_wave, ix.stride, 0, true);
+  u64 *sb = reinterpret_cast<u64 *>(L.ltable);                 // (HALVES = 2 only)
+  int32_t *ids = reinterpret_cast<int32_t *>(sb + rs);
   for (;;) {
     const int t = wave_ticket(A.cursor);
     if (t >= A.nitems) break;
@@ -300,6 +372,34 @@ __global__ __launch_bounds__(64 * kBuildWaves) void k_build_final(BuildArgs A) {
     const int endl = (item.local + 64) < part.n ? (item.local + 64) : part.n;
     for (int node = item.local; node < endl; node++) {
       int32_t *row = A.graph_rw + (part.row_base + node) * (int64_t)rs;
+      if constexpr (HALVES == 2) {
+        int a2[2];
+        u64 vm2[2];
+        const int deg = wide_row_load(row, rs, a2, vm2);
+        if (deg == 0) continue;
+        for (int i = lane; i < ix.stride; i += 64) L.qv[i] = ix.points[(row_off + node) * (int64_t)ix.stride + i];
+        wide_row_compact(a2, vm2, ids);
+        WAVE_SYNC();
+        wide_row_keys<METRIC>(ix, ids, deg, L, row_off, sb);
+        WAVE_SYNC();
+        if (A.ref_ties) {  // G[i].sort(less on the distance alone) over the row as it stands (graph.h:106)
+          if (lane == 0) std_sort_emulated(sb, deg, reinterpret_cast<int32_t *>(L.cand_key), DistOnlyLess());
+          WAVE_SYNC();
+          for (int x = lane; x < deg; x += 64) row[x] = key_id(sb[x]);
+        } else {  // rank both of the lane's keys among all deg keys (every lane reads the same sb[l]: an LDS broadcast)
+          const u64 k0 = (lane < deg) ? sb[lane] : ~0ull, k1 = (64 + lane < deg) ? sb[64 + lane] : ~0ull;
+          int r0 = 0, r1 = 0;
+          for (int l = 0; l < deg; l++) {
+            const u64 kl = sb[l];
+            r0 += (kl < k0 || (kl == k0 && l < lane)) ? 1 : 0;
+            r1 += (kl < k1 || (kl == k1 && l < 64 + lane)) ? 1 : 0;
+          }
+          if (lane < deg) row[r0] = key_id(k0);
+          if (64 + lane < deg) row[r1] = key_id(k1);
+        }
+        WAVE_SYNC();
+        continue;
+      }
       int a = -1;
       if (lane < rs) a = row[lane];
       const u64 vm = ballot64(a >= 0);
@@ -367,11 +467,12 @@ static int launch_build_insert(const BuildArgs &a, int blocks, int table_lds, vo
   size_t lds = (size_t)build_lds_bytes_per_wave(a.ix.stride, a.L, a.bits, table_lds, a.vis_cap, a.R) * kBuildWaves;
   dim3 grid(blocks), block(64 * kBuildWaves);
   hipStream_t s = (hipStream_t)stream;
-#define WANN_BL(M, T)                              \
-  do {                                             \
-    auto kern = k_build_insert<M, T>;              \
-    if (set_lds(kern, lds)) return 1;              \
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a); \
+  const bool wide = a.ix.rs > 64;  // rows of 65 .. 128 neighbours: the two-half kernels
+#define WANN_BL(M, T)                                                        \
+  do {                                                                       \
+    auto kern = wide ? k_build_insert<M, T, 2> : k_build_insert<M, T, 1>;    \
+    if (set_lds(kern, lds)) return 1;                                        \
+    hipLaunchKernelGGL(kern, grid, block, lds, s, a);                        \
   } while (0)
   if (a.ix.metric == 1) {
     if (table_lds) WANN_BL(1, true);
@@ -414,12 +515,13 @@ static int launch_build_reverse(const BuildArgs &a, int blocks, void *stream) {
   size_t lds = (size_t)build_lds_bytes_per_wave(a.ix.stride, 0, 0, 0, a.vis_cap, a.R) * kBuildWaves;
   dim3 grid(blocks), block(64 * kBuildWaves);
   hipStream_t s = (hipStream_t)stream;
+  const bool wide = a.ix.rs > 64;
   if (a.ix.metric == 1) {
-    auto kern = k_build_reverse<1>;
+    auto kern = wide ? k_build_reverse<1, 2> : k_build_reverse<1, 1>;
     if (set_lds(kern, lds)) return 1;
     hipLaunchKernelGGL(kern, grid, block, lds, s, a);
   } else {
-    auto kern = k_build_reverse<0>;
+    auto kern = wide ? k_build_reverse<0, 2> : k_build_reverse<0, 1>;
     if (set_lds(kern, lds)) return 1;
     hipLaunchKernelGGL(kern, grid, block, lds, s, a);
   }
@@ -428,10 +530,13 @@ static int launch_build_reverse(const BuildArgs &a, int blocks, void *stream) {
 
 static int launch_build_final(const BuildArgs &a, int blocks, void *stream) {
   if (blocks <= 0 || a.nitems <= 0) return 0;
-  size_t lds = (size_t)build_lds_bytes_per_wave(a.ix.stride, 0, 0, 0, 0, 0) * kBuildWaves;
+  const bool wide = a.ix.rs > 64;  // (the wide form keeps rs keys and rs ids in LDS beyond the common area)
+  const int own = wide ? a.ix.rs : 0;
+  size_t lds = (size_t)build_lds_bytes_per_wave(a.ix.stride, 0, 0, 0, own, own) * kBuildWaves;
   dim3 grid(blocks), block(64 * kBuildWaves);
-  if (a.ix.metric == 1) hipLaunchKernelGGL(k_build_final<1>, grid, block, lds, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_build_final<0>, grid, block, lds, (hipStream_t)stream, a);
+  auto kern = a.ix.metric == 1 ? (wide ? k_build_final<1, 2> : k_build_final<1, 1>) : (wide ? k_build_final<0, 2> : k_build_final<0, 1>);
+  if (set_lds(kern, lds)) return 1;
+  hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, a);
   return bcheck(hipGetLastError());
 }
 

@@ -59,7 +59,9 @@ void gpu_build_graphs(const IndexView &view, int32_t *d_graph, const std::vector
 
   const int bits = std::max<int>(10, (int)std::ceil(std::log2((double)(L * L))) - 2);
   const int table_lds = bits <= kMaxLdsBits ? 1 : 0;
-  int vis_cap = (int)(((2 * L * std::max(vis_scale, 1) + 64 + 63) / 64) * 64) + 64;
+  // the candidate buffer holds a visited list and the inserted point's own row: 64 slots for that row, rs for a wide one
+  const int row_slots = std::max(64, (int)view.rs);
+  int vis_cap = (int)(((2 * L * std::max(vis_scale, 1) + 64 + 63) / 64) * 64) + row_slots;
   if (const char *e = getenv("WANN_BUILD_VIS_CAP")) vis_cap = std::max(64, atoi(e)) * std::max(vis_scale, 1);  // tests: force the restart path
   const int wpb = build_waves_per_block();
   const int lds_insert = build_lds_bytes_per_wave(view.stride, (int)L, bits, table_lds, vis_cap, (int)R) * wpb;
@@ -70,7 +72,7 @@ void gpu_build_graphs(const IndexView &view, int32_t *d_graph, const std::vector
   const int max_insert_blocks = num_cus * insert_blocks_per_cu;
   const int max_rev_blocks = num_cus * rev_blocks_per_cu;
   const int big_blocks = std::max(1, num_cus / 2);
-  const int64_t big_cap = (int64_t)max_group + R + 64;
+  const int64_t big_cap = (int64_t)max_group + R + row_slots;
 
   DevBuf<BuildItem> d_items;
   DevBuf<int32_t> d_fresh, d_fresh_cnt, d_ints, d_pair_val, d_sorted_val, d_gstart, d_fallback, d_gtable;

@@ -414,9 +414,8 @@ void build_pending(wann_index &I, std::vector<HostPart *> &pending) {
     }
   // WANN_HOST_BUILD=1 (tests: the host builder as a cross-check) is the only way onto the host builder; a
   // visited list that outgrows its LDS buffer restarts the build ON THE GPU with a larger buffer.
-  // (R > 64: the GPU builder's rows are one wave wide -- such graphs are built by the host builder, byte-identical to the
-  // reference's like the GPU builder's)
-  if (getenv("WANN_HOST_BUILD") != nullptr || s.R > 64) {
+  // (R = 65 .. 128 included: the build kernels work such rows in two halves of 64 lanes, as the search core does)
+  if (getenv("WANN_HOST_BUILD") != nullptr) {
     build_pending_on_host(H, pending);
     for (auto &t : targets) upload_part_rows(I, *t.part, I.parts[t.part_index]);
   } else {
