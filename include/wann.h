@@ -479,6 +479,24 @@ int wann_dense_large_k_bytes(const wann_index *index);
  * wann_dense_centred: that setting (0 after wann_index_create; 0 for a null index). */
 int wann_set_dense_centred(wann_index *index, int on);
 int wann_dense_centred(const wann_index *index);
+/* Window maxima in the dense path's proof: one row of a large norm somewhere in the index.
+ * wann_set_dense_window_norms: whether the proof of the NEXT dense batches, on all three routes, bounds each query by the largest
+ * |p|^2 round ITS OWN window instead of the largest of the whole index.  The bound only has to cover the positions whose scores
+ * can reach the query's candidates and cuts -- the positions of its window: a shared-window group's window, and a cover group's
+ * query's own window as well, because candidates outside it are dropped before the selection -- and the maximum over any
+ * superset of them is still a valid bound: the lookup returns the maximum over the 64-position blocks of the filter order that
+ * cover the window.  Without the switch a single outlier row (a zero-padded document, an un-normalised embedding, a sentinel)
+ * anywhere in the index sends every query of every batch back to the exact scan; with it only the queries whose own window (or
+ * the up to 63 positions on either side of it) holds the outlier.  The table (k_norm_blocks / k_norm_levels: ceil(n / 64) words per
+ * level, about log2(n / 64) + 1 levels, under 1 MB at n = 10^6) is built once, at the first such batch; with wann_set_dense_centred in
+ * force a second one over the centred norms, and those batches are centred on a TRIMMED mean (the rows whose squared norm exceeds
+ * four times the mean squared norm are left out of the centre, which the plain mean would follow; a centred buffer of its own,
+ * n + padded row + 3 floats).  Returns the setting now in force, 0 / 1: asking for 1 on a WANN_DTYPE_U8 /
+ * WANN_DTYPE_I8 index (exact scores, no bound) leaves it at 0 and returns 0.  Applies to every replica of WANN_DEVICES; a NEGATIVE
+ * error for a null index.  Changes no result row -- only which queries are proven, rescued or handed to the scan.
+ * wann_dense_window_norms: that setting (0 after wann_index_create; 0 for a null index). */
+int wann_set_dense_window_norms(wann_index *index, int on);
+int wann_dense_window_norms(const wann_index *index);
 
 /* WIDE ROWS: stop as at k, keep up to `width` entries (not calls of the reference; it computes this and drops the tail).
  * The reference's query() (src/postfilter_vamana.h:141-188) returns the whole filtered frontier of the last beam it searched;

@@ -286,6 +286,20 @@ static void check_dense_centred() {
   CHECK((double)kCentredErr > 2.0 * u1 + u1 * u1 && (double)kCentredErr <= 2.5 * u);
 }
 
+// wann_set_dense_window_norms without a device: the sparse table's shape.  Level j holds runs of 2^j blocks; the lookup of a window
+// that spans m blocks reads level floor(log2 m), so the last level must reach a run of at least nblocks / 2 + 1 blocks, and the
+// levels of the launcher's loop (1 .. levels - 1, half = 2^(j-1)) must be exactly the ones the table has room for.
+static void check_dense_window_norms() {
+  CHECK(norm_table_words(0) == 0 && norm_table_words(1) == 1 && norm_table_words(64) == 1 && norm_table_words(65) == 4);
+  CHECK(norm_table_blocks(1000000) == 15625 && norm_table_levels(15625) == 15 && norm_table_words(1000000) * 4 < (1u << 20));
+  for (int64_t nb : {(int64_t)1, (int64_t)2, (int64_t)3, (int64_t)4, (int64_t)5, (int64_t)1023, (int64_t)1024, (int64_t)1025, (int64_t)33554432}) {
+    const int levels = norm_table_levels(nb);
+    int j = 0;  // floor(log2 nb): the level a window over every block reads
+    while (((int64_t)2 << j) <= nb) j++;
+    CHECK(levels >= 1 && j < levels && ((int64_t)1 << (levels - 1)) >= nb && (levels == 1 || ((int64_t)1 << (levels - 2)) < nb));
+  }
+}
+
 // The row-type table (wann_row_types.h) against the values written out here: every class, the caller's bytes, the device
 // pitch, the staged query's length and the kinds of unit of every id from -1 to 9.  (That the two layout rules are
 // permutations: byte_layout_sanitize_test.cpp and half_layout_sanitize_test.cpp.)
@@ -488,6 +502,7 @@ int main(int argc, char **argv) {
   check_scan_lds();
   check_dense_large_k();
   check_dense_centred();
+  check_dense_window_norms();
   check_row_types();
   check_refdump();
   // the C ABI's argument validation (no device needed for these paths) lives in wann_abi.cpp and is covered by tests/test_abi.py

@@ -1066,6 +1066,8 @@ int wann_set_dense_large_k_bytes(wann_index *I, int on) { return set_row_switch(
 int wann_dense_large_k_bytes(const wann_index *I) { return row_switch(I, kDenseLargeKBytesSwitch); }
 int wann_set_dense_centred(wann_index *I, int on) { return set_row_switch(I, kDenseCentredSwitch, on); }
 int wann_dense_centred(const wann_index *I) { return row_switch(I, kDenseCentredSwitch); }
+int wann_set_dense_window_norms(wann_index *I, int on) { return set_row_switch(I, kDenseWindowNormsSwitch, on); }
+int wann_dense_window_norms(const wann_index *I) { return row_switch(I, kDenseWindowNormsSwitch); }
 // TEST HOOK, not part of include/wann.h and no commitment: dense_row_class (wann_gemm_device.h) for rows of d elements of an
 // element type, long_rows = the switches assumed on (bit 0: wann_set_dense_long_rows, bit 1: wann_set_dense_long_float8) -- 0
 // none, 1 narrow, 2 wide, 3 long; -1: unknown type or d.  The CPU tests read the table through it without a device.

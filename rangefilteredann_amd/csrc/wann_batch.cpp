@@ -63,12 +63,36 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   }
   // wann_set_dense_centred: this batch is scored on fl(x - c) and proven on the centred norms.  The centre and those norms are
   // computed once, at the first such batch, beside the uncentred ones (a later batch may run with the switch off again).
+  // With wann_set_dense_window_norms in force as well the centre is the TRIMMED mean, in a buffer of its own (wann_host_internal.h).
   const bool centred = dense_centred_route(I.view, T.dense_centred, dense_score_view(I, T) != nullptr);
-  if (centred && !I.have_centred) {
+  const bool window_norms = T.dense_window_norms && !bytes;
+  const bool trimmed = centred && window_norms;
+  if (centred && !trimmed && !I.have_centred) {
     I.d_centred.ensure(centred_buf_floats(I.view.n, qwords));
     if (launch_centred_norms(I.view, I.d_centred.p, st)) throw HipError(std::string("k_row_centre / k_point_norms_centred: ") + gemm_launch_last_error());
     if (sorted_exact) I.device_bytes += (int64_t)I.d_centred.bytes();  // (reported where the uncentred norms are)
     I.have_centred = true;
+  }
+  if (trimmed && !I.have_centred_trim) {
+    I.d_centred_trim.ensure(centred_buf_floats(I.view.n, qwords));
+    I.d_trim.ensure(2);
+    if (launch_centred_norms_trimmed(I.view, I.d_pnorm2.p, I.d_trim.p, I.d_centred_trim.p, st))
+      throw HipError(std::string("k_norm_trim / k_row_centre_trimmed / k_point_norms_centred: ") + gemm_launch_last_error());
+    if (sorted_exact) I.device_bytes += (int64_t)(I.d_centred_trim.bytes() + I.d_trim.bytes());
+    I.have_centred_trim = true;
+  }
+  const float *centred_buf = trimmed ? I.d_centred_trim.p : I.d_centred.p;  // (norms | c | the maximum's bits)
+  // wann_set_dense_window_norms: this batch's proof reads window maxima of the norms it runs on -- the centred ones on a centred
+  // batch.  Each table is built once, at the first batch that reads it, on the stream that built its norms (stream order: after them).
+  if (window_norms) {
+    DevBuf<unsigned int> &table = centred ? I.d_norm_levels_centred : I.d_norm_levels;
+    bool &have = centred ? I.have_norm_levels_centred : I.have_norm_levels;
+    if (!have) {
+      table.ensure(norm_table_words(I.view.n));
+      if (launch_norm_table(I.view, centred ? centred_buf : I.d_pnorm2.p, table.p, st)) throw HipError(std::string("k_norm_blocks / k_norm_levels: ") + gemm_launch_last_error());
+      if (sorted_exact) I.device_bytes += (int64_t)table.bytes();  // (reported where the norms are)
+      have = true;
+    }
   }
   size_t cap = 64;
   while (cap < (size_t)nq * 2) cap <<= 1;
@@ -114,9 +138,13 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   ga.pnorm2 = I.d_pnorm2.p;
   ga.pnorm2_max_bits = I.d_pnorm2_max.p;
   if (centred) {  // (norms | c | the maximum's bits: what the score kernel's base[] and the proof's pmax read are the centred ones)
-    ga.pnorm2 = I.d_centred.p;
-    ga.centre = I.d_centred.p + I.view.n;
+    ga.pnorm2 = centred_buf;
+    ga.centre = centred_buf + I.view.n;
     ga.pnorm2_max_bits = reinterpret_cast<const unsigned int *>(ga.centre + qwords);
+  }
+  if (window_norms) {  // (the proof's pmax: window_norm_max over the table of the norms chosen above)
+    ga.norm_levels = centred ? I.d_norm_levels_centred.p : I.d_norm_levels.p;
+    ga.norm_blocks = (int32_t)norm_table_blocks(I.view.n);
   }
   ga.pterm = I.d_pterm.p;
   if (long_rows) {

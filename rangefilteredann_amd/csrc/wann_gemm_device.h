@@ -90,7 +90,25 @@ struct GemmArgs {
   // Non-null IS the flag: the score launch picks k_gemm_scores<STRIDE, true>, the proof sums |fl(q - c)|^2 and widens its bound
   // by kCentredErr, and pnorm2 / pnorm2_max_bits above point at |fl(p - c)|^2 and its maximum.  Null: everything as it was.
   const float *centre;
+  // Window maxima of the norms (wann_set_dense_window_norms): the sparse table over pnorm2 in filter order, norm_table_levels
+  // rows of norm_blocks words (k_norm_blocks / k_norm_levels), the bit patterns of the maxima.  Non-null IS the flag: the proof
+  // bounds a query by the largest norm of the 64-position blocks that cover its own window (window_norm_max) instead of
+  // *pnorm2_max_bits.  On a centred batch the table is the one over the centred norms.  Null: everything as it was.
+  const unsigned int *norm_levels;
+  int32_t norm_blocks;
 };
+
+// The sparse table of window_norm_max: level 0 holds the maximum of every 64 consecutive positions of the filter order, level j
+// the maximum of 2^j consecutive level-0 entries (the run clipped at the table's end), up to the first level whose run holds
+// every block.  n = 10^6: 15 625 blocks x 15 levels, under 1 MB.
+constexpr int kNormBlock = 64;
+constexpr int64_t norm_table_blocks(int64_t n) { return (n + kNormBlock - 1) / kNormBlock; }
+constexpr int norm_table_levels(int64_t nblocks) {
+  int levels = 1;
+  while (((int64_t)1 << (levels - 1)) < nblocks) levels++;
+  return levels;
+}
+constexpr size_t norm_table_words(int64_t n) { return n <= 0 ? 0 : (size_t)norm_table_blocks(n) * (size_t)norm_table_levels(norm_table_blocks(n)); }
 
 // What the proof's relative error gains on a centred batch, as a summand of cerr (E = 2 cerr2 (|q'|^2 + max |p'|^2)), for the two
 // elementwise roundings q' = fl(q - c), p' = fl(p - c).  Each is (x - c)(1 + delta), |delta| <= u = 2^-24 (a subtraction has no
@@ -208,6 +226,11 @@ struct GemmUnit {
   const char *(*rerank_cover)(const CoverArgs &c, void *stream);
   // float32 / float16: the centre and the centred norms into `buf` (centred_buf_floats: norms | c | maximum's bits); null elsewhere
   const char *(*centred_sums)(const IndexView &ix, float *buf, void *stream);
+  // the float types: the sparse table of window maxima over `norm2` in filter order into `table` (norm_table_words); null elsewhere
+  const char *(*norm_table)(const IndexView &ix, const float *norm2, unsigned int *table, void *stream);
+  // float32 / float16: centred_sums with the TRIMMED centre (the mean of the rows whose uncentred norm, `norm2_raw`, is at most
+  // four times the mean: k_norm_trim, k_row_centre_trimmed); trim: two floats of device memory; null elsewhere
+  const char *(*centred_sums_trimmed)(const IndexView &ix, const float *norm2_raw, float *trim, float *buf, void *stream);
 };
 
 WANN_UNIT_LOOKUP(dense, GemmUnit, gemm_unit, gemm_unit_of)  // (null: the row type has no dense unit)
@@ -215,6 +238,8 @@ WANN_UNIT_LOOKUP(dense, GemmUnit, gemm_unit, gemm_unit_of)  // (null: the row ty
 // entry points (the float32 unit): each looks up ix.dtype's unit, calls it and records the error; 0 = launched
 int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream);  // float32 / float16 / bfloat16 rows
 int launch_centred_norms(const IndexView &ix, float *buf, void *stream);                          // float32 / float16 rows: k_row_centre, k_point_norms_centred
+int launch_centred_norms_trimmed(const IndexView &ix, const float *norm2_raw, float *trim, float *buf, void *stream);  // likewise: both switches in force
+int launch_norm_table(const IndexView &ix, const float *norm2, unsigned int *table, void *stream);  // the float types: k_norm_blocks, k_norm_levels
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream);                         // uint8 / int8 rows
 int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream);  // long float32 / float16 rows
 int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream);  // long uint8 / int8 rows

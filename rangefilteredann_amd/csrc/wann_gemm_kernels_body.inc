@@ -132,6 +132,45 @@ __global__ void k_point_norms(IndexView ix, float *norm2, unsigned int *max_bits
     if (__float_as_uint(s) > __hip_atomic_load(max_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(max_bits, __float_as_uint(s));
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Window maxima of the norms (opt-in per index: wann_set_dense_window_norms).  The proof's bound E grows with the largest |p|^2 it
+// has to cover.  *max_bits above is the largest of the whole index: one row of a large norm ANYWHERE sends every query of every
+// batch back to the scan.  But a query's scores, candidates and cuts only ever come from positions of its own window, so the
+// largest norm over any SUPERSET of the window's positions bounds it as well.  A sparse table over the norms in filter order
+// answers that in two loads:
+//
+//   k_norm_blocks   level 0: one wave per kNormBlock = 64 consecutive POSITIONS, lane l reads the norm of position 64 b + l (the
+//                   sorted kinds: the position is the row, a contiguous load; a PrefilterIndex: a gather through the label
+//                   argsort), positions past n count 0; the wave's maximum, taken on the bit patterns (norms are >= 0: the
+//                   patterns order like the values), is T[0][b].
+//   k_norm_levels   level j from level j - 1: T[j][b] = max(T[j-1][b], T[j-1][b + 2^(j-1)]), the second operand clamped to the
+//                   last block -- T[j][b] is the maximum of the blocks b .. min(b + 2^j, nblocks) - 1.  A launch per level, in
+//                   stream order; once per index.
+//   window_norm_max (the proof, further down) two entries of the level whose run is the largest power of two that fits.
+// No atomics anywhere: the table, and with it every counter of the path, is the same from run to run.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_norm_blocks(IndexView ix, const float *norm2, unsigned int *level0, int nblocks) {
+  const int lane = lane_id();
+  const int b = uni((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+  if (b >= nblocks) return;  // (wave-uniform)
+  const int64_t pos = (int64_t)b * kNormBlock + lane;
+  unsigned int m = pos < ix.n ? __float_as_uint(norm2[window_row(ix, pos)]) : 0u;
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned int other = (unsigned int)__shfl_xor((int)m, o);
+    m = other > m ? other : m;
+  }
+  if (lane == 0) level0[b] = m;
+}
+
+// `below`: level j - 1, `level`: level j, half = 2^(j-1); a thread per block
+__global__ __launch_bounds__(256) void k_norm_levels(const unsigned int *below, unsigned int *level, int nblocks, int half) {
+  for (int b = (int)(blockIdx.x * blockDim.x + threadIdx.x); b < nblocks; b += (int)(gridDim.x * blockDim.x)) {
+    const int b2 = b + half < nblocks ? b + half : nblocks - 1;
+    const unsigned int x = below[b], y = below[b2];
+    level[b] = x > y ? x : y;
+  }
+}
 WANN_GNS_END
 #endif
 
@@ -194,6 +233,67 @@ __global__ void k_point_norms_centred(IndexView ix, const float *c, float *norm2
     norm2[row] = s;
     // s >= 0: the bit pattern orders like the value; only a new maximum pays for the atomic
     if (__float_as_uint(s) > __hip_atomic_load(max_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(max_bits, __float_as_uint(s));
+  }
+}
+
+// The TRIMMED centre (both switches in force: wann_set_dense_centred and wann_set_dense_window_norms).  With window maxima a row of
+// a large norm no longer costs the queries whose windows do not hold it -- except through the centre: the mean of ALL rows follows
+// such a row (one row of 2^30 among 25 000 moves it by 2^30 / 25 000 a column), and then EVERY centred norm is large.  Any c is
+// valid, so the mean is taken over the rows whose squared norm is at most kTrimFactor times the mean squared norm: by Markov's
+// inequality fewer than 1 / kTrimFactor of the rows can lie above that, k rows of one huge norm M lie above it as long as
+// k < n / kTrimFactor, and a set of rows of similar norms loses none -- its centre is the untrimmed one, bit for bit.
+//   k_norm_trim          one workgroup, two passes over the uncentred norms in a fixed order (no atomics): their sum -> the
+//                        threshold; the number of rows at or below it.  trim[0] = threshold, trim[1] = rows kept (as a float).
+//   k_row_centre_trimmed k_row_centre with the rows above the threshold left out and the sums divided by the rows kept.
+// (a sum that overflows makes the threshold infinite: nothing is left out, the centre is the untrimmed one)
+constexpr float kTrimFactor = 4.f;
+__global__ __launch_bounds__(1024) void k_norm_trim(const float *norm2, int64_t n, float *trim) {
+  __shared__ float sh[1024];
+  const int tid = threadIdx.x;
+  float s = 0.f;
+  for (int64_t r = tid; r < n; r += 1024) s += norm2[r];
+  sh[tid] = s;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (tid < o) sh[tid] += sh[tid + o];
+    __syncthreads();
+  }
+  const float thr = kTrimFactor * (sh[0] / (float)n);
+  __syncthreads();
+  __shared__ unsigned long long cnt[1024];  // (integers: with nothing left out the divisor is (float)n, k_row_centre's)
+  unsigned long long kept = 0;
+  for (int64_t r = tid; r < n; r += 1024) kept += norm2[r] <= thr ? 1u : 0u;
+  cnt[tid] = kept;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (tid < o) cnt[tid] += cnt[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    trim[0] = thr;
+    trim[1] = cnt[0] ? (float)(int64_t)cnt[0] : 1.f;  // (no row at or below the threshold: norms that are not numbers; c = 0)
+  }
+}
+
+__global__ __launch_bounds__(256) void k_row_centre_trimmed(IndexView ix, int words, float *part, int nparts, float *c, unsigned int *max_bits, int stage,
+                                                            const float *norm2, const float *trim) {
+  __shared__ float sh[128];
+  const int tid = threadIdx.x, col = tid & 127, sub = tid >> 7;
+  if (stage == 0) {
+    const float thr = trim[0];
+    const int64_t per = (ix.n + nparts - 1) / nparts, r0 = (int64_t)blockIdx.x * per, r1 = r0 + per < ix.n ? r0 + per : ix.n;
+    float s = 0.f;
+    if (col < ix.d)
+      for (int64_t r = r0 + sub; r < r1; r += 2)
+        if (norm2[r] <= thr) s += centre_row_value(ix, r, col);
+    if (sub == 1) sh[col] = s;
+    __syncthreads();
+    if (sub == 0 && col < words) part[(int64_t)blockIdx.x * words + col] = s + sh[col];
+  } else if (tid < words) {  // (one workgroup; `part` may be `c` itself, as in k_row_centre)
+    float s = 0.f;
+    for (int g = 0; g < nparts; g++) s += part[(int64_t)g * words + tid];
+    c[tid] = tid < ix.d ? s / trim[1] : 0.f;
+    if (tid == 0) *max_bits = 0u;
   }
 }
 WANN_GNS_END
@@ -1500,6 +1600,32 @@ __device__ __forceinline__ const float *centre_of(const GemmArgs &A) {
 #endif
   return nullptr;
 }
+// The largest norm the proof of a query with the window [lo, hi) of the filter order has to cover (wann_set_dense_window_norms;
+// A.norm_levels: k_norm_blocks / k_norm_levels' table).  The two runs of 2^j blocks that start at the window's first block and
+// end at its last one overlap or touch, so their maxima together are the maximum over the 64-position blocks b0 .. b1 -- every
+// position of [lo, hi) and up to 63 more on either side.  A SUPERSET of the window: the result may only be larger than the
+// window's own maximum, never smaller, which is what keeps the bound valid.  Wave-uniform (the window is the query's): the
+// indices pass through scalar registers, two loads, no loop, no LDS.  The block numbers are clamped to the table.
+__device__ __forceinline__ float window_norm_max(const GemmArgs &A, int64_t lo, int64_t hi) {
+  const int last = A.norm_blocks - 1;
+  int b0 = uni((int)(lo >> 6)), b1 = uni((int)((hi - 1) >> 6));
+  b0 = b0 < 0 ? 0 : b0 > last ? last : b0;
+  b1 = b1 < b0 ? b0 : b1 > last ? last : b1;
+  const int j = 31 - __builtin_clz((unsigned)(b1 - b0 + 1));
+  const unsigned int *level = A.norm_levels + (int64_t)j * A.norm_blocks;
+  const unsigned int x = level[b0], y = level[b1 - (1 << j) + 1];
+  return __uint_as_float(x > y ? x : y);
+}
+// The proof's pmax.  WHICH extent: the proof compares the k-th exact distance with cut_sel and cut_blk, lower bounds on the
+// SCORES of the positions of the query's window [wa, wb) that were not selected, and E has to cover the score error of exactly
+// those positions.  A shared-window group: [wa, wb) is the group's window, and nothing else is scored.  A cover group scores whole
+// position blocks, but CoverRow drops every candidate outside [wa, wb) before the selection sees it, and a block's fourth entry
+// -- which may belong to a position outside the window -- is only ever used as a number that the in-window positions the block
+// kept to itself do not score below: no statement about that position's own distance is made, so its norm need not be covered.
+// The rescue scan scores in-window positions exactly.  Hence the query's own window in both cases, not the span of the tiles.
+__device__ __forceinline__ float proof_norm_max(const GemmArgs &A, int64_t wa, int64_t wb) {
+  return A.norm_levels ? window_norm_max(A, wa, wb) : __uint_as_float(*A.pnorm2_max_bits);
+}
 #else  // byte rows
 #include "wann_gemm_kernels_bytes.inc"
 __device__ __forceinline__ float no_entry() { return __uint_as_float(kNoKey); }
@@ -1598,7 +1724,7 @@ __device__ __forceinline__ void rerank_query(const GemmArgs &A, const WaveLds &L
     const float E = 0.f;
     (void)q2;
 #else
-    const float pmax = __uint_as_float(*A.pnorm2_max_bits);
+    const float pmax = proof_norm_max(A, wa, wb);  // (the index's largest norm, or the largest round the query's own window)
     const float cerr = 3.02f * 1.52587890625e-5f + A.acc_factor * (float)(3 * ix.d + 8) * 5.9604645e-8f + (cen ? kCentredErr : 0.f);
     // + 2^-17 relative for the six mantissa bits that carry the position (|score| <= |q||p| resp. 2 (|q|^2 + |p|^2))
     const float cerr2 = cerr + 7.62939453125e-6f;
@@ -1887,7 +2013,7 @@ __device__ __forceinline__ void rerank_query_large(const GemmArgs &A, const Wave
   // E: the products the bf16 split drops (q1 p3 + q3 p1 + q2 p2 + ...) <= 3.02 * 2^-16 |q||p| (Cauchy-Schwarz over
   // the columns), fp32 accumulation of 3 d products (A.acc_factor x the rounding adder's worst case), fp32 norms and the
   // reference's own rounding.
-  const float pmax = __uint_as_float(*A.pnorm2_max_bits);
+  const float pmax = proof_norm_max(A, wa, wb);  // (as in rerank_query)
   const float cerr = 3.02f * 1.52587890625e-5f + A.acc_factor * (float)(3 * ix.d + 8) * 5.9604645e-8f + (cen ? kCentredErr : 0.f);
   // + 2^-17 relative for the six mantissa bits that carry the position (|score| <= |q||p| resp. 2 (|q|^2 + |p|^2))
   const float cerr2 = cerr + 7.62939453125e-6f;

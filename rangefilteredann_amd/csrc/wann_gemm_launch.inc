@@ -147,6 +147,21 @@ static const char *unit_point_sums(const IndexView &ix, float *norm2, unsigned i
   return gerr_of(hipGetLastError());
 }
 
+#if !WANN_BYTE_ROWS
+// the sparse table of window maxima over `norm2` (wann_set_dense_window_norms): level 0, then a launch per further level, each
+// reading the level below it -- stream order is the only dependency; once per index (and once more for the centred norms)
+static const char *unit_norm_table(const IndexView &ix, const float *norm2, unsigned int *table, void *stream) {
+  if (ix.n <= 0) return nullptr;
+  const int nblocks = (int)norm_table_blocks(ix.n), levels = norm_table_levels(nblocks);
+  const int wpb = 4;  // a wave per block of 64 positions
+  hipLaunchKernelGGL(k_norm_blocks, dim3((unsigned)((nblocks + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, ix, norm2, table, nblocks);
+  const dim3 grid((unsigned)std::min<int64_t>(1024, (nblocks + 255) / 256));
+  for (int j = 1; j < levels; j++)
+    hipLaunchKernelGGL(k_norm_levels, grid, dim3(256), 0, (hipStream_t)stream, table + (size_t)(j - 1) * nblocks, table + (size_t)j * nblocks, nblocks, 1 << (j - 1));
+  return gerr_of(hipGetLastError());
+}
+#endif
+
 #if WANN_DT == 0 || WANN_DT == 3
 // the centre, then the norms of the centred rows: three launches in stream order, once per index
 static const char *unit_centred_sums(const IndexView &ix, float *buf, void *stream) {
@@ -157,6 +172,23 @@ static const char *unit_centred_sums(const IndexView &ix, float *buf, void *stre
   float *part = ix.n >= words ? norm2 : c;  // (nparts rows of `words` floats: they fit the norms' floats, or are the one row c itself)
   hipLaunchKernelGGL(k_row_centre, dim3((unsigned)nparts), dim3(256), 0, (hipStream_t)stream, ix, words, part, nparts, c, max_bits, 0);
   hipLaunchKernelGGL(k_row_centre, dim3(1), dim3(256), 0, (hipStream_t)stream, ix, words, part, nparts, c, max_bits, 1);
+  const int wpb = 4;  // a wave per row
+  hipLaunchKernelGGL(k_point_norms_centred, dim3((unsigned)((ix.n + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, ix, c, norm2, max_bits);
+  return gerr_of(hipGetLastError());
+}
+
+// the same with the TRIMMED centre (both switches in force): the threshold and the number of rows kept from the uncentred norms
+// `norm2_raw` into trim[0 .. 1], then k_row_centre_trimmed's two stages, then the norms of the centred rows -- every row's, the
+// rows left out of the mean included
+static const char *unit_centred_sums_trimmed(const IndexView &ix, const float *norm2_raw, float *trim, float *buf, void *stream) {
+  if (ix.n <= 0) return nullptr;
+  const int words = query_words(ix), nparts = centred_parts(ix.n, words);
+  float *norm2 = buf, *c = buf + ix.n;
+  unsigned int *max_bits = reinterpret_cast<unsigned int *>(c + words);
+  float *part = ix.n >= words ? norm2 : c;
+  hipLaunchKernelGGL(k_norm_trim, dim3(1), dim3(1024), 0, (hipStream_t)stream, norm2_raw, ix.n, trim);
+  hipLaunchKernelGGL(k_row_centre_trimmed, dim3((unsigned)nparts), dim3(256), 0, (hipStream_t)stream, ix, words, part, nparts, c, max_bits, 0, norm2_raw, (const float *)trim);
+  hipLaunchKernelGGL(k_row_centre_trimmed, dim3(1), dim3(256), 0, (hipStream_t)stream, ix, words, part, nparts, c, max_bits, 1, norm2_raw, (const float *)trim);
   const int wpb = 4;  // a wave per row
   hipLaunchKernelGGL(k_point_norms_centred, dim3((unsigned)((ix.n + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, ix, c, norm2, max_bits);
   return gerr_of(hipGetLastError());
@@ -204,11 +236,11 @@ const GemmUnit &gemm_unit() {
 #if WANN_DT == 6
   static constexpr GemmUnit unit = {nullptr, nullptr, unit_gemm_scores, nullptr, nullptr};  // (only ever asked for gemm_scores: dense_prefilter)
 #elif WANN_DT == 3
-  static constexpr GemmUnit unit = {unit_point_sums, nullptr, unit_gemm_scores, unit_select_rerank, unit_rerank_cover, unit_centred_sums};
+  static constexpr GemmUnit unit = {unit_point_sums, nullptr, unit_gemm_scores, unit_select_rerank, unit_rerank_cover, unit_centred_sums, unit_norm_table, unit_centred_sums_trimmed};
 #elif WANN_HALF_ROWS || WANN_DT == 8
-  static constexpr GemmUnit unit = {unit_point_sums, nullptr, unit_gemm_scores, unit_select_rerank, unit_rerank_cover};
+  static constexpr GemmUnit unit = {unit_point_sums, nullptr, unit_gemm_scores, unit_select_rerank, unit_rerank_cover, nullptr, unit_norm_table};
 #elif WANN_DT == 0
-  static constexpr GemmUnit unit = {unit_point_sums, unit_prep_queries, unit_gemm_scores, unit_select_rerank, unit_rerank_cover, unit_centred_sums};
+  static constexpr GemmUnit unit = {unit_point_sums, unit_prep_queries, unit_gemm_scores, unit_select_rerank, unit_rerank_cover, unit_centred_sums, unit_norm_table, unit_centred_sums_trimmed};
 #else
   static constexpr GemmUnit unit = {unit_point_sums, unit_prep_queries, unit_gemm_scores, unit_select_rerank, unit_rerank_cover};
 #endif
@@ -243,6 +275,8 @@ static int unit_launch(int dtype, const char *(*GemmUnit::*fn)(P...), const char
 
 int launch_point_norms(const IndexView &ix, float *norm2, unsigned int *max_bits, void *stream) { return unit_launch(ix.dtype, &GemmUnit::point_sums, "point_sums", ix, norm2, max_bits, nullptr, stream); }
 int launch_centred_norms(const IndexView &ix, float *buf, void *stream) { return unit_launch(ix.dtype, &GemmUnit::centred_sums, "centred_sums", ix, buf, stream); }
+int launch_norm_table(const IndexView &ix, const float *norm2, unsigned int *table, void *stream) { return unit_launch(ix.dtype, &GemmUnit::norm_table, "norm_table", ix, norm2, table, stream); }
+int launch_centred_norms_trimmed(const IndexView &ix, const float *norm2_raw, float *trim, float *buf, void *stream) { return unit_launch(ix.dtype, &GemmUnit::centred_sums_trimmed, "centred_sums_trimmed", ix, norm2_raw, trim, buf, stream); }
 int launch_point_terms(const IndexView &ix, int32_t *term, void *stream) { return unit_launch(ix.dtype, &GemmUnit::point_sums, "point_sums", ix, nullptr, nullptr, term, stream); }
 int launch_split_queries(const float *queries, int64_t nq, int d, int stride, uint32_t *out, void *stream) { return record(gemm_unit().prep_queries(queries, nq, d, stride, out, stream)); }
 int launch_pack_queries(const IndexView &ix, const float *queries, int64_t nq, uint32_t *out, void *stream) { return unit_launch(ix.dtype, &GemmUnit::prep_queries, "prep_queries", queries, nq, ix.d, ix.stride, out, stream); }

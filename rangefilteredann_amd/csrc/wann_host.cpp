@@ -59,6 +59,7 @@ Tuning snapshot_tuning(wann_index &I) {
   t.dense_large_k = row_switch_in_force(I, kDenseLargeKSwitch);
   t.dense_large_k_bytes = row_switch_in_force(I, kDenseLargeKBytesSwitch);
   t.dense_centred = row_switch_in_force(I, kDenseCentredSwitch);
+  t.dense_window_norms = row_switch_in_force(I, kDenseWindowNormsSwitch);
   return t;
 }
 

@@ -201,6 +201,11 @@ struct wann_index {
   // row changes; what changes is which queries the proof settles.
   bool dense_centred_on = false;
   bool has_dense_centred() const { return wann::dense_centred_type(dtype, host().spec.metric); }
+  // wann_set_dense_window_norms (likewise): the proof of a dense batch bounds each query by the largest norm round its own window
+  // (window_norm_max over d_norm_levels) instead of the index's largest.  Never on for uint8 / int8 rows: their scores are exact,
+  // there is no bound.  No result row changes; what changes is which queries the proof settles.
+  bool dense_window_norms_on = false;
+  bool has_dense_window_norms() const { return !wann::byte_rows(dtype); }
   bool has_half_copy() const { return d_half.p != nullptr; }
   bool has_byte_copy() const { return d_bytes.p != nullptr; }
   bool has_scan_copy() const { return has_half_copy() || has_byte_copy(); }
@@ -240,6 +245,15 @@ struct wann_index {
   // centred batch and reported where d_pnorm2 is
   DevBuf<float> d_centred;
   bool have_centred = false;
+  // wann_set_dense_window_norms: the sparse tables of window maxima (norm_table_words) over d_pnorm2 and over the centred norms,
+  // each built at the first batch that reads it and reported where d_pnorm2 is.  A batch under BOTH switches is centred on the
+  // TRIMMED centre (k_norm_trim / k_row_centre_trimmed: the mean without the rows of outlying norms, which window maxima no longer
+  // pay for anywhere else): a centred buffer of its own, d_centred_trim (d_centred's layout; d_trim: the threshold and the count),
+  // and the centred table is the one over ITS norms.  d_centred stays what wann_set_dense_centred alone has always built.
+  DevBuf<unsigned int> d_norm_levels, d_norm_levels_centred;
+  bool have_norm_levels = false, have_norm_levels_centred = false;
+  DevBuf<float> d_centred_trim, d_trim;
+  bool have_centred_trim = false;
   // (touched by the blocking calls and by both asynchronous lanes, outside dense_mu for every class but PrefilterIndex)
   std::atomic<int> dense_idle{0};  // batches in a row on which the dense path found no window group (run_batch)
   std::atomic<uint32_t> dense_batches{0};
@@ -304,6 +318,7 @@ constexpr RowSwitch kDenseLongFloat8Switch = {&wann_index::dense_long_float8_on,
 constexpr RowSwitch kDenseLargeKSwitch = {&wann_index::dense_large_k_on, &wann_index::has_dense_large_k, nullptr};
 constexpr RowSwitch kDenseLargeKBytesSwitch = {&wann_index::dense_large_k_bytes_on, &wann_index::has_dense_large_k_bytes, nullptr};
 constexpr RowSwitch kDenseCentredSwitch = {&wann_index::dense_centred_on, &wann_index::has_dense_centred, nullptr};
+constexpr RowSwitch kDenseWindowNormsSwitch = {&wann_index::dense_window_norms_on, &wann_index::has_dense_window_norms, nullptr};
 // (under I.tune_mu)
 inline bool row_switch_in_force(const wann_index &I, const RowSwitch &s) { return I.*s.on && (I.*s.has_copy)(); }
 

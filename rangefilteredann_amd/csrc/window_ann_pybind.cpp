@@ -304,6 +304,10 @@ class Index {
   // the mean row (wann_set_dense_centred, off by default; False on an inner-product index or any other element type)
   bool set_dense_centred(bool on) { return set_row_switch(wann_set_dense_centred, on, "set_dense_centred failed"); }
   bool dense_centred() const { return wann_dense_centred(h_) != 0; }
+  // the dense proof bounds each query by the largest row norm round its own window, not the index's largest
+  // (wann_set_dense_window_norms, off by default; False on a uint8 / int8 index)
+  bool set_dense_window_norms(bool on) { return set_row_switch(wann_set_dense_window_norms, on, "set_dense_window_norms failed"); }
+  bool dense_window_norms() const { return wann_dense_window_norms(h_) != 0; }
 
   // float16 / bfloat16 / float8 indexes: the full-precision points (any array numpy casts to float32, in the order of the array
   // the index was created from) as the row store of the refined calls (wann_set_refine_rows); None drops the store
@@ -426,6 +430,7 @@ class Index {
     d["dense_large_k"] = wann_dense_large_k(h_);          // the index's wann_set_dense_large_k setting (likewise)
     d["dense_large_k_bytes"] = wann_dense_large_k_bytes(h_);  // the index's wann_set_dense_large_k_bytes setting (likewise)
     d["dense_centred"] = wann_dense_centred(h_);          // the index's wann_set_dense_centred setting (likewise)
+    d["dense_window_norms"] = wann_dense_window_norms(h_);  // the index's wann_set_dense_window_norms setting (likewise)
     return d;
   }
   static py::dict counters_dict(const wann_counters &c) {
@@ -524,6 +529,8 @@ static void common_defs(py::class_<C> &c) {
       .def("dense_large_k_bytes", &C::dense_large_k_bytes)
       .def("set_dense_centred", &C::set_dense_centred, "on"_a)
       .def("dense_centred", &C::dense_centred)
+      .def("set_dense_window_norms", &C::set_dense_window_norms, "on"_a)
+      .def("dense_window_norms", &C::dense_window_norms)
       .def("set_refine_rows", &C::set_refine_rows, "points"_a.none(true))
       .def("refine_rows_bytes", &C::refine_rows_bytes)
       .def("batch_search_refined", &C::search_refined, "queries"_a, "filters"_a, "num_queries"_a, "query_method"_a, "query_params"_a,
