@@ -298,6 +298,66 @@ static void check_dense_window_norms() {
     while (((int64_t)2 << j) <= nb) j++;
     CHECK(levels >= 1 && j < levels && ((int64_t)1 << (levels - 1)) >= nb && (levels == 1 || ((int64_t)1 << (levels - 2)) < nb));
   }
+  // The index arithmetic the kernels run (norm_level_half / norm_level_partner: k_norm_levels and its launcher; norm_lookup:
+  // window_norm_max), over whole small tables -- levels 0 .. 3 and most clamps are out of reach of any dense batch, whose
+  // windows hold at least 1 024 positions.  Level 0 is filled with three patterns at once (random values; rising: the maximum is
+  // the LAST block of the cover; falling: the first), the levels are built as the launcher builds them, and for every window
+  // 0 <= lo < hi <= 64 nblocks the two entries read must lie inside the table and their maximum must be the maximum of level 0
+  // over the blocks lo >> 6 .. (hi - 1) >> 6, no more and no less: at least the window's own maximum, and nothing of a block
+  // beyond that cover.  The vectors are exactly the table's words: a read outside them is AddressSanitizer's.
+  constexpr int kPat = 3;
+  std::mt19937 rng(12345);
+  std::vector<int> sizes;
+  for (int nb = 1; nb <= 70; nb++) sizes.push_back(nb);
+  for (int nb : {127, 128, 129, 641}) sizes.push_back(nb);
+  long long windows = 0;
+  for (int nb : sizes) {
+    const int levels = norm_table_levels(nb), stride = nb > 70 ? 7 : 1;
+    std::vector<unsigned int> table[kPat], cover[kPat];  // cover[b0 * nb + b1]: level 0's maximum over b0 .. b1, by brute force
+    for (int p = 0; p < kPat; p++) {
+      std::vector<unsigned int> &t = table[p];
+      t.assign((size_t)nb * levels, 0u);
+      for (int b = 0; b < nb; b++) t[b] = p == 0 ? (unsigned int)(rng() >> 1) : p == 1 ? 1000u + b : 1000000u - b;
+      for (int j = 1; j < levels; j++)
+        for (int b = 0; b < nb; b++) {
+          const int b2 = norm_level_partner(b, norm_level_half(j), nb);
+          CHECK(b2 >= 0 && b2 < nb);
+          t[(size_t)j * nb + b] = std::max(t[(size_t)(j - 1) * nb + b], t[(size_t)(j - 1) * nb + b2]);
+        }
+      cover[p].assign((size_t)nb * nb, 0u);
+      for (int b0 = 0; b0 < nb; b0++) {
+        unsigned int m = 0;
+        for (int b1 = b0; b1 < nb; b1++) cover[p][(size_t)b0 * nb + b1] = m = std::max(m, t[b1]);
+      }
+    }
+    int bad = 0;
+    for (int64_t lo = 0; lo < (int64_t)kNormBlock * nb; lo += stride)
+      for (int64_t hi = lo + 1; hi <= (int64_t)kNormBlock * nb; hi += stride) {
+        const NormLookup at = norm_lookup(lo, hi, nb);
+        windows++;
+        if (at.j < 0 || at.j >= levels || at.x < 0 || at.x >= nb || at.y < 0 || at.y >= nb) {
+          bad++;
+          continue;
+        }
+        const size_t row = (size_t)at.j * nb, want = (size_t)(lo >> 6) * nb + (size_t)((hi - 1) >> 6);
+        for (int p = 0; p < kPat; p++) bad += std::max(table[p][row + at.x], table[p][row + at.y]) != cover[p][want];
+      }
+    if (bad) fprintf(stderr, "norm table of %d blocks: %d windows whose lookup is not the maximum of their covering blocks\n", nb, bad);
+    CHECK(bad == 0);
+    // degenerate arguments: the clamps keep both entries inside the table (empty and reversed windows, positions before the
+    // first and beyond the last block)
+    for (int64_t lo : {(int64_t)-100000, (int64_t)-65, (int64_t)-64, (int64_t)-1, (int64_t)0, (int64_t)63, (int64_t)64, (int64_t)kNormBlock * nb - 1,
+                       (int64_t)kNormBlock * nb, (int64_t)kNormBlock * nb + 1, (int64_t)kNormBlock * nb + 100000, ((int64_t)1 << 30) * kNormBlock - 1})
+      for (int64_t hi : {(int64_t)-100000, (int64_t)-64, (int64_t)-1, (int64_t)0, (int64_t)1, (int64_t)64, (int64_t)65, (int64_t)kNormBlock * nb - 1,
+                         (int64_t)kNormBlock * nb, (int64_t)kNormBlock * nb + 1, (int64_t)kNormBlock * nb + 64, (int64_t)kNormBlock * nb + 100000,
+                         ((int64_t)1 << 30) * kNormBlock}) {
+        const NormLookup at = norm_lookup(lo, hi, nb);
+        CHECK(at.j >= 0 && at.j < levels && at.x >= 0 && at.x < nb && at.y >= 0 && at.y < nb && at.y + (1 << at.j) <= nb);
+        unsigned int sink = std::max(table[0][(size_t)at.j * nb + at.x], table[0][(size_t)at.j * nb + at.y]);
+        CHECK(sink >= table[0][at.x]);  // (the first run starts at block x: its maximum holds that block)
+      }
+  }
+  CHECK(windows > 200000000);  // (every window of the 70 small tables alone: sum of (64 nb)(64 nb + 1) / 2)
 }
 
 // The row-type table (wann_row_types.h) against the values written out here: every class, the caller's bytes, the device

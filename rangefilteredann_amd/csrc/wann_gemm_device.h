@@ -109,6 +109,26 @@ constexpr int norm_table_levels(int64_t nblocks) {
   return levels;
 }
 constexpr size_t norm_table_words(int64_t n) { return n <= 0 ? 0 : (size_t)norm_table_blocks(n) * (size_t)norm_table_levels(norm_table_blocks(n)); }
+// The table's index arithmetic, as the kernels use it (host_sanitize_test.cpp runs it over every window of small tables).
+// k_norm_levels: the block whose entry of the level below joins block b's, half = 2^(j-1) blocks on (what the launcher passes for
+// level j = 1 .. levels - 1), clamped to the last block.
+constexpr int norm_level_half(int j) { return 1 << (j - 1); }
+constexpr int norm_level_partner(int b, int half, int nblocks) { return b + half < nblocks ? b + half : nblocks - 1; }
+// window_norm_max: the level and the two entries (indices into that level's row) that cover the blocks of [lo, hi).  The block
+// numbers are clamped to the table; the runs of 2^j blocks from b0 on and up to b1 overlap or touch.
+struct NormLookup {
+  int j, x, y;
+};
+constexpr NormLookup norm_lookup_blocks(int b0, int b1, int nblocks) {
+  const int last = nblocks - 1;
+  b0 = b0 < 0 ? 0 : b0 > last ? last : b0;
+  b1 = b1 < b0 ? b0 : b1 > last ? last : b1;
+  const int j = 31 - __builtin_clz((unsigned)(b1 - b0 + 1));
+  return NormLookup{j, b0, b1 - (1 << j) + 1};
+}
+constexpr int norm_first_block(int64_t lo) { return (int)(lo >> 6); }
+constexpr int norm_last_block(int64_t hi) { return (int)((hi - 1) >> 6); }
+constexpr NormLookup norm_lookup(int64_t lo, int64_t hi, int nblocks) { return norm_lookup_blocks(norm_first_block(lo), norm_last_block(hi), nblocks); }
 
 // What the proof's relative error gains on a centred batch, as a summand of cerr (E = 2 cerr2 (|q'|^2 + max |p'|^2)), for the two
 // elementwise roundings q' = fl(q - c), p' = fl(p - c).  Each is (x - c)(1 + delta), |delta| <= u = 2^-24 (a subtraction has no

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void k_norm_blocks(IndexView ix, const float *
 // `below`: level j - 1, `level`: level j, half = 2^(j-1); a thread per block
 __global__ __launch_bounds__(256) void k_norm_levels(const unsigned int *below, unsigned int *level, int nblocks, int half) {
   for (int b = (int)(blockIdx.x * blockDim.x + threadIdx.x); b < nblocks; b += (int)(gridDim.x * blockDim.x)) {
-    const int b2 = b + half < nblocks ? b + half : nblocks - 1;
+    const int b2 = norm_level_partner(b, half, nblocks);
     const unsigned int x = below[b], y = below[b2];
     level[b] = x > y ? x : y;
   }
@@ -1607,13 +1607,10 @@ __device__ __forceinline__ const float *centre_of(const GemmArgs &A) {
 // window's own maximum, never smaller, which is what keeps the bound valid.  Wave-uniform (the window is the query's): the
 // indices pass through scalar registers, two loads, no loop, no LDS.  The block numbers are clamped to the table.
 __device__ __forceinline__ float window_norm_max(const GemmArgs &A, int64_t lo, int64_t hi) {
-  const int last = A.norm_blocks - 1;
-  int b0 = uni((int)(lo >> 6)), b1 = uni((int)((hi - 1) >> 6));
-  b0 = b0 < 0 ? 0 : b0 > last ? last : b0;
-  b1 = b1 < b0 ? b0 : b1 > last ? last : b1;
-  const int j = 31 - __builtin_clz((unsigned)(b1 - b0 + 1));
-  const unsigned int *level = A.norm_levels + (int64_t)j * A.norm_blocks;
-  const unsigned int x = level[b0], y = level[b1 - (1 << j) + 1];
+  const int b0 = uni(norm_first_block(lo)), b1 = uni(norm_last_block(hi));
+  const NormLookup at = norm_lookup_blocks(b0, b1, A.norm_blocks);
+  const unsigned int *level = A.norm_levels + (int64_t)at.j * A.norm_blocks;
+  const unsigned int x = level[at.x], y = level[at.y];
   return __uint_as_float(x > y ? x : y);
 }
 // The proof's pmax.  WHICH extent: the proof compares the k-th exact distance with cut_sel and cut_blk, lower bounds on the

@@ -157,7 +157,7 @@ static const char *unit_norm_table(const IndexView &ix, const float *norm2, unsi
   hipLaunchKernelGGL(k_norm_blocks, dim3((unsigned)((nblocks + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, ix, norm2, table, nblocks);
   const dim3 grid((unsigned)std::min<int64_t>(1024, (nblocks + 255) / 256));
   for (int j = 1; j < levels; j++)
-    hipLaunchKernelGGL(k_norm_levels, grid, dim3(256), 0, (hipStream_t)stream, table + (size_t)(j - 1) * nblocks, table + (size_t)j * nblocks, nblocks, 1 << (j - 1));
+    hipLaunchKernelGGL(k_norm_levels, grid, dim3(256), 0, (hipStream_t)stream, table + (size_t)(j - 1) * nblocks, table + (size_t)j * nblocks, nblocks, norm_level_half(j));
   return gerr_of(hipGetLastError());
 }
 #endif
