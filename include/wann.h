@@ -467,7 +467,7 @@ int wann_set_dense_large_k_bytes(wann_index *index, int on);
 int wann_dense_large_k_bytes(const wann_index *index);
 /* Centred operands on the dense path: data far from the origin.
  * wann_set_dense_centred: whether squared-L2 batches of a WANN_DTYPE_F32 / WANN_DTYPE_F16 index with rows of at most 128 elements
- * are scored, in the NEXT batches and on all three routes, on centred operands: the MFMA score kernel stages fl(q - c) and
+ * (WANN_DTYPE_F32: of at most 512) are scored, in the NEXT batches and on all three routes, on centred operands: the MFMA score kernel stages fl(q - c) and
  * fl(p - c), c the mean row of the index (computed once, at the first such batch, with the norms |fl(p - c)|^2: n + padded row + 1
  * floats of device memory), and the proof's bound runs on the centred norms.  |q - p|^2 is the same, the bound's terms
  * |q|^2 + max |p|^2 are not: rows and queries with a large common component (non-negative histograms, embeddings with a large

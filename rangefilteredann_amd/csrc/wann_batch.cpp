@@ -64,7 +64,8 @@ void dense_prefilter(wann_index &I, const Tuning &T, Workspace &W, const float *
   // wann_set_dense_centred: this batch is scored on fl(x - c) and proven on the centred norms.  The centre and those norms are
   // computed once, at the first such batch, beside the uncentred ones (a later batch may run with the switch off again).
   // With wann_set_dense_window_norms in force as well the centre is the TRIMMED mean, in a buffer of its own (wann_host_internal.h).
-  const bool centred = dense_centred_route(I.view, T.dense_centred, dense_score_view(I, T) != nullptr);
+  const bool byte_copy_scored = dense_score_view(I, T) != nullptr;
+  const bool centred = dense_centred_route(I.view, T.dense_centred, byte_copy_scored) || dense_centred_wide_route(I.view, T.dense_centred, byte_copy_scored);
   const bool window_norms = T.dense_window_norms && !bytes;
   const bool trimmed = centred && window_norms;
   if (centred && !trimmed && !I.have_centred) {

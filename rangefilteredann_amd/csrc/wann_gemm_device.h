@@ -86,8 +86,8 @@ struct GemmArgs {
   int32_t *out_cnt;
   int32_t *brute_list, *brute_count;  // exact scan: ungrouped queries + queries whose top-k could not be proven
   unsigned long long *prof;           // dev tool (make PROFILE=1): phase-cycle sums of k_gemm_scores
-  // A centred batch (wann_set_dense_centred; dense_centred_route): the index's centre c, `query_words` floats, zero beyond d.
-  // Non-null IS the flag: the score launch picks k_gemm_scores<STRIDE, true>, the proof sums |fl(q - c)|^2 and widens its bound
+  // A centred batch (wann_set_dense_centred; dense_centred_route / dense_centred_wide_route): the index's centre c, `query_words` floats, zero beyond d.
+  // Non-null IS the flag: the score launch picks k_gemm_scores<STRIDE, true> / k_gemm_scores_wide_centred, the proof sums |fl(q - c)|^2 and widens its bound
   // by kCentredErr, and pnorm2 / pnorm2_max_bits above point at |fl(p - c)|^2 and its maximum.  Null: everything as it was.
   const float *centre;
   // Window maxima of the norms (wann_set_dense_window_norms): the sparse table over pnorm2 in filter order, norm_table_levels
@@ -224,6 +224,12 @@ inline DenseRows dense_row_class(const IndexView &ix, bool long_switch = false, 
 // centred).  Every other batch is scored and proven as if the switch were off.
 inline bool dense_centred_route(const IndexView &ix, bool switch_on, bool byte_copy_scored) {
   return switch_on && !byte_copy_scored && dense_centred_type(ix.dtype, ix.metric) && dense_row_class(ix) == kRowsNarrow;
+}
+// ... or when, under the same switch, the rows are float32 rows of the wide class (129 .. 512 floats): k_gemm_scores_wide_centred,
+// which only the float32 unit has.  A predicate of its own -- the one above keeps answering for the narrow class alone; a batch is
+// centred when either holds.  Float16 rows beyond 128 elements, kRowsLong and every other type stay uncentred.
+inline bool dense_centred_wide_route(const IndexView &ix, bool switch_on, bool byte_copy_scored) {
+  return switch_on && !byte_copy_scored && ix.dtype == kRowsF32 && ix.metric == 0 && dense_row_class(ix) == kRowsWide;
 }
 
 // Dynamic LDS of the selection / re-rank kernels: four waves x (staged query row, candidate arrays, the merge list).  k <= 16

@@ -176,7 +176,8 @@ WANN_GNS_END
 
 #if WANN_DT == 0 || WANN_DT == 3
 // ------------------------------------------------------------------------------------------------
-// Centred operands (opt-in per index: wann_set_dense_centred; squared L2, rows of at most 128 elements).  |q - p|^2 does not change
+// Centred operands (opt-in per index: wann_set_dense_centred; squared L2, rows of at most 128 elements -- float32 rows: of at most
+// 512, k_gemm_scores_wide_centred further down; the centre and the centred norms are these kernels' for both).  |q - p|^2 does not change
 // when one vector c is taken from both sides, but the terms of the proof's bound do: E = 2 cerr2 (|q|^2 + max |p|^2) grows with
 // the data's distance from the origin, the gaps it must resolve do not.  With c the mean row, the centred k_gemm_scores scores
 // fl(q - c) against fl(p - c) and the proof runs on their norms.  Any c is valid; only the bound's size depends on it.
@@ -184,8 +185,9 @@ WANN_GNS_END
 //   k_row_centre           c[words] in fp32, once per index, in a fixed order (no floating-point atomics: c, and with it every
 //                          counter of the path, is the same from run to run).  stage 0: workgroup g sums its contiguous slice of
 //                          rows per column -- thread (column, sub) every other row of the slice, the two subs added through the
-//                          LDS -- and writes part[g][words].  stage 1, one workgroup: the partial sums in workgroup order, divided
-//                          by n; columns d .. words are zero; the maximum's bits are cleared for k_point_norms_centred.
+//                          LDS -- and writes part[g][words], 128 columns a pass.  stage 1, one workgroup: the partial sums in
+//                          workgroup order, divided by n, a thread per column and 256 columns a pass; columns d .. words are
+//                          zero; the maximum's bits are cleared for k_point_norms_centred.
 //   k_point_norms_centred  k_point_norms on fl(p_i - c_i): the fp32 subtraction the score kernel stages, element by element, so
 //                          that the norm is of the very values that are scored (|p|^2 - 2 c.p + |c|^2 would cancel instead).
 // A float16 row widens exactly first; c is float32 in both units.
@@ -205,16 +207,22 @@ __global__ __launch_bounds__(256) void k_row_centre(IndexView ix, int words, flo
   const int tid = threadIdx.x, col = tid & 127, sub = tid >> 7;
   if (stage == 0) {
     const int64_t per = (ix.n + nparts - 1) / nparts, r0 = (int64_t)blockIdx.x * per, r1 = r0 + per < ix.n ? r0 + per : ix.n;
-    float s = 0.f;
-    if (col < ix.d)
-      for (int64_t r = r0 + sub; r < r1; r += 2) s += centre_row_value(ix, r, col);
-    if (sub == 1) sh[col] = s;
-    __syncthreads();
-    if (sub == 0 && col < words) part[(int64_t)blockIdx.x * words + col] = s + sh[col];
-  } else if (tid < words) {  // (one workgroup; `part` may be `c` itself when there is one partial row: read, then written, by the same thread)
-    float s = 0.f;
-    for (int g = 0; g < nparts; g++) s += part[(int64_t)g * words + tid];
-    c[tid] = tid < ix.d ? s / (float)ix.n : 0.f;
+    for (int c0 = 0; c0 < words; c0 += 128) {  // (wide rows, up to 512 words: a pass per 128 columns, each column summed in the order it always was)
+      const int cc = c0 + col;
+      float s = 0.f;
+      if (cc < ix.d)
+        for (int64_t r = r0 + sub; r < r1; r += 2) s += centre_row_value(ix, r, cc);
+      if (c0) __syncthreads();  // (the pass before has read sh)
+      if (sub == 1) sh[col] = s;
+      __syncthreads();
+      if (sub == 0 && cc < words) part[(int64_t)blockIdx.x * words + cc] = s + sh[col];
+    }
+  } else {  // (one workgroup; `part` may be `c` itself when there is one partial row: read, then written, by the same thread)
+    for (int i = tid; i < words; i += 256) {
+      float s = 0.f;
+      for (int g = 0; g < nparts; g++) s += part[(int64_t)g * words + i];
+      c[i] = i < ix.d ? s / (float)ix.n : 0.f;
+    }
     if (tid == 0) *max_bits = 0u;
   }
 }
@@ -282,17 +290,23 @@ __global__ __launch_bounds__(256) void k_row_centre_trimmed(IndexView ix, int wo
   if (stage == 0) {
     const float thr = trim[0];
     const int64_t per = (ix.n + nparts - 1) / nparts, r0 = (int64_t)blockIdx.x * per, r1 = r0 + per < ix.n ? r0 + per : ix.n;
-    float s = 0.f;
-    if (col < ix.d)
-      for (int64_t r = r0 + sub; r < r1; r += 2)
-        if (norm2[r] <= thr) s += centre_row_value(ix, r, col);
-    if (sub == 1) sh[col] = s;
-    __syncthreads();
-    if (sub == 0 && col < words) part[(int64_t)blockIdx.x * words + col] = s + sh[col];
-  } else if (tid < words) {  // (one workgroup; `part` may be `c` itself, as in k_row_centre)
-    float s = 0.f;
-    for (int g = 0; g < nparts; g++) s += part[(int64_t)g * words + tid];
-    c[tid] = tid < ix.d ? s / trim[1] : 0.f;
+    for (int c0 = 0; c0 < words; c0 += 128) {  // (a pass per 128 columns, as in k_row_centre)
+      const int cc = c0 + col;
+      float s = 0.f;
+      if (cc < ix.d)
+        for (int64_t r = r0 + sub; r < r1; r += 2)
+          if (norm2[r] <= thr) s += centre_row_value(ix, r, cc);
+      if (c0) __syncthreads();
+      if (sub == 1) sh[col] = s;
+      __syncthreads();
+      if (sub == 0 && cc < words) part[(int64_t)blockIdx.x * words + cc] = s + sh[col];
+    }
+  } else {  // (one workgroup; `part` may be `c` itself, as in k_row_centre)
+    for (int i = tid; i < words; i += 256) {
+      float s = 0.f;
+      for (int g = 0; g < nparts; g++) s += part[(int64_t)g * words + i];
+      c[i] = i < ix.d ? s / trim[1] : 0.f;
+    }
     if (tid == 0) *max_bits = 0u;
   }
 }
@@ -1272,6 +1286,185 @@ __global__ __launch_bounds__(256, 1) void k_gemm_scores_wide4(GemmArgs A) {
 #pragma unroll
           for (int r = 0; r < 4; r++) {
             const float sc = fmaf(scale, acc[j][4 * g + r], b4[r]);
+            const float x = __uint_as_float((__float_as_uint(sc) & ~63u) | (uint32_t)(16 * j + 4 * g + r));
+            insert4(m1, m2, m3, m4, x);
+          }
+        }
+      if (live) erow[(c0 - p_begin) >> 6] = f32x4{m1, m2, m3, m4};
+    }
+#undef WANN_REQUEST
+  }
+}
+
+// Centred scoring of rows of 129 .. 512 floats (wann_set_dense_centred; squared L2 only: dense_centred_wide_route): both operands
+// are fl(x - c), c = A.centre -- the vector k_point_norms_centred took from every row and the proof takes from every query.
+// One body for two, three and four slabs, and the unit of work is k_gemm_scores_wide4's half slab at every slab count: the points
+// travel HBM -> LDS directly into the raw area R, and c is taken from a value on the one way every slab count shares, between R
+// and split2 -- no block in flight in registers anywhere, so the A operand's registers are all a slab count adds.
+//   LDS: Ps | base[2][128] | rid[2][128] | cs[512] | R (32 KiB) | SLABS = 4: the low halves of the last slab's A operand
+//   cs   the centre, staged once per workgroup: `stride` floats of A.centre (zero from d on), zero from there to 512 -- a query
+//        column or a point column beyond the row therefore stays exactly the zero it was made
+//   A    a lane's query elements leave the staging tile as fl(q - c) (dead rows and columns >= d: exactly zero, as in the narrow
+//        centred kernel -- a dead row would otherwise score -c against every point) and are split after that: what the registers
+//        hold is the split of the very vector whose norm the proof sums
+//   B    slab sl of c comes off a point's 16 bytes as they leave R; a piece beyond the row is zeroed first (its load was clamped
+//        into the row)
+// base[] takes the centred norms (A.pnorm2 points at them).  MFMA order, accumulators across slabs, selection network, position
+// bits and hand-over are k_gemm_scores_wide4's; the next step's rows and norms are asked for in the step's last two slabs.
+template <int SLABS>
+__global__ __launch_bounds__(256, 1) void k_gemm_scores_wide_centred(GemmArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const IndexView &ix = A.ix;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  constexpr int W = 128, S = W / 16, RB = 4 * W + 16;
+  constexpr int SR = SLABS == 4 ? 3 : SLABS;  // slabs whose low halves stay in registers
+  unsigned char *Ps = smem;                                    // [128][RB]
+  float *base = reinterpret_cast<float *>(smem + 128 * RB);    // [2][128] per staged point: |fl(p - c)|^2, by step parity
+  int *rid = reinterpret_cast<int *>(base + 256);              // [2][128] point rows of a step, by step parity
+  float *cs = reinterpret_cast<float *>(rid + 256);            // [512] the centre
+  unsigned char *const R = reinterpret_cast<unsigned char *>(cs + 512);  // raw half slab: piece x of wave wv at (4 x + wv) KiB + 16 lane
+  [[maybe_unused]] u32x4 *const alds = reinterpret_cast<u32x4 *>(R + 32 * 1024) + wv * (S * 64) + lane;  // (four slabs)
+  constexpr int s4 = W >> 2, nit = s4 >> 1, nx = s4 >> 2;
+  const int half = lane >> 5, col = lane & 31;
+  const int ntiles = A.plan[P_NTILES];
+  const int stride = ix.stride;
+  for (int i = tid; i < 512; i += 256) cs[i] = i < stride ? A.centre[i] : 0.f;  // (visible after the barrier that opens the first tile)
+
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const GemmGroup grp = A.groups[A.tile_group[t]];
+    const int tl = t - grp.tile0, ch = tl / grp.nqt, q0 = (tl - ch * grp.nqt) << 7;
+    const int64_t w = grp.b - grp.a, wlast = w - 1;
+    const int64_t p_begin = (int64_t)ch * kGemmPointChunk;
+    const int64_t p_end = (p_begin + kGemmPointChunk < w) ? (p_begin + kGemmPointChunk) : w;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (nothing of the previous tile is on its way into R any more)
+    __syncthreads();  // the previous tile is done with the staging area
+    if (tid < 128) rid[tid] = window_row(ix, grp.a + min(p_begin + tid, wlast));
+    // A operand, slab by slab through the LDS: row 32 wv + col, columns 128 sl + 16 s + 8 half + (0..7) of fl(q - c)
+    u32x4 ah[S * SLABS], al[S * SR];
+    {
+      constexpr int DP = W + 4;
+      float *Qs = reinterpret_cast<float *>(Ps);
+      const int dlast = ix.d - 1;
+#pragma unroll
+      for (int sl = 0; sl < SLABS; sl++) {
+        if (sl) __syncthreads();
+#pragma unroll 2
+        for (int it = 0; it < nit; it++) {
+          const int idx = tid + it * 256;
+          const int r = idx / s4, c = W * sl + (idx - r * s4) * 4;
+          const bool live = q0 + r < grp.qcount;
+          const float *src = A.queries + (int64_t)A.gq[grp.qoff + (live ? q0 + r : grp.qcount - 1)] * ix.d;
+          f32x4 v;
+          v[0] = src[min(c + 0, dlast)]; v[1] = src[min(c + 1, dlast)]; v[2] = src[min(c + 2, dlast)]; v[3] = src[min(c + 3, dlast)];
+          const f32x4 cv = *reinterpret_cast<const f32x4 *>(cs + c);
+#pragma unroll
+          for (int e = 0; e < 4; e++) v[e] = (live && c + e < ix.d) ? v[e] - cv[e] : 0.f;
+          *reinterpret_cast<f32x4 *>(Qs + r * DP + (c - W * sl)) = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < S; s++) {
+          const float *qp = Qs + (32 * wv + col) * DP + 16 * s + 8 * half;
+          const f32x4 v0 = *reinterpret_cast<const f32x4 *>(qp), v1 = *reinterpret_cast<const f32x4 *>(qp + 4);
+          uint32_t h, l;
+          u32x4 lo4;
+          split2(v0[0], v0[1], h, l); ah[S * sl + s][0] = h; lo4[0] = l;
+          split2(v0[2], v0[3], h, l); ah[S * sl + s][1] = h; lo4[1] = l;
+          split2(v1[0], v1[1], h, l); ah[S * sl + s][2] = h; lo4[2] = l;
+          split2(v1[2], v1[3], h, l); ah[S * sl + s][3] = h; lo4[3] = l;
+          if (sl < SR) al[S * sl + s] = lo4;
+          else alds[s * 64] = lo4;
+        }
+      }
+    }
+    __syncthreads();
+    const int myrow = q0 + 32 * wv + col;
+    const bool live = myrow < grp.qcount;
+    const int64_t nsteps = (w + 127) >> 7;
+    f32x4 *erow = reinterpret_cast<f32x4 *>(A.scores + grp.soff) + ((int64_t)(live ? myrow : q0) * nsteps + (p_begin >> 7)) * 2 + half;
+    // half slab (SL, HF) of the step whose rows are ROWS -> R: thread (row tid >> 2 of the half, 16-byte column group tid & 3)
+    // brings eight pieces, 64 bytes apart.  Only the LAST slab can reach beyond the row (the row is longer than SLABS - 1 slabs):
+    // its pieces are clamped into the row, every other slab's offsets are constants beside the lane's 4 (tid & 3)
+#define WANN_REQUEST(ROWS, SL, HF)                                                                                        \
+  {                                                                                                                       \
+    const float *src_ = ix.points + (int64_t)(ROWS)[64 * (HF) + (tid >> 2)] * stride + 4 * (tid & 3);                     \
+    _Pragma("unroll") for (int x = 0; x < nx; x++) {                                                                      \
+      const int cf_ = W * (SL) + 16 * x;                                                                                  \
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src_ + ((SL) == SLABS - 1 ? min(cf_, stride - 4 - 4 * (tid & 3)) : cf_)), \
+                                       (__attribute__((address_space(3))) void *)(R + (4 * x + wv) * 1024), 16, 0, 0);     \
+    }                                                                                                                     \
+  }
+    float pre_n = 0.f;
+    int pre_rid = 0;
+    if (tid < 128) pre_n = A.pnorm2[rid[tid]];
+    WANN_REQUEST(rid, 0, 0)
+    f32x16 acc[4];
+    int par = 0;
+    for (int64_t c0 = p_begin; c0 < p_end; c0 += 128, par ^= 1) {
+      int *const rid_cur = rid + 128 * par, *const rid_nxt = rid + 128 * (par ^ 1);
+      float *const base_cur = base + 128 * par;
+#pragma unroll
+      for (int sl = 0; sl < SLABS; sl++) {
+#pragma unroll
+        for (int hf = 0; hf < 2; hf++) {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my pieces of the unit have landed (and the row numbers / norms asked for earlier)
+          {
+            unsigned char *dst = Ps + (64 * hf + (tid >> 2)) * RB + 8 * (tid & 3);
+#pragma unroll
+            for (int x = 0; x < nx; x++) {
+              const int cf = W * sl + 4 * (tid & 3) + 16 * x;  // (at most 508: cs holds 512)
+              f32x4 v = *reinterpret_cast<const f32x4 *>(R + (4 * x + wv) * 1024 + 16 * lane);
+              if (sl == SLABS - 1 && cf >= stride) v = f32x4{0.f, 0.f, 0.f, 0.f};  // beyond the row (the last slab alone): zero, and c is zero there
+              v -= *reinterpret_cast<const f32x4 *>(cs + cf);
+              uint32_t h0, l0, h1, l1;
+              split2(v[0], v[1], h0, l0);
+              split2(v[2], v[3], h1, l1);
+              *reinterpret_cast<uint2 *>(dst + 32 * x) = make_uint2(h0, h1);
+              *reinterpret_cast<uint2 *>(dst + 2 * W + 32 * x) = make_uint2(l0, l1);
+            }
+          }
+          // (the rows of the next step are written by the thread that reads them back for the norms; rid_nxt was last read by
+          // the requests of the step before, at least two barriers ago)
+          if (tid < 128) {
+            if (sl == 0 && hf == 0) base_cur[tid] = (c0 + tid < p_end) ? pre_n : kHuge;  // positions beyond the window never win
+            if (sl == SLABS - 2 && hf == 0) pre_rid = window_row(ix, grp.a + min(c0 + 128 + tid, wlast));
+            if (sl == SLABS - 2 && hf == 1) rid_nxt[tid] = pre_rid;
+            if (sl == SLABS - 1 && hf == 0) pre_n = A.pnorm2[rid_nxt[tid]];
+          }
+          __syncthreads();  // the unit is staged; R is free
+          if (hf == 0) WANN_REQUEST(rid_cur, sl, 1)
+          else if (sl + 1 < SLABS) WANN_REQUEST(rid_cur, sl + 1, 0)
+          else if (c0 + 128 < p_end) WANN_REQUEST(rid_nxt, 0, 0)
+          if (sl == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[2 * hf][r] = acc[2 * hf + 1][r] = 0.f;
+          }
+          const unsigned char *pb = Ps + col * RB + 16 * half;
+#pragma unroll
+          for (int s = 0; s < S; s++) {
+            const bf16x8 a_hi = __builtin_bit_cast(bf16x8, ah[S * sl + s]);
+            const bf16x8 a_lo = __builtin_bit_cast(bf16x8, sl < SR ? al[S * sl + s] : alds[s * 64]);
+#pragma unroll
+            for (int j = 2 * hf; j < 2 * hf + 2; j++) {
+              const bf16x8 bh = *reinterpret_cast<const bf16x8 *>(pb + j * 32 * RB + 32 * s);
+              const bf16x8 bl = *reinterpret_cast<const bf16x8 *>(pb + j * 32 * RB + 2 * W + 32 * s);
+              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl, a_hi, acc[j], 0, 0, 0);
+              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, a_lo, acc[j], 0, 0, 0);
+              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, a_hi, acc[j], 0, 0, 0);
+            }
+          }
+        }
+      }
+      // the four smallest of this lane's 64 scores, sorted; low six mantissa bits = 16 j + reg (which position)
+      float m1 = kHuge, m2 = kHuge, m3 = kHuge, m4 = kHuge;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+          const f32x4 b4 = *reinterpret_cast<const f32x4 *>(base_cur + 32 * j + 8 * g + 4 * half);
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const float sc = fmaf(-2.f, acc[j][4 * g + r], b4[r]);
             const float x = __uint_as_float((__float_as_uint(sc) & ~63u) | (uint32_t)(16 * j + 4 * g + r));
             insert4(m1, m2, m3, m4, x);
           }

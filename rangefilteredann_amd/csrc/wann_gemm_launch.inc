@@ -40,13 +40,16 @@ static const char *unit_rerank_cover(const CoverArgs &c, void *stream) {
 #endif
 
 // centred: the batch is scored on fl(x - c) (GemmArgs::centre) -- the float32 and float16 units' narrow kernel has that instance,
-// no other kernel and no other unit: asking for it there is an error, never the uncentred kernel in its place
+// the float32 unit has k_gemm_scores_wide_centred for its wide class, no other kernel and no other unit has one: asking for it
+// there is an error, never the uncentred kernel in its place
 static ScoreKernel pick_score_kernel(const IndexView &ix, bool centred) {
   // (a type whose long class is the index's own switch: the host admitted the batch with it, this unit only picks the kernel)
   const DenseRows rows = dense_row_class(ix, dense_long_switch_type(ix.dtype), dense_long_float8_type(ix.dtype));
   const int words = query_words(ix);
   void (*kern)(GemmArgs) = nullptr;
-#if WANN_DT == 0 || WANN_DT == 3
+#if WANN_DT == 0
+  if (centred && rows != kRowsNarrow && rows != kRowsWide) return {};
+#elif WANN_DT == 3
   if (centred && rows != kRowsNarrow) return {};
 #else
   if (centred) return {};
@@ -82,6 +85,12 @@ static ScoreKernel pick_score_kernel(const IndexView &ix, bool centred) {
   // (the one-byte shadow rows of a float32 index: narrow only; dense_row_class names no other class for them)
 #else
   if (rows == kRowsLong) return {k_gemm_scores_long, (size_t)2 * 128 * (4 * 128 + 16) + 2 * 128 * 4, 1, true};
+  if (rows == kRowsWide && centred) {  // the same tile on fl(x - c): every slab count through the raw half slab
+    const int slabs = (words + 127) / 128;
+    kern = slabs == 2 ? k_gemm_scores_wide_centred<2> : slabs == 3 ? k_gemm_scores_wide_centred<3> : k_gemm_scores_wide_centred<4>;
+    // staged points | base[2][128], rid[2][128] | c, 512 floats | the raw half slab | four slabs: the low halves of the last slab's A operand
+    return {kern, (size_t)128 * (4 * 128 + 16) + 4 * 128 * 4 + 512 * 4 + (size_t)32 * 1024 + (slabs == 4 ? (size_t)4 * 8 * 64 * 16 : 0), 1, false};
+  }
   if (rows == kRowsWide) {  // slabs of 128, A operand in registers, one workgroup per CU
     const int slabs = (words + 127) / 128;
     // (four slabs: + the low halves of the last slab's A operand; the overlapped kernel: + its parity arrays and the raw half slab)

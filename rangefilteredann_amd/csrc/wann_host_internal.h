@@ -196,8 +196,8 @@ struct wann_index {
   // k_large_rerank_cover_b (select_keys_large; rows of up to 512 bytes return the keys' distances and fetch no selected row).
   bool dense_large_k_bytes_on = false;
   bool has_dense_large_k_bytes() const { return wann::byte_rows(dtype); }
-  // wann_set_dense_centred (likewise): squared-L2 dense batches of a float32 / float16 index with rows of at most 128 elements are
-  // scored on fl(x - c), c the mean row, and proven on the centred norms (dense_centred_route, wann_gemm_device.h).  No result
+  // wann_set_dense_centred (likewise): squared-L2 dense batches of a float32 / float16 index with rows of at most 128 elements (float32: at most 512) are
+  // scored on fl(x - c), c the mean row, and proven on the centred norms (dense_centred_route / dense_centred_wide_route, wann_gemm_device.h).  No result
   // row changes; what changes is which queries the proof settles.
   bool dense_centred_on = false;
   bool has_dense_centred() const { return wann::dense_centred_type(dtype, host().spec.metric); }

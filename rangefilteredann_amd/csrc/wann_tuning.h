@@ -56,7 +56,7 @@ struct Tuning {
   bool dense_long_rows = false; // wann_set_dense_long_rows: bfloat16 rows of 129 .. 2048 elements take the dense path (k_gemm_scores_bfslab)
   bool dense_long_float8 = false; // wann_set_dense_long_float8: float8 rows of 129 .. 2048 elements likewise (k_gemm_scores_f8slab)
   bool dense_large_k = false;     // wann_set_dense_large_k: k = 17 .. 128 takes the dense path (k_large_rerank; never on a uint8 / int8 index)
-  bool dense_centred = false;     // wann_set_dense_centred: squared-L2 dense batches of narrow float32 / float16 rows are scored and proven on centred operands
+  bool dense_centred = false;     // wann_set_dense_centred: squared-L2 dense batches of narrow float32 / float16 rows and of wide float32 rows are scored and proven on centred operands
   bool dense_window_norms = false; // wann_set_dense_window_norms: the dense proof bounds a query by the largest norm round its own window (never on a uint8 / int8 index)
   bool dense_large_k_bytes = false;  // wann_set_dense_large_k_bytes: the same on a uint8 / int8 index, and on no other (k_large_rerank_b)
 

@@ -300,7 +300,7 @@ class Index {
   // the same on a uint8 / int8 index, on k_large_rerank_b (wann_set_dense_large_k_bytes, off by default; False on any other element type)
   bool set_dense_large_k_bytes(bool on) { return set_row_switch(wann_set_dense_large_k_bytes, on, "set_dense_large_k_bytes failed"); }
   bool dense_large_k_bytes() const { return wann_dense_large_k_bytes(h_) != 0; }
-  // squared-L2 dense batches of a float32 / float16 index (rows of at most 128 elements) are scored and proven on operands centred on
+  // squared-L2 dense batches of a float32 / float16 index (rows of at most 128 elements; float32: at most 512) are scored and proven on operands centred on
   // the mean row (wann_set_dense_centred, off by default; False on an inner-product index or any other element type)
   bool set_dense_centred(bool on) { return set_row_switch(wann_set_dense_centred, on, "set_dense_centred failed"); }
   bool dense_centred() const { return wann_dense_centred(h_) != 0; }

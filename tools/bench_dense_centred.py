@@ -1,18 +1,23 @@
 """Dev tool: what wann_set_dense_centred costs and gains on tools/bench_prefilter.py's adversarial shape (100 clusters of 10 000 unit
-rows, d = 100, float32, squared L2, 99 queries per cluster, window = the cluster, k = 10), with mu added to rows and queries:
+rows, d = 100 or --d D, float32, squared L2, 99 queries per cluster, window = the cluster, k = 10), with mu added to rows and queries:
   mu = 0   data that does not need centring -- the price of the subtraction,
   mu = 64  a common offset no uncentred proof settles -- the switch off is the parent commit's call: every query ends in the scan.
 Legs per mu, one index, one process, alternating: off, on, off, on; a leg is 3 warm-up calls + WANN_PF_REPS (21) timed ones, device
 time from the HIP events round the batch (counters()["device_ms"]) and the host clock round the synchronising call.  Ids and
 distance bits of every leg are compared with the first.  WANN_PF_ONLY=on / off runs mu = 0 with that setting alone (for a kernel
-trace: the score kernel's time per launch).  Run from the repo root; prints one JSON object."""
-import json, os, sys, time
+trace: the score kernel's time per launch).  --legs off,off: other legs than off,on,off,on (a build without the kernel under test as
+the reference of the same job).  Run from the repo root; prints one JSON object."""
+import argparse, json, os, sys, time
 import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
 import torch
 import window_ann as wa
 
-NCLU, PER, D, K, REPS = 100, 10000, 100, 10, int(os.environ.get("WANN_PF_REPS", "21"))
+ap = argparse.ArgumentParser()
+ap.add_argument("--d", type=int, default=100)
+ap.add_argument("--legs", default="off,on,off,on")
+args = ap.parse_args()
+NCLU, PER, D, K, REPS = 100, 10000, args.d, 10, int(os.environ.get("WANN_PF_REPS", "21"))
 rng = np.random.default_rng(0)
 cent = rng.standard_normal((NCLU, D)).astype(np.float32)
 X = cent[np.repeat(np.arange(NCLU), PER)] + 0.1 * rng.standard_normal((NCLU * PER, D)).astype(np.float32)
@@ -29,8 +34,8 @@ it, dt = torch.empty((nq, K), dtype=torch.int32, device=dev), torch.empty((nq, K
 
 
 def legs(mu, order):
-    idx = wa.PrefilterIndexFloatEuclidian((X.astype(np.float64) + mu).astype(np.float32), labels)
-    Qt = torch.from_numpy((Q.astype(np.float64) + mu).astype(np.float32)).to(dev)
+    idx = wa.PrefilterIndexFloatEuclidian(X + np.float32(mu), labels)
+    Qt = torch.from_numpy(Q + np.float32(mu)).to(dev)
     out, first = [], None
     for on in order:
         assert idx.set_dense_centred(on) is on
@@ -54,6 +59,7 @@ only = os.environ.get("WANN_PF_ONLY")
 if only in ("on", "off"):
     print(json.dumps(dict(mu=0, calls=3 + REPS, leg=legs(0.0, [only == "on"])[0])))
     sys.exit(0)
-res = {f"mu={mu:g}": legs(mu, [False, True, False, True]) for mu in (0.0, 64.0)}
+order = [leg == "on" for leg in args.legs.split(",")]
+res = {f"mu={mu:g}": legs(mu, order) for mu in (0.0, 64.0)}
 print(json.dumps(dict(workload=f"adversarial {NCLU}x{PER} d={D} float32 Euclidian + mu, {nq} queries, window = 1 cluster, k = {K}",
-                      legs="wann_set_dense_centred off / on, alternating (off, on, off, on), one index per mu, one process", timed_calls_per_leg=REPS, **res)))
+                      legs=f"wann_set_dense_centred {args.legs}, one index per mu, one process", timed_calls_per_leg=REPS, **res)))
